@@ -2,18 +2,22 @@
 """bench.py -- throughput of the RX demodulation hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c4|pfb|c1]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path through the C ABI over one 1 M-sample buffer of
 synthetic IQ that is already resident in HBM (a ring of distinct buffers made by the HIP
 source kernel before the timed region).  The headline workload is BASELINE.json's largest
-single-GPU configuration, C3 (2048-tone DDC, decim 1000, 200 Msps); C2, the PFB, the chirp
-path and the real-time tone count are reported under `extras`.
+single-GPU configuration, C3 (2048-tone DDC, decim 1000, 200 Msps).
 
-Timed region: W warm-up steps, then R repetitions of the K steps, R chosen so that the
-region lasts at least --min-seconds (default 1 s: a few hundred microseconds of kernels
-say nothing about the power-capped steady state the chip settles into), bracketed by a
-barrier + device synchronise on both sides; `ms_per_step` = elapsed / (K*R) (max over
-ranks), `repeats` = R.
+Timed region: W warm-up steps, then exactly the K steps, bracketed by a barrier + device
+synchronise on both sides, no events inside; `ms_per_step` = elapsed / K (max over ranks).
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/iq_out.npy.
+
+Everything else runs only under --full: the `sustained` rate (the K steps repeated until
+the region lasts at least --min-seconds, default 1 s: a few hundred microseconds of kernels
+say nothing about the power-capped steady state the chip settles into) with the hipEvent
+roofline of the dominant kernel, the in-order pass, the host-pointer rates, C2, the PFB,
+the chirp path and the real-time tone count under `extras`, and the CPU baselines.
 
 One independent synthetic 200 Msps stream per GPU, no inter-GPU data traffic (front-end
 streams are independent: SURVEY.md section 8e), so scaling is "weak" and `value` is the
@@ -22,7 +26,7 @@ torch.distributed.run; the process group is used ONLY for the barrier and the
 max-over-ranks of the elapsed time (RCCL when every rank has a GPU of its own, gloo when
 ranks share a device -- the one-GPU rehearsal).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with
+Rank 0 prints ONE JSON line with, under --full,
   roofline      dominant kernel: ALGORITHMIC flops per launch, N(6+4f)L,
                 over its average launch duration with the chip to itself (in-order entry,
                 hipEvents on the launch stream) against the dense peak of the pipe it runs
@@ -53,6 +57,7 @@ FP32_PEAK_TFLOPS = 157.3        # MI355X_MICROARCH.md: FP32 vector == FP32 matri
 F16_MFMA_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: dense f16/bf16 MFMA
 PROFILE_EVERY = int(os.environ.get("GSDR_BENCH_PROFILE_EVERY", "8"))   # timed region: every n-th launch
 PIPE_DEPTH = int(os.environ.get("GSDR_BENCH_DEPTH", "3"))   # buffers outstanding, <= GSDR_PIPELINE_DEPTH (4)
+WARMUP_SECONDS = 0.5            # plain run: the chip at its clocks before the W warm-up steps (time_workload)
 CPU_PROCS_CAP = int(os.environ.get("GSDR_BENCH_CPU_PROCS", "16"))      # one GPU's share of the box's cores
 
 WORKLOADS = {
@@ -238,8 +243,9 @@ def run_steps(dem, bufs, out, steps, stream=None, k0=0):
 
 def run_steps_pipelined(dem, bufs, outs, steps, k0=0):
     """gsdr_demod_submit_device / gsdr_demod_wait: up to len(outs) buffers outstanding, one
-    output buffer each; every submitted buffer is waited for before this returns."""
-    depth, pending = len(outs), 0
+    output buffer each; every submitted buffer is waited for before this returns.  Returns the
+    valid length of the last buffer (the waits come back in submission order)."""
+    depth, pending, n = len(outs), 0, 0
     for k in range(k0, k0 + steps):
         if pending == depth:
             dem.wait()
@@ -247,8 +253,9 @@ def run_steps_pipelined(dem, bufs, outs, steps, k0=0):
         dem.submit_device(bufs[k % len(bufs)], outs[k % depth])
         pending += 1
     while pending:
-        dem.wait()
+        n = dem.wait()
         pending -= 1
+    return n
 
 
 def time_workload(engine, wl, device, seed, steps, warmup, dist=None, n_tones=None, api="inorder",
@@ -259,32 +266,50 @@ def time_workload(engine, wl, device, seed, steps, warmup, dist=None, n_tones=No
     api "pipelined": gsdr_demod_submit_device / gsdr_demod_wait, PIPE_DEPTH outstanding: the
     kernels of consecutive buffers overlap on the GPU (include/gsdr.h).
     R: repetitions of the K steps so that the timed region lasts >= min_seconds (estimated from
-    one untimed pass of K steps, maximum over ranks so that every rank runs the same count)."""
+    one untimed pass of K steps, maximum over ranks so that every rank runs the same count).
+    min_seconds None: the K steps once (R = 1), no untimed pass, no events in the region; before
+    the W warm-up steps a second handle of the same workload runs for WARMUP_SECONDS.
+    `out` / `n_out`: the output buffer of the last timed step and its valid length."""
     dem, bufs, outs, N = engine.build(wl, device, seed, n_tones=n_tones)
     stream = engine.stream(device)
 
-    def run(count, k0):
+    def run(count, k0, handle=None):
+        d, b, o = handle or (dem, bufs, outs)
         if api == "pipelined":
-            run_steps_pipelined(dem, bufs, outs, count, k0)
-        else:
-            run_steps(dem, bufs, outs[0], count, stream, k0)
+            return run_steps_pipelined(d, b, o, count, k0)
+        return run_steps(d, b, o[0], count, stream, k0)
 
     engine.sync(device)
+    twin = None
+    if min_seconds is None and WARMUP_SECONDS > 0:
+        # out of idle the chip takes a while to reach its clocks, longer than a short --warmup lasts; a throwaway
+        # handle takes that time, so that the timed handle's stream (and what --dump-outputs writes) depends on
+        # --warmup and --steps alone
+        twin = engine.build(wl, device, seed, n_tones=n_tones)[:3]
+        t0, k = time.perf_counter(), 0
+        while time.perf_counter() - t0 < WARMUP_SECONDS:
+            run(max(warmup, 10), k, twin)
+            engine.sync(device)
+            k += max(warmup, 10)
     run(warmup, 0)
     engine.sync(device)
-    # how long do K steps take?  (untimed pass; also part of the warm-up)
-    t0 = time.perf_counter()
-    run(steps, warmup)
-    engine.sync(device)
-    est = max_over_ranks(dist, time.perf_counter() - t0, device)
-    if fixed_repeats:
-        repeats = int(fixed_repeats)
+    if min_seconds is None:
+        repeats, every, k0 = 1, 0, warmup
     else:
-        # (the untimed pass runs warmer caches and a cooler chip than the steady state: aim 15 % over)
-        repeats = max(1, int(math.ceil(1.15 * min_seconds / max(est, 1e-9))))
-        repeats = max(1, min(repeats, int(max_seconds / max(est, 1e-9)) or 1))
+        # how long do K steps take?  (untimed pass; also part of the warm-up)
+        t0 = time.perf_counter()
+        run(steps, warmup)
+        engine.sync(device)
+        est = max_over_ranks(dist, time.perf_counter() - t0, device)
+        if fixed_repeats:
+            repeats = int(fixed_repeats)
+        else:
+            # (the untimed pass runs warmer caches and a cooler chip than the steady state: aim 15 % over)
+            repeats = max(1, int(math.ceil(1.15 * min_seconds / max(est, 1e-9))))
+            repeats = max(1, min(repeats, int(max_seconds / max(est, 1e-9)) or 1))
+        every = PROFILE_EVERY if profile_every is None else profile_every
+        k0 = warmup + steps
     total = steps * repeats
-    every = PROFILE_EVERY if profile_every is None else profile_every
     if every > 0:
         # hipEvents around every n-th launch of the dominant kernel, inside the timed region, on
         # the stream it is launched on (around every launch they cost ~6 us of stream time per step)
@@ -292,7 +317,7 @@ def time_workload(engine, wl, device, seed, steps, warmup, dist=None, n_tones=No
     barrier(dist, device)
     engine.sync(device)
     t0 = time.perf_counter()
-    run(total, warmup + steps)
+    n_out = run(total, k0)
     engine.sync(device)
     t1 = time.perf_counter()
     barrier(dist, device)
@@ -301,8 +326,12 @@ def time_workload(engine, wl, device, seed, steps, warmup, dist=None, n_tones=No
     kname = dem.kernel_name
     desc = dem.describe() if hasattr(dem, "describe") else {}
     dem.close()
+    if twin:
+        twin[0].close()
+    out = outs[(k0 + total - 1) % len(outs)] if api == "pipelined" else outs[0]
     return dict(elapsed=elapsed, local_elapsed=t1 - t0, kernel_launches=kn, kernel_ms=kms, steps=steps,
-                repeats=repeats, total_steps=total, kernel=kname, n_tones=N, api=api, engine=desc)
+                repeats=repeats, total_steps=total, kernel=kname, n_tones=N, api=api, engine=desc,
+                out=out, n_out=n_out)
 
 
 def host_api_rates(wl, device, seed, seconds=0.4):
@@ -635,6 +664,21 @@ def fp32_valu_extras(engine, device, seed):
                 max_realtime_tones_200Msps=dict(value=best, decim=1000, pf_average=4, buffers=200, probes=probes))
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out, n, channels):
+    """DIR/iq_out.npy: the valid part of the last step's output buffer as float32
+    [sample][channel][re, im]; above DUMP_BYTES, a fixed seeded subset of the channels."""
+    import numpy as np
+    y = out[:n].cpu().numpy().view(np.float32).reshape(n // channels, channels, 2)
+    if y.nbytes > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // (y.shape[0] * 8))
+        y = y[:, np.sort(np.random.default_rng(0).choice(channels, keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "iq_out.npy"), np.ascontiguousarray(y))
+
+
 # --------------------------------------------------------------------------
 def main(argv=None, engine=None):
     ap = argparse.ArgumentParser()
@@ -644,15 +688,20 @@ def main(argv=None, engine=None):
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--api", default="auto", choices=["auto", "inorder", "pipelined"],
                     help="entry the timed steps go through; auto = pipelined for the DDC (DIRECT, TONES) workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output of the last timed step (rank 0) to DIR/iq_out.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: sustained rate and rooflines, in-order pass, "
+                         "host-pointer rates, extras, CPU baselines")
     ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the K steps are repeated until the timed region is at least this long")
+                    help="--full: the sustained pass repeats the K steps until its timed region is at least this long")
     ap.add_argument("--tones", type=int, default=0,
                     help="override the workload's tone count (experiments; the line says so in config.tones_per_stream)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C2 / PFB / chirp / max-tone extras")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the C2 / PFB / chirp / max-tone extras")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-pointer (PCIe-inclusive) rates: profiling runs want the traced kernels to be "
-                         "those of the timed entry only")
+                    help="--full: skip the host-pointer (PCIe-inclusive) rates: profiling runs want the traced kernels "
+                         "to be those of the timed entry only")
     ap.add_argument("--ablation", action="store_true",
                     help="allow a timing-only ablation build (GSDR_LIB / -DGSDR_TIMING_BUILD); the line is marked invalid")
     args = ap.parse_args(argv)
@@ -680,7 +729,7 @@ def main(argv=None, engine=None):
         wl = WORKLOADS[args.workload] = dict(wl, n_tones=args.tones, name=wl["name"] + f" [tones overridden: {args.tones}]")
     seed = stream_seed(rank)
     cpu = {}
-    if not stub and world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and not stub and world == 1 and rank == 0 and not args.no_cpu:
         cpu = cpu_baselines(args.workload, seed)      # before the GPU is touched (fork)
 
     import torch
@@ -709,14 +758,16 @@ def main(argv=None, engine=None):
     # and keep one stream (an event between calls costs 2 - 3 us of stream time: profiles/r03_pfb_api_ab.log)
     api = args.api if args.api != "auto" else ("pipelined" if wl["kind"] == "direct" else "inorder")
 
-    m = _measure_with_ctl(engine, args.workload, device, ctl_device, seed, args.steps, args.warmup, dist, api,
-                          args.min_seconds)
-    r = m["r"]
+    ceng, cdev = _with_ctl(engine, device, ctl_device, dist)
+    r = time_workload(ceng, wl, cdev, seed, args.steps, args.warmup, dist, api=api, min_seconds=None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["out"], r["n_out"], r["n_tones"])
+    value = r["total_steps"] * L * world / r["elapsed"] / 1e6
     line = {
         "metric": "IQ Msamples/s ingested (one synthetic 200 Msps stream per GPU)",
-        "value": round(m["value"], 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+        "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "repeats": r["repeats"], "timed_region_s": round(r["elapsed"], 4),
-        "ms_per_step": round(m["ms_per_step"], 5), "higher_is_better": True,
+        "ms_per_step": round(r["elapsed"] / r["total_steps"] * 1e3, 5), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None,
         "dtype": "f32 (f16 hi/lo-split MFMA, f32 accumulate)" if r["kernel"].startswith("ddc_mfma") else "f32",
         "dtype_note": ("complex64 in and out, fp32 accumulate; the DDC multiplies on the f16 MFMA as three products "
@@ -734,12 +785,18 @@ def main(argv=None, engine=None):
                           if api == "pipelined" else
                           "device-resident extension of the C ABI: gsdr_demod_process_device, one stream "
                           "(inputs and outputs stay in HBM)"},
-        "realtime_factor": round(m["value"] / world / (wl.get("rate", RATE) / 1e6), 3),
-        "roofline": m["roofline"], "roofline_hbm": m["roofline_hbm"],
+        "realtime_factor": round(value / world / (wl.get("rate", RATE) / 1e6), 3),
         "engine": dict(r["engine"], build=build_info),
     }
-    if "inorder" in m:
-        line["inorder"] = m["inorder"]
+    if args.full:
+        m = measure(ceng, args.workload, cdev, seed, args.steps, args.warmup, dist, api, args.min_seconds)
+        line["sustained"] = dict(value=round(m["value"], 2), ms_per_step=round(m["ms_per_step"], 5),
+                                 repeats=m["r"]["repeats"], timed_region_s=round(m["r"]["elapsed"], 4),
+                                 note=f"the K steps repeated until the region lasts >= {args.min_seconds} s, "
+                                      "hipEvents around every n-th launch inside it (roofline)")
+        line["roofline"], line["roofline_hbm"] = m["roofline"], m["roofline_hbm"]
+        if "inorder" in m:
+            line["inorder"] = m["inorder"]
     if world > 1:
         # every rank's own clock around its own timed region: a straggler shows here, not only in the maximum
         local = gather_over_ranks(dist, r["local_elapsed"], ctl_device)
@@ -748,7 +805,7 @@ def main(argv=None, engine=None):
     if timing_env or "timing_build 0" not in build_info and not stub:
         line["INVALID"] = f"timing-only ablation build or switches ({timing_env or build_info}): not a benchmark"
 
-    if world == 1 and rank == 0 and not stub:
+    if args.full and world == 1 and rank == 0 and not stub:
         ha = None if args.no_host_api else host_api_rates(wl, device, seed)
         if ha:
             line["host_api"] = ha
@@ -781,11 +838,11 @@ def main(argv=None, engine=None):
     return line
 
 
-def _measure_with_ctl(engine, key, device, ctl_device, seed, steps, warmup, dist, api, min_seconds):
-    """measure() with the reduction tensors of barrier()/max_over_ranks() on `ctl_device`
-    (None = CPU, for a gloo control plane beside GPU work)."""
+def _with_ctl(engine, device, ctl_device, dist):
+    """(engine, device) for time_workload()/measure() with the reduction tensors of
+    barrier()/max_over_ranks() on `ctl_device` (None = CPU, for a gloo control plane beside GPU work)."""
     if dist is None or ctl_device is device:
-        return measure(engine, key, device, seed, steps, warmup, dist, api, min_seconds)
+        return engine, device
 
     class Wrapped:
         """engine whose sync() still drains the GPU while the collectives stay on the CPU"""
@@ -797,7 +854,7 @@ def _measure_with_ctl(engine, key, device, ctl_device, seed, steps, warmup, dist
             return self.e.stream(device)
         def build(self, wl, _dev, seed, ring=8, n_tones=None):
             return self.e.build(wl, device, seed, ring=ring, n_tones=n_tones)
-    return measure(Wrapped(engine), key, ctl_device, seed, steps, warmup, dist, api, min_seconds)
+    return Wrapped(engine), ctl_device
 
 
 if __name__ == "__main__":

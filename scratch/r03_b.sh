@@ -9,4 +9,4 @@ for w in c3 c2 c4 pfb; do
   f=$(find $GRAFT_REPO_ROOT/gpurun_out/prof_r03_$w -name "*kernel_stats.csv" | head -1); head -6 "$f"
 done
 cd $GRAFT_REPO_ROOT
-timeout -k 10 600 python bench.py > gpurun_out/r03_bench_b.json 2> gpurun_out/r03_bench_b.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full > "${OUT:-.}/r03_bench_b.json" 2> "${OUT:-.}/r03_bench_b.err"; echo "bench rc=$?"

@@ -4,7 +4,7 @@
 set -e
 # built here: make -C gpu_sdr_amd/csrc OUT=scratch/libgsdr_abN.so FLAGS="... -DGSDR_TIMING_BUILD -DGSDR_ABLATE=N"
 # (the two libraries are built beforehand: see the FLAGS in the git history of this file; -DGSDR_TIMING_BUILD -DGSDR_ABLATE=1|2)
-run() { python bench.py --workload c3 --api inorder --no-extras --no-cpu --no-host-api --steps 100 --warmup 10 --min-seconds 0.5 $2 2>/dev/null | python -c "
+run() { python bench.py --full --workload c3 --api inorder --no-extras --no-cpu --no-host-api --steps 100 --warmup 10 --min-seconds 0.5 $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-28s us/step %7.2f  kernel_us %7.2f %s' % ('$1', d['ms_per_step']*1e3, r['kernel_us'], r['kernel']))"; }

@@ -1961,3 +1961,26 @@ def test_two_front_ends_on_one_gpu_do_not_disturb_each_other(cuda_device, gsdr_l
     assert not errors, errors
     assert heavy_n[0] > 1000 and all(r >= 3 for r in rounds.values()), (heavy_n, rounds)
     assert bad == {k: 0 for k in cases}, (bad, rounds)
+
+
+@pytest.mark.parametrize("key", ["c1", "pfb", "c4"])
+def test_bench_dump_is_the_last_timed_step(key, cuda_device, gsdr_lib, tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same arrays, and they are what the hot path returns for
+    the last timed step (the warm-up and timed steps of the stream, replayed through gsdr_demod_process_device)."""
+    import torch
+    import bench
+    args = ["--workload", key, "--steps", "3", "--warmup", "2"]
+    lines = [bench.main(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    a, b = (np.load(tmp_path / d / "iq_out.npy") for d in ("a", "b"))
+    np.testing.assert_array_equal(a, b)
+    assert a.dtype == np.float32 and [ln["steps"] for ln in lines] == [3, 3]
+    dem, bufs, outs, N = bench.HipEngine().build(bench.WORKLOADS[key], cuda_device, bench.stream_seed(0))
+    for k in range(5):
+        n = dem.process_device(bufs[k % len(bufs)], outs[0])
+    torch.cuda.synchronize()
+    want = outs[0][:n].cpu().numpy().reshape(-1, N)
+    dem.close()
+    y = a[..., 0] + 1j * a[..., 1]
+    assert y.shape == want.shape and n > 0
+    err = np.linalg.norm(y - want, axis=0) / np.linalg.norm(want, axis=0)
+    assert err.max() <= TOL, err.max()

@@ -138,7 +138,7 @@ def _bench_worker(rank, world, port, q):
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         line = bench.main(["--gpus", str(world), "--steps", "20", "--warmup", "2", "--min-seconds", "0.2",
-                           "--workload", "c3"], engine=_StubEngine(rank))
+                           "--workload", "c3", "--full"], engine=_StubEngine(rank))
     q.put((rank, buf.getvalue(), line))
 
 
@@ -163,21 +163,86 @@ def test_bench_main_two_ranks_stub_engine():
     assert line["config"]["key"] == "c3" and line["config"]["streams"] == 2
     assert line["config"]["control_plane"] == "gloo"
     assert line["scaling"] == "weak" and line["vs_baseline"] is None
-    # both ranks agreed on the same repeat count (MAX of the per-rank estimates -> from the slow rank)
-    assert res[0][2]["repeats"] == res[1][2]["repeats"] >= 1
-    R = line["repeats"]
-    assert line["timed_region_s"] >= 0.2 * 0.8
+    # the headline times the 20 steps once
+    assert line["repeats"] == 1
+    # the sustained pass of --full: both ranks agreed on the same repeat count (MAX of the per-rank estimates ->
+    # from the slow rank)
+    su = line["sustained"]
+    assert res[0][2]["sustained"]["repeats"] == res[1][2]["sustained"]["repeats"] == su["repeats"] >= 1
+    assert su["timed_region_s"] >= 0.2 * 0.8
     # the slow rank (2 ms per step) sets the elapsed time; value = samples of BOTH ranks / that
+    for d in (line, su):
+        ms = d["ms_per_step"]
+        assert 1.9 <= ms <= 4.0, ms
+        want = 2 * 1_000_000 / (ms * 1e-3) / 1e6
+        assert abs(d["value"] - want) / want < 1e-3
     ms = line["ms_per_step"]
-    assert 1.9 <= ms <= 4.0, ms
-    want = 2 * 20 * R * 1_000_000 / (ms * 1e-3 * 20 * R) / 1e6
-    assert abs(line["value"] - want) / want < 1e-3
     assert line["roofline"] is not None and line["roofline"]["kernel"] == "stub_kernel"
     # every rank's own clock is in the line: the fast rank (1 ms per step) is visibly twice as fast as the slow one
     pr = line["per_rank"]
     assert [p["rank"] for p in pr] == [0, 1]
     assert 0.9 <= pr[0]["ms_per_step"] <= 1.9 and 1.9 <= pr[1]["ms_per_step"] <= 4.0, pr
     assert pr[1]["ms_per_step"] <= ms * 1.001
+
+
+class _DumpDemod(_StubDemod):
+    """_StubDemod that writes 100 * (its call count) + [0 .. 5] into the first 6 samples of each output"""
+    n = 6
+
+    def _fill(self, out):
+        import torch
+        out[:self.n] = torch.arange(self.n) + 100 * self.calls
+
+    def process_device(self, buf, out, stream):
+        super().process_device(buf, out, stream)
+        self._fill(out)
+        return self.n
+
+    def submit_device(self, buf, out):
+        super().submit_device(buf, out)
+        self._fill(out)
+
+    def wait(self):
+        super().wait()
+        return self.n
+
+
+class _DumpEngine(_StubEngine):
+    """three channels, CPU output buffers; keeps the demodulators it made"""
+
+    def __init__(self):
+        super().__init__(0)
+        self.demods = []
+
+    def build(self, wl, device, seed, ring=8, n_tones=None):
+        import torch
+        import bench
+        self.demods.append(_DumpDemod(1e-3))
+        outs = [torch.zeros(8, dtype=torch.complex64) for _ in range(bench.PIPE_DEPTH)]
+        return self.demods[-1], [None] * ring, outs, 3
+
+
+@pytest.mark.parametrize("api", ["pipelined", "inorder"])
+def test_bench_plain_run_times_exactly_k_steps(api, tmp_path, monkeypatch):
+    """Without --full: the warm-up, then exactly --steps timed steps, once, without events; nothing else is
+    measured; --dump-outputs writes the output of the last timed step."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    eng = _DumpEngine()
+    line = bench.main(["--steps", "20", "--warmup", "2", "--api", api, "--dump-outputs", str(tmp_path)], engine=eng)
+    # the timed handle: 2 warm-up + 20 timed steps; the second one is the throwaway handle that warms the chip up first
+    assert len(eng.demods) == 2 and eng.demods[0].calls == 22 and eng.demods[1].calls >= 10
+    assert not hasattr(eng.demods[0], "every")
+    assert line["steps"] == 20 and line["warmup"] == 2 and line["repeats"] == 1
+    assert abs(line["timed_region_s"] / (line["ms_per_step"] * 1e-3) - 20) < 0.1
+    assert not {"sustained", "roofline", "inorder", "host_api", "extras", "cpu_baseline"} & set(line)
+    y = np.load(tmp_path / "iq_out.npy")
+    assert y.dtype == np.float32 and y.shape == (2, 3, 2)
+    np.testing.assert_array_equal(y[..., 0].ravel(), np.arange(6) + 2200)
+    np.testing.assert_array_equal(y[..., 1], 0)
 
 
 def test_bench_refuses_timing_switches():
