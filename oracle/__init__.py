@@ -1,6 +1,6 @@
 """CPU oracle for the GPU_SDR RX demodulation path -- TEST INFRASTRUCTURE ONLY.
 
-"parity unpinned": see oracle/gsdr_oracle.h.  Only tests/, __graft_entry__.smoke()
+Pinned to the reference's own compiled code: see oracle/gsdr_oracle.h and oracle/refpin.py.  Only tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg may import this package; gpu_sdr_amd must not.
 
 Thin ctypes binding over oracle/liboracle.so (built by oracle/Makefile).

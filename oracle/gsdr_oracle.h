@@ -5,14 +5,15 @@
  * libgsdr.so) may include, link or call this.  Allowed users: tests/,
  * __graft_entry__.smoke() and the cpu_baseline leg of bench.py.
  *
- * PARITY STATUS: "parity unpinned".  The reference ships no tests, fixtures or
- * golden vectors for this path, and its sources need
- * CUDA/cuBLAS/cuFFT/boost/UHD headers that this image lacks, so it cannot be
- * built here without writing stand-ins for them (not allowed).  This oracle is
- * therefore a restatement of the reference *source text*, function by
- * function, each citing the file:line it follows; it is additionally checked
- * against closed forms and against the handful of numeric probes recorded in
- * SURVEY.md section 9 (tests/golden/survey_probes.json).
+ * PARITY STATUS: pinned.  This oracle is a restatement of the reference
+ * *source text*, function by function, each citing the file:line it follows.
+ * It is held to the reference's own code: oracle/build_ref.py compiles the
+ * reference's kernels, FIR class, RX_buffer_demodulator and buffer helpers
+ * for the host (oracle/_ref/libgsdr_ref.so; cuBLAS / cuFFT are fp64
+ * stand-ins), tests/golden/ref_*.npz were recorded from it, and
+ * tests/test_reference_pin.py requires this oracle to match them (DESIGN.md
+ * section 2).  Closed forms and the probes of SURVEY.md section 9
+ * (tests/golden/survey_probes.json) check it as well.
  *
  * All citations are relative to /root/reference.
  */

@@ -3,9 +3,10 @@
 TEST INFRASTRUCTURE ONLY (same rule as oracle/gsdr_oracle.c: only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import it).
 
-Why it exists: the reference ships no fixtures and can be neither built nor
-imported in this image, so nothing reference-held pins the C oracle ("parity
-unpinned").  This file is the second opinion BASELINE.md
+Why it exists: the reference ships no fixtures, and until oracle/build_ref.py
+compiled its RX path for the host nothing reference-held pinned the C oracle
+(tests/test_reference_pin.py now holds both restatements
+to that compiled code).  This file is the second opinion BASELINE.md
 section 3 / SURVEY.md section 8(d) C1 planned: written from the reference
 source lines cited below -- NOT from gsdr_oracle.c -- in vectorised numpy, and
 it mirrors the reference's *mechanics* (its device buffers, the cuBLAS calls in

@@ -1,6 +1,7 @@
 """Regenerates the frozen regression vectors in this directory FROM THE ORACLE
-(oracle/gsdr_oracle.c).  They are NOT reference outputs: the reference cannot
-be built or imported in this image ("Oracle").  Purpose: freeze
+(oracle/gsdr_oracle.c).  They are NOT reference outputs: those are
+tests/golden/ref_*.npz, recorded from the reference's own compiled code by
+make_ref_golden.py.  Purpose: freeze
 the oracle's behaviour so that a later edit cannot silently move the target of
 every GPU parity test.  Inputs are seeded; run `python tests/golden/make_golden.py`.
 """
