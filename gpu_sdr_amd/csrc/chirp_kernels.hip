@@ -407,19 +407,18 @@ hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
 hipError_t launch_chirp_lockin(const float2 *carry, int carry_len, const float2 *in,
                                const float *profile, int ppt, int valid, float2 *out,
                                unsigned long long index0, const ChirpShape &cs, hipStream_t st,
-                               float2 *partial, int partial_cap) {
+                               bool split, float2 *partial, int partial_cap) {
     if (valid <= 0) return hipSuccess;
     // the fast kernel needs windows made of whole steps that start on a step boundary:
     // true for every window the demodulator forms (ppt = length*decim, see enqueue_chirp)
     const bool fast = chirp_fits_32(cs) && ppt % (int)cs.length == 0 && index0 % cs.length == 0;
     if (fast && partial && valid <= 512) {
         // few points with many samples each: deal a point's stretches to several waves (GSDR_CHIRP_SPLIT=0: never)
-        const char *e = std::getenv("GSDR_CHIRP_SPLIT");
         const long long decim = ppt / (long long)cs.length, nst = ((long long)cs.length + 255) / 256, total = decim * nst;
         long long parts = (4096 + valid - 1) / valid;            // ~4096 waves in the launch
         if (parts > total / 4) parts = total / 4;                // at least four stretches per wave
         if (parts > partial_cap / valid) parts = partial_cap / valid;
-        if (!(e && e[0] == '0') && parts >= 2 && total >= 16 && total < 0x7fffffffLL) {
+        if (split && parts >= 2 && total >= 16 && total < 0x7fffffffLL) {
             const long long per_part = (total + parts - 1) / parts;
             parts = (total + per_part - 1) / per_part;
             const long long waves = (long long)valid * parts;

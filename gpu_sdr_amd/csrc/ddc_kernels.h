@@ -15,6 +15,48 @@
 
 namespace gsdr {
 
+// The run-time GSDR_* switches (A/B runs and the tests; INTEGRATION.md, "Run-time knobs"), read from the environment
+// by read_switches() when a handle is created and kept by it: nothing reads the environment after that.  Each field
+// holds what the variable selects, with the default when it is unset or empty; -1 / 0 marked "unset" leave the
+// default to the one place that uses the field.
+struct Switches {
+    bool ddc_mfma = true;       // GSDR_DDC_MFMA, 1: matrix-core DDC where its shape rules hold; 0: ddc_flat_kernel (F <= 4)
+    bool ddc_few = true;        // GSDR_DDC_FEW, 1: ddc_few_kernel for a handful of tones at decim >= 512; 0: never
+    bool ddc_pipe = true;       // GSDR_DDC_PIPE, 1: ddc_flat_kernel where it may run; 0: the generic ddc_kernel
+    int ddc_k = -1;             // GSDR_DDC_K, -1 unset: phasor-table length 16 / the flat kernel's sub-block by shape
+    int ddc_waves = 0;          // GSDR_DDC_WAVES_PER_SIMD, 0 unset: resident waves per SIMD, 6 (flat kernel) or 4; <= 0: 4
+    int ddc_nch = 0;            // GSDR_DDC_NCH, 0: chunks per DDC launch by the grid rule; > 0: that many
+    unsigned ddc_lds = 0;       // GSDR_DDC_LDS, 0: dummy LDS bytes per DDC workgroup (occupancy cap)
+    int ddc_prefetch = 1;       // GSDR_DDC_PREFETCH, 1: ddc_flat_kernel prefetches the IQ stream into L2; 0: not
+    bool ddc_autotune = true;   // GSDR_DDC_AUTOTUNE, 1: ddc_flat_kernel's grid timed at create; 0: ratio 1.3
+    int mfma_asm = 4;           // GSDR_MFMA_ASM, 4: ring16 loop; 5: its 8-wave form; 2: round 1's ring; else the C++ kernel
+    int mfma_tt = 1;            // GSDR_MFMA_TT, 1: C++ kernel tone tiles per wave (1 or 2)
+    int mfma_pk = 32;           // GSDR_MFMA_PK, 32: C++ kernel phasor block (16 or 32)
+    int mfma_w = 4;             // GSDR_MFMA_W, 4: C++ kernel waves per workgroup (2 or 4)
+    int mfma_rt = 0;            // GSDR_MFMA_RT, 0: ring kernel row tiles per workgroup chosen per launch; 1, 2: forced
+    bool mfma_w8 = true;        // GSDR_MFMA_W8, 1: in-order launches that fit run the 8-wave ring16 kernel; 0: never
+    int mfma_prec = -1;         // GSDR_MFMA_PREC, -1: pre-converted operands per launch; 1: always; else never
+    int mfma_timing = 0;        // GSDR_MFMA_TIMING, 0: timing-only modes 1 - 3 (builds with -DGSDR_TIMING_BUILD only)
+    bool noise_fft = true;      // GSDR_NOISE_FFT, 1: NOISE through the polyphase filter + FFT; 0: every bin a DDC tone
+    bool tones_fft = true;      // GSDR_TONES_FFT, 1: TONES through filter + FFT + bin selection; 0: every bin a DDC tone
+    bool pfb_lds = true;        // GSDR_PFB_LDS, 1: TONES / NOISE inside the LDS where the frame fits; 0: never
+    int pfb_bluestein = -1;     // GSDR_PFB_BLUESTEIN, -1 unset: Bluestein in the LDS for primes above 127 only; 1: also others; 0: never
+    int pfb_cu = -1;            // GSDR_PFB_CU, -1: pfb_cu_kernel by shape; 0: never; 1: forced (other values: forced, fill rule kept)
+    bool pfb_direct = true;     // GSDR_PFB_DIRECT, 1: pfb_cu_kernel filters straight out of global memory; 0: through the LDS
+    int pfb_col = -1;           // GSDR_PFB_COL, -1: staged filter column-wise by shape; 1: column-wise; 0: point-wise
+    int pfb_cu_nt = 0;          // GSDR_PFB_CU_NT, 0: pfb_cu_kernel workgroup by shape; 512: two per unit; else 1024
+    bool pfb_teams = true;      // GSDR_PFB_TEAMS, 1: the frames of a run go through their stages in teams; 0: in step
+    bool pfb_radix8 = true;     // GSDR_PFB_RADIX8, 1: radix 8 / 6 / 10 stages in the LDS; 0: radix 4 / 2
+    int pfb_fr = 0;             // GSDR_PFB_FR, 0: pfb_lds_kernel frames per workgroup by shape; > 0: that many
+    int pfb_wide = -1;          // GSDR_PFB_WIDE, -1: pfb_lds_kernel 512 threads from 2048 points; 1: always; 0: 256
+    int mix_few = 32;           // GSDR_MIX_FEW, 32: up to how many tones mix_few_kernel runs (decim 0); 0: never
+    bool chirp_split = true;    // GSDR_CHIRP_SPLIT, 1: long lock-in points summed by several waves; 0: a wave per point
+    bool pipe_queues = true;    // GSDR_PIPE_QUEUES, 1: compute streams with a CU mask (a queue each); 0: plain streams
+    bool pipe_overlap = true;   // GSDR_PIPE_OVERLAP, 1: consecutive submitted DIRECT buffers on rotating streams; 0: one
+    int pipe_streams = 3;       // GSDR_PIPE_STREAMS, 3: compute streams the overlap rotates over (1 ... 3, else 3)
+};
+Switches read_switches();
+
 // Shape of one DDC launch; passed to the kernels by value.
 struct DdcShape {
     int N;                     // tones
@@ -60,13 +102,13 @@ struct DdcLaunch {
 // is recorded right after ddc_kernel, before the fixup.
 hipError_t launch_ddc(int F, int K, const DdcLaunch &a, hipStream_t st, hipEvent_t stop);
 const char *ddc_few_kernel_name();
-// Undecimated DIRECT (decim == 0).
-hipError_t launch_mix(int K, const DdcLaunch &a, hipStream_t st);
+// Undecimated DIRECT (decim == 0); mix_few: Switches::mix_few.
+hipError_t launch_mix(int K, const DdcLaunch &a, int mix_few, hipStream_t st);
 
 hipError_t launch_ddc_flat_main(int F, int PK, const DdcLaunch &a, hipStream_t st);
 const char *ddc_kernel_name();
 const char *ddc_flat_kernel_name();
-const char *mix_kernel_name(int n_tones);   // at most 32 tones: several sample phases per wave
+const char *mix_kernel_name(int n_tones, int tw, long long total, int K, int mix_few);   // what launch_mix runs
 
 // ---- DDC on the matrix cores (ddc_mfma.hip) --------------------------------
 struct MfmaShape {
@@ -179,21 +221,29 @@ constexpr int kPfbLdsMaxN = 8192;
 constexpr int kPfbLdsMaxPrime = 127;
 constexpr int kPfbLdsTwMaxN = 4096;                       // up to here the twiddle table sits in the LDS as well
 constexpr int kPfbLdsMaxBytes = (2 * kPfbLdsMaxN + kPfbLdsMaxPrime + 1) * 8;   // two frame buffers + roots: 129 KiB of the 160 KiB
-int pfb_lds_plan(int n, int *radices16);                 // number of stages, -1 when the length does not fit
+int pfb_lds_plan(int n, int *radices16, bool radix8);    // number of stages, -1 when the length does not fit
 // logical window [carry (new_0 samples) | in (window_len - new_0)]; frames_n complete frames -> out[frame][n_out]
 // (sel: bin per output column, nullptr = all nfft bins); W[spare_begin .. +spare_n) -> carry_out
 // (round 3) a run of consecutive frames per compute unit when it fits the LDS, else a frame per workgroup; `blue`:
 // transform through Bluestein's identity at length blue->m (frame lengths with a prime factor above kPfbLdsMaxPrime;
 // tw is then the table of length m, blue->d_tw)
+// `*kernel`: the name of the kernel launched (left alone when nothing was)
 hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, const float *window, const float2 *tw,
                           int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
                           float2 *carry_out, int spare_begin, int spare_n, long long window_len, hipStream_t st,
-                          const FftPlan *blue = nullptr);
-const char *pfb_lds_kernel_name();
-const char *pfb_cu_kernel_name();
-bool pfb_cu_fits(int nfft, int avg, int len);                      // does one frame fit the run kernel's LDS layout
-void fft_env_reload();                                              // the cached GSDR_PFB_* switches are read again
-bool pfb_cu_takes(int nfft, int avg, int len, bool bluestein, int frames_per_call);     // ... and is it the kernel launch_pfb_lds() runs (for calls of about that many frames)
+                          const FftPlan *blue, const Switches &sw, const char **kernel);
+bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw);  // does one frame fit the run kernel's LDS layout
+// Which of the two kernels launch_pfb_lds() runs for a call of frames_n frames, and its shape
+struct PfbChoice {
+    bool cu;                   // pfb_cu_kernel (a run of frames per compute unit); false: pfb_lds_kernel
+    int threads;               // per workgroup
+    int G;                     // frames per workgroup (pfb_lds_kernel: FR)
+    int twl;                   // the twiddle table sits in the LDS too
+    size_t lds;                // dynamic LDS bytes
+    int b_off, b_len, col, direct, dir_s, dir_gs, teams;   // pfb_cu_kernel only, see PfbCuArgs
+};
+PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n_out, int cus, const Switches &sw);
+const char *pfb_kernel_name(const PfbChoice &c);
 
 // ---- chirp ---------------------------------------------------------------
 struct ChirpShape {
@@ -210,7 +260,7 @@ hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
 hipError_t launch_chirp_lockin(const float2 *carry, int carry_len, const float2 *in,
                                const float *profile, int ppt, int valid, float2 *out,
                                unsigned long long index0, const ChirpShape &cs, hipStream_t st,
-                               float2 *partial = nullptr, int partial_cap = 0);   // partial sums of split points (may be null)
+                               bool split, float2 *partial, int partial_cap);   // partial sums of split points (may be null)
 hipError_t launch_warm(hipStream_t st);
 // TX tone comb: out[s] = sum_k q0[k] w_k^(start + s), s < n; fmod = f mod rate, btab[k][64] = w_k^lo,
 // ctab[k][16] = w_k^(64 j), w_k = e^(+2 pi i f_k / rate) (ref: tone_gen, cpp/kernels.cu:589-684)

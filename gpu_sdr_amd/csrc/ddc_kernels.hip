@@ -535,17 +535,19 @@ hipError_t launch_ddc(int F, int K, const DdcLaunch &a, hipStream_t st, hipEvent
     return e;
 }
 
-// up to how many tones mix_few_kernel runs: same box, per 1 M-sample buffer, against mix_small_kernel / mix_kernel:
-// 1 tone 6.8 against 14.3 us, 4: 11.4 / 15.8, 8: 16 / 21, 16: 27 / 32, 32: 68 / 77 - 82, 64: 144 / 110
-// (profiles/r03_mix_rate.log).  GSDR_MIX_FEW=<n> moves the limit (0: the older kernels; read at every call, the
-// tests use it).
-static int mix_few_max() {
-    const char *e = std::getenv("GSDR_MIX_FEW");
-    return e && e[0] ? std::atoi(e) : 32;
+// The kernel launch_mix runs.  mix_few: up to how many tones mix_few_kernel runs -- same box, per 1 M-sample buffer,
+// against mix_small_kernel / mix_kernel: 1 tone 6.8 against 14.3 us, 4: 11.4 / 15.8, 8: 16 / 21, 16: 27 / 32,
+// 32: 68 / 77 - 82, 64: 144 / 110 (profiles/r03_mix_rate.log).  GSDR_MIX_FEW=<n> moves the limit (0: the older kernels).
+enum class Mix { Few, Small, Plain };
+static Mix mix_variant(int n_tones, int tw, long long total, int K, int mix_few) {
+    if (n_tones <= mix_few && tw == 1 && total > 0) return Mix::Few;
+    if (n_tones <= 32 && tw == 1 && (K == 16 || K == 32)) return Mix::Small;
+    return Mix::Plain;
 }
 
-hipError_t launch_mix(int K, const DdcLaunch &a, hipStream_t st) {
-    if (a.sh.N <= mix_few_max() && a.sh.TW == 1 && a.sh.total > 0) {
+hipError_t launch_mix(int K, const DdcLaunch &a, int mix_few, hipStream_t st) {
+    const Mix v = mix_variant(a.sh.N, a.sh.TW, a.sh.total, K, mix_few);
+    if (v == Mix::Few) {
         // very few tones: a lane per (sample, tone) with a phasor of its own (mix_few_kernel)
         int tshift = 0;
         while ((1 << tshift) < a.sh.N) ++tshift;
@@ -557,7 +559,7 @@ hipError_t launch_mix(int K, const DdcLaunch &a, hipStream_t st) {
         hipLaunchKernelGGL(mix_few_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a.x, a.fmod, a.out, a.sh, tshift, (int)steps);
         return hipGetLastError();
     }
-    if (a.sh.N <= 32 && a.sh.TW == 1 && (K == 16 || K == 32)) {
+    if (v == Mix::Small) {
         // few tones: several sample phases per wave (mix_small_kernel); T >= 2 keeps S = 64 / T <= K / ... <= 32
         int tshift = 1;
         while ((1 << tshift) < a.sh.N) ++tshift;
@@ -584,6 +586,9 @@ hipError_t launch_mix(int K, const DdcLaunch &a, hipStream_t st) {
 
 const char *ddc_kernel_name() { return "ddc_kernel"; }
 const char *ddc_few_kernel_name() { return "ddc_few_kernel"; }
-const char *mix_kernel_name(int n_tones) { return n_tones <= mix_few_max() ? "mix_few_kernel" : n_tones <= 32 ? "mix_small_kernel" : "mix_kernel"; }
+const char *mix_kernel_name(int n_tones, int tw, long long total, int K, int mix_few) {
+    const Mix v = mix_variant(n_tones, tw, total, K, mix_few);
+    return v == Mix::Few ? "mix_few_kernel" : v == Mix::Small ? "mix_small_kernel" : "mix_kernel";
+}
 
 }  // namespace gsdr

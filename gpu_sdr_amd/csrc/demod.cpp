@@ -42,14 +42,63 @@ constexpr int kChirpPartials = 16384;    // float2 slots for the partial sums of
 constexpr int kStageSets = kPipeStreams + 1;
 constexpr int kScaleSlots = kPipeStreams + 2;
 
-inline int env_int(const char *name, int dflt) {
-    const char *v = std::getenv(name);
-    return (v && *v) ? std::atoi(v) : dflt;
-}
-
 }  // namespace
 
+// The one reader of the environment ("Run-time knobs"): a variable that is unset or empty keeps the
+// default; values out of range are mapped as noted in gsdr::Switches.
+gsdr::Switches gsdr::read_switches() {
+    auto is_set = [](const char *name) {
+        const char *v = std::getenv(name);
+        return v && *v ? v : nullptr;
+    };
+    auto env = [&](const char *name, int unset) {
+        const char *v = is_set(name);
+        return v ? std::atoi(v) : unset;
+    };
+    Switches s;
+    s.ddc_mfma = env("GSDR_DDC_MFMA", 1) != 0;
+    s.ddc_few = env("GSDR_DDC_FEW", 1) != 0;
+    s.ddc_pipe = env("GSDR_DDC_PIPE", 1) != 0;
+    s.ddc_k = env("GSDR_DDC_K", -1);
+    s.ddc_waves = env("GSDR_DDC_WAVES_PER_SIMD", 0);
+    if (s.ddc_waves <= 0 && is_set("GSDR_DDC_WAVES_PER_SIMD")) s.ddc_waves = 4;
+    s.ddc_nch = env("GSDR_DDC_NCH", 0);
+    s.ddc_lds = (unsigned)env("GSDR_DDC_LDS", 0);
+    s.ddc_prefetch = env("GSDR_DDC_PREFETCH", 1);
+    s.ddc_autotune = env("GSDR_DDC_AUTOTUNE", 1) != 0;
+    s.mfma_asm = env("GSDR_MFMA_ASM", 4);
+    s.mfma_tt = env("GSDR_MFMA_TT", 1) == 2 ? 2 : 1;
+    s.mfma_pk = env("GSDR_MFMA_PK", 32) == 16 ? 16 : 32;
+    s.mfma_w = env("GSDR_MFMA_W", 4) == 2 ? 2 : 4;
+    s.mfma_rt = env("GSDR_MFMA_RT", 0);
+    if (s.mfma_rt < 0 || s.mfma_rt > 2) s.mfma_rt = 0;
+    s.mfma_w8 = env("GSDR_MFMA_W8", 1) != 0;
+    s.mfma_prec = env("GSDR_MFMA_PREC", -1);
+    s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
+    s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
+    s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
+    s.pfb_lds = env("GSDR_PFB_LDS", 1) != 0;
+    s.pfb_bluestein = is_set("GSDR_PFB_BLUESTEIN") ? env("GSDR_PFB_BLUESTEIN", 0) != 0 : -1;
+    s.pfb_cu = env("GSDR_PFB_CU", -1);
+    s.pfb_direct = env("GSDR_PFB_DIRECT", 1) != 0;
+    s.pfb_col = env("GSDR_PFB_COL", -1);
+    if (s.pfb_col > 0) s.pfb_col = 1;
+    s.pfb_cu_nt = env("GSDR_PFB_CU_NT", 0);
+    s.pfb_teams = env("GSDR_PFB_TEAMS", 1) != 0;
+    s.pfb_radix8 = env("GSDR_PFB_RADIX8", 1) != 0;
+    s.pfb_fr = env("GSDR_PFB_FR", 0);
+    s.pfb_wide = env("GSDR_PFB_WIDE", -1);
+    s.mix_few = env("GSDR_MIX_FEW", 32);
+    s.chirp_split = env("GSDR_CHIRP_SPLIT", 1) != 0;
+    s.pipe_queues = env("GSDR_PIPE_QUEUES", 1) != 0;
+    s.pipe_overlap = env("GSDR_PIPE_OVERLAP", 1) != 0;
+    s.pipe_streams = env("GSDR_PIPE_STREAMS", kPipeStreams);
+    if (s.pipe_streams < 1 || s.pipe_streams > kPipeStreams) s.pipe_streams = kPipeStreams;
+    return s;
+}
+
 struct gsdr_demod {
+    gsdr::Switches sw;      // the GSDR_* switches, read when the handle was created
     int mode = GSDR_NODSP;
     int device = -1;
     hipStream_t stream = nullptr;
@@ -83,10 +132,7 @@ struct gsdr_demod {
     int simds = 1024;                  // SIMDs of the device (4 per CU)
     int nch_max = 1;                   // chunks of the DIRECT launch (fixed nblk)
     int tails_nch = 0;                 // chunk count the tails buffer was sized for (0: not yet)
-    int nch_force = 0;                 // GSDR_DDC_NCH: experiment override
     double waves_ratio = 1.3;          // grid waves / resident waves (autotuned in create)
-    unsigned lds_bytes = 0;            // GSDR_DDC_LDS: dummy LDS per workgroup (occupancy cap)
-    int prefetch = 1;                  // GSDR_DDC_PREFETCH: L2 prefetch of the IQ stream
     std::vector<float> window;         // taps (DIRECT) / PFB window / VNA profile, real part
     float *d_taps_t = nullptr;
     float *d_taps_p = nullptr;         // zero-padded [nsub*K+2][FP] copy for ddc_flat_kernel
@@ -106,11 +152,9 @@ struct gsdr_demod {
     gsdr::MfmaKernel mf_kind = gsdr::MfmaKernel::AsmRing;
     gsdr::MfmaShape mf{};              // fields that do not change between calls
     int last_rt = 0;                   // row tiles per workgroup of the last launch (describe())
-    bool w8_auto = true;               // GSDR_MFMA_W8: 8-wave workgroups for in-order launches of one round
     // pre-converted operands (ddc_convert_kernel + ddc_mfma_ring16p_kernel) for launches of many
     // rounds: one image set per staging set (the main kernels of the calls in flight read theirs)
     bool prec = false;                 // image sets allocated: the path may be chosen
-    int prec_mode = -1;                // GSDR_MFMA_PREC
     uint4 *d_img[kStageSets] = {};
     uint4 *d_bfrag = nullptr;
     float2 *d_ptab = nullptr, *d_dtab = nullptr;
@@ -127,7 +171,6 @@ struct gsdr_demod {
     // pipelined entries (gsdr_demod_submit*): consecutive DIRECT calls go to two compute
     // streams in turn, so that their kernels overlap (see pipeline_compute)
     hipStream_t s_main[kPipeStreams] = {};
-    int pipe_streams = kPipeStreams;   // how many of them are used (GSDR_PIPE_STREAMS)
     hipEvent_t ev_abs[4] = {nullptr, nullptr, nullptr, nullptr};    // staging pass of call j done
     // Streams that carry work of this handle nobody has been ordered behind yet.  The carry, the
     // scale slots, the raw windows and the head/tail copies pass from one call to the next ON THE
@@ -142,7 +185,6 @@ struct gsdr_demod {
     std::vector<hipStream_t> dirty;
     hipEvent_t ev_join = nullptr;
     bool pipe_overlap = false;         // set around the compute of an overlapped call
-    bool pipe_overlap_allowed = true;  // GSDR_PIPE_OVERLAP, read when the pipeline is created
     unsigned long long pipe_seq = 0;   // overlapped calls so far
     unsigned long long call_no = 0;    // absmax slot rotation
     // ---- TONES ----
@@ -168,7 +210,6 @@ struct gsdr_demod {
     // ---- TONES / NOISE, a frame per workgroup: filter + in-LDS transform + bin selection (fft_kernels.hip) ----
     bool pfb_lds = false;
     bool pfb_blue = false;                           // ... through Bluestein's identity (h->fft holds chirp, transform, twiddles)
-    bool pfb_cu = false;                             // ... by the run-per-compute-unit kernel (pfb_cu_kernel)
     float2 *d_pfb_tw = nullptr;                      // w_nfft^k
     int *d_pfb_sel = nullptr;                        // TONES: bin of every output column
     float2 *d_pfb_carry[kStageSets] = {};            // the samples a call leaves over (at most F*nfft)
@@ -222,6 +263,15 @@ hipError_t upload(T **dst, const std::vector<T> &src) {
     if (e != hipSuccess) return e;
     if (src.empty()) return hipSuccess;
     return hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// compute units of the current device (256 when it cannot be asked)
+int device_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    return cus;
 }
 
 // exp(-2*pi*i * ph/rate) for an exact integer phase, in double.
@@ -314,8 +364,8 @@ int pick_chunks(const gsdr_demod *h, int nblk) {
     const int TW = h->TW > 0 ? h->TW : 1;
     const long long cap = (h->F > 1) ? nblk / (h->F - 1) : nblk;  // every chunk >= F-1 blocks
     if (cap < 1) return 1;
-    long long nch = h->nch_force > 0
-                        ? (h->nch_force < cap ? h->nch_force : cap)
+    long long nch = h->sw.ddc_nch > 0
+                        ? (h->sw.ddc_nch < cap ? h->sw.ddc_nch : cap)
                         : balanced_near((long long)(h->waves_ratio * h->target_waves) / TW, nblk, cap);
     // never more chunks than the tails buffer has slots for (0 = not allocated yet)
     if (h->tails_nch > 0 && nch > h->tails_nch) nch = h->tails_nch;
@@ -335,13 +385,13 @@ int setup_ddc_common(gsdr_demod *h, int F, int M, unsigned rate,
     // a shape they do not take (windows shorter than a buffer row, ...) goes to the generic ddc_kernel:
     // it is compiled without packed FP32, which is not safe beside the matrix-core loop of another
     // handle on the same GPU (rule 3).  GSDR_DDC_PIPE=0 forces the generic kernel.
-    h->pipe = allow_flat && env_int("GSDR_DDC_PIPE", 1) != 0 && F <= 4 && env_int("GSDR_DDC_MFMA", 1) == 0;
+    h->pipe = allow_flat && h->sw.ddc_pipe && F <= 4 && !h->sw.ddc_mfma;
     if (h->pipe) {
         // sub-block length: whole sub-blocks per block, cheapest total
         // (padded samples + ~3.3 sample-equivalents of fold work per sub-block).  40 since round 3: half the
         // folds and phasor steps of 20 at 124 instead of 82 registers (4 waves per SIMD instead of 5):
         // C3 460 -> 440 us in order (profiles/r03_flat_k.log)
-        int forced = env_int("GSDR_DDC_K", 0);
+        int forced = h->sw.ddc_k;
         if (forced != 12 && forced != 16 && forced != 20 && forced != 40) forced = 0;
         double best = 1e300;
         for (int k : {40, 20, 16, 12}) {
@@ -357,27 +407,19 @@ int setup_ddc_common(gsdr_demod *h, int F, int M, unsigned rate,
         h->pad = nsub * h->K - M;
         h->R = M - (nsub - 1) * h->K;   // length of the last sub-block in real samples
     } else {
-        h->K = env_int("GSDR_DDC_K", 16) == 32 ? 32 : 16;
+        h->K = h->sw.ddc_k == 32 ? 32 : 16;
         h->R = M % h->K;
     }
-    int cus = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     // resident waves per SIMD of the kernel actually used (VGPR-limited)
-    const int wps = env_int("GSDR_DDC_WAVES_PER_SIMD", h->pipe ? 6 : 4);
-    h->simds = cus * 4;
-    h->target_waves = h->simds * (wps > 0 ? wps : 4);
-    h->nch_force = env_int("GSDR_DDC_NCH", 0);
-    h->lds_bytes = (unsigned)env_int("GSDR_DDC_LDS", 0);
-    h->prefetch = env_int("GSDR_DDC_PREFETCH", 1);
+    h->simds = device_cus() * 4;
+    h->target_waves = h->simds * (h->sw.ddc_waves > 0 ? h->sw.ddc_waves : h->pipe ? 6 : 4);
     // the tails buffer must hold the largest chunk count any launch may pick:
     // largest autotune ratio (1.7) x the +20 % window of balanced_near(), or the
     // forced count, but never more than one chunk per F-1 blocks
     {
         const long long cap = (F > 1) ? max_nblk / (F - 1) : max_nblk;
         long long worst = (long long)(1.7 * 1.2 * h->target_waves) / h->TW + 2;
-        if (h->nch_force > worst) worst = h->nch_force;
+        if (h->sw.ddc_nch > worst) worst = h->sw.ddc_nch;
         if (worst > cap) worst = cap;
         h->tails_nch = (int)(worst < 1 ? 1 : worst);
     }
@@ -400,22 +442,35 @@ void finish_shape(DdcShape &sh) {
     sh.m_mod_rate = (unsigned)sh.M % sh.rate;
 }
 
+// Pre-converted operands (ddc_convert_kernel + ddc_mfma_ring16p_kernel) for a launch of
+// ngt row tiles of the AsmRing16 kernel.  GSDR_MFMA_PREC: 1 = always (tests), 0 = never, default:
+//   in-order entries      launches of four rounds of workgroups or more (-9 % at 16 k ... 64 k tones;
+//                         below that the pass, which runs in front of the loop there, costs more);
+//   overlapped entries    launches of half a round or more with windows of 32 blocks or more: the
+//                         pass of buffer j+1 runs beside the loop of buffer j (C3 139 -> 130.5 us per
+//                         buffer, TONES 1024/1230 76.8 -> 74.0; C2, 13 blocks: neutral, not used).
+bool prec_pays(const gsdr_demod *h, long long ngt, bool overlap) {
+    const long long wgs4 = ((ngt + 7) / 8) * 8 * h->mf.ntq;
+    const long long nhi = (h->mf.nk8 + 3) / 4;
+    return h->sw.mfma_prec == 1 ||
+           (h->sw.mfma_prec < 0 && (wgs4 >= 4LL * (h->simds / 2) || (overlap && wgs4 >= h->simds / 4 && nhi >= 32)));
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
 int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
     const int F = h->F, M = h->M;
     const unsigned rate = h->nco_rate;
-    h->mf_TT = env_int("GSDR_MFMA_TT", 1) == 2 ? 2 : 1;
-    h->mf_PK = env_int("GSDR_MFMA_PK", 32) == 16 ? 16 : 32;
-    h->mf_W = env_int("GSDR_MFMA_W", 4);
-    if (h->mf_W != 2 && h->mf_W != 4) h->mf_W = 4;
+    h->mf_TT = h->sw.mfma_tt;
+    h->mf_PK = h->sw.mfma_pk;
+    h->mf_W = h->sw.mfma_w;
     if (h->mf_W > h->mf_PK / 8) h->mf_W = h->mf_PK / 8;   // every wave converts whole k-steps
     // the assembly main loops exist for the default shape only; GSDR_MFMA_ASM: 4 = LDS operand ring
     // on v_mfma_f32_16x16x32_f16 (default since round 2: the same cycles per FLOP for less energy,
     // +7 % on C3 under the power cap), 5 = that loop for workgroups of eight waves, 2 = the ring on
     // v_mfma_f32_32x32x16_f16 (round 1's production kernel), 0 = the compiler-scheduled kernel (A/B runs, tests)
-    const int asm_kind = env_int("GSDR_MFMA_ASM", 4);
+    const int asm_kind = h->sw.mfma_asm;
     const bool asm_shape = h->mf_TT == 1 && h->mf_PK == 32 && h->mf_W == 4;
     h->mf_kind = gsdr::MfmaKernel::Cxx;
     if (asm_kind == 2 && asm_shape) h->mf_kind = gsdr::MfmaKernel::AsmRing;
@@ -475,13 +530,11 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
     sh.m_mod_rate = (unsigned)M % rate;
     sh.unscale = unscale;
 #ifdef GSDR_TIMING_BUILD
-    sh.timing_mode = env_int("GSDR_MFMA_TIMING", 0);   // ablation builds only (scratch/), never shipped
+    sh.timing_mode = h->sw.mfma_timing;   // ablation builds only (scratch/), never shipped
 #else
     sh.timing_mode = 0;
 #endif
-    sh.rt = env_int("GSDR_MFMA_RT", 0);   // 0: chosen per launch in enqueue_mfma
-    h->w8_auto = env_int("GSDR_MFMA_W8", 1) != 0;
-    if (sh.rt < 0 || sh.rt > 2) sh.rt = 0;
+    sh.rt = h->sw.mfma_rt;   // 0: chosen per launch in enqueue_mfma
     if (direct) {
         // row tile 0 and the last row tile read from copies with the carry in front
         // and zeros behind (sizes: ddc_mfma_kernel's reach, 8*nk8 samples per row)
@@ -495,21 +548,13 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
             HIPCHK(h, hipMemset(h->d_tail[i], 0, tail_n * sizeof(float2)));
         }
     }
-    // Pre-converted operands (ddc_convert_kernel + ddc_mfma_ring16p_kernel).
-    // GSDR_MFMA_PREC: 1 = always (tests), 0 = never, default = per launch in enqueue_mfma:
-    //   in-order entries      launches of four rounds of workgroups or more (-9 % at 16 k ... 64 k tones;
-    //                         below that the pass, which runs in front of the loop there, costs more);
-    //   overlapped entries    launches of half a round or more with windows of 32 blocks or more: the
-    //                         pass of buffer j+1 runs beside the loop of buffer j (C3 139 -> 130.5 us per
-    //                         buffer, TONES 1024/1230 76.8 -> 74.0; C2, 13 blocks: neutral, not used).
+    // pre-converted operands: allocated when a launch of this handle may use them (the largest row count, in an
+    // overlapped entry), up to 8 GiB of images
     if (h->mf_kind == gsdr::MfmaKernel::AsmRing16) {
-        h->prec_mode = env_int("GSDR_MFMA_PREC", -1);
         const long long max_rows = direct ? h->L / M : (long long)h->batching;
         const long long ngt_max = (max_rows + 31) / 32;
         const long long nhi = (pl.nk8 + 3) / 4;
-        const long long wgs4 = ((ngt_max + 7) / 8) * 8 * sh.ntq;
-        bool want = h->prec_mode == 1 ||
-                    (h->prec_mode < 0 && (wgs4 >= 4LL * (h->simds / 2) || (wgs4 >= h->simds / 4 && nhi >= 32)));
+        bool want = prec_pays(h, ngt_max, /*overlap=*/true);
         const size_t img_n = (size_t)ngt_max * (size_t)nhi * 512;   // uint4 per image set
         if (want && img_n * sizeof(uint4) > (size_t)8 << 30) want = false;
         for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, dev_alloc(&h->d_img[i], img_n));
@@ -577,7 +622,7 @@ int record_begin(gsdr_demod *h, hipStream_t st, hipEvent_t *stop) {
 // and keeps the fastest.  Runs once in create(); GSDR_DDC_AUTOTUNE=0 keeps 1.3.
 int autotune_chunks(gsdr_demod *h, int nblk) {
     h->waves_ratio = 1.3;
-    if (!h->pipe || h->nch_force > 0 || env_int("GSDR_DDC_AUTOTUNE", 1) == 0 || nblk < 1) {
+    if (!h->pipe || h->sw.ddc_nch > 0 || !h->sw.ddc_autotune || nblk < 1) {
         h->nch_max = pick_chunks(h, nblk);
         return 0;
     }
@@ -611,7 +656,7 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
         a.tails = h->d_tails;
         a.tails_nch = h->tails_nch;
         a.pipe = true;
-        a.lds_bytes = h->lds_bytes;
+        a.lds_bytes = h->sw.ddc_lds;
         a.sh.N = h->ddc_channels;
         a.sh.Npad = h->Npad;
         a.sh.TW = h->TW;
@@ -620,7 +665,7 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
         a.sh.nblk = nblk;
         a.sh.nch = pick_chunks(h, nblk);
         a.sh.xlast = (long long)nblk * h->M + h->pad - 4;
-        a.sh.prefetch = h->prefetch;
+        a.sh.prefetch = h->sw.ddc_prefetch;
         finish_shape(a.sh);
         float ms = 0.f;
         for (int it = 0; it < 4 && !rc; ++it) {  // first iteration warms up
@@ -741,17 +786,10 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     // partners), that kernel ends 4-7 % earlier (C3: 145 against 152-158 us).  The overlapped entries
     // keep the 4-wave kernel: there the next buffer's workgroups fill the slots the older ones free.
     gsdr::MfmaKernel kind = h->mf_kind;
-    bool use_prec = false;
-    if (kind == gsdr::MfmaKernel::AsmRing16 && h->prec && a.sh.rt <= 1) {
-        const long long wgs4 = (long long)((a.sh.ngt + 7) / 8) * 8 * a.sh.ntq;
-        const int nhi = (a.sh.nk8 + 3) / 4;
-        use_prec = h->prec_mode == 1 || wgs4 >= 4LL * (h->simds / 2) ||
-                   (h->pipe_overlap && wgs4 >= h->simds / 4 && nhi >= 32);
-    }
-    if (use_prec) {
+    if (kind == gsdr::MfmaKernel::AsmRing16 && h->prec && a.sh.rt <= 1 && prec_pays(h, a.sh.ngt, h->pipe_overlap)) {
         kind = gsdr::MfmaKernel::AsmRing16P;
         a.img = h->d_img[hs];
-    } else if (kind == gsdr::MfmaKernel::AsmRing16 && !h->pipe_overlap && h->w8_auto) {
+    } else if (kind == gsdr::MfmaKernel::AsmRing16 && !h->pipe_overlap && h->sw.mfma_w8) {
         const long long wgs4 = (long long)((a.sh.ngt + 7) / 8) * 8 * a.sh.ntq;
         const long long wgs8 = (long long)((a.sh.ngt + 7) / 8) * 8 * ((a.sh.ntg + 7) / 8);
         if (a.sh.rt <= 1 && wgs4 > h->simds / 4 && wgs4 <= h->simds / 2 && wgs8 <= h->simds / 4)
@@ -772,8 +810,8 @@ int enqueue_direct(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st)
     a.taps_p = h->d_taps_p;
     a.pipe = h->pipe && h->decim > 0 && h->L >= 4;
     a.few = h->few;
-    a.lds_bytes = h->lds_bytes;
-    a.sh.prefetch = h->prefetch;
+    a.lds_bytes = h->sw.ddc_lds;
+    a.sh.prefetch = h->sw.ddc_prefetch;
     a.btab = h->d_btab;
     a.wk = h->d_wk;
     a.wrem = h->d_wrem;
@@ -825,7 +863,7 @@ int enqueue_direct(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st)
         a.sh.nch = (int)nch;
         finish_shape(a.sh);
         if (record_begin(h, st, &stop)) return -1;
-        HIPCHK(h, gsdr::launch_mix(h->K, a, st));
+        HIPCHK(h, gsdr::launch_mix(h->K, a, h->sw.mix_few, st));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
         ret = (long long)h->N * h->L;                        // :457
     }
@@ -866,7 +904,7 @@ int enqueue_noise_fft(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t 
 // ref: process_pfb (:486-565) and process_pfb_spec (:568-649), decim == 0: one launch, a frame per
 // workgroup.  The logical raw_input is [what the previous call left over | the new buffer]; nothing is
 // staged: the kernel reads both parts in place and writes this call's leftovers (:504-509, :590-596)
-// into the other carry buffer.
+// into the other carry buffer.  h->kernel_name becomes the kernel launched.
 int enqueue_pfb_lds(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     const int cb = h->bh.current_batch;
     const float2 *carry = h->d_pfb_carry[h->win_seq % kStageSets];
@@ -882,8 +920,8 @@ int enqueue_pfb_lds(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st
     const float2 *tw = h->pfb_blue ? h->fft.d_tw : h->d_pfb_tw;
     hipEvent_t stop = nullptr;
     if (record_begin(h, st, &stop)) return -1;
-    HIPCHK(h, gsdr::launch_pfb_lds(carry, h->bh.new_0, in, h->d_fft_win, tw, h->nfft, h->F, cb,
-                                   sel, h->ddc_channels, out, carry_out, h->bh.spare_begin, spare_n, wlen, st, blue));
+    HIPCHK(h, gsdr::launch_pfb_lds(carry, h->bh.new_0, in, h->d_fft_win, tw, h->nfft, h->F, cb, sel, h->ddc_channels, out,
+                                   carry_out, h->bh.spare_begin, spare_n, wlen, st, blue, h->sw, &h->kernel_name));
     if (stop) HIPCHK(h, hipEventRecord(stop, st));
     h->win_seq++;
     const int ret = h->ddc_channels * cb;  // :546 (TONES), copy_size :638 (NOISE)
@@ -936,8 +974,8 @@ int enqueue_pfb(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
         a.sh.M = h->M;
         a.sh.nblk = cb + h->F - 1;  // frame r spans blocks r .. r+F-1
         a.pipe = h->pipe;
-        a.lds_bytes = h->lds_bytes;
-        a.sh.prefetch = h->prefetch;
+        a.lds_bytes = h->sw.ddc_lds;
+        a.sh.prefetch = h->sw.ddc_prefetch;
         a.sh.xlast = (long long)a.sh.nblk * h->M + h->pad - 4;  // a window is allocated twice as long
         a.sh.g_off = h->F - 1;      // DDC output G <-> frame r = G-(F-1)
         const int nch = pick_chunks(h, a.sh.nblk);
@@ -973,8 +1011,8 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
             h->cs.period;
         if (record_begin(h, st, &stop)) return -1;
         HIPCHK(h, gsdr::launch_chirp_lockin(h->d_ccarry[h->cparity], h->carry_len, in,
-                                            h->d_profile, h->ppt, valid, out, idx0, h->cs, st, h->d_chirp_part,
-                                            h->d_chirp_part ? kChirpPartials : 0));
+                                            h->d_profile, h->ppt, valid, out, idx0, h->cs, st, h->sw.chirp_split,
+                                            h->d_chirp_part, h->d_chirp_part ? kChirpPartials : 0));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
         // :369-380 the reference keeps the last new0 DEMODULATED samples; we
         // keep the same raw samples and re-demodulate them next call.
@@ -1001,21 +1039,15 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
     return ret;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *gsdr_last_error(const gsdr_demod *h) {
-    return h ? h->err.c_str() : g_create_error.c_str();
-}
-
-gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
+// gsdr_demod_create with the switches given (gsdr_demod_prepare's rehearsal twin takes its parent's)
+gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
     g_create_error.clear();
     if (!p) {
         g_create_error = "null parameters";
         return nullptr;
     }
     gsdr_demod *h = new gsdr_demod();
+    h->sw = sw;
     {
         h->pc = *p;
         auto keep = [](auto &dst, const auto *src, int n) {
@@ -1118,10 +1150,10 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
                 // tone lane / matrix column, and a launch is as long as one workgroup's walk (72 us per 1 M-sample
                 // buffer for 1 ... 256 tones at decim 1000).  ddc_few_kernel splits the block over the lanes of a wave
                 // per (chunk, tone): 16 tones at decim 1000 in 15 us (profiles/r03_shape_sweep.log).  GSDR_DDC_FEW=0: off.
-                h->few = !rc && env_int("GSDR_DDC_MFMA", 1) != 0 && env_int("GSDR_DDC_FEW", 1) != 0 && !h->pipe &&
+                h->few = !rc && sw.ddc_mfma && sw.ddc_few && !h->pipe &&
                          M >= 512 && h->N <= 32 && h->TW == 1;
                 if (h->few) h->kernel_name = gsdr::ddc_few_kernel_name();
-                if (!rc && !h->few && env_int("GSDR_DDC_MFMA", 1) != 0 && h->L / M >= F - 1 && h->L >= 4 && F <= 33 &&
+                if (!rc && !h->few && sw.ddc_mfma && h->L / M >= F - 1 && h->L >= 4 && F <= 33 &&
                     (M * F + 31) / 32 * 32 - M * F <= M)
                     rc = setup_mfma(h, /*direct=*/true, tone);
                 if (!rc && !h->mfma) rc = autotune_chunks(h, (int)(h->L / M));
@@ -1131,8 +1163,8 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
                 h->F = 1;
                 h->M = 1;
                 h->window.assign(1, 1.f);
-                h->kernel_name = gsdr::mix_kernel_name(h->N);
                 rc = setup_ddc_common(h, 1, 1, (unsigned)p->rate, tone, 1, /*allow_flat=*/false);
+                h->kernel_name = gsdr::mix_kernel_name(h->N, h->TW, h->L, h->K, sw.mix_few);
                 h->capacity = (long long)h->N * h->L;
             }
             break;
@@ -1151,7 +1183,7 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
             // NOISE: polyphase filter + batched FFT of every frame (fft_kernels.hip), any fft_tones.
             // GSDR_NOISE_FFT=0 evaluates every bin as a DDC tone instead (round 1's path: O(fft_tones)
             // per sample, kept for A/B runs and refused above 16384 bins)
-            const bool noise_fft = noise && env_int("GSDR_NOISE_FFT", 1) != 0;
+            const bool noise_fft = noise && sw.noise_fft;
             if (!need(!noise || noise_fft || p->fft_tones <= 16384,
                       "NOISE without the FFT stage (GSDR_NOISE_FFT=0) supports fft_tones <= 16384")) return nullptr;
             h->nfft = p->fft_tones;
@@ -1178,22 +1210,19 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
             // GSDR_PFB_LDS=0, GSDR_TONES_FFT=0 (TONES only) or such a length leave TONES to the DDC
             // kernels (every selected bin as a tone) and NOISE to the global-memory FFT stages.
             int radices16[16];
-            const bool direct_ok = gsdr::pfb_lds_plan(h->nfft, radices16) >= 0;
+            const bool direct_ok = gsdr::pfb_lds_plan(h->nfft, radices16, sw.pfb_radix8) >= 0;
             // a prime factor above 127 (or GSDR_PFB_BLUESTEIN=1: any length, for tests): Bluestein's identity inside
             // the workgroup, when a frame at the padded length m = 2^ceil(log2(2 nfft - 1)) fits the LDS
             long long blue_m = 1;
             while (blue_m < 2LL * h->nfft - 1) blue_m <<= 1;
-            const bool blue_ok = (!direct_ok || env_int("GSDR_PFB_BLUESTEIN", 0) != 0) && env_int("GSDR_PFB_BLUESTEIN", 1) != 0 &&
-                                 blue_m <= gsdr::kPfbLdsMaxN && gsdr::pfb_cu_fits(h->nfft, F, (int)blue_m);
-            const bool lds_path = env_int("GSDR_PFB_LDS", 1) != 0 && (direct_ok || blue_ok) &&
-                                  (noise ? noise_fft : env_int("GSDR_TONES_FFT", 1) != 0);
+            const bool blue_ok = (sw.pfb_bluestein < 0 ? !direct_ok : sw.pfb_bluestein != 0) &&
+                                 blue_m <= gsdr::kPfbLdsMaxN && gsdr::pfb_cu_fits(h->nfft, F, (int)blue_m, sw);
+            const bool lds_path = sw.pfb_lds && (direct_ok || blue_ok) && (noise ? noise_fft : sw.tones_fft);
             if (lds_path) {
                 h->pfb_lds = true;
                 h->pfb_blue = blue_ok;
                 h->F = F;
                 h->M = h->nfft;
-                h->pfb_cu = gsdr::pfb_cu_takes(h->nfft, F, blue_ok ? (int)blue_m : h->nfft, blue_ok, (int)(h->L / h->nfft));
-                h->kernel_name = h->pfb_cu ? gsdr::pfb_cu_kernel_name() : gsdr::pfb_lds_kernel_name();
                 std::vector<float2> tw((size_t)h->nfft);
                 for (int k = 0; k < h->nfft; ++k) {
                     const double a = -2.0 * M_PI * (double)k / (double)h->nfft;
@@ -1209,6 +1238,9 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
                     ok = dev_alloc(&h->d_pfb_carry[i], ncarry) == hipSuccess &&
                          hipMemset(h->d_pfb_carry[i], 0, ncarry * sizeof(float2)) == hipSuccess;
                 if (!need(ok, "PFB allocation failed")) return nullptr;
+                // the kernel of a call of L / nfft frames (each launch reports its own, enqueue_pfb_lds)
+                h->kernel_name = gsdr::pfb_kernel_name(gsdr::pfb_choose(h->nfft, F, blue_ok ? &h->fft : nullptr,
+                                                                        (int)(h->L / h->nfft), n_ch, device_cus(), sw));
                 h->capacity = (long long)n_ch * h->batching;               // :147 / :288
                 break;
             }
@@ -1216,7 +1248,7 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
             // memory (§4.5) -- NOISE keeps every bin, TONES picks its bins out of a scratch spectrum.  For
             // TONES this replaces one DDC per bin when the frame is long (above 8192 points a frame is a
             // window of 32 768+ samples: the DDC rows become thousand-block loops on a handful of workgroups)
-            const bool tones_global = !noise && env_int("GSDR_TONES_FFT", 1) != 0;
+            const bool tones_global = !noise && sw.tones_fft;
             if (noise_fft || tones_global) {
                 h->noise_fft = true;
                 h->F = F;
@@ -1256,7 +1288,7 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
             // every carried sample of the raw window must come from the previous buffer
             // (absmax covers this buffer and the one before)
             // and the padding behind the last window must stay inside the raw buffer's spare half
-            if (!rc && env_int("GSDR_DDC_MFMA", 1) != 0 && (long long)h->nfft * (F + 1) <= h->L &&
+            if (!rc && sw.ddc_mfma && (long long)h->nfft * (F + 1) <= h->L &&
                 (long long)h->nfft * h->batching >= 40)
                 rc = setup_mfma(h, /*direct=*/false, tone);
             if (!rc && !h->mfma) rc = autotune_chunks(h, (int)(h->L / h->nfft) + F - 1);
@@ -1323,6 +1355,16 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) {
     }
     return h;
 }
+
+}  // namespace
+
+extern "C" {
+
+const char *gsdr_last_error(const gsdr_demod *h) {
+    return h ? h->err.c_str() : g_create_error.c_str();
+}
+
+gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gsdr::read_switches()); }
 
 int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev,
                               void *hip_stream) {
@@ -1444,17 +1486,13 @@ static int pipeline_init_parts(gsdr_demod *h) {
     HIPCHK(h, hipGetDeviceProperties(&prop, dev));
     std::vector<uint32_t> all_units((size_t)(prop.multiProcessorCount + 31) / 32, 0xffffffffu);
     if (prop.multiProcessorCount % 32) all_units.back() = (1u << (prop.multiProcessorCount % 32)) - 1u;
-    const bool own_queues = env_int("GSDR_PIPE_QUEUES", 1) != 0;
     for (int i = 0; i < kPipeStreams; ++i) {
-        if (own_queues &&
+        if (h->sw.pipe_queues &&
             hipExtStreamCreateWithCUMask(&h->s_main[i], (uint32_t)all_units.size(), all_units.data()) == hipSuccess)
             continue;
         (void)hipGetLastError();
         HIPCHK(h, hipStreamCreateWithPriority(&h->s_main[i], hipStreamNonBlocking, prio_least));
     }
-    h->pipe_streams = env_int("GSDR_PIPE_STREAMS", kPipeStreams);
-    h->pipe_overlap_allowed = env_int("GSDR_PIPE_OVERLAP", 1) != 0;
-    if (h->pipe_streams < 1 || h->pipe_streams > kPipeStreams) h->pipe_streams = kPipeStreams;
     for (int i = 0; i < 4; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_abs[i], hipEventDisableTiming));
     return 0;
 }
@@ -1482,8 +1520,8 @@ static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, 
     // of rotating streams together (carry, completion) cost more than their overlap gives -- per 1 M-sample buffer
     // 16.3 against 12.0 us in order at 1024 points, 17.0 against 10.2 at 256, 25.7 against 15.4 at 1230
     // (profiles/r03_pfb_api_ab.log)
-    const bool overlap = h->pipe_overlap_allowed && h->mfma && !h->pfb_lds && ddc;
-    hipStream_t cs = overlap ? h->s_main[h->pipe_seq % (unsigned)h->pipe_streams] : h->stream;
+    const bool overlap = h->sw.pipe_overlap && h->mfma && !h->pfb_lds && ddc;
+    hipStream_t cs = overlap ? h->s_main[h->pipe_seq % (unsigned)h->sw.pipe_streams] : h->stream;
     if (up) HIPCHK(h, hipStreamWaitEvent(cs, up, 0));
     if (overlap) {
         // behind in-order calls made on other streams since (their carry, slot and window writes);
@@ -1542,7 +1580,7 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     HIPCHK(h, hipDeviceSynchronize());
     if (what & GSDR_PREPARE_REHEARSE) {
         // a twin with the same parameters takes the process-wide first-use costs (see include/gsdr.h)
-        gsdr_demod *twin = gsdr_demod_create(&h->pc);
+        gsdr_demod *twin = demod_create(&h->pc, h->sw);
         gsdr_c64 *pin_in = nullptr, *pin_out = nullptr;
         bool ok = twin != nullptr;
         ok = ok && hipHostMalloc((void **)&pin_in, (size_t)h->L * sizeof(gsdr_c64)) == hipSuccess;
@@ -1691,7 +1729,7 @@ void gsdr_demod_close(gsdr_demod *h) {
 
 int gsdr_pfb_lds_stages(int fft_tones, int *radices) {
     int tmp[16];
-    const int n = gsdr::pfb_lds_plan(fft_tones, tmp);
+    const int n = gsdr::pfb_lds_plan(fft_tones, tmp, gsdr::read_switches().pfb_radix8);
     if (radices)
         for (int i = 0; i < n && i < 16; ++i) radices[i] = tmp[i];
     return n;
@@ -1746,7 +1784,7 @@ int gsdr_demod_profile_read(gsdr_demod *h, double *total_ms) {
 
 const char *gsdr_demod_kernel_name(const gsdr_demod *h) { return h ? h->kernel_name : "none"; }
 
-void gsdr_reload_env(void) { gsdr::fft_env_reload(); }
+void gsdr_reload_env(void) {}   // kept for callers built against older headers: a handle reads the switches once
 
 const char *gsdr_build_info(void) {
 #ifdef GSDR_TIMING_BUILD
@@ -1769,7 +1807,7 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
          h->noise_fft ? "fp32 Stockham FFT behind the polyphase filter" : h->mfma ? "f16 MFMA, hi/lo split" : (h->mode == GSDR_CHIRP ? "fp32 VALU, integer phase" : (h->pipe ? "packed fp32 VALU" : "fp32 VALU"));
     s += "\", \"channels\": " + std::to_string(h->ddc_channels > 0 ? h->ddc_channels : h->N);
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
-    s += ", \"pipeline_streams\": " + std::to_string(h->pipe_ready ? h->pipe_streams : env_int("GSDR_PIPE_STREAMS", kPipeStreams));
+    s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"timing_build\": ";
 #ifdef GSDR_TIMING_BUILD
     s += "1";

@@ -27,32 +27,6 @@
 
 namespace gsdr {
 
-// The GSDR_PFB_* switches below exist for A/B runs and for the tests that drive every kernel variant.  They are read
-// once and cached (a launch must not walk the environment); gsdr_reload_env() (include/gsdr.h) makes the next use
-// read them again.
-static std::atomic<int> g_env_generation{0};
-void fft_env_reload() { g_env_generation.fetch_add(1); }
-namespace {
-struct EnvSwitch {
-    const char *name;
-    int unset;                 // value when the variable is not set (or empty)
-    std::atomic<int> seen{-1}, value{0};
-    EnvSwitch(const char *n, int u) : name(n), unset(u) {}
-    int get() {
-        const int g = g_env_generation.load(std::memory_order_relaxed);
-        if (seen.load(std::memory_order_acquire) != g) {
-            const char *e = std::getenv(name);
-            value.store(e && e[0] ? std::atoi(e) : unset, std::memory_order_relaxed);
-            seen.store(g, std::memory_order_release);
-        }
-        return value.load(std::memory_order_relaxed);
-    }
-};
-EnvSwitch env_radix8{"GSDR_PFB_RADIX8", 1}, env_direct{"GSDR_PFB_DIRECT", 1}, env_col{"GSDR_PFB_COL", -1},
-    env_cu_nt{"GSDR_PFB_CU_NT", 0}, env_cu{"GSDR_PFB_CU", -1}, env_fr{"GSDR_PFB_FR", 0}, env_wide{"GSDR_PFB_WIDE", -1},
-    env_teams{"GSDR_PFB_TEAMS", 1};
-}  // namespace
-
 // No packed FP32 in these kernels: a NOISE handle may run beside the matrix-core DDC of another handle
 // (two front-ends on one GPU), and v_pk_*_f32 with a high-half broadcast is unreliable in a wave that
 // shares its SIMD with an MFMA loop (rule R3, DESIGN.md section 4.1, tools/ubench_pk_hazard.hip).
@@ -1526,7 +1500,7 @@ hipError_t launch_pfb_filter(const float2 *raw, const float *window, int nfft, i
 // butterflies, any larger prime through the one-output-per-item stage).  Empty when n does not fit:
 // n > kPfbLdsMaxN, more than 16 stages, or a prime factor above kPfbLdsMaxPrime (its stage is O(R) per
 // output: a 1021-point prime frame would be a plain DFT).
-int pfb_lds_plan(int n, int *radices) {
+int pfb_lds_plan(int n, int *radices, bool radix8) {
     if (n < 1 || n > kPfbLdsMaxN) return -1;
     int cnt = 0, m = n;
     auto push = [&](int r) { if (cnt < 16) radices[cnt] = r; ++cnt; };
@@ -1551,15 +1525,14 @@ int pfb_lds_plan(int n, int *radices) {
     //     waves to hide each other's latencies (1024 points: two radix-16 stages take what four radix-4 stages took);
     //   * 8 (= 4 x 2) otherwise: one thread in eight points keeps half of the threads busy;
     //   * a single 2 left over joins a 3 or a 5: radix 6 / 10 (1230 = 41 * 6 * 5, 1000 = 8 * 5 * 5 * 5).
-    // GSDR_PFB_RADIX8=0: 4s and 2s as in round 2 (A/B runs)
-    const bool fat = env_radix8.get() != 0;
+    // radix8 = false (GSDR_PFB_RADIX8=0): 4s and 2s as in round 2 (A/B runs)
     if (n >= 4096)
         while (m % 16 == 0) { push(16); m /= 16; }
-    if (fat)
+    if (radix8)
         while (m % 8 == 0) { push(8); m /= 8; }
     while (m % 4 == 0) { push(4); m /= 4; }
-    if (fat && m % 2 == 0 && m % 3 == 0) { push(6); m /= 6; }
-    if (fat && m % 2 == 0 && m % 5 == 0) { push(10); m /= 10; }
+    if (radix8 && m % 2 == 0 && m % 3 == 0) { push(6); m /= 6; }
+    if (radix8 && m % 2 == 0 && m % 5 == 0) { push(10); m /= 10; }
     for (int q : {2, 3, 5, 7, 11, 13})
         while (m % q == 0) { push(q); m /= q; }
     return cnt <= 16 ? cnt : -1;
@@ -1570,9 +1543,8 @@ int pfb_lds_plan(int n, int *radices) {
 // same box, per 1 M-sample buffer: 256 points 10.1 against 10.3 us, 512: 10.2 / 10.8, 1024: 10.7 / 12.2, 2048:
 // 10.4 / 11.9; 16 points 9.9 against 9.4 and 64 points equal: short frames stay a frame set per workgroup
 // (profiles/r03_pfb_ab_direct.log).  GSDR_PFB_DIRECT=0 switches the direct filter off, and this rule with it.
-static bool pfb_cu_direct_pays(int nfft, int avg) {
-    const int direct_env = env_direct.get();
-    return direct_env && avg >= 1 && avg <= 4 && nfft >= 128;
+static bool pfb_cu_direct_pays(int nfft, int avg, const Switches &sw) {
+    return sw.pfb_direct && avg >= 1 && avg <= 4 && nfft >= 128;
 }
 
 // Shape of the run-per-compute-unit kernel for frames of nfft points transformed at length `len` (nfft, or
@@ -1615,113 +1587,128 @@ static double pfb_cu_fill(int nfft, int avg, int len, int frames_n, int cus) {
     const long long blocks = (frames_n + G - 1) / G, rounds = (blocks + cus - 1) / cus;
     return (double)frames_n / ((double)G * cus * rounds);
 }
-static bool pfb_cu_has_big_prime(int nfft) {
-    int r[16];
-    const int nr = pfb_lds_plan(nfft, r);
-    return nr > 0 && r[0] > 13;
-}
 
-bool pfb_cu_fits(int nfft, int avg, int len) {
+bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw) {
     int G, bo, bl, twl;
     size_t bytes;
     if (!(nfft >= 1 && avg >= 1 && len >= nfft && len <= kPfbLdsMaxN)) return false;
     if (pfb_cu_shape(nfft, avg, len, 1, G, bo, bl, twl, bytes)) return true;
     // the direct filter keeps no raw samples in the LDS: a frame of up to four columns per thread fits without them
-    return pfb_cu_direct_pays(nfft, avg) && nfft <= 4 * kPfbCuThreads &&
+    return pfb_cu_direct_pays(nfft, avg, sw) && nfft <= 4 * kPfbCuThreads &&
            pfb_cu_shape(nfft, avg, len, 1, G, bo, bl, twl, bytes, kPfbCuThreads, kPfbCuMaxBytes, false);
 }
 
-static hipError_t launch_pfb_cu(const float2 *carry, int new_0, const float2 *in, const float *window, const float2 *tw,
-                                int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
-                                float2 *carry_out, int spare_begin, int spare_n, const FftPlan *blue, hipStream_t st,
-                                bool &taken) {
-    taken = false;
-    PfbCuArgs a{};
-    const int len = blue ? blue->m : nfft;
-    if (blue) {
-        if (blue->n != nfft || blue->m < 2 * nfft - 1 || blue->n_radices > 16 || !blue->d_chirp || !blue->d_bhat)
-            return hipErrorInvalidValue;
-        a.n_radices = blue->n_radices;
-        for (int i = 0; i < a.n_radices; ++i) a.radices[i] = blue->radices[i];
-    } else {
-        a.n_radices = pfb_lds_plan(nfft, a.radices);
-        if (a.n_radices < 0) return hipSuccess;            // not this kernel's length
-    }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
-    static std::atomic<int> cu_count[64];
-    if (cu_count[dev].load() == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        cu_count[dev].store(cus);
-    }
-    cus = cu_count[dev].load();
+// The run kernel's shape for a call of frames_n frames; false when it does not take the call.  radices: the stages
+// of the transform (of length len: nfft, or Bluestein's m when blue).
+static bool pfb_cu_choose(PfbChoice &c, int nfft, int avg, int len, bool blue, int n_radices, const int *radices,
+                          int frames_n, int n_out, int cus, const Switches &sw) {
     // one workgroup per compute unit: G consecutive frames each (frames_n == 0: a launch that only copies the carry)
-    int want = frames_n > 0 ? (frames_n + cus - 1) / cus : 1;
-    size_t lds = 0;
-    if (n_out > nfft) return hipSuccess;                  // the bin table in the LDS is sized for n_out <= nfft
+    const int want = frames_n > 0 ? (frames_n + cus - 1) / cus : 1;
+    if (n_out > nfft) return false;                       // the bin table in the LDS is sized for n_out <= nfft
+    const bool big_prime = n_radices > 0 && radices[0] > 13;
     // the direct filter's variant for G frames on `threads` threads: 0 = none
     // (GSDR_PFB_DIRECT=0: staged through the LDS; GSDR_PFB_COL=0/1, GSDR_PFB_CU_NT=512/1024: A/B runs)
-    const int direct_env = env_direct.get();
-    const int col_env = env_col.get() < 0 ? -1 : (env_col.get() != 0);
-    const int nt_env = env_cu_nt.get();
     auto direct_variant = [&](int G, int threads, int &dir_s, int &dir_gs) {
         const int cpt = (nfft + threads - 1) / threads;
         dir_s = cpt == 1 ? threads / nfft : 1;             // groups of threads (frames shorter than the workgroup)
         dir_gs = (G + dir_s - 1) / dir_s;                  // frames per group
         const int nb = dir_gs + 3;                         // (the register shapes are those of four taps)
-        if (avg < 1 || avg > 4 || !direct_env) return 0;
+        if (avg < 1 || avg > 4 || !sw.pfb_direct) return 0;
         if (cpt == 1 && nb <= 11) return dir_s > 1 ? 4 : 1;
         if (cpt <= 2 && nb <= 7) return 2;
         if (cpt <= 3 && nb <= 5) return 5;
         if (cpt <= 4 && nb <= 4) return 3;
         return 0;
     };
-    int threads = kPfbCuThreads;
-    a.direct = 0;
+    c.threads = kPfbCuThreads;
     // two workgroups of 512 threads per unit, half the frames each, when the direct filter takes them -- for frames
     // below 1024 points without a matrix-core stage: same box, 128 ... 512 points 9.7 - 10.0 against 10.2 - 10.3 us,
     // 1000: 12.4 / 12.9; from 1024 points on the full workgroup wins (1024: 10.9 against 11.2, 2048: 10.5 / 11.9,
     // and the matrix-core stage wants its sixteen waves: 1230: 13.5 / 17.0), profiles/r03_pfb_ab_nt.log
-    const bool half_pays = nt_env == 512 || (nt_env == 0 && nfft < 1024 && !(a.n_radices > 0 && a.radices[0] > 13));
-    if (half_pays && avg >= 1 && avg <= 4 && direct_env) {
+    const bool half_pays = sw.pfb_cu_nt == 512 || (sw.pfb_cu_nt == 0 && nfft < 1024 && !big_prime);
+    if (half_pays && avg >= 1 && avg <= 4 && sw.pfb_direct) {
         const int want2 = frames_n > 0 ? (frames_n + 2 * cus - 1) / (2 * cus) : 1;
         int G2 = 0, bo = 0, bl = 0, twl2 = 0, ds = 1, dg = 1;
         size_t lds2 = 0;
         if (pfb_cu_shape(nfft, avg, len, want2, G2, bo, bl, twl2, lds2, 512, kPfbCuMaxBytes / 2, false)) {
             const int v = direct_variant(G2, 512, ds, dg);
             if (v) {
-                threads = 512;
-                a.G = G2; a.b_off = bo; a.b_len = bl; a.twl = twl2; lds = lds2;
-                a.direct = v; a.dir_s = ds; a.dir_gs = dg; a.col = 1;
+                c.threads = 512;
+                c.G = G2; c.b_off = bo; c.b_len = bl; c.twl = twl2; c.lds = lds2;
+                c.direct = v; c.dir_s = ds; c.dir_gs = dg; c.col = 1;
             }
         }
     }
-    if (threads == kPfbCuThreads) {
-        if (pfb_cu_shape(nfft, avg, len, want, a.G, a.b_off, a.b_len, a.twl, lds)) {
+    if (c.threads == kPfbCuThreads) {
+        if (pfb_cu_shape(nfft, avg, len, want, c.G, c.b_off, c.b_len, c.twl, c.lds)) {
             // column-wise filter: four taps, and enough columns for every thread
-            a.col = avg == 4 && (col_env < 0 ? nfft >= kPfbCuThreads / 2 : col_env == 1);
-            a.direct = direct_variant(a.G, kPfbCuThreads, a.dir_s, a.dir_gs);
+            c.col = avg == 4 && (sw.pfb_col < 0 ? nfft >= kPfbCuThreads / 2 : sw.pfb_col == 1);
+            c.direct = direct_variant(c.G, kPfbCuThreads, c.dir_s, c.dir_gs);
         } else {
             // no room for the raw samples of a run: the direct filter needs none (4096 points: a frame per unit)
-            if (!pfb_cu_shape(nfft, avg, len, want, a.G, a.b_off, a.b_len, a.twl, lds, kPfbCuThreads, kPfbCuMaxBytes, false))
-                return hipSuccess;                         // does not fit: the caller's other kernel
-            a.col = 1;
-            while (a.G >= 1 && !(a.direct = direct_variant(a.G, kPfbCuThreads, a.dir_s, a.dir_gs))) --a.G;
-            if (a.G < 1) return hipSuccess;
+            if (!pfb_cu_shape(nfft, avg, len, want, c.G, c.b_off, c.b_len, c.twl, c.lds, kPfbCuThreads, kPfbCuMaxBytes, false))
+                return false;                              // does not fit: the other kernel
+            c.col = 1;
+            while (c.G >= 1 && !(c.direct = direct_variant(c.G, kPfbCuThreads, c.dir_s, c.dir_gs))) --c.G;
+            if (c.G < 1) return false;
         }
     }
-    {
-        const bool cu_forced = env_cu.get() == 1;
-        if (!blue && !cu_forced && threads == kPfbCuThreads && !(a.n_radices > 0 && a.radices[0] > 13) &&
-            pfb_cu_fill(nfft, avg, len, frames_n, cus) < 0.7)
-            return hipSuccess;                             // the frame-per-workgroup kernel fills the chip better
+    if (!blue && sw.pfb_cu != 1 && c.threads == kPfbCuThreads && !big_prime && pfb_cu_fill(nfft, avg, len, frames_n, cus) < 0.7)
+        return false;                                      // the frame-per-workgroup kernel fills the chip better
+    // teams: the frames of a run go through their stages independently (GSDR_PFB_TEAMS=0: all waves in step)
+    bool plain = !blue && n_radices > 0;
+    for (int i = 0; i < n_radices; ++i) plain = plain && radices[i] <= 16;
+    c.teams = plain && sw.pfb_teams && c.G >= 2 && c.threads % c.G == 0 && (c.threads / c.G) % 64 == 0;
+    c.cu = true;
+    return true;
+}
+
+PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n_out, int cus, const Switches &sw) {
+    PfbChoice c{};
+    int r[16];
+    const int nr = pfb_lds_plan(nfft, r, sw.pfb_radix8);
+    // A run of frames per compute unit (round 3) when the run fits the LDS and the length has a stage other than
+    // radix 2 / 4 / 8 / 16 -- a prime above 13 (its stage runs on the matrix cores there), 3, 5, 7 ... --, goes
+    // through Bluestein, or has four taps and at least 128 points (the direct filter, pfb_cu_direct_pays()).
+    // Measured per 1 M-sample buffer (profiles/r03_pfb_sweep.log): 1230 points 19.7 -> 13.1 us, 1016: 21.5 -> 13.5,
+    // 1024: 12.6 -> 10.9.  GSDR_PFB_CU=0 / 1 forces.
+    const int cu_mode = sw.pfb_cu < 0 ? -1 : (sw.pfb_cu != 0);
+    bool cu_wanted = cu_mode == 1 || blue != nullptr;
+    if (cu_mode < 0 && !blue) {
+        for (int i = 0; i < nr; ++i) cu_wanted |= (r[i] != 4 && r[i] != 2 && r[i] != 16 && r[i] != 8);
+        cu_wanted |= pfb_cu_direct_pays(nfft, avg, sw);
     }
-    {
-        // teams: the frames of a run go through their stages independently (GSDR_PFB_TEAMS=0: all waves in step)
-        bool plain = !blue && a.n_radices > 0;
-        for (int i = 0; i < a.n_radices; ++i) plain = plain && a.radices[i] <= 16;
-        a.teams = plain && env_teams.get() != 0 && a.G >= 2 && threads % a.G == 0 && (threads / a.G) % 64 == 0;
+    if (cu_wanted && (blue ? pfb_cu_choose(c, nfft, avg, blue->m, true, blue->n_radices, blue->radices, frames_n, n_out, cus, sw)
+                           : nr >= 0 && pfb_cu_choose(c, nfft, avg, nfft, false, nr, r, frames_n, n_out, cus, sw)))
+        return c;
+    // a frame set per workgroup: short frames share one, at least ~1024 points of work per workgroup; GSDR_PFB_FR sets
+    // the frames, GSDR_PFB_WIDE the 512 threads per frame (A/B runs)
+    c = PfbChoice{};
+    c.G = nfft >= 1024 ? 1 : (1024 + nfft - 1) / nfft;
+    if (sw.pfb_fr > 0 && (long long)sw.pfb_fr * nfft <= 4096) c.G = sw.pfb_fr;
+    if (c.G > 64) c.G = 64;
+    c.twl = nfft <= kPfbLdsTwMaxN;
+    c.threads = (sw.pfb_wide >= 0 ? sw.pfb_wide != 0 : nfft >= 2048) ? 512 : 256;
+    c.lds = ((size_t)2 * c.G * nfft + kPfbLdsMaxPrime + 1 + (c.twl ? nfft : 0)) * sizeof(float2);   // two frame sets + roots (+ twiddles)
+    return c;
+}
+
+const char *pfb_kernel_name(const PfbChoice &c) { return c.cu ? "pfb_cu_kernel" : "pfb_lds_kernel"; }
+
+static hipError_t launch_pfb_cu(const PfbChoice &c, const float2 *carry, int new_0, const float2 *in, const float *window,
+                                const float2 *tw, int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
+                                float2 *carry_out, int spare_begin, int spare_n, const FftPlan *blue, bool radix8, int dev,
+                                hipStream_t st, const char **kernel) {
+    PfbCuArgs a{};
+    const int len = blue ? blue->m : nfft;
+    if (blue) {
+        a.n_radices = blue->n_radices;
+        for (int i = 0; i < a.n_radices; ++i) a.radices[i] = blue->radices[i];
+    } else {
+        a.n_radices = pfb_lds_plan(nfft, a.radices, radix8);
     }
+    a.G = c.G; a.b_off = c.b_off; a.b_len = c.b_len; a.twl = c.twl;
+    a.col = c.col; a.direct = c.direct; a.dir_s = c.dir_s; a.dir_gs = c.dir_gs; a.teams = c.teams;
     a.carry = carry; a.in = in; a.window = window; a.tw = tw; a.sel = sel; a.out = out; a.carry_out = carry_out;
     a.chirp = blue ? blue->d_chirp : nullptr;
     a.bhat = blue ? blue->d_bhat : nullptr;
@@ -1749,7 +1736,6 @@ static hipError_t launch_pfb_cu(const float2 *carry, int new_0, const float2 *in
     }
     a.blocks_per_xcd = (a.main_blocks + 7u) / 8u;
     const unsigned spare_blocks = (unsigned)((spare_n + 2047) / 2048);
-    taken = true;
     if (a.main_blocks + spare_blocks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{0};
     if (!(attr_done.load() >> dev & 1ULL)) {
@@ -1761,62 +1747,47 @@ static hipError_t launch_pfb_cu(const float2 *carry, int new_0, const float2 *in
         attr_done.fetch_or(1ULL << dev);
     }
     void *kargs[] = {&a};
-    const void *fn = threads == 512 ? (a.twl ? reinterpret_cast<const void *>(pfb_cu_kernel<true, 512>) : reinterpret_cast<const void *>(pfb_cu_kernel<false, 512>))
-                                    : (a.twl ? reinterpret_cast<const void *>(pfb_cu_kernel<true, 1024>) : reinterpret_cast<const void *>(pfb_cu_kernel<false, 1024>));
-    return hipLaunchKernel(fn, dim3(a.blocks_per_xcd * 8u + spare_blocks), dim3(threads), kargs, lds, st);
+    const void *fn = c.threads == 512 ? (a.twl ? reinterpret_cast<const void *>(pfb_cu_kernel<true, 512>) : reinterpret_cast<const void *>(pfb_cu_kernel<false, 512>))
+                                      : (a.twl ? reinterpret_cast<const void *>(pfb_cu_kernel<true, 1024>) : reinterpret_cast<const void *>(pfb_cu_kernel<false, 1024>));
+    *kernel = pfb_kernel_name(c);
+    return hipLaunchKernel(fn, dim3(a.blocks_per_xcd * 8u + spare_blocks), dim3(c.threads), kargs, c.lds, st);
 }
 
 hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, const float *window, const float2 *tw,
                           int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
                           float2 *carry_out, int spare_begin, int spare_n, long long window_len, hipStream_t st,
-                          const FftPlan *blue) {
+                          const FftPlan *blue, const Switches &sw, const char **kernel) {
     if (avg < 1 || frames_n < 0 || n_out < 1 || new_0 < 0 || spare_n < 0 || spare_begin < 0 || nfft < 1 ||
         !in || !window || !tw || !out || (new_0 > 0 && !carry) || (spare_n > 0 && !carry_out) || (!sel && n_out != nfft))
         return hipErrorInvalidValue;
-    // every read stays inside the logical window [carry | in]
+    // every read stays inside the logical window [carry | in]; 32-bit window positions in the kernels
     if ((frames_n > 0 && (long long)(frames_n + avg - 1) * nfft > window_len) ||
         (long long)spare_begin + spare_n > window_len || new_0 > window_len || window_len > 0x7fffffffLL - nfft)
         return hipErrorInvalidValue;
-    // A run of frames per compute unit (round 3) when the run fits the LDS and the length has a stage other than
-    // radix 2 / 4 / 8 / 16 -- a prime above 13 (its stage runs on the matrix cores there), 3, 5, 7 ... --, goes
-    // through Bluestein, or has four taps and at least 128 points (the direct filter, pfb_cu_direct_pays()).
-    // Measured per 1 M-sample buffer (profiles/r03_pfb_sweep.log): 1230 points 19.7 -> 13.1 us, 1016: 21.5 -> 13.5,
-    // 1024: 12.6 -> 10.9.  GSDR_PFB_CU=0 / 1 forces.
-    const int cu_mode = env_cu.get() < 0 ? -1 : (env_cu.get() != 0);
-    bool cu_wanted = cu_mode == 1 || blue != nullptr;
-    if (cu_mode < 0 && !blue) {
-        int r[16];
-        const int nr = pfb_lds_plan(nfft, r);
-        for (int i = 0; i < nr; ++i) cu_wanted |= (r[i] != 4 && r[i] != 2 && r[i] != 16 && r[i] != 8);
-        cu_wanted |= pfb_cu_direct_pays(nfft, avg);
+    if (blue && (blue->n != nfft || blue->m < 2 * nfft - 1 || blue->n_radices > 16 || !blue->d_chirp || !blue->d_bhat))
+        return hipErrorInvalidValue;
+    // (a function attribute belongs to the device it was set on: once per device of this process)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
+    static std::atomic<int> cu_count[64];
+    if (cu_count[dev].load() == 0) {
+        int cus = 256;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        cu_count[dev].store(cus);
     }
-    if (cu_wanted) {
-        bool taken = false;
-        const hipError_t e = launch_pfb_cu(carry, new_0, in, window, tw, nfft, avg, frames_n, sel, n_out, out, carry_out,
-                                           spare_begin, spare_n, blue, st, taken);
-        if (e != hipSuccess || taken) return e;
-        if (blue) return hipErrorInvalidValue;             // only the run kernel knows Bluestein's identity
-    }
+    const PfbChoice c = pfb_choose(nfft, avg, blue, frames_n, n_out, cu_count[dev].load(), sw);
+    if (c.cu)
+        return launch_pfb_cu(c, carry, new_0, in, window, tw, nfft, avg, frames_n, sel, n_out, out, carry_out, spare_begin,
+                             spare_n, blue, sw.pfb_radix8, dev, st, kernel);
+    if (blue) return hipErrorInvalidValue;                 // only the run kernel knows Bluestein's identity
     PfbLdsArgs a{};
-    a.n_radices = pfb_lds_plan(nfft, a.radices);
-    if (a.n_radices < 0 || avg < 1 || frames_n < 0 || n_out < 1 || new_0 < 0 || spare_n < 0 || spare_begin < 0 ||
-        !in || !window || !tw || !out || (new_0 > 0 && !carry) || (spare_n > 0 && !carry_out) || (!sel && n_out != nfft))
-        return hipErrorInvalidValue;
-    // every read stays inside the logical window [carry | in]
-    if ((frames_n > 0 && (long long)(frames_n + avg - 1) * nfft > window_len) ||
-        (long long)spare_begin + spare_n > window_len || new_0 > window_len)
-        return hipErrorInvalidValue;
+    a.n_radices = pfb_lds_plan(nfft, a.radices, sw.pfb_radix8);
+    if (a.n_radices < 0) return hipErrorInvalidValue;
     a.carry = carry; a.in = in; a.window = window; a.tw = tw; a.sel = sel; a.out = out; a.carry_out = carry_out;
     a.n = nfft; a.F = avg; a.frames_n = frames_n; a.n_out = n_out; a.new_0 = new_0;
     a.spare_begin = spare_begin; a.spare_n = spare_n;
-    // short frames share a workgroup: at least ~1024 points of work per workgroup
-    a.FR = nfft >= 1024 ? 1 : (1024 + nfft - 1) / nfft;
-    const int fr_env = env_fr.get();      // A/B runs
-    const int wide_env = env_wide.get();
-    if (fr_env > 0 && (long long)fr_env * nfft <= 4096) a.FR = fr_env;
-    if (a.FR > 64) a.FR = 64;
+    a.FR = c.G;
     a.main_blocks = (unsigned)((frames_n + a.FR - 1) / a.FR);
-    if (window_len > 0x7fffffffLL - nfft) return hipErrorInvalidValue;     // 32-bit window positions in the kernel
     auto magic = [](long long d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / (unsigned long long)d + 1ULL); };
     a.mag_n = magic(nfft);
     a.mag_nout = magic(n_out);
@@ -1838,17 +1809,12 @@ hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, cons
     const unsigned spare_blocks = (unsigned)((spare_n + 2047) / 2048);
     if (a.main_blocks + spare_blocks == 0) return hipSuccess;
     const unsigned grid = a.blocks_per_xcd * 8u + spare_blocks;
-    const bool twl = nfft <= kPfbLdsTwMaxN;
-    const size_t lds = ((size_t)2 * a.FR * nfft + kPfbLdsMaxPrime + 1 + (twl ? nfft : 0)) * sizeof(float2);   // two frame sets + roots (+ twiddles)
-    // (a function attribute belongs to the device it was set on: once per device of this process)
     static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
-    const bool wide = wide_env >= 0 ? wide_env != 0 : nfft >= 2048;                      // 512 threads per frame
-    const void *fn = twl ? (wide ? reinterpret_cast<const void *>(pfb_lds_kernel<true, 512>)
-                                 : reinterpret_cast<const void *>(pfb_lds_kernel<true, 256>))
-                         : (wide ? reinterpret_cast<const void *>(pfb_lds_kernel<false, 512>)
-                                 : reinterpret_cast<const void *>(pfb_lds_kernel<false, 256>));
+    const bool wide = c.threads == 512;
+    const void *fn = c.twl ? (wide ? reinterpret_cast<const void *>(pfb_lds_kernel<true, 512>)
+                                   : reinterpret_cast<const void *>(pfb_lds_kernel<true, 256>))
+                           : (wide ? reinterpret_cast<const void *>(pfb_lds_kernel<false, 512>)
+                                   : reinterpret_cast<const void *>(pfb_lds_kernel<false, 256>));
     if (!(attr_done.load() >> dev & 1ULL)) {
         for (const void *f : {reinterpret_cast<const void *>(pfb_lds_kernel<true, 256>),
                               reinterpret_cast<const void *>(pfb_lds_kernel<true, 512>),
@@ -1859,30 +1825,10 @@ hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, cons
         }
         attr_done.fetch_or(1ULL << dev);
     }
-    if (lds > (size_t)kPfbLdsMaxBytes) return hipErrorInvalidValue;
+    if (c.lds > (size_t)kPfbLdsMaxBytes) return hipErrorInvalidValue;
     void *kargs[] = {&a};
-    return hipLaunchKernel(fn, dim3(grid), dim3(wide ? 512 : 256), kargs, lds, st);
-}
-
-const char *pfb_lds_kernel_name() { return "pfb_lds_kernel"; }
-const char *pfb_cu_kernel_name() { return "pfb_cu_kernel"; }
-// which of the two kernels launch_pfb_lds() runs for this shape (describe(), the profiler's name)
-bool pfb_cu_takes(int nfft, int avg, int len, bool bluestein, int frames_per_call) {
-    const int cu_mode = env_cu.get() < 0 ? -1 : (env_cu.get() != 0);
-    if (!bluestein) {
-        int r[16];
-        const int nr = pfb_lds_plan(nfft, r);
-        if (cu_mode == 0 || nr < 0) return false;
-        bool wanted = cu_mode == 1 || pfb_cu_direct_pays(nfft, avg);
-        for (int i = 0; i < nr; ++i) wanted |= (r[i] != 4 && r[i] != 2 && r[i] != 16 && r[i] != 8);
-        if (!wanted) return false;
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        if (cu_mode != 1 && nfft >= kPfbCuThreads && !pfb_cu_has_big_prime(nfft) && pfb_cu_fill(nfft, avg, len, frames_per_call, cus) < 0.7)
-            return false;
-    }
-    return pfb_cu_fits(nfft, avg, len);
+    *kernel = pfb_kernel_name(c);
+    return hipLaunchKernel(fn, dim3(grid), dim3(c.threads), kargs, c.lds, st);
 }
 
 const char *fft_kernel_name() { return "fft_pass_kernel"; }

@@ -145,15 +145,16 @@ int gsdr_abi_version(void);
  * (-DGSDR_TIMING_BUILD, scratch/ only) whose kernels can be told to skip work;
  * the shipped library is always 0 and bench.py refuses anything else. */
 const char *gsdr_build_info(void);
-/* Diagnostic: the GSDR_PFB_* environment switches (A/B runs, kernel variants in the tests) are read
- * once and cached -- a launch does not walk the environment.  This makes their next use read them again.  Handles
- * created earlier keep the kernel NAME they reported; which kernel a call runs follows the new values. */
+/* Does nothing.  The GSDR_* environment switches (A/B runs, kernel variants in the tests) are read
+ * when a handle is created, and the handle keeps them; set them before gsdr_demod_create().  Kept for callers
+ * built against older headers, where it made later launches read some of the switches again. */
 void gsdr_reload_env(void);
 /* One-line JSON object describing the engine this handle resolved to: mode,
- * dominant kernel, kernel family, row tiles per workgroup, pipeline streams,
- * and every GSDR_* environment variable that was set in the process (the
- * tuning knobs are read at create time).  Returns the text length (truncated
- * to cap-1 characters + NUL). */
+ * kernel (that of the last launch, see gsdr_demod_kernel_name), kernel family,
+ * row tiles per workgroup, pipeline streams, and every GSDR_* environment
+ * variable that is set in the process (the handle itself read the switches
+ * when it was created).  Returns the text length (truncated to cap-1
+ * characters + NUL). */
 int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap);
 /* gsdr_w_type actually dispatched (ref: USRP_demodulator.cpp:19-25,56). */
 int gsdr_demod_mode(const gsdr_demod *h);
@@ -178,7 +179,9 @@ void gsdr_demod_profile_enable(gsdr_demod *h, int enable);
 /* Synchronises the recorded events; returns the number of timed launches and
  * their summed duration in milliseconds. */
 int gsdr_demod_profile_read(gsdr_demod *h, double *total_ms);
-/* Name of the dominant kernel for the active mode (as rocprofv3 reports it). */
+/* Name of the kernel that carried the last call (as rocprofv3 reports it; the
+ * CHIRP lock-in reports chirp_lockin_kernel for all its variants); before the
+ * first call, the one a call of buffer_len samples runs. */
 const char *gsdr_demod_kernel_name(const gsdr_demod *h);
 
 /* ---- host-side pieces of the path (usable without a GPU) ---------------- */

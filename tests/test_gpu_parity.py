@@ -952,15 +952,13 @@ PFB_VARIANT_SHAPES = [
 @pytest.mark.parametrize("nfft,avg,L,nbuf", PFB_VARIANT_SHAPES, ids=lambda v: str(v))
 def test_noise_every_kernel_variant(cuda_device, gsdr_lib, oracle_mod, monkeypatch, nfft, avg, L, nbuf, env, kernel, what):
     """Every variant of the in-LDS TONES / NOISE kernels on the same inputs against the oracle:
-    the switches are the A/B switches of the library (GSDR_PFB_*), re-read through gsdr_reload_env().  The default
+    the switches are the A/B switches of the library (GSDR_PFB_*), read when the handle is created.  The default
     suite only sees the variant the library picks for a shape."""
     import gpu_sdr_amd as g
-    from gpu_sdr_amd import _lib
     for k in ("GSDR_PFB_CU", "GSDR_PFB_DIRECT", "GSDR_PFB_COL", "GSDR_PFB_CU_NT", "GSDR_PFB_RADIX8", "GSDR_PFB_TEAMS"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    _lib.lib().gsdr_reload_env()
     try:
         rng = np.random.default_rng(5200 + nfft)
         p = g.param(mode="RX", rate=1_000_000, buffer_len=L, decim=0, pf_average=avg, fft_tones=nfft,
@@ -990,7 +988,6 @@ def test_noise_every_kernel_variant(cuda_device, gsdr_lib, oracle_mod, monkeypat
     finally:
         for k in env:
             monkeypatch.delenv(k, raising=False)
-        _lib.lib().gsdr_reload_env()
 
 
 def test_noise_beyond_16384_bins(cuda_device, gsdr_lib):

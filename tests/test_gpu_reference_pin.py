@@ -86,12 +86,10 @@ def test_reference_fixture(cuda_device, gsdr_lib, mode, c, entry, engine):
 @pytest.mark.parametrize("mode,c", fixture_ids(["tones", "noise"]), ids=lambda v: str(v))
 def test_reference_fixture_pfb_variants(cuda_device, gsdr_lib, monkeypatch, mode, c, env, kernel, what):
     """The TONES / NOISE fixtures under every switch of test_noise_every_kernel_variant."""
-    from gpu_sdr_amd import _lib
     for k in [k for k in os.environ if k.startswith("GSDR_")]:
         monkeypatch.delenv(k)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    _lib.lib().gsdr_reload_env()
     try:
         g = load(mode)
         cfg = json.loads(str(g[f"c{c}_config"]))
@@ -99,7 +97,6 @@ def test_reference_fixture_pfb_variants(cuda_device, gsdr_lib, monkeypatch, mode
     finally:
         for k in env:
             monkeypatch.delenv(k, raising=False)
-        _lib.lib().gsdr_reload_env()
 
 
 @pytest.mark.parametrize("c", range(len(G.CASES["direct"])))

@@ -214,6 +214,36 @@ def test_no_cpu_fallback_in_product():
                 assert "gsdr_oracle" not in txt and "liboracle" not in txt, f
 
 
+def test_switches_are_read_only_by_the_reader():
+    """The GSDR_* switches are read from the environment in one place, gsdr::read_switches() (ddc_kernels.h), when a
+    handle is created: no other code of the library calls getenv, so no launch reads a switch and a handle reports
+    and runs what its own snapshot selects.  (Calls only: "GSDR_..." in an error text or a comment is fine.)"""
+    csrc = os.path.join(ROOT, "gpu_sdr_amd", "csrc")
+    # comments and string / character literals dropped, the code kept
+    lexeme = re.compile(r'"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'|//[^\n]*|/\*.*?\*/', re.S)
+    call = re.compile(r"\b(?:secure_)?getenv\s*\(")
+    reader_calls = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".cpp", ".hip", ".h", ".hpp")):
+            continue
+        code = lexeme.sub(lambda m: "\n" * m.group(0).count("\n") or " ", open(os.path.join(csrc, f)).read())
+        span = (0, 0)
+        d = re.search(r"\bread_switches\s*\(\s*\)\s*\{", code)
+        if d:
+            depth, i = 0, d.end() - 1
+            while True:
+                depth += {"{": 1, "}": -1}.get(code[i], 0)
+                if depth == 0:
+                    break
+                i += 1
+            span = (d.end(), i)
+        for m in call.finditer(code):
+            line = code.count("\n", 0, m.start()) + 1
+            assert span[0] <= m.start() < span[1], f"{f}:{line}: getenv outside gsdr::read_switches()"
+            reader_calls += 1
+    assert reader_calls >= 1
+
+
 @pytest.mark.parametrize("gen,header", [("gen_ddc_mfma_ring.py", "ddc_mfma_ring_gen.h"),
                                         ("gen_ddc_mfma_ring16.py", "ddc_mfma_ring16_gen.h"),
                                         ("gen_ddc_mfma_ring16w8.py", "ddc_mfma_ring16w8_gen.h"),
