@@ -23,12 +23,15 @@
 // four waves of a workgroup take four tone groups of the same rows, and workgroups of
 // the same rows sit on one XCD.
 //
-// One algorithm, five kernels (all parity-tested, tests/test_gpu_parity.py):
+// One algorithm, six kernels (all parity-tested, tests/test_gpu_parity.py):
 //   ddc_mfma_ring16_kernel    production: assembly main loop on v_mfma_f32_16x16x32_f16
 //                             (tools/gen_ddc_mfma_ring16.py), converted A operand shared by the four
 //                             waves through an LDS ring
 //   ddc_mfma_ring16p_kernel   the same loop fed with operands converted once per buffer by
 //                             ddc_convert_kernel (tools/gen_ddc_mfma_ring16p.py): long launches, streams
+//   ddc_mfma_ring16p3_kernel  the pre-converted loop with three real products per complex multiply
+//                             (tools/gen_ddc_mfma_ring16p3.py, fed by ddc_convert3_kernel; tests/test_gpu_mfma3.py):
+//                             36 instead of 48 MFMAs per block, a property of the handle (GSDR_MFMA_3M)
 //   ddc_mfma_ring16w8_kernel  the same loop for workgroups of eight waves
 //                             (tools/gen_ddc_mfma_ring16w8.py): single launches of one round
 //   ddc_mfma_ring_kernel      round 1's production kernel, the ring loop on v_mfma_f32_32x32x16_f16
@@ -47,6 +50,7 @@
 #include "ddc_mfma_ring16_gen.h"
 #include "ddc_mfma_ring16w8_gen.h"
 #include "ddc_mfma_ring16p_gen.h"
+#include "ddc_mfma_ring16p3_gen.h"
 
 namespace gsdr {
 
@@ -919,6 +923,131 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     ring16p_tile(a, lds, gt0, 1, tg, wave, active);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Three real products per complex multiply (tools/gen_ddc_mfma_ring16p3.py).
+// With x*h' = a + i*b and the phasor w = c + i*d:  K1 = sum (a+b)*c, K2 = sum a*(d-c), K3 = sum b*(c+d),
+// Re = K1 - K3, Im = K1 + K2: three real GEMMs over the 32 samples of a block (36 MFMAs) instead of two
+// over 64 interleaved components (48).  ddc_convert3_kernel writes the 12-KiB slot image of a (row tile,
+// block): piece 4*comp + 2*sp + rh of 1 KiB, comp 0 = a+b, 1 = a, 2 = b, sp 0 = fp16 hi, 1 = lo, lane l of a
+// piece = row 16*rh + (l & 15), samples 8*(l >> 4) .. +7 -- the order ds_read_b128 hands them to the MFMA.
+// a and b are the products of split_pair bit for bit; a+b is one fp32 add of the two (no contraction).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void split_one(float v, _Float16 &hi, _Float16 &lo) {
+#pragma clang fp contract(off)
+    hi = (_Float16)v;
+    lo = (_Float16)(v - (float)hi);
+}
+
+__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert3_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi) {
+    const MfmaShape &sh = a.sh;
+    const int l = threadIdx.x & 63, rh = threadIdx.x >> 6;
+    const int r = 16 * rh + (l & 15), g = l >> 4;
+    const int gt = blockIdx.x / nhi, blk = blockIdx.x - gt * nhi;
+    const int o = gt * 32 + r;
+    const float S = exp2_bits(row_scale_exp(a, o));
+    const int oc = o < sh.nout ? o : sh.nout - 1;
+    const float2 *xbase = gt == 0 ? a.head + sh.carry_len : (gt == sh.ngt - 1 ? a.tail - sh.tail0 : a.x);
+    const int k0 = blk * 32 + 8 * g;      // first of this lane's eight samples of the window
+    const float4u *px = reinterpret_cast<const float4u *>(xbase + ((long long)(oc + sh.woff) * sh.M + k0));
+    const float4v x0 = px[0], x1 = px[1], x2 = px[2], x3 = px[3];
+    const float4v h0 = *reinterpret_cast<const float4v *>(a.taps + k0) * S;
+    const float4v h1 = *reinterpret_cast<const float4v *>(a.taps + k0 + 4) * S;
+    const float xr[8] = {x0.x, x0.z, x1.x, x1.z, x2.x, x2.z, x3.x, x3.z};
+    const float xi[8] = {x0.y, x0.w, x1.y, x1.w, x2.y, x2.w, x3.y, x3.w};
+    const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+    half8 hi[3], lo[3];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma clang fp contract(off)
+        const float pa = mul_legacy(xr[j], hs[j]), pb = mul_legacy(xi[j], hs[j]);
+        const float ps = pa + pb;
+        _Float16 h, w;
+        split_one(ps, h, w);
+        hi[0][j] = h;
+        lo[0][j] = w;
+        split_one(pa, h, w);
+        hi[1][j] = h;
+        lo[1][j] = w;
+        split_one(pb, h, w);
+        hi[2][j] = h;
+        lo[2][j] = w;
+    }
+    uint4 *dst = img + (size_t)blockIdx.x * (GSDR_MFMA_RING16P3_SLOT / 16) + rh * 64 + l;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dst[(4 * c) * 64] = __builtin_bit_cast(uint4, hi[c]);
+        dst[(4 * c + 2) * 64] = __builtin_bit_cast(uint4, lo[c]);
+    }
+}
+
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3_tile(
+    const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
+    constexpr int KS = 4;
+    const MfmaShape &sh = a.sh;
+    const int Np = sh.NT32 * 32;
+    const int nhi = (sh.nk8 + KS - 1) / KS;
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = (int)(tid & 63u);
+    const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
+    const unsigned bo = (unsigned)tg * (12 * 1024u) + (unsigned)lane * 16u;
+    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
+    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
+    // this wave copies pieces 3*wave .. 3*wave + 2 of every image
+    const unsigned io0 = (unsigned)wave * 3072u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u;
+    const unsigned wrs = lds_base + (unsigned)wave * 3072u;
+    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P3_SLOT / 16)),
+                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
+    asm volatile(GSDR_MFMA_RING16P3_TEXT
+                 :
+                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),
+                   [accaddr] "v"(accaddr), [ib_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ibb)),
+                   [ib_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ibb >> 32))),
+                   [wrs] "s"(__builtin_amdgcn_readfirstlane((int)wrs)),
+                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
+                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
+                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
+                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
+                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 16u))),
+                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi))
+                 : GSDR_MFMA_RING16P3_CLOBBERS);
+    if (active) {
+        unsigned tid2 = threadIdx.x;
+        asm volatile("" : "+v"(tid2));
+        const int lane2 = (int)(tid2 & 63u);
+        float16v accr, acci;
+        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                accr[qd * 4 + j] = vr[j];
+                acci[qd * 4 + j] = vi[j];
+            }
+        }
+        store_tile16(a, gt, tg, lane2, kScaleFromTable, accr, acci);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3_kernel(
+    const MfmaLaunch a) {
+    constexpr int W = 4;
+    // ring (4 slots of 12 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P3_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P3_BYTES >= 4 * 8192, "the accumulators fit");
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int gt0 = (q / sh.ntq) * 8 + xcd;
+    if (gt0 >= sh.ngt) return;
+    const int tg_raw = (q % sh.ntq) * W + wave;
+    const bool active = tg_raw < sh.ntg;
+    const int tg = active ? tg_raw : sh.ntg - 1;
+    ring16p3_tile(a, lds, gt0, tg, wave, active);
+}
+
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
 // new buffer) or of region B (what the previous call left in front), a wave 512 of them: sixteen bytes per lane and
 // load, all four loads of a wave in flight at once -- one memory round trip per wave.  Maxima per segment:
@@ -1176,6 +1305,50 @@ void mfma_build_tables(const MfmaPlan &pl, const std::vector<unsigned> &fmod_in,
     for (int t = 0; t < pl.MF; ++t) taps[t] = std::ldexp(window[t], -eh);
 }
 
+// Tables of the three-product loop (ddc_mfma_ring16p3_kernel): per 32-tone tile twelve B images
+// f = (comp*2 + th)*2 + sp of c, (d-c), (c+d) -- w = c + i*d, formed in double, rounded once, split hi/lo;
+// lane l holds tone 16*th + (l & 15), element j <-> sample 8*(l >> 4) + j of the block -- and per (block, tone)
+// the block phasor as (Pr, Pi, Pr-Pi, Pr+Pi).  One row more than there are blocks: the loop loads the
+// phasors of a block while it computes the one before.
+void mfma_build_tables3(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                        std::vector<float4> &ptab3) {
+    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
+    const unsigned rate = pl.rate;
+    bfrag3.assign((size_t)tiles * 12 * 64, uint4{0, 0, 0, 0});
+    for (int T = 0; T < tiles; ++T)
+        for (int th = 0; th < 2; ++th)
+            for (int lane = 0; lane < 64; ++lane) {
+                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
+                unsigned short img[3][2][8];
+                for (int j = 0; j < 8; ++j) {
+                    const int lo = 8 * (lane >> 4) + j;
+                    double wr, wi;
+                    host_phasor((fm * (unsigned long long)lo) % rate, rate, wr, wi);
+                    const float v[3] = {(float)wr, (float)(wi - wr), (float)(wr + wi)};
+                    for (int c = 0; c < 3; ++c) {
+                        const unsigned short hb = to_half_bits(v[c]);
+                        img[c][0][j] = hb;
+                        img[c][1][j] = to_half_bits(v[c] - from_half_bits(hb));
+                    }
+                }
+                for (int c = 0; c < 3; ++c)
+                    for (int sp = 0; sp < 2; ++sp) {
+                        uint4 w;
+                        __builtin_memcpy(&w, img[c][sp], 16);
+                        const int f = (c * 2 + th) * 2 + sp;
+                        bfrag3[((size_t)T * 12 + f) * 64 + lane] = w;
+                    }
+            }
+    const int nhi = (pl.nk8 + 3) / 4;
+    ptab3.assign((size_t)(nhi + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int hi = 0; hi < nhi; ++hi)
+        for (int n = 0; n < Np; ++n) {
+            double re, im;
+            host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)hi * 32) % rate)) % rate, rate, re, im);
+            ptab3[(size_t)hi * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
+        }
+}
+
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
     if (!s.x || s.n < 1 || s.nb < 0 || (s.nb > 0 && !s.b) || s.carry_len < 0 || s.carry_len > s.n || s.head_n < 0 ||
         s.head_n > s.n || s.tail0 < 0 || s.tail0 > s.n || !s.seg || !s.seg_clear || s.seg_len < 64 ||
@@ -1227,6 +1400,20 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
         hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
         return hipGetLastError();
     }
+    if (kind == MfmaKernel::AsmRing16P3) {
+        // the three-product conversion pass, then its loop (a.img: ngt * nhi images of 12 KiB)
+        if (TT != 1 || PK != 32 || W != 4 || !a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
+        const int nhi = (sh.nk8 + 3) / 4;
+        const long long cgrid = (long long)sh.ngt * nhi;
+        const int gt8 = (sh.ngt + 7) / 8;
+        const long long grid = (long long)gt8 * 8 * sh.ntq;
+        if (cgrid < 1 || cgrid > 0x7fffffffLL || grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ddc_convert3_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, const_cast<uint4 *>(a.img), nhi);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
     if (kind == MfmaKernel::AsmRing16W8) {
         if (TT != 1 || PK != 32 || W != 4) return hipErrorInvalidValue;
         const int gt8 = (sh.ngt + 7) / 8;
@@ -1261,7 +1448,7 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
 }
 
 const char *ddc_mfma_kernel_name(MfmaKernel kind) {
-    return kind == MfmaKernel::AsmRing16P ? "ddc_mfma_ring16p_kernel" : kind == MfmaKernel::AsmRing16W8 ? "ddc_mfma_ring16w8_kernel" : kind == MfmaKernel::AsmRing16 ? "ddc_mfma_ring16_kernel" : kind == MfmaKernel::AsmRing ? "ddc_mfma_ring_kernel" : "ddc_mfma_kernel";
+    return kind == MfmaKernel::AsmRing16P || kind == MfmaKernel::AsmRing16P3 ? "ddc_mfma_ring16p_kernel" : kind == MfmaKernel::AsmRing16W8 ? "ddc_mfma_ring16w8_kernel" : kind == MfmaKernel::AsmRing16 ? "ddc_mfma_ring16_kernel" : kind == MfmaKernel::AsmRing ? "ddc_mfma_ring_kernel" : "ddc_mfma_kernel";
 }
 
 }  // namespace gsdr

@@ -74,6 +74,7 @@ gsdr::Switches gsdr::read_switches() {
     if (s.mfma_rt < 0 || s.mfma_rt > 2) s.mfma_rt = 0;
     s.mfma_w8 = env("GSDR_MFMA_W8", 1) != 0;
     s.mfma_prec = env("GSDR_MFMA_PREC", -1);
+    s.mfma_3m = env("GSDR_MFMA_3M", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -156,6 +157,11 @@ struct gsdr_demod {
     // rounds: one image set per staging set (the main kernels of the calls in flight read theirs)
     bool prec = false;                 // image sets allocated: the path may be chosen
     uint4 *d_img[kStageSets] = {};
+    // three real products per complex multiply (ddc_convert3_kernel + ddc_mfma_ring16p3_kernel, DESIGN.md section
+    // 4.1d): decided once, in setup_mfma; such a handle sends EVERY matrix-core launch through that pair
+    bool mac3 = false;
+    uint4 *d_bfrag3 = nullptr;
+    float4 *d_ptab3 = nullptr;
     uint4 *d_bfrag = nullptr;
     float2 *d_ptab = nullptr, *d_dtab = nullptr;
     float *d_mtaps = nullptr;
@@ -456,6 +462,17 @@ bool prec_pays(const gsdr_demod *h, long long ngt, bool overlap) {
            (h->sw.mfma_prec < 0 && (wgs4 >= 4LL * (h->simds / 2) || (overlap && wgs4 >= h->simds / 4 && nhi >= 32)));
 }
 
+// Three real products per complex multiply for a handle that has pre-converted images.
+// The three operands a+b, d-c, c+d carry sqrt(2) more quantisation noise than a, b, c, d; on the weakest tones of a
+// 60 dB comb that stays inside the project's rule (error <= max(1e-5, 3 x the reference's own fp32 error)) only
+// where the window is long enough to average it: kMac3MinBlocks is the shortest window, in 32-sample blocks, from
+// which test_gpu_mfma3.py::test_hdr_comb_sets_threshold measured the rule kept at every tested length.
+// GSDR_MFMA_3M: 1 = wherever there are images, 0 = never.
+constexpr long long kMac3MinBlocks = 94;
+bool mac3_chosen(const gsdr_demod *h, bool images, long long nhi) {
+    return images && (h->sw.mfma_3m == 1 || (h->sw.mfma_3m < 0 && nhi >= kMac3MinBlocks));
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
@@ -555,13 +572,22 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const long long ngt_max = (max_rows + 31) / 32;
         const long long nhi = (pl.nk8 + 3) / 4;
         bool want = prec_pays(h, ngt_max, /*overlap=*/true);
-        const size_t img_n = (size_t)ngt_max * (size_t)nhi * 512;   // uint4 per image set
+        const bool mac3 = mac3_chosen(h, want, nhi);
+        const size_t img_n = (size_t)ngt_max * (size_t)nhi * (mac3 ? 768 : 512);   // uint4 per image set: 12 / 8 KiB per block
         if (want && img_n * sizeof(uint4) > (size_t)8 << 30) want = false;
         for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, dev_alloc(&h->d_img[i], img_n));
         h->prec = want;
+        h->mac3 = want && mac3;
+        if (h->mac3) {
+            std::vector<uint4> bfrag3;
+            std::vector<float4> ptab3;
+            gsdr::mfma_build_tables3(pl, fmod, bfrag3, ptab3);
+            HIPCHK(h, upload(&h->d_bfrag3, bfrag3));
+            HIPCHK(h, upload(&h->d_ptab3, ptab3));
+        }
     }
     h->mfma = true;
-    h->kernel_name = gsdr::ddc_mfma_kernel_name(h->mf_kind);
+    h->kernel_name = gsdr::ddc_mfma_kernel_name(h->mac3 ? gsdr::MfmaKernel::AsmRing16P3 : h->mf_kind);
     return 0;
 }
 
@@ -718,6 +744,7 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     sg.seg_clear = h->d_segmax + (size_t)next * h->nseg_alloc;
     sg.nseg_alloc = h->nseg_alloc;
     sg.seg_len = (long long)h->seg_k * a.sh.M;
+    if (h->mac3) a.sh.rt = 1;       // one kernel pair for every launch of the handle
     if (a.sh.rt == 0) {
         // Two row tiles per workgroup (the second keeps the phasor images: 64 KiB less to load, one
         // preamble less, half as many workgroups).  Measured at decim 100 (13-block windows) for
@@ -786,7 +813,13 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     // partners), that kernel ends 4-7 % earlier (C3: 145 against 152-158 us).  The overlapped entries
     // keep the 4-wave kernel: there the next buffer's workgroups fill the slots the older ones free.
     gsdr::MfmaKernel kind = h->mf_kind;
-    if (kind == gsdr::MfmaKernel::AsmRing16 && h->prec && a.sh.rt <= 1 && prec_pays(h, a.sh.ngt, h->pipe_overlap)) {
+    if (h->mac3) {
+        // whatever the entry, the stream pattern or the row count: one arithmetic per handle
+        kind = gsdr::MfmaKernel::AsmRing16P3;
+        a.img = h->d_img[hs];
+        a.bfrag3 = h->d_bfrag3;
+        a.ptab3 = h->d_ptab3;
+    } else if (kind == gsdr::MfmaKernel::AsmRing16 && h->prec && a.sh.rt <= 1 && prec_pays(h, a.sh.ngt, h->pipe_overlap)) {
         kind = gsdr::MfmaKernel::AsmRing16P;
         a.img = h->d_img[hs];
     } else if (kind == gsdr::MfmaKernel::AsmRing16 && !h->pipe_overlap && h->sw.mfma_w8) {
@@ -1705,7 +1738,7 @@ void gsdr_demod_close(gsdr_demod *h) {
                     h->d_wrem,    h->d_fmod,    h->d_tails,    h->d_carry[0], h->d_carry[1],
                     h->d_profile, h->d_ccarry[0], h->d_ccarry[1],
                     h->d_bfrag,   h->d_ptab,    h->d_dtab,     h->d_mtaps,    h->d_mfmod,
-                    h->d_segmax};
+                    h->d_segmax,  h->d_bfrag3,  h->d_ptab3};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < kStageSets; ++i) {
@@ -1807,6 +1840,8 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
          h->noise_fft ? "fp32 Stockham FFT behind the polyphase filter" : h->mfma ? "f16 MFMA, hi/lo split" : (h->mode == GSDR_CHIRP ? "fp32 VALU, integer phase" : (h->pipe ? "packed fp32 VALU" : "fp32 VALU"));
     s += "\", \"channels\": " + std::to_string(h->ddc_channels > 0 ? h->ddc_channels : h->N);
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
+    s += ", \"complex_mac\": " + std::to_string(h->mfma && h->mac3 ? 3 : 4);
+    s += ", \"complex_mac_min_blocks\": " + std::to_string(kMac3MinBlocks);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"timing_build\": ";
 #ifdef GSDR_TIMING_BUILD

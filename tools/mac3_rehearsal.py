@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""CPU rehearsal of the matrix-core DDC arithmetic with four and with three real products per
+complex multiply, on the high-dynamic-range combs of
+tests/test_gpu_parity.py::test_direct_high_dynamic_range_comb (first buffer).
+
+Emulated, in numpy: one power-of-two scale per output row (row_scale_exp of csrc/ddc_mfma.hip), the
+tap product rounded to fp32, every MFMA operand split into fp16 hi + lo (three of the four
+cross products kept), exact products, one fp32 rounding per 32-sample block sum, the block phasor
+applied with fp32 FMAs, the row phasor in fp32.  Against oracle.Direct (fp64), with the reference's
+own fp32 order (oracle/recipe_b.py, complex64) beside it; bound = max(1e-5, 3 x err32) per tone.
+
+Reads nothing but oracle/ and gpu_sdr_amd/source.py.
+
+    python3 tools/mac3_rehearsal.py > profiles/mac3_rehearsal.log
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import oracle                                  # noqa: E402
+from oracle import recipe_b                    # noqa: E402
+from gpu_sdr_amd.source import host_tones      # noqa: E402
+
+f32, f64 = np.float32, np.float64
+
+
+def split(v):
+    """fp32 -> fp16 hi + fp16 lo (v_cvt_f16_f32 round to nearest even; residual formed in fp32)"""
+    v = v.astype(f32)
+    with np.errstate(over="ignore"):
+        hi = v.astype(np.float16)
+        lo = (v - hi.astype(f32)).astype(np.float16)
+    return hi.astype(f64), lo.astype(f64)
+
+
+def gemm3(a, b):
+    """sum over the block of hi*hi + hi*lo + lo*hi, products exact, one rounding to fp32"""
+    ah, al = split(a)
+    bh, bl = split(b)
+    return (ah @ bh + ah @ bl + al @ bh).astype(f32)
+
+
+def fma(acc, p, k):
+    return (acc.astype(f64) + p.astype(f64) * k.astype(f64)).astype(f32)
+
+
+def phasor(ph, rate):
+    ang = 2.0 * np.pi * (np.asarray(ph, dtype=f64) / rate)
+    return np.cos(ang), -np.sin(ang)
+
+
+def emulate(x, taps, freq, rate, M, F, products):
+    """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128"""
+    N, MF = len(freq), M * F
+    nout = len(x) // M
+    rows = np.arange(F - 1, nout)
+    nhi = (MF + 31) // 32
+    fm = np.mod(np.asarray(freq, dtype=np.int64), rate)
+    eh = int(np.frexp(np.abs(taps).max())[1])
+    hp = np.zeros(nhi * 32, dtype=f32)
+    hp[:MF] = np.ldexp(taps.astype(f32), -eh)
+    xp = np.concatenate([x, np.zeros(32, dtype=np.complex64)])
+    start = (rows - F + 1) * M
+    win = xp[start[:, None] + np.arange(nhi * 32)[None, :]]
+    inside = np.arange(nhi * 32) < MF
+    mx = np.maximum(np.abs(win.real), np.abs(win.imag))[:, inside].max(axis=1).astype(f32)
+    e = (mx.view(np.uint32) >> 23) & 0xff
+    se = np.clip(140 - e.astype(np.int64), -100, 100)
+    S = np.ldexp(f32(1), se).astype(f32)
+    hs = hp[None, :] * S[:, None]
+    a = np.where(inside[None, :], (win.real.astype(f32) * hs).astype(f32), f32(0))
+    b = np.where(inside[None, :], (win.imag.astype(f32) * hs).astype(f32), f32(0))
+    accr = np.zeros((len(rows), N), dtype=f32)
+    acci = np.zeros((len(rows), N), dtype=f32)
+    lo = np.arange(32, dtype=np.int64)
+    wr, wi = phasor((fm[None, :] * lo[:, None]) % rate, rate)            # [32][N]
+    c, d = wr.astype(f32), wi.astype(f32)
+    for blk in range(nhi):
+        ab, bb = a[:, 32 * blk: 32 * blk + 32], b[:, 32 * blk: 32 * blk + 32]
+        pr, pi = phasor((fm * ((blk * 32) % rate)) % rate, rate)
+        if products == 4:
+            re = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([c, -d], axis=0)))
+            im = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([d, c], axis=0)))
+            prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
+            accr = fma(fma(accr, prf, re), -pif, im)
+            acci = fma(fma(acci, prf, im), pif, re)
+        else:
+            k1 = gemm3((ab + bb).astype(f32), c)
+            k2 = gemm3(ab, (wi - wr).astype(f32))
+            k3 = gemm3(bb, (wr + wi).astype(f32))
+            prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
+            pm, pp = (pr - pi).astype(f32)[None, :], (pr + pi).astype(f32)[None, :]
+            accr = fma(fma(fma(accr, pm, k1), -pif, k2), -prf, k3)
+            acci = fma(fma(fma(acci, pp, k1), prf, k2), -pif, k3)
+    # row phasor w^(start of the window) / S * 2^eh, in fp32: tile phasor x row-in-tile phasor
+    gt, r = rows // 32, rows % 32
+    back = ((F - 1) * M) % rate
+    tile_ph = (fm[None, :] * ((gt * 32 * M + rate - back) % rate)[:, None]) % rate
+    br, bi = phasor(tile_ph, rate)
+    dr, di = phasor((fm[None, :] * ((r * M) % rate)[:, None]) % rate, rate)
+    inv = (np.ldexp(f32(1), -se) * f32(np.ldexp(1.0, eh))).astype(f32)[:, None]
+    br, bi, dr, di = br.astype(f32), bi.astype(f32), (dr.astype(f32) * inv).astype(f32), (di.astype(f32) * inv).astype(f32)
+    rr = (br * dr - bi * di).astype(f32)
+    ri = (br * di + bi * dr).astype(f32)
+    yr = (accr * rr - acci * ri).astype(f32)
+    yi = (accr * ri + acci * rr).astype(f32)
+    return yr.astype(f64) + 1j * yi.astype(f64)
+
+
+def comb(N, rate, L, span_db, rng):
+    freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
+    ampl = (10.0 ** (-np.linspace(0.0, span_db, N) / 20.0)).astype(np.float32)
+    phase = rng.uniform(0, 2 * np.pi, N).astype(np.float32)
+    return freq, host_tones(L, 0, rate, freq, ampl, phase, sigma=1e-5, seed=50)
+
+
+def main():
+    N, rate, F = 64, 200_000_000, 4
+    print("span_dB  M  blocks | err32 (reference fp32 order) | 4 products: worst err, worst err/bound | 3 products: worst err, worst err/bound | median, max per-tone ratio 3/4")
+    for span_db, decims in ((60, (2000, 1000, 750, 500, 375, 256, 100)), (40, (1000,))):
+        for M in decims:
+            n, rt = (32, 10_000_000) if M == 100 else (N, rate)
+            L = 1000 * M if M == 100 else 200 * M
+            freq, x = comb(n, rt, L, span_db, np.random.default_rng(4242 + span_db))
+            ref = oracle.Direct(freq, rt, M, F, L)
+            taps = ref.taps()
+            yr = ref.process(x).astype(np.complex128)[F:]
+            y32 = recipe_b.Direct(freq, rt, M, F, L, acc=np.complex64).process(x).astype(np.complex128)[F:]
+            den = np.linalg.norm(yr, axis=0)
+            err32 = np.linalg.norm(y32 - yr, axis=0) / den
+            bound = np.maximum(1e-5, 3.0 * err32)
+            errs = {}
+            for products in (4, 3):
+                y = emulate(x, taps, freq, rt, M, F, products)[1:]      # rows F .. as the test
+                errs[products] = np.linalg.norm(y - yr, axis=0) / den
+            ratio = errs[3] / errs[4]
+            print(f"{span_db:3d} {M:5d} {(M * F + 31) // 32:4d} | {err32.max():.3e} | {errs[4].max():.3e} {(errs[4] / bound).max():.3f} | "
+                  f"{errs[3].max():.3e} {(errs[3] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
