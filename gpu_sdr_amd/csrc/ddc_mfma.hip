@@ -32,6 +32,9 @@
 //   ddc_mfma_ring16p3_kernel  the pre-converted loop with three real products per complex multiply
 //                             (tools/gen_ddc_mfma_ring16p3.py, fed by ddc_convert3_kernel; tests/test_gpu_mfma3.py):
 //                             36 instead of 48 MFMAs per block, a property of the handle (GSDR_MFMA_3M)
+//   ddc_mfma_ring16p3r2_kernel  that loop with phasor images of 64 samples: the partial sums are rotated into the
+//                             accumulators once per pair of blocks (tools/gen_ddc_mfma_ring16p3r2.py,
+//                             tests/test_gpu_mfma3r2.py; GSDR_MFMA_3M_ROT)
 //   ddc_mfma_ring16w8_kernel  the same loop for workgroups of eight waves
 //                             (tools/gen_ddc_mfma_ring16w8.py): single launches of one round
 //   ddc_mfma_ring_kernel      round 1's production kernel, the ring loop on v_mfma_f32_32x32x16_f16
@@ -51,6 +54,7 @@
 #include "ddc_mfma_ring16w8_gen.h"
 #include "ddc_mfma_ring16p_gen.h"
 #include "ddc_mfma_ring16p3_gen.h"
+#include "ddc_mfma_ring16p3r2_gen.h"
 
 namespace gsdr {
 
@@ -1048,6 +1052,82 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     ring16p3_tile(a, lds, gt0, tg, wave, active);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The three-product loop with one rotation per PAIR of blocks (tools/gen_ddc_mfma_ring16p3r2.py, DESIGN.md section
+// 4.1e): 24 phasor images per 32-tone tile (samples 0..63) resident in 96 AGPRs, the second block of a pair
+// accumulates onto the first one's partial sums, P = w^(64*pair).  Same images (ddc_convert3_kernel), same ring,
+// same grid and epilogue as ddc_mfma_ring16p3_kernel; a.bfrag3 / a.ptab3 hold the tables of mfma_build_tables3r2.
+// ---------------------------------------------------------------------------------------------
+static_assert(GSDR_MFMA_RING16P3R2_SLOT == GSDR_MFMA_RING16P3_SLOT, "one image format for both three-product loops");
+
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3r2_tile(
+    const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
+    constexpr int KS = 4;
+    const MfmaShape &sh = a.sh;
+    const int Np = sh.NT32 * 32;
+    const int nhi = (sh.nk8 + KS - 1) / KS;
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = (int)(tid & 63u);
+    const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
+    const unsigned bo = (unsigned)tg * (24 * 1024u) + (unsigned)lane * 16u;
+    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
+    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
+    // this wave copies pieces 3*wave .. 3*wave + 2 of every image
+    const unsigned io0 = (unsigned)wave * 3072u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u;
+    const unsigned wrs = lds_base + (unsigned)wave * 3072u;
+    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P3R2_SLOT / 16)),
+                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
+    asm volatile(GSDR_MFMA_RING16P3R2_TEXT
+                 :
+                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),
+                   [accaddr] "v"(accaddr), [ib_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ibb)),
+                   [ib_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ibb >> 32))),
+                   [wrs] "s"(__builtin_amdgcn_readfirstlane((int)wrs)),
+                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
+                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
+                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
+                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
+                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 16u))),
+                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi))
+                 : GSDR_MFMA_RING16P3R2_CLOBBERS);
+    if (active) {
+        unsigned tid2 = threadIdx.x;
+        asm volatile("" : "+v"(tid2));
+        const int lane2 = (int)(tid2 & 63u);
+        float16v accr, acci;
+        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                accr[qd * 4 + j] = vr[j];
+                acci[qd * 4 + j] = vi[j];
+            }
+        }
+        store_tile16(a, gt, tg, lane2, kScaleFromTable, accr, acci);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3r2_kernel(
+    const MfmaLaunch a) {
+    constexpr int W = 4;
+    // ring (4 slots of 12 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P3R2_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P3R2_BYTES >= 4 * 8192, "the accumulators fit");
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int gt0 = (q / sh.ntq) * 8 + xcd;
+    if (gt0 >= sh.ngt) return;
+    const int tg_raw = (q % sh.ntq) * W + wave;
+    const bool active = tg_raw < sh.ntg;
+    const int tg = active ? tg_raw : sh.ntg - 1;
+    ring16p3r2_tile(a, lds, gt0, tg, wave, active);
+}
+
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
 // new buffer) or of region B (what the previous call left in front), a wave 512 of them: sixteen bytes per lane and
 // load, all four loads of a wave in flight at once -- one memory round trip per wave.  Maxima per segment:
@@ -1349,6 +1429,49 @@ void mfma_build_tables3(const MfmaPlan &pl, const std::vector<unsigned> &fmod, s
         }
 }
 
+// Tables of the pair-rotating three-product loop (ddc_mfma_ring16p3r2_kernel): the images of mfma_build_tables3 for
+// the 64 samples of a PAIR of blocks -- f = half*12 + (comp*2 + th)*2 + sp, element j of lane l <-> sample
+// 32*half + 8*(l >> 4) + j -- and the phasor of every pair, w_n^(64*pair), one row more than there are pairs.
+void mfma_build_tables3r2(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                          std::vector<float4> &ptab3) {
+    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
+    const unsigned rate = pl.rate;
+    bfrag3.assign((size_t)tiles * 24 * 64, uint4{0, 0, 0, 0});
+    for (int T = 0; T < tiles; ++T)
+        for (int half = 0; half < 2; ++half)
+            for (int th = 0; th < 2; ++th)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
+                    unsigned short img[3][2][8];
+                    for (int j = 0; j < 8; ++j) {
+                        const int lo = 32 * half + 8 * (lane >> 4) + j;
+                        double wr, wi;
+                        host_phasor((fm * (unsigned long long)lo) % rate, rate, wr, wi);
+                        const float v[3] = {(float)wr, (float)(wi - wr), (float)(wr + wi)};
+                        for (int c = 0; c < 3; ++c) {
+                            const unsigned short hb = to_half_bits(v[c]);
+                            img[c][0][j] = hb;
+                            img[c][1][j] = to_half_bits(v[c] - from_half_bits(hb));
+                        }
+                    }
+                    for (int c = 0; c < 3; ++c)
+                        for (int sp = 0; sp < 2; ++sp) {
+                            uint4 w;
+                            __builtin_memcpy(&w, img[c][sp], 16);
+                            const int f = half * 12 + (c * 2 + th) * 2 + sp;
+                            bfrag3[((size_t)T * 24 + f) * 64 + lane] = w;
+                        }
+                }
+    const int npair = ((pl.nk8 + 3) / 4 + 1) / 2;
+    ptab3.assign((size_t)(npair + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int p = 0; p < npair; ++p)
+        for (int n = 0; n < Np; ++n) {
+            double re, im;
+            host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)p * 64) % rate)) % rate, rate, re, im);
+            ptab3[(size_t)p * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
+        }
+}
+
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
     if (!s.x || s.n < 1 || s.nb < 0 || (s.nb > 0 && !s.b) || s.carry_len < 0 || s.carry_len > s.n || s.head_n < 0 ||
         s.head_n > s.n || s.tail0 < 0 || s.tail0 > s.n || !s.seg || !s.seg_clear || s.seg_len < 64 ||
@@ -1400,8 +1523,9 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
         hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
         return hipGetLastError();
     }
-    if (kind == MfmaKernel::AsmRing16P3) {
-        // the three-product conversion pass, then its loop (a.img: ngt * nhi images of 12 KiB)
+    if (kind == MfmaKernel::AsmRing16P3 || kind == MfmaKernel::AsmRing16P3R2) {
+        // the three-product conversion pass, then its loop (a.img: ngt * nhi images of 12 KiB), rotating per block
+        // or per pair of blocks: a.bfrag3 / a.ptab3 are the tables of that loop
         if (TT != 1 || PK != 32 || W != 4 || !a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
         const int nhi = (sh.nk8 + 3) / 4;
         const long long cgrid = (long long)sh.ngt * nhi;
@@ -1411,7 +1535,10 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
         hipLaunchKernelGGL(ddc_convert3_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, const_cast<uint4 *>(a.img), nhi);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+        if (kind == MfmaKernel::AsmRing16P3R2)
+            hipLaunchKernelGGL(ddc_mfma_ring16p3r2_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
         return hipGetLastError();
     }
     if (kind == MfmaKernel::AsmRing16W8) {
@@ -1448,7 +1575,7 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
 }
 
 const char *ddc_mfma_kernel_name(MfmaKernel kind) {
-    return kind == MfmaKernel::AsmRing16P || kind == MfmaKernel::AsmRing16P3 ? "ddc_mfma_ring16p_kernel" : kind == MfmaKernel::AsmRing16W8 ? "ddc_mfma_ring16w8_kernel" : kind == MfmaKernel::AsmRing16 ? "ddc_mfma_ring16_kernel" : kind == MfmaKernel::AsmRing ? "ddc_mfma_ring_kernel" : "ddc_mfma_kernel";
+    return kind == MfmaKernel::AsmRing16P || kind == MfmaKernel::AsmRing16P3 || kind == MfmaKernel::AsmRing16P3R2 ? "ddc_mfma_ring16p_kernel" : kind == MfmaKernel::AsmRing16W8 ? "ddc_mfma_ring16w8_kernel" : kind == MfmaKernel::AsmRing16 ? "ddc_mfma_ring16_kernel" : kind == MfmaKernel::AsmRing ? "ddc_mfma_ring_kernel" : "ddc_mfma_kernel";
 }
 
 }  // namespace gsdr

@@ -75,6 +75,7 @@ gsdr::Switches gsdr::read_switches() {
     s.mfma_w8 = env("GSDR_MFMA_W8", 1) != 0;
     s.mfma_prec = env("GSDR_MFMA_PREC", -1);
     s.mfma_3m = env("GSDR_MFMA_3M", -1);
+    s.mfma_3m_rot = env("GSDR_MFMA_3M_ROT", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -160,6 +161,7 @@ struct gsdr_demod {
     // three real products per complex multiply (ddc_convert3_kernel + ddc_mfma_ring16p3_kernel, DESIGN.md section
     // 4.1d): decided once, in setup_mfma; such a handle sends EVERY matrix-core launch through that pair
     bool mac3 = false;
+    bool rot2 = false;                 // ... through ddc_mfma_ring16p3r2_kernel: one rotation per pair of blocks (section 4.1e)
     uint4 *d_bfrag3 = nullptr;
     float4 *d_ptab3 = nullptr;
     uint4 *d_bfrag = nullptr;
@@ -473,6 +475,18 @@ bool mac3_chosen(const gsdr_demod *h, bool images, long long nhi) {
     return images && (h->sw.mfma_3m == 1 || (h->sw.mfma_3m < 0 && nhi >= kMac3MinBlocks));
 }
 
+// A three-product handle rotates its partial sums into the accumulators once per pair of blocks
+// (ddc_mfma_ring16p3r2_kernel) instead of once per block: half the rotation FMAs, phasor images
+// of 64 samples instead of 32, and fewer fp32 roundings at the size of the partial sums (one rotation stage per pair,
+// the small cross terms of the hi/lo split summed first).  kRot2MinBlocks is the shortest window from which
+// test_gpu_mfma3r2.py::test_hdr_comb_default_keeps_the_rule measured the rule of kMac3MinBlocks kept at every tested
+// length (err / bound 0.84, 0.78, 0.56 at 94, 125, 250 blocks; shorter windows were not measured and keep the
+// 32-sample loop).  GSDR_MFMA_3M_ROT: 2 = every three-product handle, 1 (or anything else) = never.
+constexpr long long kRot2MinBlocks = 94;
+bool rot2_chosen(const gsdr_demod *h, bool mac3, long long nhi) {
+    return mac3 && nhi >= 1 && (h->sw.mfma_3m_rot == 2 || (h->sw.mfma_3m_rot < 0 && nhi >= kRot2MinBlocks));
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
@@ -578,10 +592,14 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, dev_alloc(&h->d_img[i], img_n));
         h->prec = want;
         h->mac3 = want && mac3;
+        h->rot2 = rot2_chosen(h, h->mac3, nhi);
         if (h->mac3) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
-            gsdr::mfma_build_tables3(pl, fmod, bfrag3, ptab3);
+            if (h->rot2)
+                gsdr::mfma_build_tables3r2(pl, fmod, bfrag3, ptab3);
+            else
+                gsdr::mfma_build_tables3(pl, fmod, bfrag3, ptab3);
             HIPCHK(h, upload(&h->d_bfrag3, bfrag3));
             HIPCHK(h, upload(&h->d_ptab3, ptab3));
         }
@@ -815,7 +833,7 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     gsdr::MfmaKernel kind = h->mf_kind;
     if (h->mac3) {
         // whatever the entry, the stream pattern or the row count: one arithmetic per handle
-        kind = gsdr::MfmaKernel::AsmRing16P3;
+        kind = h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3;
         a.img = h->d_img[hs];
         a.bfrag3 = h->d_bfrag3;
         a.ptab3 = h->d_ptab3;
@@ -1842,6 +1860,8 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
     s += ", \"complex_mac\": " + std::to_string(h->mfma && h->mac3 ? 3 : 4);
     s += ", \"complex_mac_min_blocks\": " + std::to_string(kMac3MinBlocks);
+    s += ", \"rotation_blocks\": " + std::to_string(h->mfma && h->mac3 && h->rot2 ? 2 : 1);
+    s += ", \"rotation_min_blocks\": " + std::to_string(kRot2MinBlocks);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"timing_build\": ";
 #ifdef GSDR_TIMING_BUILD

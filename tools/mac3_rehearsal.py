@@ -9,9 +9,14 @@ cross products kept), exact products, one fp32 rounding per 32-sample block sum,
 applied with fp32 FMAs, the row phasor in fp32.  Against oracle.Direct (fp64), with the reference's
 own fp32 order (oracle/recipe_b.py, complex64) beside it; bound = max(1e-5, 3 x err32) per tone.
 
+--rot-span 64: the three-product arithmetic with the block sum taken over 64 samples (phasor images of 64 samples,
+one rotation per pair of blocks; the window padded with zero taps to whole pairs) beside the
+32-sample one, on the 60 dB comb at the three longest windows.
+
 Reads nothing but oracle/ and gpu_sdr_amd/source.py.
 
     python3 tools/mac3_rehearsal.py > profiles/mac3_rehearsal.log
+    python3 tools/mac3_rehearsal.py --rot-span 64 > profiles/mac3r2_rehearsal.log
 """
 import os
 import sys
@@ -53,20 +58,22 @@ def phasor(ph, rate):
     return np.cos(ang), -np.sin(ang)
 
 
-def emulate(x, taps, freq, rate, M, F, products):
-    """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128"""
+def emulate(x, taps, freq, rate, M, F, products, span=32):
+    """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128.
+    span: samples per block sum and rotation (64: the pair rotation of section 4.1e, three products only)"""
+    assert span == 32 or products == 3
     N, MF = len(freq), M * F
     nout = len(x) // M
     rows = np.arange(F - 1, nout)
-    nhi = (MF + 31) // 32
+    nhi = (MF + span - 1) // span
     fm = np.mod(np.asarray(freq, dtype=np.int64), rate)
     eh = int(np.frexp(np.abs(taps).max())[1])
-    hp = np.zeros(nhi * 32, dtype=f32)
+    hp = np.zeros(nhi * span, dtype=f32)
     hp[:MF] = np.ldexp(taps.astype(f32), -eh)
-    xp = np.concatenate([x, np.zeros(32, dtype=np.complex64)])
+    xp = np.concatenate([x, np.zeros(span, dtype=np.complex64)])
     start = (rows - F + 1) * M
-    win = xp[start[:, None] + np.arange(nhi * 32)[None, :]]
-    inside = np.arange(nhi * 32) < MF
+    win = xp[start[:, None] + np.arange(nhi * span)[None, :]]
+    inside = np.arange(nhi * span) < MF
     mx = np.maximum(np.abs(win.real), np.abs(win.imag))[:, inside].max(axis=1).astype(f32)
     e = (mx.view(np.uint32) >> 23) & 0xff
     se = np.clip(140 - e.astype(np.int64), -100, 100)
@@ -76,12 +83,12 @@ def emulate(x, taps, freq, rate, M, F, products):
     b = np.where(inside[None, :], (win.imag.astype(f32) * hs).astype(f32), f32(0))
     accr = np.zeros((len(rows), N), dtype=f32)
     acci = np.zeros((len(rows), N), dtype=f32)
-    lo = np.arange(32, dtype=np.int64)
-    wr, wi = phasor((fm[None, :] * lo[:, None]) % rate, rate)            # [32][N]
+    lo = np.arange(span, dtype=np.int64)
+    wr, wi = phasor((fm[None, :] * lo[:, None]) % rate, rate)            # [span][N]
     c, d = wr.astype(f32), wi.astype(f32)
     for blk in range(nhi):
-        ab, bb = a[:, 32 * blk: 32 * blk + 32], b[:, 32 * blk: 32 * blk + 32]
-        pr, pi = phasor((fm * ((blk * 32) % rate)) % rate, rate)
+        ab, bb = a[:, span * blk: span * blk + span], b[:, span * blk: span * blk + span]
+        pr, pi = phasor((fm * ((blk * span) % rate)) % rate, rate)
         if products == 4:
             re = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([c, -d], axis=0)))
             im = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([d, c], axis=0)))
@@ -118,7 +125,32 @@ def comb(N, rate, L, span_db, rng):
     return freq, host_tones(L, 0, rate, freq, ampl, phase, sigma=1e-5, seed=50)
 
 
+def main_span(span):
+    N, rate, F, span_db = 64, 200_000_000, 4, 60
+    print(f"span_dB  M  blocks | err32 (reference fp32 order) | 3 products, rotation per 32: worst err, worst err/bound | "
+          f"rotation per {span}: worst err, worst err/bound | median, max per-tone ratio {span}/32")
+    for M in (2000, 1000, 750):
+        L = 200 * M
+        freq, x = comb(N, rate, L, span_db, np.random.default_rng(4242 + span_db))
+        ref = oracle.Direct(freq, rate, M, F, L)
+        taps = ref.taps()
+        yr = ref.process(x).astype(np.complex128)[F:]
+        y32 = recipe_b.Direct(freq, rate, M, F, L, acc=np.complex64).process(x).astype(np.complex128)[F:]
+        den = np.linalg.norm(yr, axis=0)
+        err32 = np.linalg.norm(y32 - yr, axis=0) / den
+        bound = np.maximum(1e-5, 3.0 * err32)
+        errs = {}
+        for sp in (32, span):
+            y = emulate(x, taps, freq, rate, M, F, 3, span=sp)[1:]
+            errs[sp] = np.linalg.norm(y - yr, axis=0) / den
+        ratio = errs[span] / errs[32]
+        print(f"{span_db:3d} {M:5d} {(M * F + 31) // 32:4d} | {err32.max():.3e} | {errs[32].max():.3e} {(errs[32] / bound).max():.3f} | "
+              f"{errs[span].max():.3e} {(errs[span] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
+
+
 def main():
+    if "--rot-span" in sys.argv:
+        return main_span(int(sys.argv[sys.argv.index("--rot-span") + 1]))
     N, rate, F = 64, 200_000_000, 4
     print("span_dB  M  blocks | err32 (reference fp32 order) | 4 products: worst err, worst err/bound | 3 products: worst err, worst err/bound | median, max per-tone ratio 3/4")
     for span_db, decims in ((60, (2000, 1000, 750, 500, 375, 256, 100)), (40, (1000,))):
