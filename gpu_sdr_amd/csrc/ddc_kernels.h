@@ -154,7 +154,7 @@ struct MfmaLaunch {
     float2 *out;
     const uint4 *img;          // AsmRing16P: [ngt][nhi] pre-converted ring-slot images of 8 KiB (ddc_convert_kernel);
                                // AsmRing16P3: of 12 KiB (ddc_convert3_kernel)
-    const uint4 *bfrag3;       // AsmRing16P3: phasor images c, d-c, c+d, see mfma_build_tables3; AsmRing16P3R2: of mfma_build_tables3r2
+    const uint4 *bfrag3;       // AsmRing16P3 / AsmRing16P3R2: phasor images c, d-c, c+d of mfma_build_tables3, span 1 / 2
     const float4 *ptab3;       // AsmRing16P3: [ceil(nk8/4) + 1][NT32*32]  (Pr, Pi, Pr-Pi, Pr+Pi) of w_n^(hi*32);
                                // AsmRing16P3R2: [ceil(ceil(nk8/4) / 2) + 1][NT32*32] of w_n^(pair*64)
     MfmaShape sh;
@@ -171,10 +171,9 @@ void mfma_build_tables(const MfmaPlan &pl, const std::vector<unsigned> &fmod_in,
                        std::vector<uint4> &bfrag, std::vector<float2> &ptab,
                        std::vector<float2> &dtab, std::vector<float> &taps,
                        std::vector<unsigned> &fmod, float &unscale);
-void mfma_build_tables3(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+// span: blocks of 32 samples per rotation of the three-product loop, 1 (AsmRing16P3) or 2 (AsmRing16P3R2)
+void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                         std::vector<float4> &ptab3);
-void mfma_build_tables3r2(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
-                          std::vector<float4> &ptab3);
 // The staging pass in front of the matrix-core kernels.  The logical stream of a call is T = [B | A]: A the new
 // buffer x[0 .. n), B what the previous call left in front of it (DIRECT: the raw-sample carry, read from the head
 // copy the previous pass wrote; TONES: the unconsumed end of the previous raw window, copied to b_dst).  One pass
@@ -203,7 +202,7 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
 // AsmRing16 / AsmRing16P / AsmRing16W8: assembly main loops on the 16x16x32 MFMA (production, pre-converted
 // operands, eight-wave workgroups); AsmRing16P3: the pre-converted loop with three real products per complex
 // multiply (chosen per handle, demod.cpp), AsmRing16P3R2: that loop rotating its partial sums once per pair of
-// blocks (tables of mfma_build_tables3r2 in bfrag3 / ptab3); AsmRing: round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled
+// blocks (tables of mfma_build_tables3 with span 2 in bfrag3 / ptab3); AsmRing: round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled
 // (TT, PK, W apply to it only; the assembly kernels are TT = 1, PK = 32, W = 4).
 enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2 };
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);

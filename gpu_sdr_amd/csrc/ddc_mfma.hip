@@ -125,6 +125,18 @@ __device__ __forceinline__ unsigned lane_xor(unsigned v, int d) {
     return (unsigned)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)v);
 }
 
+// The thread id from a value the compiler cannot see through.  An assembly loop leaves the compiler twelve
+// registers of its own (v0..v11): what it would carry across the loop it would have to park in AGPRs, so everything
+// per lane is derived again, in front of the loop and behind it, from a fresh id.
+__device__ __forceinline__ unsigned fresh_tid() {
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    return tid;
+}
+// Scalar operands of the assembly loops: a wave-uniform value, and a 64-bit base as the pair NAME_lo / NAME_hi.
+#define GSDR_SGPR(v) "s"(__builtin_amdgcn_readfirstlane((int)(v)))
+#define GSDR_SGPR_PAIR(name, v) [name##_lo] GSDR_SGPR((unsigned)(v)), [name##_hi] GSDR_SGPR((unsigned)((v) >> 32))
+
 // Timing-only builds (WRONG results: no stores / one block only) exist for the ablation tables of
 // DESIGN.md only.  They are compiled in by -DGSDR_TIMING_BUILD (scratch/ablate*.sh); the shipped
 // library has no such path: the two predicates fold to false.
@@ -441,12 +453,7 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
     const int nhi = timing_one_block(sh) ? 1 : (sh.nk8 + KS - 1) / KS;
-    // Everything per lane is derived again for every tile, from an id the compiler cannot see
-    // through: it has twelve registers of its own across the assembly (v0..v11), and what it
-    // would carry over from the first tile it would have to park in AGPRs.
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int lane = (int)(tid & 63u);
+    const int lane = (int)(fresh_tid() & 63u);     // and so is everything per lane derived again for every tile
     const int r = lane & 31, hh = lane >> 5;
     const float S = exp2_bits(row_scale_exp(a, gt * 32 + r));   // this lane converts row r of the tile
     const unsigned to = (unsigned)((4 * hh + 8 * wave) * 4);
@@ -479,23 +486,12 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     asm volatile(GSDR_MFMA_RING_TEXT
                  :
                  : [xo] "v"(xo), [to] "v"(to), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(lane16), [wr16] "v"(wr16),
-                   [accaddr] "v"(accaddr), [xb_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)xb)),
-                   [xb_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(xb >> 32))),
-                   [tp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)tpb)),
-                   [tp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(tpb >> 32))),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 8u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi)),
-                   [first] "s"(__builtin_amdgcn_readfirstlane(first)),
-                   [scale] "v"(S)
+                   [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(xb, xb), GSDR_SGPR_PAIR(tp, tpb), GSDR_SGPR_PAIR(pp, ppb),
+                   GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 8u), [nhi] GSDR_SGPR(nhi),
+                   [first] GSDR_SGPR(first), [scale] "v"(S)
                  : GSDR_MFMA_RING_CLOBBERS);
     if (active && !timing_no_stores(sh)) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int lane2 = (int)(tid2 & 63u);
+        const int lane2 = (int)(fresh_tid() & 63u);
         const int se_self = row_scale_exp(a, gt * 32 + (lane2 & 31));   // again: nothing lives across the assembly
         float16v accr, acci;
         const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
@@ -608,14 +604,32 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void st
     }
 }
 
+// Behind every loop of the ring16 family: the wave's 32 x 32 accumulators come back from its 8 KiB of the LDS
+// (where the loop left them, real parts in the first four 1-KiB pieces, imaginary parts in the other four) and go
+// out through store_tile16.  lane: of a fresh_tid(); se_known: see store_tile16.
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16_epilogue(
+    const MfmaLaunch &a, const uint4 *lds, int gt, int tg, int wave, int lane, int se_known) {
+    float16v accr, acci;
+    const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane;
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            accr[qd * 4 + j] = vr[j];
+            acci[qd * 4 + j] = vi[j];
+        }
+    }
+    store_tile16(a, gt, tg, lane, se_known, accr, acci);
+}
+
 __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16_tile(
     const MfmaLaunch &a, uint4 *lds, unsigned *lds_scale, int gt, int first, int tg, int wave, bool active) {
     constexpr int KS = 4;
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
     const int nhi = timing_one_block(sh) ? 1 : (sh.nk8 + KS - 1) / KS;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
+    const unsigned tid = fresh_tid();
     const int lane = (int)(tid & 63u);
     const int r = lane & 31, hh = lane >> 5;
     // this lane converts row r of the tile: the segments of the maxima table its window covers (the loop's
@@ -658,39 +672,17 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     asm volatile(GSDR_MFMA_RING16_TEXT
                  :
                  : [xo] "v"(xo), [to] "v"(to), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16), [wr16] "v"(wr16),
-                   [accaddr] "v"(accaddr), [xb_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)xb)),
-                   [xb_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(xb >> 32))),
-                   [tp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)tpb)),
-                   [tp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(tpb >> 32))),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 8u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi)),
-                   [first] "s"(__builtin_amdgcn_readfirstlane(first)),
-                   [sgo] "v"(sgo), [sgn] "v"(sgn), [seaddr] "v"(seaddr),
-                   [sg_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)sgb)),
-                   [sg_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(sgb >> 32)))
+                   [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(xb, xb), GSDR_SGPR_PAIR(tp, tpb), GSDR_SGPR_PAIR(pp, ppb),
+                   GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 8u), [nhi] GSDR_SGPR(nhi),
+                   [first] GSDR_SGPR(first), [sgo] "v"(sgo), [sgn] "v"(sgn), [seaddr] "v"(seaddr),
+                   GSDR_SGPR_PAIR(sg, sgb)
                  : GSDR_MFMA_RING16_CLOBBERS);
     stamp(3);
     if (active && !timing_no_stores(sh)) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
+        const unsigned tid2 = fresh_tid();
         const int lane2 = (int)(tid2 & 63u);
-        const int se_self = (int)(lds_scale[tid2] >> 23) - 127;      // the bits of S = 2^se, left by the loop
-        float16v accr, acci;
-        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                accr[qd * 4 + j] = vr[j];
-                acci[qd * 4 + j] = vi[j];
-            }
-        }
-        store_tile16(a, gt, tg, lane2, se_self, accr, acci);
+        // the bits of S = 2^se, left by the loop
+        ring16_epilogue(a, lds, gt, tg, wave, lane2, (int)(lds_scale[tid2] >> 23) - 127);
     }
 }
 
@@ -754,8 +746,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((target("no-packed-fp32-ops")
     const int tg = active ? tg_raw : sh.ntg - 1;
     const int Np = sh.NT32 * 32;
     const int nhi = timing_one_block(sh) ? 1 : (sh.nk8 + KS - 1) / KS;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
+    const unsigned tid = fresh_tid();
     const int lane = (int)(tid & 63u);
     const int r = lane & 31, hh = lane >> 5;
     const int kw = wave & 3;                  // old k-step this wave converts (in its blocks)
@@ -793,24 +784,16 @@ __global__ __launch_bounds__(512, 2) __attribute__((target("no-packed-fp32-ops")
     asm volatile(GSDR_MFMA_RING16W8_TEXT
                  :
                  : [xo] "v"(xo), [to] "v"(to), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16), [wr16] "v"(wr16),
-                   [accaddr] "v"(accaddr), [xb_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)xb)),
-                   [xb_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(xb >> 32))),
-                   [tp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)tpb)),
-                   [tp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(tpb >> 32))),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 8u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi)),
-                   [role] "s"(__builtin_amdgcn_readfirstlane(wave >> 2)),
-                   [sgo] "v"(sgo), [sgn] "v"(sgn), [seaddr] "v"(seaddr),
-                   [sg_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)sgb)),
-                   [sg_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(sgb >> 32)))
+                   [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(xb, xb), GSDR_SGPR_PAIR(tp, tpb), GSDR_SGPR_PAIR(pp, ppb),
+                   GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 8u), [nhi] GSDR_SGPR(nhi),
+                   [role] GSDR_SGPR(wave >> 2), [sgo] "v"(sgo), [sgn] "v"(sgn), [seaddr] "v"(seaddr),
+                   GSDR_SGPR_PAIR(sg, sgb)
                  : GSDR_MFMA_RING16W8_CLOBBERS);
     if (active && !timing_no_stores(sh)) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
+        // ring16_epilogue, spelled out: here the read-back addresses the kernel's own array, and through the helper's
+        // pointer the compiler schedules and allocates the whole kernel differently (the other loops read back in
+        // their tile functions, which get `lds` as a pointer either way)
+        const unsigned tid2 = fresh_tid();
         const int lane2 = (int)(tid2 & 63u);
         const int se_self = (int)(lds_scale[tid2] >> 23) - 127;      // the bits of S = 2^se, left by the loop
         float16v accr, acci;
@@ -863,9 +846,7 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
     const int nhi = (sh.nk8 + KS - 1) / KS;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int lane = (int)(tid & 63u);
+    const int lane = (int)(fresh_tid() & 63u);
     const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 8u;
     const unsigned bo = (unsigned)tg * (KS * 4 * 1024u) + (unsigned)lane * 16u;
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
@@ -880,34 +861,11 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     asm volatile(GSDR_MFMA_RING16P_TEXT
                  :
                  : [io_hi] "v"(io_hi), [io_lo] "v"(io_lo), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),
-                   [accaddr] "v"(accaddr), [ib_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ibb)),
-                   [ib_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ibb >> 32))),
-                   [wrs] "s"(__builtin_amdgcn_readfirstlane((int)wrs)),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 8u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi)),
-                   [first] "s"(__builtin_amdgcn_readfirstlane(first))
+                   [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs), GSDR_SGPR_PAIR(pp, ppb),
+                   GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 8u), [nhi] GSDR_SGPR(nhi),
+                   [first] GSDR_SGPR(first)
                  : GSDR_MFMA_RING16P_CLOBBERS);
-    if (active) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int lane2 = (int)(tid2 & 63u);
-        float16v accr, acci;
-        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                accr[qd * 4 + j] = vr[j];
-                acci[qd * 4 + j] = vi[j];
-            }
-        }
-        store_tile16(a, gt, tg, lane2, kScaleFromTable, accr, acci);
-    }
+    if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p_kernel(
@@ -984,17 +942,24 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
     }
 }
 
+// The loop that rotates once per PAIR of blocks (tools/gen_ddc_mfma_ring16p3r2.py) is the
+// same tile with another asm statement: 24 phasor images per 32-tone tile (samples 0..63) resident in 96 AGPRs,
+// the second block of a pair accumulates onto the first one's partial sums, P = w^(64*pair).  Same images
+// (ddc_convert3_kernel), same ring, same grid and epilogue; a.bfrag3 / a.ptab3 hold the tables of
+// mfma_build_tables3 for a span of one block or of two.
+static_assert(GSDR_MFMA_RING16P3R2_SLOT == GSDR_MFMA_RING16P3_SLOT, "one image format for both three-product loops");
+
+template <bool kPairs>
 __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3_tile(
     const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
     constexpr int KS = 4;
+    constexpr unsigned kImages = kPairs ? 24 : 12;      // 1-KiB phasor images per 32-tone tile
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
     const int nhi = (sh.nk8 + KS - 1) / KS;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int lane = (int)(tid & 63u);
+    const int lane = (int)(fresh_tid() & 63u);
     const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
-    const unsigned bo = (unsigned)tg * (12 * 1024u) + (unsigned)lane * 16u;
+    const unsigned bo = (unsigned)tg * (kImages * 1024u) + (unsigned)lane * 16u;
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
     const unsigned rd16 = lds_base + (unsigned)lane * 16u;
     // this wave copies pieces 3*wave .. 3*wave + 2 of every image
@@ -1003,36 +968,16 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
     const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P3_SLOT / 16)),
                              ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
-    asm volatile(GSDR_MFMA_RING16P3_TEXT
-                 :
-                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),
-                   [accaddr] "v"(accaddr), [ib_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ibb)),
-                   [ib_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ibb >> 32))),
-                   [wrs] "s"(__builtin_amdgcn_readfirstlane((int)wrs)),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 16u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi))
-                 : GSDR_MFMA_RING16P3_CLOBBERS);
-    if (active) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int lane2 = (int)(tid2 & 63u);
-        float16v accr, acci;
-        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                accr[qd * 4 + j] = vr[j];
-                acci[qd * 4 + j] = vi[j];
-            }
-        }
-        store_tile16(a, gt, tg, lane2, kScaleFromTable, accr, acci);
-    }
+#define GSDR_RING16P3_OPERANDS                                                                                     \
+    [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),                \
+        [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs), GSDR_SGPR_PAIR(pp, ppb),            \
+        GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u), [nhi] GSDR_SGPR(nhi)
+    if constexpr (kPairs)
+        asm volatile(GSDR_MFMA_RING16P3R2_TEXT : : GSDR_RING16P3_OPERANDS : GSDR_MFMA_RING16P3R2_CLOBBERS);
+    else
+        asm volatile(GSDR_MFMA_RING16P3_TEXT : : GSDR_RING16P3_OPERANDS : GSDR_MFMA_RING16P3_CLOBBERS);
+#undef GSDR_RING16P3_OPERANDS
+    if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3_kernel(
@@ -1049,66 +994,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     const int tg_raw = (q % sh.ntq) * W + wave;
     const bool active = tg_raw < sh.ntg;
     const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3_tile(a, lds, gt0, tg, wave, active);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The three-product loop with one rotation per PAIR of blocks (tools/gen_ddc_mfma_ring16p3r2.py, DESIGN.md section
-// 4.1e): 24 phasor images per 32-tone tile (samples 0..63) resident in 96 AGPRs, the second block of a pair
-// accumulates onto the first one's partial sums, P = w^(64*pair).  Same images (ddc_convert3_kernel), same ring,
-// same grid and epilogue as ddc_mfma_ring16p3_kernel; a.bfrag3 / a.ptab3 hold the tables of mfma_build_tables3r2.
-// ---------------------------------------------------------------------------------------------
-static_assert(GSDR_MFMA_RING16P3R2_SLOT == GSDR_MFMA_RING16P3_SLOT, "one image format for both three-product loops");
-
-__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3r2_tile(
-    const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
-    constexpr int KS = 4;
-    const MfmaShape &sh = a.sh;
-    const int Np = sh.NT32 * 32;
-    const int nhi = (sh.nk8 + KS - 1) / KS;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int lane = (int)(tid & 63u);
-    const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
-    const unsigned bo = (unsigned)tg * (24 * 1024u) + (unsigned)lane * 16u;
-    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
-    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
-    // this wave copies pieces 3*wave .. 3*wave + 2 of every image
-    const unsigned io0 = (unsigned)wave * 3072u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u;
-    const unsigned wrs = lds_base + (unsigned)wave * 3072u;
-    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
-    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P3R2_SLOT / 16)),
-                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
-    asm volatile(GSDR_MFMA_RING16P3R2_TEXT
-                 :
-                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),
-                   [accaddr] "v"(accaddr), [ib_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ibb)),
-                   [ib_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ibb >> 32))),
-                   [wrs] "s"(__builtin_amdgcn_readfirstlane((int)wrs)),
-                   [pp_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)ppb)),
-                   [pp_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(ppb >> 32))),
-                   [bf_lo] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)bfb)),
-                   [bf_hi] "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(bfb >> 32))),
-                   [pstride] "s"(__builtin_amdgcn_readfirstlane((int)((unsigned)Np * 16u))),
-                   [nhi] "s"(__builtin_amdgcn_readfirstlane(nhi))
-                 : GSDR_MFMA_RING16P3R2_CLOBBERS);
-    if (active) {
-        unsigned tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int lane2 = (int)(tid2 & 63u);
-        float16v accr, acci;
-        const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                accr[qd * 4 + j] = vr[j];
-                acci[qd * 4 + j] = vi[j];
-            }
-        }
-        store_tile16(a, gt, tg, lane2, kScaleFromTable, accr, acci);
-    }
+    ring16p3_tile<false>(a, lds, gt0, tg, wave, active);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3r2_kernel(
@@ -1125,7 +1011,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     const int tg_raw = (q % sh.ntq) * W + wave;
     const bool active = tg_raw < sh.ntg;
     const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3r2_tile(a, lds, gt0, tg, wave, active);
+    ring16p3_tile<true>(a, lds, gt0, tg, wave, active);
 }
 
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
@@ -1270,12 +1156,19 @@ void host_phasor(unsigned long long ph, unsigned rate, double &re, double &im) {
     im = -std::sin(ang);
 }
 
+// Grid of a kernel whose workgroup blockIdx.x takes rt row tiles of XCD blockIdx.x % 8 (row tile gt belongs to XCD
+// gt % 8), `cols` workgroups to a row tile.  0: nothing to launch, or more workgroups than a grid holds.
+unsigned ring_grid(int ngt, int cols, int rt) {
+    const int gt8 = ((ngt + 7) / 8 + rt - 1) / rt;
+    const long long grid = (long long)gt8 * 8 * cols;
+    return grid < 1 || grid > 0x7fffffffLL ? 0u : (unsigned)grid;
+}
+
 template <int TT, int PK, int W>
 hipError_t launch_tpw(const MfmaLaunch &a, hipStream_t st) {
-    const int gt8 = (a.sh.ngt + 7) / 8;
-    const long long grid = (long long)gt8 * 8 * a.sh.ntq;
-    if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((ddc_mfma_kernel<TT, PK, W>), dim3((unsigned)grid), dim3(64 * W), 0, st, a);
+    const unsigned grid = ring_grid(a.sh.ngt, a.sh.ntq, 1);
+    if (!grid) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((ddc_mfma_kernel<TT, PK, W>), dim3(grid), dim3(64 * W), 0, st, a);
     return hipGetLastError();
 }
 
@@ -1385,60 +1278,20 @@ void mfma_build_tables(const MfmaPlan &pl, const std::vector<unsigned> &fmod_in,
     for (int t = 0; t < pl.MF; ++t) taps[t] = std::ldexp(window[t], -eh);
 }
 
-// Tables of the three-product loop (ddc_mfma_ring16p3_kernel): per 32-tone tile twelve B images
-// f = (comp*2 + th)*2 + sp of c, (d-c), (c+d) -- w = c + i*d, formed in double, rounded once, split hi/lo;
-// lane l holds tone 16*th + (l & 15), element j <-> sample 8*(l >> 4) + j of the block -- and per (block, tone)
-// the block phasor as (Pr, Pi, Pr-Pi, Pr+Pi).  One row more than there are blocks: the loop loads the
-// phasors of a block while it computes the one before.
-void mfma_build_tables3(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+// Tables of the three-product loops.  `span`: the blocks of 32 samples the loop rotates at a time, 1
+// (ddc_mfma_ring16p3_kernel) or 2 (ddc_mfma_ring16p3r2_kernel).  Per 32-tone tile 12 * span B images
+// f = half*12 + (comp*2 + th)*2 + sp of c, (d-c), (c+d) -- w = c + i*d, formed in double, rounded once, split hi/lo;
+// lane l holds tone 16*th + (l & 15), element j <-> sample 32*half + 8*(l >> 4) + j of the span -- and per (span, tone)
+// the phasor w_n^(32*span*row) as (Pr, Pi, Pr-Pi, Pr+Pi).  One row more than there are spans: the loop loads the
+// phasors of a span while it computes the one before.
+void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                         std::vector<float4> &ptab3) {
     const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
     const unsigned rate = pl.rate;
-    bfrag3.assign((size_t)tiles * 12 * 64, uint4{0, 0, 0, 0});
+    const int nimg = 12 * span;
+    bfrag3.assign((size_t)tiles * nimg * 64, uint4{0, 0, 0, 0});
     for (int T = 0; T < tiles; ++T)
-        for (int th = 0; th < 2; ++th)
-            for (int lane = 0; lane < 64; ++lane) {
-                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
-                unsigned short img[3][2][8];
-                for (int j = 0; j < 8; ++j) {
-                    const int lo = 8 * (lane >> 4) + j;
-                    double wr, wi;
-                    host_phasor((fm * (unsigned long long)lo) % rate, rate, wr, wi);
-                    const float v[3] = {(float)wr, (float)(wi - wr), (float)(wr + wi)};
-                    for (int c = 0; c < 3; ++c) {
-                        const unsigned short hb = to_half_bits(v[c]);
-                        img[c][0][j] = hb;
-                        img[c][1][j] = to_half_bits(v[c] - from_half_bits(hb));
-                    }
-                }
-                for (int c = 0; c < 3; ++c)
-                    for (int sp = 0; sp < 2; ++sp) {
-                        uint4 w;
-                        __builtin_memcpy(&w, img[c][sp], 16);
-                        const int f = (c * 2 + th) * 2 + sp;
-                        bfrag3[((size_t)T * 12 + f) * 64 + lane] = w;
-                    }
-            }
-    const int nhi = (pl.nk8 + 3) / 4;
-    ptab3.assign((size_t)(nhi + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int hi = 0; hi < nhi; ++hi)
-        for (int n = 0; n < Np; ++n) {
-            double re, im;
-            host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)hi * 32) % rate)) % rate, rate, re, im);
-            ptab3[(size_t)hi * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
-        }
-}
-
-// Tables of the pair-rotating three-product loop (ddc_mfma_ring16p3r2_kernel): the images of mfma_build_tables3 for
-// the 64 samples of a PAIR of blocks -- f = half*12 + (comp*2 + th)*2 + sp, element j of lane l <-> sample
-// 32*half + 8*(l >> 4) + j -- and the phasor of every pair, w_n^(64*pair), one row more than there are pairs.
-void mfma_build_tables3r2(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
-                          std::vector<float4> &ptab3) {
-    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
-    const unsigned rate = pl.rate;
-    bfrag3.assign((size_t)tiles * 24 * 64, uint4{0, 0, 0, 0});
-    for (int T = 0; T < tiles; ++T)
-        for (int half = 0; half < 2; ++half)
+        for (int half = 0; half < span; ++half)
             for (int th = 0; th < 2; ++th)
                 for (int lane = 0; lane < 64; ++lane) {
                     const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
@@ -1459,16 +1312,16 @@ void mfma_build_tables3r2(const MfmaPlan &pl, const std::vector<unsigned> &fmod,
                             uint4 w;
                             __builtin_memcpy(&w, img[c][sp], 16);
                             const int f = half * 12 + (c * 2 + th) * 2 + sp;
-                            bfrag3[((size_t)T * 24 + f) * 64 + lane] = w;
+                            bfrag3[((size_t)T * nimg + f) * 64 + lane] = w;
                         }
                 }
-    const int npair = ((pl.nk8 + 3) / 4 + 1) / 2;
-    ptab3.assign((size_t)(npair + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int p = 0; p < npair; ++p)
+    const int nrow = ((pl.nk8 + 3) / 4 + span - 1) / span;
+    ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int row = 0; row < nrow; ++row)
         for (int n = 0; n < Np; ++n) {
             double re, im;
-            host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)p * 64) % rate)) % rate, rate, re, im);
-            ptab3[(size_t)p * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
+            host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)row * 32 * span) % rate)) % rate, rate, re, im);
+            ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
         }
 }
 
@@ -1509,73 +1362,71 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
     if (a.x != a.tail && sh.ngt > 2 && (long long)(32 * (sh.ngt - 1) - 1 + sh.woff) * sh.M + reach > sh.nx)
         return hipErrorInvalidValue;
     if (sh.ngt > 1 && (long long)(32 * (sh.ngt - 1) + sh.woff) * sh.M < sh.tail0) return hipErrorInvalidValue;
-    if (kind == MfmaKernel::AsmRing16P) {
-        // the conversion pass, then the loop that copies its images (a.img: ngt * nhi images of 8 KiB)
-        if (TT != 1 || PK != 32 || W != 4 || !a.img) return hipErrorInvalidValue;
-        const int nhi = (sh.nk8 + 3) / 4;
-        const long long cgrid = (long long)sh.ngt * nhi;
-        const int gt8 = (sh.ngt + 7) / 8;
-        const long long grid = (long long)gt8 * 8 * sh.ntq;
-        if (cgrid < 1 || cgrid > 0x7fffffffLL || grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ddc_convert_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, a, const_cast<uint4 *>(a.img), nhi);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        return hipGetLastError();
+    if (kind == MfmaKernel::Cxx) {
+        if (TT == 2 && PK == 32) return launch_tp<2, 32>(W, a, st);
+        if (TT == 1 && PK == 32) return launch_tp<1, 32>(W, a, st);
+        if (TT == 2 && PK == 16) return launch_tp<2, 16>(W, a, st);
+        if (TT == 1 && PK == 16) return launch_tp<1, 16>(W, a, st);
+        return hipErrorInvalidValue;
     }
-    if (kind == MfmaKernel::AsmRing16P3 || kind == MfmaKernel::AsmRing16P3R2) {
-        // the three-product conversion pass, then its loop (a.img: ngt * nhi images of 12 KiB), rotating per block
-        // or per pair of blocks: a.bfrag3 / a.ptab3 are the tables of that loop
-        if (TT != 1 || PK != 32 || W != 4 || !a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
-        const int nhi = (sh.nk8 + 3) / 4;
-        const long long cgrid = (long long)sh.ngt * nhi;
-        const int gt8 = (sh.ngt + 7) / 8;
-        const long long grid = (long long)gt8 * 8 * sh.ntq;
-        if (cgrid < 1 || cgrid > 0x7fffffffLL || grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ddc_convert3_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, const_cast<uint4 *>(a.img), nhi);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (kind == MfmaKernel::AsmRing16P3R2)
-            hipLaunchKernelGGL(ddc_mfma_ring16p3r2_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        return hipGetLastError();
+    if (TT != 1 || PK != 32 || W != 4) return hipErrorInvalidValue;      // the assembly kernels
+    unsigned grid = 0;
+    switch (kind) {
+        case MfmaKernel::AsmRing16P:
+        case MfmaKernel::AsmRing16P3:
+        case MfmaKernel::AsmRing16P3R2: {
+            // the conversion pass, then the loop that copies its images (a.img: ngt * nhi images of 8 KiB, or of 12 KiB
+            // for the three-product loops, whose tables a.bfrag3 / a.ptab3 are those of the loop launched)
+            const bool three = kind != MfmaKernel::AsmRing16P;
+            if (!a.img || (three && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
+            const int nhi = (sh.nk8 + 3) / 4;
+            const long long cgrid = (long long)sh.ngt * nhi;
+            grid = ring_grid(sh.ngt, sh.ntq, 1);
+            if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
+            uint4 *img = const_cast<uint4 *>(a.img);
+            if (three)
+                hipLaunchKernelGGL(ddc_convert3_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi);
+            else
+                hipLaunchKernelGGL(ddc_convert_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, a, img, nhi);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            if (kind == MfmaKernel::AsmRing16P3R2)
+                hipLaunchKernelGGL(ddc_mfma_ring16p3r2_kernel, dim3(grid), dim3(256), 0, st, a);
+            else if (three)
+                hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3(grid), dim3(256), 0, st, a);
+            else
+                hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3(grid), dim3(256), 0, st, a);
+            return hipGetLastError();
+        }
+        case MfmaKernel::AsmRing16W8:
+            if (!(grid = ring_grid(sh.ngt, (sh.ntg + 7) / 8, 1))) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(ddc_mfma_ring16w8_kernel, dim3(grid), dim3(512), 0, st, a);
+            return hipGetLastError();
+        case MfmaKernel::AsmRing16:
+        case MfmaKernel::AsmRing:
+            // sh.rt: row tiles per workgroup, one after the other on the workgroup's XCD
+            if (sh.rt < 0 || sh.rt > 8 || !(grid = ring_grid(sh.ngt, sh.ntq, sh.rt > 1 ? sh.rt : 1)))
+                return hipErrorInvalidValue;
+            if (kind == MfmaKernel::AsmRing16)
+                hipLaunchKernelGGL(ddc_mfma_ring16_kernel, dim3(grid), dim3(256), 0, st, a);
+            else
+                hipLaunchKernelGGL(ddc_mfma_ring_kernel, dim3(grid), dim3(256), 0, st, a);
+            return hipGetLastError();
+        default:
+            return hipErrorInvalidValue;
     }
-    if (kind == MfmaKernel::AsmRing16W8) {
-        if (TT != 1 || PK != 32 || W != 4) return hipErrorInvalidValue;
-        const int gt8 = (sh.ngt + 7) / 8;
-        const long long grid = (long long)gt8 * 8 * ((sh.ntg + 7) / 8);
-        if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ddc_mfma_ring16w8_kernel, dim3((unsigned)grid), dim3(512), 0, st, a);
-        return hipGetLastError();
-    }
-    if (kind == MfmaKernel::AsmRing16) {
-        if (TT != 1 || PK != 32 || W != 4 || sh.rt < 0 || sh.rt > 8) return hipErrorInvalidValue;
-        const int rt = sh.rt > 1 ? sh.rt : 1;
-        const int gt8 = ((sh.ngt + 7) / 8 + rt - 1) / rt;
-        const long long grid = (long long)gt8 * 8 * sh.ntq;
-        if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ddc_mfma_ring16_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    if (kind == MfmaKernel::AsmRing) {
-        if (TT != 1 || PK != 32 || W != 4 || sh.rt < 0 || sh.rt > 8) return hipErrorInvalidValue;
-        const int rt = sh.rt > 1 ? sh.rt : 1;
-        const int gt8 = ((sh.ngt + 7) / 8 + rt - 1) / rt;   // groups of rt row tiles per XCD
-        const long long grid = (long long)gt8 * 8 * sh.ntq;
-        if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ddc_mfma_ring_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    if (TT == 2 && PK == 32) return launch_tp<2, 32>(W, a, st);
-    if (TT == 1 && PK == 32) return launch_tp<1, 32>(W, a, st);
-    if (TT == 2 && PK == 16) return launch_tp<2, 16>(W, a, st);
-    if (TT == 1 && PK == 16) return launch_tp<1, 16>(W, a, st);
-    return hipErrorInvalidValue;
 }
 
 const char *ddc_mfma_kernel_name(MfmaKernel kind) {
-    return kind == MfmaKernel::AsmRing16P || kind == MfmaKernel::AsmRing16P3 || kind == MfmaKernel::AsmRing16P3R2 ? "ddc_mfma_ring16p_kernel" : kind == MfmaKernel::AsmRing16W8 ? "ddc_mfma_ring16w8_kernel" : kind == MfmaKernel::AsmRing16 ? "ddc_mfma_ring16_kernel" : kind == MfmaKernel::AsmRing ? "ddc_mfma_ring_kernel" : "ddc_mfma_kernel";
+    switch (kind) {
+        case MfmaKernel::AsmRing16P:
+        case MfmaKernel::AsmRing16P3:
+        case MfmaKernel::AsmRing16P3R2: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
+        case MfmaKernel::AsmRing16W8: return "ddc_mfma_ring16w8_kernel";
+        case MfmaKernel::AsmRing16: return "ddc_mfma_ring16_kernel";
+        case MfmaKernel::AsmRing: return "ddc_mfma_ring_kernel";
+        default: return "ddc_mfma_kernel";
+    }
 }
 
 }  // namespace gsdr

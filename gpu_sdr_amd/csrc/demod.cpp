@@ -596,10 +596,7 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         if (h->mac3) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
-            if (h->rot2)
-                gsdr::mfma_build_tables3r2(pl, fmod, bfrag3, ptab3);
-            else
-                gsdr::mfma_build_tables3(pl, fmod, bfrag3, ptab3);
+            gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
             HIPCHK(h, upload(&h->d_bfrag3, bfrag3));
             HIPCHK(h, upload(&h->d_ptab3, ptab3));
         }

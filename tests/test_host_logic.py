@@ -248,10 +248,12 @@ def test_switches_are_read_only_by_the_reader():
                                         ("gen_ddc_mfma_ring16.py", "ddc_mfma_ring16_gen.h"),
                                         ("gen_ddc_mfma_ring16w8.py", "ddc_mfma_ring16w8_gen.h"),
                                         ("gen_ddc_mfma_ring16p.py", "ddc_mfma_ring16p_gen.h"),
+                                        ("gen_ddc_mfma_ring16p3.py", "ddc_mfma_ring16p3_gen.h"),
+                                        ("gen_ddc_mfma_ring16p3r2.py", "ddc_mfma_ring16p3r2_gen.h"),
                                         ("gen_ddc_steps.py", "ddc_steps_gen.h")])
 def test_generated_headers_are_current(gen, header):
     """The committed assembly headers are exactly what their generators produce
-    (the two MFMA generators print, gen_ddc_steps.py rewrites its file)."""
+    (the MFMA generators print, gen_ddc_steps.py rewrites its file)."""
     import subprocess
     import sys
     path = os.path.join(ROOT, "gpu_sdr_amd", "csrc", header)
@@ -267,7 +269,7 @@ def test_generated_headers_are_current(gen, header):
 
 
 RING_HEADERS = ["ddc_mfma_ring_gen.h", "ddc_mfma_ring16_gen.h", "ddc_mfma_ring16w8_gen.h",
-                "ddc_mfma_ring16p_gen.h"]
+                "ddc_mfma_ring16p_gen.h", "ddc_mfma_ring16p3_gen.h", "ddc_mfma_ring16p3r2_gen.h"]
 
 
 def test_generated_loops_obey_the_hazard_rules(tmp_path):

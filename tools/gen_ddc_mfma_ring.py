@@ -40,7 +40,8 @@ debugging session; tools/check_asm_rules.py re-checks R1..R3 on the emitted text
     python3 tools/gen_ddc_mfma_ring.py > gpu_sdr_amd/csrc/ddc_mfma_ring_gen.h
 """
 import os
-import sys
+
+from ddc_mfma_gen import Counters, ar, print_header, vr
 
 # timing-only builds (WRONG results): GEN_ABLATE=rot,prod,lds,gload,bar,bimg drops the rotation
 # FMAs / the conversion arithmetic / the operand reads of the ring / the input loads / the barrier
@@ -82,49 +83,8 @@ S_PSTRIDE = 58
 SGPR_CLOBBER = list(range(36, 80))
 
 
-def vr(base, n=1):
-    return f"v{base}" if n == 1 else f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
-
-
 def bfrag(ks, c, sp):
     return ar((((ks * 2 + c) * 2) + sp) * 4)
-
-
-class Counters:
-    """Outstanding LDS (lgkmcnt) and vector-memory (vmcnt) operations in issue order."""
-
-    def __init__(self, out):
-        self.out = out
-        self.lgkm = []
-        self.vm = []
-
-    def issue_lgkm(self, tag):
-        self.lgkm.append(tag)
-
-    def issue_vm(self, tag):
-        self.vm.append(tag)
-
-    def _need(self, lst, tag, name):
-        if tag not in lst:
-            return
-        i = len(lst) - 1 - lst[::-1].index(tag)
-        n = len(lst) - 1 - i
-        self.out.append(f"s_waitcnt {name}({n})")
-        del lst[: i + 1]
-
-    def need_lgkm(self, tag):
-        self._need(self.lgkm, tag, "lgkmcnt")
-
-    def need_vm(self, tag):
-        self._need(self.vm, tag, "vmcnt")
-
-    def drain_lgkm(self):
-        self.out.append("s_waitcnt lgkmcnt(0)")
-        self.lgkm = []
 
 
 def rotate_ops(cset, p):
@@ -432,27 +392,9 @@ def generate():
 
 
 def main():
-    lines = generate()
-    PFX = "GSDR_MFMA_RING"
-    print("// GENERATED by tools/gen_ddc_mfma_ring.py -- do not edit.")
-    print("// Main loop of ddc_mfma_ring_kernel: see the generator for the schedule and register map.")
-    print("#pragma once")
-    print(f"#define {PFX}_VB {VB}")
-    print(f"#define {PFX}_BYTES {3 * SLOT}")
-    print(f"#define {PFX}_TEXT \\")
-    for ln in lines:
-        if ln.startswith(";"):
-            continue
-        print(f'    "{ln}\\n\\t" \\')
-    print('    ""')
-    clob = [f'"v{i}"' for i in NVGPR_CLOBBER] + [f'"a{i}"' for i in range(NAGPR)] + \
-           [f'"s{i}"' for i in SGPR_CLOBBER] + ['"vcc"', '"scc"', '"memory"']
-    print(f"#define {PFX}_CLOBBERS \\")
-    for i in range(0, len(clob), 12):
-        tail = ", \\" if i + 12 < len(clob) else ""
-        print("    " + ", ".join(clob[i:i + 12]) + tail)
-    n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
-    print(f"// {len(lines)} lines, {n_mfma} MFMAs, VGPRs v{VB}..v{V_LAST}, AGPRs a0..a{NAGPR - 1}")
+    print_header("GSDR_MFMA_RING", __file__,
+                 "Main loop of ddc_mfma_ring_kernel",
+                 generate(), vb=VB, v_last=V_LAST, nagpr=NAGPR, sgprs=SGPR_CLOBBER, nbytes=3 * SLOT)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,8 @@ contiguous each, no VGPR, no VALU), three blocks ahead of their use in a ring of
     python3 tools/gen_ddc_mfma_ring16p.py > gpu_sdr_amd/csrc/ddc_mfma_ring16p_gen.h
 """
 import os
-import sys
+
+from ddc_mfma_gen import ORDER, Counters, ar, bfrag, first_use, last_use, print_header, rotate_ops, vr
 
 # timing-only builds (WRONG results): GEN_ABLATE=rot,prod,lds,gload,bar,bimg drops the rotation
 # FMAs / the conversion arithmetic / the operand reads of the ring / the input loads / the barrier
@@ -58,107 +59,8 @@ S_PSTRIDE = 58
 SGPR_CLOBBER = list(range(36, 80))
 
 
-def vr(base, n=1):
-    return f"v{base}" if n == 1 else f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
-
-
 def frag(k2, rh, sp):
     return F0 + 16 * k2 + 8 * rh + 4 * sp
-
-
-def bfrag(k2, th, c, sp):
-    return ar(((((k2 * 2 + th) * 2 + c) * 2) + sp) * 4)
-
-
-class Counters:
-    """Outstanding LDS (lgkmcnt) and vector-memory (vmcnt) operations in issue order."""
-
-    def __init__(self, out):
-        self.out = out
-        self.lgkm = []
-        self.vm = []
-
-    def issue_lgkm(self, tag):
-        self.lgkm.append(tag)
-
-    def issue_vm(self, tag):
-        self.vm.append(tag)
-
-    def _need(self, lst, tag, name):
-        if tag not in lst:
-            return
-        i = len(lst) - 1 - lst[::-1].index(tag)
-        n = len(lst) - 1 - i
-        self.out.append(f"s_waitcnt {name}({n})")
-        del lst[: i + 1]
-
-    def need_lgkm(self, tag):
-        self._need(self.lgkm, tag, "lgkmcnt")
-
-    def need_vm(self, tag):
-        self._need(self.vm, tag, "vmcnt")
-
-    def drain_lgkm(self):
-        self.out.append("s_waitcnt lgkmcnt(0)")
-        self.lgkm = []
-
-
-def rotate_ops(cset, p):
-    """acc += P * C: 64 v_fma_f32 in four sweeps (an accumulator is read again 16
-    instructions after it was written).  p = (Pr, Pi)."""
-    cr, ci = cset
-    ops = []
-    for term in range(4):
-        for i in range(16):
-            th = (i >> 2) & 1            # register i belongs to tile (rh, th) = (i >> 3, (i >> 2) & 1)
-            pr, pi = vr(p + 2 * th), vr(p + 2 * th + 1)
-            a_r, a_i = vr(ACC[0] + i), vr(ACC[1] + i)
-            c_r, c_i = vr(cr + i), vr(ci + i)
-            if term == 0:
-                ops.append(f"v_fma_f32 {a_r}, {pr}, {c_r}, {a_r}")
-            elif term == 1:
-                ops.append(f"v_fma_f32 {a_i}, {pr}, {c_i}, {a_i}")
-            elif term == 2:
-                ops.append(f"v_fma_f32 {a_r}, -{pi}, {c_i}, {a_r}")
-            else:
-                ops.append(f"v_fma_f32 {a_i}, {pi}, {c_r}, {a_i}")
-    return ops
-
-
-# MFMA order inside k-step k2: (row half, hi|lo of the A fragment) major.  Entries:
-# (rh, sp_a, th, c, sp_b); the first 8 of a row half use its hi fragment (products hi*hi, hi*lo),
-# the next 4 its lo fragment (lo*hi).
-def kstep_order():
-    seq = []
-    for rh in range(2):
-        for sp_b in range(2):
-            for th in range(2):
-                for c in range(2):
-                    seq.append((rh, 0, th, c, sp_b))
-        for th in range(2):
-            for c in range(2):
-                seq.append((rh, 1, th, c, 0))
-    return seq
-
-
-ORDER = kstep_order()
-assert len(ORDER) == 24
-
-
-def first_use(k2, rh, sp):
-    """gap (0..47) of the first MFMA that reads fragment (k2, rh, sp)"""
-    for m, e in enumerate(ORDER):
-        if e[0] == rh and e[1] == sp:
-            return 24 * k2 + m
-    raise AssertionError
-
-
-def last_use(k2, rh, sp):
-    return max(24 * k2 + m for m, e in enumerate(ORDER) if e[0] == rh and e[1] == sp)
 
 
 def frag_for(label, k2, rh, sp):
@@ -202,7 +104,7 @@ def iteration(cnt, out, cur, prev, p_cur, p_prev, label):
     Block b computes from ring slot RD, prefetches block b+1's first fragments from RDN and
     starts the copy of block b+3's image into slot WR (free since the barrier that ended b-1)."""
     out.append(f"; ---- block iteration, C set {label}")
-    rot = rotate_ops(prev, p_prev)
+    rot = rotate_ops(ACC, prev, p_prev)
     other = "B" if label == "A" else "A"
     S_P, N_P = SB[label]["p"], SB[other]["p"]
     NG = 48
@@ -374,13 +276,13 @@ def generate():
     o("s_waitcnt vmcnt(0)")
     o("s_nop 15")
     o("s_nop 15")
-    out.extend(rotate_ops(CB, PB))
+    out.extend(rotate_ops(ACC, CB, PB))
     o("s_branch 3f")
     o("2:")
     o("s_waitcnt vmcnt(0)")
     o("s_nop 15")
     o("s_nop 15")
-    out.extend(rotate_ops(CA, PA))
+    out.extend(rotate_ops(ACC, CA, PA))
     o("3:")
     # every image copy has landed (vmcnt(0) above) and every wave is past the last barrier: the
     # ring is idle, the accumulators go to the C++ epilogue through it
@@ -394,27 +296,9 @@ def generate():
 
 
 def main():
-    lines = generate()
-    PFX = "GSDR_MFMA_RING16P"
-    print("// GENERATED by tools/gen_ddc_mfma_ring16p.py -- do not edit.")
-    print("// Main loop of ddc_mfma_ring16p_kernel (pre-converted operands by LDS-DMA, v_mfma_f32_16x16x32_f16): see the generator for the schedule and register map.")
-    print("#pragma once")
-    print(f"#define {PFX}_VB {VB}")
-    print(f"#define {PFX}_BYTES {NSLOT * SLOT}")
-    print(f"#define {PFX}_TEXT \\")
-    for ln in lines:
-        if ln.startswith(";"):
-            continue
-        print(f'    "{ln}\\n\\t" \\')
-    print('    ""')
-    clob = [f'"v{i}"' for i in NVGPR_CLOBBER] + [f'"a{i}"' for i in range(NAGPR)] + \
-           [f'"s{i}"' for i in SGPR_CLOBBER] + ['"vcc"', '"scc"', '"memory"']
-    print(f"#define {PFX}_CLOBBERS \\")
-    for i in range(0, len(clob), 12):
-        tail = ", \\" if i + 12 < len(clob) else ""
-        print("    " + ", ".join(clob[i:i + 12]) + tail)
-    n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
-    print(f"// {len(lines)} lines, {n_mfma} MFMAs, VGPRs v{VB}..v{V_LAST}, AGPRs a0..a{NAGPR - 1}")
+    print_header("GSDR_MFMA_RING16P", __file__,
+                 "Main loop of ddc_mfma_ring16p_kernel (pre-converted operands by LDS-DMA, v_mfma_f32_16x16x32_f16)",
+                 generate(), vb=VB, v_last=V_LAST, nagpr=NAGPR, sgprs=SGPR_CLOBBER, nbytes=NSLOT * SLOT)
 
 
 if __name__ == "__main__":

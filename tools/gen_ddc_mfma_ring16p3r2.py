@@ -34,7 +34,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_ddc_mfma_ring16p import Counters, ar, vr   # noqa: E402
+from ddc_mfma_gen import Counters, ar, print_header, vr   # noqa: E402
 from gen_ddc_mfma_ring16p3 import (ABLATE, ACC, ADDR, F0, KB, NC, NG, NSLOT, S_BF, S_K, S_M0, S_NHI1, S_NLEFT,   # noqa: E402
                                    S_PSTRIDE, S_RD, S_RD2, S_RDN, S_T0, S_WR, S_WRS, S_XB, SB, SGPR_CLOBBER, SLOT, VB,
                                    dma_ops, frag, image_pointer, piece)
@@ -308,28 +308,9 @@ def generate():
 
 
 def main():
-    lines = generate()
-    PFX = "GSDR_MFMA_RING16P3R2"
-    print("// GENERATED by tools/gen_ddc_mfma_ring16p3r2.py -- do not edit.")
-    print("// Main loop of ddc_mfma_ring16p3r2_kernel (the three-product loop of ddc_mfma_ring16p3_gen.h with phasor images of 64 samples: one rotation per pair of blocks): see the generator for the schedule and register map.")
-    print("#pragma once")
-    print(f"#define {PFX}_VB {VB}")
-    print(f"#define {PFX}_SLOT {SLOT}")
-    print(f"#define {PFX}_BYTES {NSLOT * SLOT}")
-    print(f"#define {PFX}_TEXT \\")
-    for ln in lines:
-        if ln.startswith(";"):
-            continue
-        print(f'    "{ln}\\n\\t" \\')
-    print('    ""')
-    clob = [f'"v{i}"' for i in NVGPR_CLOBBER] + [f'"a{i}"' for i in range(NAGPR)] + \
-           [f'"s{i}"' for i in SGPR_CLOBBER] + ['"vcc"', '"scc"', '"memory"']
-    print(f"#define {PFX}_CLOBBERS \\")
-    for i in range(0, len(clob), 12):
-        tail = ", \\" if i + 12 < len(clob) else ""
-        print("    " + ", ".join(clob[i:i + 12]) + tail)
-    n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
-    print(f"// {len(lines)} lines, {n_mfma} MFMAs, VGPRs v{VB}..v{V_LAST}, AGPRs a0..a{NAGPR - 1}")
+    print_header("GSDR_MFMA_RING16P3R2", __file__,
+                 "Main loop of ddc_mfma_ring16p3r2_kernel (the three-product loop of ddc_mfma_ring16p3_gen.h with phasor images of 64 samples: one rotation per pair of blocks)",
+                 generate(), vb=VB, v_last=V_LAST, nagpr=NAGPR, sgprs=SGPR_CLOBBER, nbytes=NSLOT * SLOT, slot=SLOT)
 
 
 if __name__ == "__main__":
