@@ -113,6 +113,9 @@ hipError_t launch_ddc_flat_main(int F, int PK, const DdcLaunch &a, hipStream_t s
 const char *ddc_kernel_name();
 const char *ddc_flat_kernel_name();
 const char *mix_kernel_name(int n_tones, int tw, long long total, int K, int mix_few);   // what launch_mix runs
+// sc16 input: out[k] = (float(in[k].i) * scale, float(in[k].q) * scale), k < n; `in` holds n interleaved int16 pairs
+// (4-byte aligned), `out` is 8-byte aligned; cus = compute units the grid is sized to.  n <= 0 launches nothing.
+hipError_t launch_widen_sc16(const void *in, float2 *out, long long n, float scale, int cus, hipStream_t st);
 
 // ---- DDC on the matrix cores (ddc_mfma.hip) --------------------------------
 struct MfmaShape {

@@ -33,6 +33,7 @@
 //     reference's FIR::_dout carry, cpp/fir.cu:64-69).
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 
 #include "ddc_device.h"
@@ -581,6 +582,65 @@ hipError_t launch_mix(int K, const DdcLaunch &a, int mix_few, hipStream_t st) {
                            a.fmod, a.out, a.sh);
     else
         return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- sc16 input: interleaved int16 I/Q widened to float2 -----------------------------------------------
+// out[k] = (float(in[k].i) * scale, float(in[k].q) * scale): an exact conversion and ONE IEEE multiply per
+// component, nothing fused into it (there is no addition a compiler could contract it with), so the result is
+// bit for bit what a host computes.  12 bytes per sample, memory bound:
+//   * a lane takes four samples per step: one 16-byte load, two 16-byte stores; consecutive lanes take
+//     consecutive groups, so a wave reads 1 KiB and writes 2 KiB contiguous per step;
+//   * `head` (0 .. 3) samples in front are converted one by one, so that the 16-byte loads are aligned
+//     whatever sample the caller's view starts at (the source needs 4-byte alignment only); the stores are
+//     declared 8-byte aligned, which is all a float2 view guarantees -- the destination is 16-byte aligned
+//     behind the head or it is not, the hardware takes dword-aligned 16-byte global stores either way;
+//   * up to three samples behind the last whole group are converted one by one as well;
+//   * the grid is sized to the compute units (launch_widen_sc16), the groups are walked in a grid-stride loop.
+typedef float widen_f4 __attribute__((ext_vector_type(4), aligned(8)));
+typedef int widen_i4 __attribute__((ext_vector_type(4), aligned(16)));
+
+__device__ __forceinline__ float2 widen_one(int iq, float scale) {
+    // i in the low half, q in the high half (little endian: I first in memory)
+    return make_float2((float)(short)(iq & 0xffff) * scale, (float)(iq >> 16) * scale);
+}
+
+__global__ __launch_bounds__(256) GSDR_NO_PK void widen_sc16_kernel(const int *__restrict__ in, float2 *__restrict__ out,
+                                                                    int head, long long ngroups, int tail, float scale) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long body = (long long)head + 4 * ngroups;
+    if (gid < head) out[gid] = widen_one(in[gid], scale);
+    if (gid < tail) out[body + gid] = widen_one(in[body + gid], scale);
+    const widen_i4 *src = reinterpret_cast<const widen_i4 *>(in + head);
+    float2 *dst = out + head;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long g = gid; g < ngroups; g += stride) {
+        const widen_i4 v = src[g];
+        const float2 a = widen_one(v.x, scale), b = widen_one(v.y, scale);
+        const float2 c = widen_one(v.z, scale), d = widen_one(v.w, scale);
+        widen_f4 lo, hi;
+        lo.x = a.x; lo.y = a.y; lo.z = b.x; lo.w = b.y;
+        hi.x = c.x; hi.y = c.y; hi.z = d.x; hi.w = d.y;
+        widen_f4 *o = reinterpret_cast<widen_f4 *>(dst + 4 * g);
+        o[0] = lo;
+        o[1] = hi;
+    }
+}
+
+hipError_t launch_widen_sc16(const void *in, float2 *out, long long n, float scale, int cus, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (((uintptr_t)in & 3) || ((uintptr_t)out & 7)) return hipErrorInvalidValue;
+    long long head = (long long)((16 - ((uintptr_t)in & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const long long ngroups = (n - head) / 4;
+    const int tail = (int)(n - head - 4 * ngroups);
+    // eight workgroups of four waves per compute unit hold every wave slot the kernel can use; fewer groups: fewer blocks
+    long long blocks = (ngroups + 255) / 256;
+    const long long cap = (long long)(cus > 0 ? cus : 256) * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(widen_sc16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const int *>(in), out,
+                       (int)head, ngroups, tail, scale);
     return hipGetLastError();
 }
 

@@ -115,9 +115,16 @@ struct gsdr_demod {
 
     // host-pointer entry staging
     float2 *d_in = nullptr, *d_out = nullptr;
+    // sc16 input (gsdr_demod_*_sc16): the scale of the widening; the half-size upload buffer of the host-pointer
+    // entry (widened into d_in); the buffer gsdr_demod_process_device_sc16 widens the caller's samples into
+    float sc16_scale = 1.0f / 32768.0f;
+    gsdr_sc16 *d_in16 = nullptr;
+    float2 *d_wide = nullptr;
+    int cus = 256;                     // compute units of the device (grid of the widening kernel)
     // pipelined host-pointer entry (gsdr_demod_submit / _wait)
     struct Slot {
         float2 *d_in = nullptr, *d_out = nullptr;
+        gsdr_sc16 *d_in16 = nullptr;       // gsdr_demod_submit_sc16: upload target, widened into d_in
         hipEvent_t up = nullptr, done = nullptr, down = nullptr;
         hipEvent_t wait_ev = nullptr;      // what gsdr_demod_wait() waits for: down (host) / done (device)
         int n = 0;
@@ -1141,6 +1148,7 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
             fail_create(h, "hipSetDevice failed (no such GPU?)");
             return nullptr;
         }
+        h->cus = device_cus();
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         // ref: :41-44 low priority stream for tone modes, :186-189 high for chirp
@@ -1414,6 +1422,13 @@ const char *gsdr_last_error(const gsdr_demod *h) {
 
 gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gsdr::read_switches()); }
 
+// The body of gsdr_demod_process_device and of its sc16 twin.  in16 != nullptr: the samples arrive as sc16 and are
+// widened into `wide` first (NODSP: straight into out) -- BEHIND the join below, because `wide` belongs to the handle:
+// enqueued in front of it, the widening of this call could overwrite the buffer while the predecessor call, on another
+// stream, still reads it.
+static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 *in16, float2 *wide, float2 *out,
+                               hipStream_t st);
+
 int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev,
                               void *hip_stream) {
     if (!h) return -1;
@@ -1422,7 +1437,24 @@ int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *o
         return -1;
     }
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)hip_stream;  // NULL is HIP's null stream, as everywhere in HIP
+    // NULL is HIP's null stream, as everywhere in HIP
+    return process_device_body(h, reinterpret_cast<const float2 *>(in_dev), nullptr, nullptr,
+                               reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
+}
+
+int gsdr_demod_process_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, void *hip_stream) {
+    if (!h) return -1;
+    if (!in_dev || !out_dev) {
+        h->err = "null buffer";
+        return -1;
+    }
+    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
+    if (h->mode != GSDR_NODSP && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
+    return process_device_body(h, nullptr, in_dev, h->d_wide, reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
+}
+
+static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 *in16, float2 *wide, float2 *out,
+                               hipStream_t st) {
     // An in-order call is a join point: it runs behind everything this handle has in flight on
     // other streams (an earlier call on another stream, overlapped calls still running).  Free on
     // the usual path (same stream as the call before).  Overlapped calls order themselves among
@@ -1430,8 +1462,12 @@ int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *o
     if (!h->pipe_overlap) {
         if (join_streams(h, st, [](hipStream_t) { return false; })) return -1;
     }
-    const float2 *in = reinterpret_cast<const float2 *>(in_dev);
-    float2 *out = reinterpret_cast<float2 *>(out_dev);
+    if (in16) {
+        if (h->mode == GSDR_NODSP) wide = out;
+        HIPCHK(h, gsdr::launch_widen_sc16(in16, wide, h->L, h->sc16_scale, h->cus, st));
+        if (h->mode == GSDR_NODSP) return (int)h->L;
+        in = wide;
+    }
     int n;
     switch (h->mode) {
         case GSDR_DIRECT: n = enqueue_direct(h, in, out, st); break;
@@ -1471,6 +1507,33 @@ int gsdr_demod_process(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_hos
         HIPCHK(h, hipMemcpyAsync(out_host, h->d_out, (size_t)ret * sizeof(float2),
                                  hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // ref: :393,:462,:555
+    return ret;
+}
+
+int gsdr_demod_process_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *out_host) {
+    if (!h) return -1;
+    if (!in_host || !out_host) {
+        h->err = "null buffer";
+        return -1;
+    }
+    if (h->mode == GSDR_NODSP) {  // the complex64 entry copies on the host, this one widens there
+        gsdr_widen_sc16_host(in_host, out_host, h->L, h->sc16_scale);
+        return (int)h->L;
+    }
+    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_in) {
+        HIPCHK(h, dev_alloc(&h->d_in, (size_t)h->L));
+        HIPCHK(h, dev_alloc(&h->d_out, (size_t)h->capacity));
+    }
+    if (!h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
+    // half the bytes over the host link; widened into the staging buffer of the complex64 entry
+    HIPCHK(h, hipMemcpyAsync(h->d_in16, in_host, (size_t)h->L * sizeof(gsdr_sc16), hipMemcpyHostToDevice, h->stream));
+    const int ret = process_device_body(h, nullptr, h->d_in16, h->d_in, h->d_out, h->stream);
+    if (ret < 0) return ret;
+    if (ret > 0)
+        HIPCHK(h, hipMemcpyAsync(out_host, h->d_out, (size_t)ret * sizeof(float2),
+                                 hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return ret;
 }
 
@@ -1561,7 +1624,9 @@ static int pipeline_init_parts(gsdr_demod *h) {
 //     slots j-1 .. j-S, the pass of call j writes head/tail set j, the carry part of head j+1,
 //     slot j and clears slot j+1 -- disjoint modulo kStageSets = S+1 and kScaleSlots = S+2.
 // Every other mode keeps the one compute stream.  GSDR_PIPE_OVERLAP=0 does so for DIRECT too.
-static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, const float2 *in, float2 *out) {
+// in16 != nullptr (NODSP through gsdr_demod_submit_device_sc16 only): sc16 samples, widened straight into out.
+static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, const float2 *in, float2 *out,
+                            const gsdr_sc16 *in16 = nullptr) {
     const bool ddc = (h->mode == GSDR_DIRECT && h->decim > 0) ||
                      h->mode == GSDR_TONES || h->mode == GSDR_NOISE;
     // TONES / NOISE inside the LDS keep the one compute stream: a launch is 10 - 15 us, the events that tie the calls
@@ -1583,13 +1648,20 @@ static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, 
     }
     if (overlap && h->pipe_seq > 0) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_abs[(h->pipe_seq - 1) % 4], 0));
     h->pipe_overlap = overlap;
-    const int n = gsdr_demod_process_device(h, reinterpret_cast<const gsdr_c64 *>(in),
-                                            reinterpret_cast<gsdr_c64 *>(out), cs);
+    const int n = process_device_body(h, in, in16, nullptr, out, cs);
     h->pipe_overlap = false;
     if (overlap) h->pipe_seq++;
     if (n < 0) return -1;
     HIPCHK(h, hipEventRecord(sl.done, cs));
     return n;
+}
+
+// the device buffers of a pipeline slot, each created when the first entry that needs it asks for it
+static int slot_buffers(gsdr_demod *h, gsdr_demod::Slot &sl, bool in, bool out, bool in16) {
+    if (in && !sl.d_in) HIPCHK(h, dev_alloc(&sl.d_in, (size_t)h->L));
+    if (out && !sl.d_out) HIPCHK(h, dev_alloc(&sl.d_out, (size_t)h->capacity));
+    if (in16 && !sl.d_in16) HIPCHK(h, dev_alloc(&sl.d_in16, (size_t)h->L));
+    return 0;
 }
 
 int gsdr_demod_prepare(gsdr_demod *h, int what) {
@@ -1603,12 +1675,12 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     if (what & (GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST)) {
         if (pipeline_init(h)) return -1;
     }
-    if (what & GSDR_PREPARE_PIPELINE_HOST) {
-        for (auto &sl : h->slot)
-            if (!sl.d_in) {
-                HIPCHK(h, dev_alloc(&sl.d_in, (size_t)h->L));
-                HIPCHK(h, dev_alloc(&sl.d_out, (size_t)h->capacity));
-            }
+    const bool sc16 = (what & GSDR_PREPARE_SC16) != 0;
+    if (sc16 && (what & GSDR_PREPARE_HOST) && !h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
+    if (sc16 && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
+    for (auto &sl : h->slot) {
+        const bool host = (what & GSDR_PREPARE_PIPELINE_HOST) != 0;
+        if (slot_buffers(h, sl, host || (sc16 && (what & GSDR_PREPARE_PIPELINE)), host, host && sc16)) return -1;
     }
     // first use of a stream (its hardware queue), of the copy engines in both directions and of
     // the code object costs milliseconds: pay them here, not on the first packets
@@ -1616,11 +1688,14 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     if (h->pipe_ready) {
         for (int i = 0; i < kPipeStreams; ++i) HIPCHK(h, gsdr::launch_warm(h->s_main[i]));
         float2 *pin = nullptr;
+        // (no more than the slot holds: a copy past a buffer of fewer than 512 samples is refused, and the error it
+        // leaves behind was reported by the next launch that asked for one -- the rehearsal's)
+        const size_t warm = (size_t)h->L * sizeof(float2) < 4096 ? (size_t)h->L * sizeof(float2) : 4096;
         if (h->slot[0].d_in && hipHostMalloc((void **)&pin, 4096) == hipSuccess) {
             std::memset(pin, 0, 4096);
-            (void)hipMemcpyAsync(h->slot[0].d_in, pin, 4096, hipMemcpyHostToDevice, h->s_up);
+            (void)hipMemcpyAsync(h->slot[0].d_in, pin, warm, hipMemcpyHostToDevice, h->s_up);
             (void)hipStreamSynchronize(h->s_up);
-            (void)hipMemcpyAsync(pin, h->slot[0].d_in, 4096, hipMemcpyDeviceToHost, h->s_down);
+            (void)hipMemcpyAsync(pin, h->slot[0].d_in, warm, hipMemcpyDeviceToHost, h->s_down);
             (void)hipStreamSynchronize(h->s_down);
             (void)hipHostFree(pin);
         }
@@ -1650,6 +1725,23 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
                 }
                 while (ok && pending-- > 0) ok = gsdr_demod_wait(twin) >= 0;
             }
+            // the sc16 forms of the same entries (first launch of the widening kernel, on both streams it runs on);
+            // the zeros of pin_in serve as L sc16 samples too
+            const gsdr_sc16 *pin_in16 = reinterpret_cast<const gsdr_sc16 *>(pin_in);
+            if (ok && sc16 && (what & GSDR_PREPARE_HOST))
+                for (int k = 0; k < 2 && ok; ++k) ok = gsdr_demod_process_sc16(twin, pin_in16, pin_out) >= 0;
+            if (ok && sc16 && (what & GSDR_PREPARE_PIPELINE_HOST)) {
+                int pending = 0;
+                for (int k = 0; k < GSDR_PIPELINE_DEPTH + 2 && ok; ++k) {
+                    if (pending == GSDR_PIPELINE_DEPTH) {
+                        ok = gsdr_demod_wait(twin) >= 0;
+                        --pending;
+                    }
+                    ok = ok && gsdr_demod_submit_sc16(twin, pin_in16, pin_out) == 0;
+                    ++pending;
+                }
+                while (ok && pending-- > 0) ok = gsdr_demod_wait(twin) >= 0;
+            }
         }
         if (!ok) h->err = std::string("rehearsal failed: ") + (twin ? twin->err : g_create_error);
         if (pin_in) (void)hipHostFree(pin_in);
@@ -1660,9 +1752,10 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     return 0;
 }
 
-int gsdr_demod_submit(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host) {
+// gsdr_demod_submit and gsdr_demod_submit_sc16 (in16_host != nullptr)
+static int submit_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *in16_host, gsdr_c64 *out_host) {
     if (!h) return -1;
-    if (!in_host || !out_host) {
+    if (!(in_host || in16_host) || !out_host) {
         h->err = "null buffer";
         return -1;
     }
@@ -1673,12 +1766,16 @@ int gsdr_demod_submit(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
     if (pipeline_init(h)) return -1;
     auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
-    if (!sl.d_in) {
-        HIPCHK(h, dev_alloc(&sl.d_in, (size_t)h->L));
-        HIPCHK(h, dev_alloc(&sl.d_out, (size_t)h->capacity));
-    }
+    if (slot_buffers(h, sl, true, true, in16_host != nullptr)) return -1;
     // the slot is free: its previous download was waited for in gsdr_demod_wait()
-    HIPCHK(h, hipMemcpyAsync(sl.d_in, in_host, (size_t)h->L * sizeof(float2), hipMemcpyHostToDevice, h->s_up));
+    if (in16_host) {
+        // half the bytes, then the widening, both on the upload stream in front of sl.up: it overlaps the kernels of
+        // the buffer before and does not lengthen the compute stream
+        HIPCHK(h, hipMemcpyAsync(sl.d_in16, in16_host, (size_t)h->L * sizeof(gsdr_sc16), hipMemcpyHostToDevice, h->s_up));
+        HIPCHK(h, gsdr::launch_widen_sc16(sl.d_in16, sl.d_in, h->L, h->sc16_scale, h->cus, h->s_up));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(sl.d_in, in_host, (size_t)h->L * sizeof(float2), hipMemcpyHostToDevice, h->s_up));
+    }
     HIPCHK(h, hipEventRecord(sl.up, h->s_up));
     const int n = pipeline_compute(h, sl, sl.up, sl.d_in, sl.d_out);
     if (n < 0) return -1;
@@ -1690,6 +1787,14 @@ int gsdr_demod_submit(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host
     sl.n = n;
     h->pipe_count++;
     return 0;
+}
+
+int gsdr_demod_submit(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host) {
+    return submit_host(h, in_host, nullptr, out_host);
+}
+
+int gsdr_demod_submit_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *out_host) {
+    return submit_host(h, nullptr, in_host, out_host);
 }
 
 int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev) {
@@ -1707,6 +1812,37 @@ int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *ou
     auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
     const int n = pipeline_compute(h, sl, nullptr, reinterpret_cast<const float2 *>(in_dev),
                                    reinterpret_cast<float2 *>(out_dev));
+    if (n < 0) return -1;
+    sl.wait_ev = sl.done;
+    sl.n = n;
+    h->pipe_count++;
+    return 0;
+}
+
+int gsdr_demod_submit_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev) {
+    if (!h) return -1;
+    if (!in_dev || !out_dev) {
+        h->err = "null buffer";
+        return -1;
+    }
+    if (h->pipe_count >= GSDR_PIPELINE_DEPTH) {
+        h->err = "pipeline full: call gsdr_demod_wait() first";
+        return -1;
+    }
+    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
+    if (pipeline_init(h)) return -1;
+    auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
+    int n;
+    if (h->mode == GSDR_NODSP) {
+        n = pipeline_compute(h, sl, nullptr, nullptr, reinterpret_cast<float2 *>(out_dev), in_dev);
+    } else {
+        // in_dev is complete (the contract of the complex64 entry): widened into the slot's input buffer -- free, its last
+        // reader was waited for in gsdr_demod_wait() -- on the upload stream, beside the kernels of the buffer before
+        if (slot_buffers(h, sl, true, false, false)) return -1;
+        HIPCHK(h, gsdr::launch_widen_sc16(in_dev, sl.d_in, h->L, h->sc16_scale, h->cus, h->s_up));
+        HIPCHK(h, hipEventRecord(sl.up, h->s_up));
+        n = pipeline_compute(h, sl, sl.up, sl.d_in, reinterpret_cast<float2 *>(out_dev));
+    }
     if (n < 0) return -1;
     sl.wait_ev = sl.done;
     sl.n = n;
@@ -1741,6 +1877,7 @@ void gsdr_demod_close(gsdr_demod *h) {
     for (auto &sl : h->slot) {
         if (sl.d_in) (void)hipFree(sl.d_in);
         if (sl.d_out) (void)hipFree(sl.d_out);
+        if (sl.d_in16) (void)hipFree(sl.d_in16);
     }
     pipeline_teardown(h);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -1749,7 +1886,8 @@ void gsdr_demod_close(gsdr_demod *h) {
         (void)hipEventDestroy(e.second);
     }
     if (h->d_chirp_part) (void)hipFree(h->d_chirp_part);
-    void *ptrs[] = {h->d_in,      h->d_out,     h->d_taps_t,   h->d_taps_p,   h->d_stage,    h->d_btab,     h->d_wk,
+    void *ptrs[] = {h->d_in16,    h->d_wide,
+                    h->d_in,      h->d_out,     h->d_taps_t,   h->d_taps_p,   h->d_stage,    h->d_btab,     h->d_wk,
                     h->d_wrem,    h->d_fmod,    h->d_tails,    h->d_carry[0], h->d_carry[1],
                     h->d_profile, h->d_ccarry[0], h->d_ccarry[1],
                     h->d_bfrag,   h->d_ptab,    h->d_dtab,     h->d_mtaps,    h->d_mfmod,
@@ -1773,6 +1911,32 @@ void gsdr_demod_close(gsdr_demod *h) {
         if (h->d_pfb_carry[i]) (void)hipFree(h->d_pfb_carry[i]);
     if (h->stream) (void)hipStreamDestroy(h->stream);  // ref: 03_implement.md:58-63
     delete h;
+}
+
+int gsdr_demod_set_sc16_scale(gsdr_demod *h, float scale) {
+    if (!h) return -1;
+    if (!std::isfinite(scale) || !(scale > 0.f)) {
+        h->err = "sc16 scale must be finite and > 0";
+        return -1;
+    }
+    h->sc16_scale = scale;
+    return 0;
+}
+
+float gsdr_demod_sc16_scale(const gsdr_demod *h) { return h ? h->sc16_scale : 0.f; }
+
+int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream) {
+    if (n < 0 || (n > 0 && (!in_dev || !out_dev))) {
+        g_create_error = "gsdr_widen_sc16_device: null buffer";
+        return -1;
+    }
+    const hipError_t e = gsdr::launch_widen_sc16(in_dev, reinterpret_cast<float2 *>(out_dev), n, scale, device_cus(),
+                                                 (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_widen_sc16_device: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return 0;
 }
 
 int gsdr_pfb_lds_stages(int fft_tones, int *radices) {

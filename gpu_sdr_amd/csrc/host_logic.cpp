@@ -209,4 +209,13 @@ void gsdr_chirp_derive_tx(int rate, int freq0, int chirp_f, int swipe_s,
     cp->f0 = (start > -2147483649.0 && start < 2147483648.0) ? (int)start : INT_MIN;
 }
 
+// sc16 input widened on the host: an exact int16 -> float conversion and one IEEE multiply per component, what
+// widen_sc16_kernel (ddc_kernels.hip) computes on the device, bit for bit.
+void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float scale) {
+    for (long long k = 0; k < n; ++k) {
+        out[k].x = (float)in[k].i * scale;
+        out[k].y = (float)in[k].q * scale;
+    }
+}
+
 }  // extern "C"

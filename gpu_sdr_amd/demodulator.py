@@ -102,6 +102,22 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+SC16_DEFAULT_SCALE = 2.0 ** -15
+
+
+def _is_sc16(x) -> bool:
+    """An sc16 buffer: contiguous int16 array or tensor of shape (..., 2), I first (struct gsdr_sc16)."""
+    if _is_torch(x):
+        import torch
+        return x.dtype == torch.int16 and x.dim() >= 2 and x.shape[-1] == 2 and x.is_contiguous()
+    return (isinstance(x, np.ndarray) and x.dtype == np.int16 and x.ndim >= 2 and x.shape[-1] == 2
+            and x.flags.c_contiguous)
+
+
+def _sc16_rows(x) -> int:
+    return int(x.numel() if _is_torch(x) else x.size) // 2
+
+
 class RX_buffer_demodulator:
     """class RX_buffer_demodulator, headers/USRP_demodulator.hpp:13-33.
 
@@ -110,6 +126,10 @@ class RX_buffer_demodulator:
     the device state.  ``in``/``out`` are numpy complex64 arrays (host path,
     synchronous like the reference) or torch complex64 CUDA tensors (device
     path, enqueued on the current torch stream, not synchronised).
+
+    sc16 input: ``process``, ``process_device``, ``submit`` and ``submit_device`` also take ``in`` as a contiguous
+    int16 array / CUDA tensor of shape (..., 2) (I, Q) with at least buffer_len rows; it is widened to
+    ``float(v) * sc16_scale`` on the way in (gsdr_demod_*_sc16) and demodulated as the complex64 it stands for.
     """
 
     def __init__(self, init_parameters: param, init_diagnostic: bool = False,
@@ -166,11 +186,24 @@ class RX_buffer_demodulator:
     def kernel_name(self) -> str:
         return self._L.gsdr_demod_kernel_name(self._h).decode()
 
-    def prepare(self, host: bool = True, pipeline: bool = True, pipeline_host: bool = True, rehearse: bool = True) -> None:
+    @property
+    def sc16_scale(self) -> float:
+        """Factor of the sc16 widening (gsdr_demod_sc16_scale); 2^-15 unless set.  Must be finite and > 0."""
+        return float(self._L.gsdr_demod_sc16_scale(self._h))
+
+    @sc16_scale.setter
+    def sc16_scale(self, scale: float) -> None:
+        if self._L.gsdr_demod_set_sc16_scale(self._h, C.c_float(scale)) != 0:
+            raise GsdrError(self._L.gsdr_last_error(self._h).decode())
+
+    def prepare(self, host: bool = True, pipeline: bool = True, pipeline_host: bool = True, rehearse: bool = True,
+                sc16: bool = False) -> None:
         """gsdr_demod_prepare: create now what the entries would create on first use; `rehearse` also runs a
         throw-away twin through a few buffers of zeros (the process-wide first-use costs of kernels, pinned
-        copies and streams: 5 - 7 ms each, otherwise paid by the first packets)."""
+        copies and streams: 5 - 7 ms each, otherwise paid by the first packets); `sc16`: the same for the sc16
+        forms of the entries named (GSDR_PREPARE_SC16)."""
         what = (1 if host else 0) | (2 if pipeline else 0) | (4 if pipeline_host else 0) | (8 if rehearse else 0)
+        what |= 16 if sc16 else 0
         if self._L.gsdr_demod_prepare(self._h, what) != 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
 
@@ -200,15 +233,17 @@ class RX_buffer_demodulator:
             raise GsdrError("demodulator is closed")
         if _is_torch(in_buffer) or _is_torch(out_buffer):
             return self.process_device(in_buffer, out_buffer)
-        if in_buffer.dtype != np.complex64 or out_buffer.dtype != np.complex64:
-            raise TypeError("buffers must be complex64 (float2)")
-        if in_buffer.size < self.parameters.buffer_len:
+        sc16 = _is_sc16(in_buffer)
+        if not (sc16 or in_buffer.dtype == np.complex64) or out_buffer.dtype != np.complex64:
+            raise TypeError("buffers must be complex64 (float2); the input may be contiguous int16 of shape (..., 2)")
+        if (_sc16_rows(in_buffer) if sc16 else in_buffer.size) < self.parameters.buffer_len:
             raise ValueError("input buffer shorter than parameters.buffer_len")
         if out_buffer.size < self.out_capacity:
             raise ValueError(f"output buffer needs room for {self.out_capacity} samples")
         if not (in_buffer.flags.c_contiguous and out_buffer.flags.c_contiguous):
             raise ValueError("buffers must be contiguous")
-        n = self._L.gsdr_demod_process(self._h, in_buffer.ctypes.data, out_buffer.ctypes.data)
+        entry = self._L.gsdr_demod_process_sc16 if sc16 else self._L.gsdr_demod_process
+        n = entry(self._h, in_buffer.ctypes.data, out_buffer.ctypes.data)
         if n < 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
         return n
@@ -218,43 +253,53 @@ class RX_buffer_demodulator:
         import torch
         if not self._h:
             raise GsdrError("demodulator is closed")
-        for t in (in_tensor, out_tensor):
-            if not (t.is_cuda and t.dtype == torch.complex64 and t.is_contiguous()):
-                raise TypeError("need contiguous complex64 CUDA tensors")
-        if in_tensor.numel() < self.parameters.buffer_len:
+        sc16 = self._check_tensors(in_tensor, out_tensor)
+        if (_sc16_rows(in_tensor) if sc16 else in_tensor.numel()) < self.parameters.buffer_len:
             raise ValueError("input tensor shorter than parameters.buffer_len")
         if out_tensor.numel() < self.out_capacity:
             raise ValueError(f"output tensor needs room for {self.out_capacity} samples")
         if stream is None:
             stream = torch.cuda.current_stream(in_tensor.device)
-        n = self._L.gsdr_demod_process_device(self._h, in_tensor.data_ptr(), out_tensor.data_ptr(),
-                                              C.c_void_p(stream.cuda_stream))
+        entry = self._L.gsdr_demod_process_device_sc16 if sc16 else self._L.gsdr_demod_process_device
+        n = entry(self._h, in_tensor.data_ptr(), out_tensor.data_ptr(), C.c_void_p(stream.cuda_stream))
         if n < 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
         return n
 
+    @staticmethod
+    def _check_tensors(in_tensor, out_tensor) -> bool:
+        """TypeError unless both are contiguous CUDA tensors, complex64 -- or, the input only, sc16: True then."""
+        import torch
+        sc16 = _is_sc16(in_tensor)
+        for t, ok in ((in_tensor, sc16 or in_tensor.dtype == torch.complex64), (out_tensor, out_tensor.dtype == torch.complex64)):
+            if not (t.is_cuda and ok and t.is_contiguous()):
+                raise TypeError("need contiguous complex64 CUDA tensors (the input may be contiguous int16 of shape (..., 2))")
+        return sc16
+
     def submit(self, in_buffer: np.ndarray, out_buffer: np.ndarray) -> None:
         """Pipelined host-pointer entry (gsdr_demod_submit): returns at once; the
         buffers (ideally pinned) must stay alive until the matching wait()."""
-        if in_buffer.dtype != np.complex64 or out_buffer.dtype != np.complex64:
-            raise TypeError("buffers must be complex64 (float2)")
-        if in_buffer.size < self.parameters.buffer_len or out_buffer.size < self.out_capacity:
+        sc16 = _is_sc16(in_buffer)
+        if not (sc16 or in_buffer.dtype == np.complex64) or out_buffer.dtype != np.complex64:
+            raise TypeError("buffers must be complex64 (float2); the input may be contiguous int16 of shape (..., 2)")
+        rows = _sc16_rows(in_buffer) if sc16 else in_buffer.size
+        if rows < self.parameters.buffer_len or out_buffer.size < self.out_capacity:
             raise ValueError("buffer too small")
-        if self._L.gsdr_demod_submit(self._h, in_buffer.ctypes.data, out_buffer.ctypes.data) != 0:
+        entry = self._L.gsdr_demod_submit_sc16 if sc16 else self._L.gsdr_demod_submit
+        if entry(self._h, in_buffer.ctypes.data, out_buffer.ctypes.data) != 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
 
     def submit_device(self, in_tensor, out_tensor) -> None:
         """Pipelined device-pointer entry (gsdr_demod_submit_device): in_tensor must be
         complete (synchronise its producer first), out_tensor distinct per outstanding call."""
-        import torch
         if not self._h:
             raise GsdrError("demodulator is closed")
-        for t in (in_tensor, out_tensor):
-            if not (t.is_cuda and t.dtype == torch.complex64 and t.is_contiguous()):
-                raise TypeError("need contiguous complex64 CUDA tensors")
-        if in_tensor.numel() < self.parameters.buffer_len or out_tensor.numel() < self.out_capacity:
+        sc16 = self._check_tensors(in_tensor, out_tensor)
+        rows = _sc16_rows(in_tensor) if sc16 else in_tensor.numel()
+        if rows < self.parameters.buffer_len or out_tensor.numel() < self.out_capacity:
             raise ValueError("tensor too small")
-        if self._L.gsdr_demod_submit_device(self._h, in_tensor.data_ptr(), out_tensor.data_ptr()) != 0:
+        entry = self._L.gsdr_demod_submit_device_sc16 if sc16 else self._L.gsdr_demod_submit_device
+        if entry(self._h, in_tensor.data_ptr(), out_tensor.data_ptr()) != 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
 
     def wait(self) -> int:
@@ -286,6 +331,42 @@ class RX_buffer_demodulator:
             self.close()
         except Exception:
             pass
+
+
+def widen_sc16(in_buffer, out=None, scale: float = SC16_DEFAULT_SCALE, stream=None):
+    """sc16 -> complex64 on its own: ``out[k] = (float(in[k, 0]) * scale, float(in[k, 1]) * scale)``, an exact
+    conversion and one float32 multiply.  ``in_buffer``: contiguous int16 of shape (..., 2); a CUDA tensor is
+    widened on the device (gsdr_widen_sc16_device, enqueued on `stream` / the current torch stream, not
+    synchronised), a numpy array on the host (gsdr_widen_sc16_host, needs no GPU) -- bit-identical results.
+    ``out``: contiguous complex64 of at least as many samples (created when None).  Returns ``out``."""
+    if not _is_sc16(in_buffer):
+        raise TypeError("need a contiguous int16 array or tensor of shape (..., 2)")
+    n = _sc16_rows(in_buffer)
+    L = _lib.lib()
+    if _is_torch(in_buffer):
+        import torch
+        if not in_buffer.is_cuda:
+            raise TypeError("a tensor must live on the GPU (pass a numpy array for the host path)")
+        if out is None:
+            out = torch.empty(in_buffer.shape[:-1], dtype=torch.complex64, device=in_buffer.device)
+        if not (_is_torch(out) and out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous()):
+            raise TypeError("out must be a contiguous complex64 CUDA tensor")
+        if out.numel() < n:
+            raise ValueError("out is shorter than the input")
+        if stream is None:
+            stream = torch.cuda.current_stream(in_buffer.device)
+        if L.gsdr_widen_sc16_device(in_buffer.data_ptr(), out.data_ptr(), n, C.c_float(scale),
+                                    C.c_void_p(stream.cuda_stream)) != 0:
+            raise GsdrError(L.gsdr_last_error(None).decode())
+        return out
+    if out is None:
+        out = np.empty(in_buffer.shape[:-1], dtype=np.complex64)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.complex64 and out.flags.c_contiguous):
+        raise TypeError("out must be a contiguous complex64 array")
+    if out.size < n:
+        raise ValueError("out is shorter than the input")
+    L.gsdr_widen_sc16_host(in_buffer.ctypes.data, out.ctypes.data, n, C.c_float(scale))
+    return out
 
 
 # ---- host-side helpers of the path, straight from the library --------------

@@ -169,6 +169,35 @@ class RX_buffer_demodulator {
         return gsdr_demod_submit_device(handle_, reinterpret_cast<const gsdr_c64*>(in_dev),
                                         reinterpret_cast<gsdr_c64*>(out_dev)) == 0;
     }
+    //! sc16 input (extension, see "sc16 input" in gsdr.h): the same four entries for interleaved int16 I/Q, each
+    //! "widen by the handle's scale (2^-15 unless set), then the float2 entry"; may be mixed with the float2 calls
+    bool set_sc16_scale(float scale) {
+        if (gsdr_demod_set_sc16_scale(handle_, scale) == 0) return true;
+        std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(handle_));
+        return false;
+    }
+    //! creates what the sc16 entries need up front and rehearses them, as the constructor does for the float2 ones
+    bool prepare_sc16() {
+        return gsdr_demod_prepare(handle_, GSDR_PREPARE_HOST | GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST |
+                                               GSDR_PREPARE_REHEARSE | GSDR_PREPARE_SC16) == 0;
+    }
+    int process(const gsdr_sc16* in, float2** out) {
+        const int n = gsdr_demod_process_sc16(handle_, in, reinterpret_cast<gsdr_c64*>(*out));
+        if (n < 0) {
+            std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(handle_));
+            return 0;
+        }
+        return n;
+    }
+    int process_device(const gsdr_sc16* in_dev, float2* out_dev, void* hip_stream) {
+        return gsdr_demod_process_device_sc16(handle_, in_dev, reinterpret_cast<gsdr_c64*>(out_dev), hip_stream);
+    }
+    bool submit(const gsdr_sc16* in, float2** out) {
+        return gsdr_demod_submit_sc16(handle_, in, reinterpret_cast<gsdr_c64*>(*out)) == 0;
+    }
+    bool submit_device(const gsdr_sc16* in_dev, float2* out_dev) {
+        return gsdr_demod_submit_device_sc16(handle_, in_dev, reinterpret_cast<gsdr_c64*>(out_dev)) == 0;
+    }
     int wait() {
         const int n = gsdr_demod_wait(handle_);
         if (n == -1) std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(handle_));

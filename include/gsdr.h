@@ -25,6 +25,8 @@ extern "C" {
 /* complex64, layout-identical to CUDA/HIP float2 (x = re, y = im).
  * ref: every buffer in headers/USRP_demodulator.hpp is float2*. */
 typedef struct gsdr_c64 { float x, y; } gsdr_c64;
+/* interleaved 16-bit I/Q as a radio delivers it (UHD "sc16": I first), 4 bytes per sample */
+typedef struct gsdr_sc16 { int16_t i, q; } gsdr_sc16;
 
 /* ref: headers/USRP_server_settings.hpp:114  enum w_type */
 enum gsdr_w_type {
@@ -129,7 +131,37 @@ int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *ou
  * process show none): the rehearsal pays them at set-up time, so that the first packets are not late.
  * The state of `h` itself (carry, NCO phase, call count) is untouched. */
 #define GSDR_PREPARE_REHEARSE 8
+/* GSDR_PREPARE_SC16: also what the sc16 entries below create on first use -- the half-size upload buffers of the
+ * host-pointer entries the other bits name, the input buffers of the pipeline slots (gsdr_demod_submit_device_sc16)
+ * and the buffer gsdr_demod_process_device_sc16 widens into; with GSDR_PREPARE_REHEARSE the twin also goes through the
+ * sc16 host-pointer entries named, so that the first launch of the widening kernel is not paid by the first packet.
+ * Without this bit nothing of that is allocated. */
+#define GSDR_PREPARE_SC16 16
 int gsdr_demod_prepare(gsdr_demod *h, int what);
+
+/* ---- sc16 input (an extension: the reference has UHD convert to fc32 on the host, ref:
+ * cpp/USRP_hardware_manager.cpp:764-816) -------------------------------------------------
+ * Every RX entry above in a form that takes interleaved int16 I/Q.  Each is exactly "widen, then the complex64
+ * entry": sample k becomes (float(i) * scale, float(q) * scale) -- an exact conversion and one IEEE single-precision
+ * multiply, nothing fused into it -- and the demodulation that follows is the one of the complex64 entry, kernel
+ * for kernel.  Contracts, return values and ordering rules are those of the complex64 entries; both kinds of call
+ * may be mixed freely on one handle (the stream state does not know the difference).  The host-pointer entries
+ * upload 4 bytes per sample instead of 8 and widen on the device (NODSP: gsdr_demod_process_sc16 widens on the
+ * host, the device entries widen straight into out_dev).
+ * The scale is a property of the handle: 2^-15 by default (exact: full scale maps to [-1, 1)); it must be finite
+ * and > 0, otherwise gsdr_demod_set_sc16_scale returns -1, leaves a message in gsdr_last_error(h) and keeps the
+ * old value.  A caller who wants the values their UHD would have delivered as fc32 sets the factor that UHD applies. */
+int gsdr_demod_set_sc16_scale(gsdr_demod *h, float scale);
+float gsdr_demod_sc16_scale(const gsdr_demod *h);
+int gsdr_demod_process_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *out_host);
+int gsdr_demod_process_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, void *hip_stream);
+int gsdr_demod_submit_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *out_host);
+int gsdr_demod_submit_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev);
+/* The widening on its own.  _device: in_dev (4-byte aligned) and out_dev (8-byte aligned) are device pointers to n
+ * samples, the kernel is enqueued on hip_stream and not synchronised; returns 0, or -1 with the reason in
+ * gsdr_last_error(NULL).  _host: the same arithmetic on the CPU, bit for bit (needs no GPU). */
+int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream);
+void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float scale);
 
 /* ref: RX_buffer_demodulator::close, cpp/USRP_demodulator.cpp:333 (+ :466-698).
  * Frees every device allocation and the stream, then the handle itself. */

@@ -14,11 +14,15 @@
 //
 //   hipcc -O2 -std=c++17 -Iinclude tools/rx_link.cpp -Lgpu_sdr_amd -lgsdr \
 //         -Wl,-rpath,$PWD/gpu_sdr_amd -lpthread -o /tmp/rx_link
-//   rx_link [n_tones=256] [decim=100] [buffers=200] [pipe]
+//   rx_link [n_tones=256] [decim=100] [buffers=200] [pipe] [sc16]
 // With "pipe" the loop uses the pipelined submit()/wait() pair (upload, kernels
 // and download of successive buffers overlap) instead of the synchronous process().
+// With "sc16" (after "pipe" when both are given) the RX thread hands over interleaved int16 I/Q, as a radio delivers
+// it: the source is quantised once, before the timed loop (full scale = 1.0), into pinned pools half the size, and
+// the loop drives the sc16 overloads of the class (4 bytes per sample over the host link instead of 8).
 //
-//   rx_link file <config.txt> <in.c64> <out.c64> [pipe]
+//   rx_link file <config.txt> <in.c64> <out.c64> [pipe] [sc16]
+// (with "sc16" the input file holds whole buffers of int16 I, Q pairs instead of complex64)
 // The same loop over a recorded stream (tests/test_gpu_rxlink.py): config.txt holds
 // "key value..." lines (mode DIRECT|TONES|CHIRP|NOISE|NODSP, rate, buffer_len, decim,
 // pf_average, fft_tones, freq ..., chirp_f ..., swipe_s ..., chirp_t ...); in.c64 holds
@@ -26,6 +30,7 @@
 // valid lengths are printed, as the streamer would put them into the packet headers.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -137,10 +142,12 @@ static int tx_mode(int argc, char **argv) {
 
 static int file_mode(int argc, char **argv) {
     if (argc < 5) {
-        std::fprintf(stderr, "usage: rx_link file <config.txt> <in.c64> <out.c64> [pipe]\n");
+        std::fprintf(stderr, "usage: rx_link file <config.txt> <in.c64> <out.c64> [pipe] [sc16]\n");
         return 2;
     }
     const bool pipelined = argc > 5 && std::string(argv[5]) == "pipe";
+    const bool sc16 = argc > 5 && std::string(argv[argc - 1]) == "sc16";
+    const size_t in_bytes = sc16 ? sizeof(gsdr_sc16) : sizeof(float2);   // per input sample
     param p;
     p.mode = RX;
     p.rate = 0; p.gain = 0; p.bw = 0; p.tone = 0; p.samples = 0; p.delay = 0; p.burst_on = p.burst_off = 0;
@@ -172,17 +179,18 @@ static int file_mode(int argc, char **argv) {
     FILE *fin = std::fopen(argv[3], "rb"), *fout = std::fopen(argv[4], "wb");
     if (!fin || !fout || L == 0) { std::fprintf(stderr, "cannot open the stream files\n"); return 2; }
     std::fseek(fin, 0, SEEK_END);
-    const long long n_buffers = std::ftell(fin) / (long long)(L * sizeof(float2));
+    const long long n_buffers = std::ftell(fin) / (long long)(L * in_bytes);
     std::fseek(fin, 0, SEEK_SET);
     p.samples = (size_t)n_buffers * L;
 
     RX_buffer_demodulator::device_index() = 0;
     RX_buffer_demodulator *demodulator = new RX_buffer_demodulator(&p);  // link_threads.cpp:121
+    if (sc16 && !demodulator->prepare_sc16()) { std::fprintf(stderr, "prepare_sc16 failed\n"); return 1; }
     const size_t out_len = (size_t)gsdr_demod_out_capacity_of(demodulator);
     const int pool = GSDR_PIPELINE_DEPTH + 1;
-    std::vector<float2 *> in_pool(pool), out_pool(pool);
+    std::vector<float2 *> in_pool(pool), out_pool(pool);     // sc16: the input buffers hold gsdr_sc16, half the bytes
     for (int i = 0; i < pool; ++i)
-        if (hipHostMalloc((void **)&in_pool[i], L * sizeof(float2)) != hipSuccess ||
+        if (hipHostMalloc((void **)&in_pool[i], L * in_bytes) != hipSuccess ||
             hipHostMalloc((void **)&out_pool[i], out_len * sizeof(float2)) != hipSuccess) {
             std::fprintf(stderr, "pinned allocation failed\n");
             return 1;
@@ -200,14 +208,15 @@ static int file_mode(int argc, char **argv) {
     for (long long k = 0; recv_samples < p.samples; ++k) {                       // :647
         const int slot = (int)(k % pool);
         if (pipelined && (int)in_flight.size() == GSDR_PIPELINE_DEPTH) retire();  // frees slot k % pool
-        if (std::fread(in_pool[slot], sizeof(float2), L, fin) != L) { std::fprintf(stderr, "short read\n"); return 1; }
+        if (std::fread(in_pool[slot], in_bytes, L, fin) != L) { std::fprintf(stderr, "short read\n"); return 1; }
         recv_samples += L;                                                        // :660
         float2 *in = in_pool[slot], *out = out_pool[slot];
+        const gsdr_sc16 *in16 = reinterpret_cast<const gsdr_sc16 *>(in);
         if (pipelined) {
-            if (!demodulator->submit(&in, &out)) { std::fprintf(stderr, "submit failed\n"); return 1; }
+            if (!(sc16 ? demodulator->submit(in16, &out) : demodulator->submit(&in, &out))) { std::fprintf(stderr, "submit failed\n"); return 1; }
             in_flight.push(slot);
         } else {
-            const int n = demodulator->process(&in, &out);                        // :666
+            const int n = sc16 ? demodulator->process(in16, &out) : demodulator->process(&in, &out);  // :666
             lengths.push_back(n);
             std::fwrite(out, sizeof(float2), (size_t)n, fout);
         }
@@ -216,8 +225,8 @@ static int file_mode(int argc, char **argv) {
     demodulator->close();
     std::fclose(fin);
     std::fclose(fout);
-    std::printf("{\"harness\": \"rx_single_link file%s\", \"channels\": %d, \"buffers\": %lld, \"lengths\": [",
-                pipelined ? " (submit/wait)" : "", channels, n_buffers);
+    std::printf("{\"harness\": \"rx_single_link file%s%s\", \"channels\": %d, \"buffers\": %lld, \"lengths\": [",
+                pipelined ? " (submit/wait)" : "", sc16 ? " sc16" : "", channels, n_buffers);
     for (size_t i = 0; i < lengths.size(); ++i) std::printf("%s%d", i ? ", " : "", lengths[i]);
     std::printf("]}\n");
     for (int i = 0; i < pool; ++i) { (void)hipHostFree(in_pool[i]); (void)hipHostFree(out_pool[i]); }
@@ -231,6 +240,7 @@ int main(int argc, char **argv) {
     const int decim = argc > 2 ? std::atoi(argv[2]) : 100;
     const int n_buffers = argc > 3 ? std::atoi(argv[3]) : 200;
     const bool pipelined = argc > 4 && std::string(argv[4]) == "pipe";
+    const bool sc16 = argc > 4 && std::string(argv[argc - 1]) == "sc16";
     const size_t L = 1000000;  // DEFAULT_BUFFER_LEN, ref: headers/USRP_server_settings.hpp:102
     const int rate = 200000000;
 
@@ -252,19 +262,27 @@ int main(int argc, char **argv) {
 
     RX_buffer_demodulator::device_index() = 0;
     RX_buffer_demodulator *demodulator = new RX_buffer_demodulator(&p);  // link_threads.cpp:121
+    if (sc16 && !demodulator->prepare_sc16()) { std::fprintf(stderr, "prepare_sc16 failed\n"); return 1; }
 
-    // pinned pools (preallocator<float2> uses cudaMallocHost)
+    // pinned pools (preallocator<float2> uses cudaMallocHost); sc16: the input pool holds gsdr_sc16, half the bytes
     const int pool = 8;
     const size_t out_len = L * std::max<size_t>(p.data_mem_mult, 1);
     std::vector<float2 *> in_pool(pool), out_pool(pool);
     for (int i = 0; i < pool; ++i) {
-        if (hipHostMalloc((void **)&in_pool[i], L * sizeof(float2)) != hipSuccess ||
+        if (hipHostMalloc((void **)&in_pool[i], L * (sc16 ? sizeof(gsdr_sc16) : sizeof(float2))) != hipSuccess ||
             hipHostMalloc((void **)&out_pool[i], out_len * sizeof(float2)) != hipSuccess) {
             std::fprintf(stderr, "pinned allocation failed\n");
             return 1;
         }
         std::normal_distribution<float> g(0.f, 0.1f);
-        for (size_t j = 0; j < L; ++j) in_pool[i][j] = float2{g(rng), g(rng)};
+        // the same source either way; quantised here, once, outside the timed loop (full scale 1.0, saturating)
+        auto q = [](float v) { return (int16_t)std::min(32767.f, std::max(-32768.f, std::nearbyint(v * 32768.f))); };
+        gsdr_sc16 *in16 = reinterpret_cast<gsdr_sc16 *>(in_pool[i]);
+        for (size_t j = 0; j < L; ++j) {
+            const float2 v = float2{g(rng), g(rng)};
+            if (sc16) in16[j] = gsdr_sc16{q(v.x), q(v.y)};
+            else in_pool[i][j] = v;
+        }
     }
 
     BlockingQueue<RX_wrapper> rx_queue, stream_queue;
@@ -316,10 +334,12 @@ int main(int argc, char **argv) {
         const auto a = std::chrono::steady_clock::now();
         if (pipelined) {
             if ((int)in_flight.size() == GSDR_PIPELINE_DEPTH) retire();
-            demodulator->submit(&rx_buffer.buffer, &output_buffer);
+            if (sc16) demodulator->submit(reinterpret_cast<const gsdr_sc16 *>(rx_buffer.buffer), &output_buffer);
+            else demodulator->submit(&rx_buffer.buffer, &output_buffer);
             in_flight.push({rx_buffer, output_buffer});
         } else {
-            rx_buffer.length = demodulator->process(&rx_buffer.buffer, &output_buffer);  // :666
+            rx_buffer.length = sc16 ? demodulator->process(reinterpret_cast<const gsdr_sc16 *>(rx_buffer.buffer), &output_buffer)
+                                    : demodulator->process(&rx_buffer.buffer, &output_buffer);  // :666
             in_free.push(rx_buffer.buffer);                                    // :669
             rx_buffer.buffer = output_buffer;                                  // :672
             stream_queue.push(rx_buffer);                                      // :676
@@ -341,7 +361,7 @@ int main(int argc, char **argv) {
                 "\"msamples_per_s_pcie_inclusive\": %.1f, \"ms_per_buffer\": %.3f, \"worst_ms\": %.3f, \"worst_at_call\": %lld, "
                 "\"worst_ms_after_first_%d_calls\": %.3f, \"calls_above_3ms\": %lld, "
                 "\"realtime_factor_200Msps\": %.2f, \"streamed_samples\": %lld}\n",
-                pipelined ? " (submit/wait)" : "", n_tones, decim, n_buffers, msps, sec / n_buffers * 1e3, worst_ms, worst_at,
+                pipelined ? (sc16 ? " (submit/wait) sc16" : " (submit/wait)") : (sc16 ? " sc16" : ""), n_tones, decim, n_buffers, msps, sec / n_buffers * 1e3, worst_ms, worst_at,
                 2 * GSDR_PIPELINE_DEPTH, worst_steady_ms, calls_above_3ms, msps / 200.0,
                 streamed.load());
     for (int i = 0; i < pool; ++i) { (void)hipHostFree(in_pool[i]); (void)hipHostFree(out_pool[i]); }
