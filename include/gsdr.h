@@ -115,6 +115,21 @@ int gsdr_demod_wait(gsdr_demod *h);
  * leave idle (GSDR_PIPE_OVERLAP=0: strictly one after the other). */
 int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev);
 
+/* Extents and alignment of device pointers -- gsdr_demod_process_device, gsdr_demod_submit_device and their sc16
+ * forms below:
+ *  - exactly buffer_len samples are read from in_dev: in_dev[0, buffer_len).  Nothing in front of it or behind it is
+ *    read, whatever the decimation, the tile sizes of the kernel or the padding of its windows (where a kernel
+ *    reads in whole blocks, the rows that would leave the buffer are served from copies the handle owns), and
+ *    in_dev is never written;
+ *  - only out_dev[0, gsdr_demod_out_capacity()) is written, and the returned length n is <= that capacity;
+ *    out_dev[0, n) is valid, what a call leaves in out_dev[n, capacity) is unspecified;
+ *  - the pointers need their natural alignment only: 8 bytes for gsdr_c64, 4 bytes for gsdr_sc16 input.  They may
+ *    point anywhere into a larger allocation, and the output does not depend, bit for bit, on where they point or on
+ *    what lies around the buffers.
+ * (What tests/test_gpu_extents.py can and cannot see of this: DESIGN.md section 3.)
+ * The writers further down (gsdr_txgen_get_device, gsdr_txgen_tones_fill, gsdr_source_tones, gsdr_source_chirp)
+ * write exactly the n (gsdr_txgen_get_device: buffer_len) samples they are asked for, to an 8-byte aligned out_dev. */
+
 /* Creates now what the entries above would otherwise create on first use (device
  * staging buffers of the host-pointer entries, the streams, events and per-slot
  * buffers of the pipelined ones), so that the first buffers of a measurement are not
