@@ -90,6 +90,10 @@ SIGNATURES = [
     ("gsdr_demod_submit_device_sc16", C.c_int, [_vp, _vp, _vp]),
     ("gsdr_widen_sc16_device", C.c_int, [_vp, _vp, C.c_longlong, C.c_float, _vp]),
     ("gsdr_widen_sc16_host", None, [_vp, _vp, C.c_longlong, C.c_float]),
+    ("gsdr_demod_set_frame_average", C.c_int, [_vp, C.c_int, C.c_int]),
+    ("gsdr_demod_frame_average", C.c_int, [_vp, _ip]),
+    ("gsdr_frame_average_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    ("gsdr_frame_average_host", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     ("gsdr_demod_close", None, [_vp]),
     ("gsdr_last_error", C.c_char_p, [_vp]),
     ("gsdr_abi_version", C.c_int, []),

@@ -230,6 +230,11 @@ hipError_t launch_pfb_filter(const float2 *raw, const float *window, int nfft, i
                              hipStream_t st);
 // out[frame][u] = spectra[frame][sel[u]], u < n_out (ref: tone_select, cpp/kernels.cu:520-554)
 hipError_t launch_pfb_select(const float2 *spectra, int nfft, int frames_n, const int *sel, int n_out, float2 *out, hipStream_t st);
+// mean of k consecutive frames per channel (the contract: include/gsdr.h, gsdr_frame_average_device): frames
+// [n_frames][n_ch] behind `count` < k frames already summed in acc_in; (count + n_frames) / k rows to out, the open
+// group's sums (or zeros) to acc_out; one launch, also when n_frames == 0
+hipError_t launch_pfb_average(const float2 *frames, long long n_frames, int n_ch, int k, int kind, int count, const float2 *acc_in,
+                              float2 *acc_out, float2 *out, hipStream_t st);
 const char *fft_kernel_name();
 // The whole PFB of a frame in one workgroup (filter, in-LDS transform, bin selection): frames of up to
 // kPfbLdsMaxN points whose prime factors do not exceed kPfbLdsMaxPrime.

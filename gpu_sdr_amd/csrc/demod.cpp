@@ -228,6 +228,12 @@ struct gsdr_demod {
     float2 *d_pfb_tw = nullptr;                      // w_nfft^k
     int *d_pfb_sel = nullptr;                        // TONES: bin of every output column
     float2 *d_pfb_carry[kStageSets] = {};            // the samples a call leaves over (at most F*nfft)
+    // ---- TONES / NOISE, mean of avg_k consecutive frames (gsdr_demod_set_frame_average; 1: off, nothing below is used) ----
+    int avg_k = 1, avg_kind = GSDR_AVERAGE_COMPLEX;
+    int avg_count = 0;                               // frames of the open group, summed in d_avg_acc[avg_seq % 2]
+    unsigned long long avg_seq = 0;                  // launches of pfb_average_kernel so far: they read one accumulator, write the other
+    float2 *d_avg_frames = nullptr;                  // [batching][ddc_channels]: where the PFB writes its frames instead of `out`
+    float2 *d_avg_acc[2] = {nullptr, nullptr};       // [ddc_channels] each
     // ---- CHIRP ----
     ChirpShape cs{};
     int ppt = 0;
@@ -1049,6 +1055,25 @@ int enqueue_pfb(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     return ret;
 }
 
+// TONES / NOISE with gsdr_demod_set_frame_average(k > 1): the PFB writes its frames to the handle's frame buffer, and
+// pfb_average_kernel behind it on the same stream writes the groups that complete to `out` and the sums of the open
+// group to the other accumulator.  The bookkeeping is host integers, so the returned length is known at once.  The
+// chain of accumulators is ordered like the raw-window carry: by the stream, and by join_streams when it changes.
+int enqueue_pfb_average(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
+    const int cb = h->bh.current_batch;
+    const size_t ev0 = h->ev_used;
+    if (enqueue_pfb(h, in, h->d_avg_frames, st) < 0) return -1;
+    if (cb <= 0) return 0;
+    const long long rows = ((long long)h->avg_count + cb) / h->avg_k;
+    HIPCHK(h, gsdr::launch_pfb_average(h->d_avg_frames, cb, h->ddc_channels, h->avg_k, h->avg_kind, h->avg_count,
+                                       h->d_avg_acc[h->avg_seq % 2], h->d_avg_acc[(h->avg_seq + 1) % 2], out, st));
+    // the profile pair of this call (if it is a timed one) closes behind the averaging: recorded again, an event keeps the later point
+    if (h->ev_used > ev0) HIPCHK(h, hipEventRecord(h->ev_pool[h->ev_used - 1].second, st));
+    h->avg_seq++;
+    h->avg_count = (int)(((long long)h->avg_count + cb) % h->avg_k);
+    return (int)(rows * h->ddc_channels);
+}
+
 // ref: process_chirp, cpp/USRP_demodulator.cpp:342-397
 int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     hipEvent_t stop = nullptr;
@@ -1472,7 +1497,7 @@ static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 
     switch (h->mode) {
         case GSDR_DIRECT: n = enqueue_direct(h, in, out, st); break;
         case GSDR_TONES:
-        case GSDR_NOISE: n = enqueue_pfb(h, in, out, st); break;
+        case GSDR_NOISE: n = h->avg_k > 1 ? enqueue_pfb_average(h, in, out, st) : enqueue_pfb(h, in, out, st); break;
         case GSDR_CHIRP: n = enqueue_chirp(h, in, out, st); break;
         case GSDR_NODSP:  // ref: process_nodsp :335-339
             HIPCHK(h, hipMemcpyAsync(out, in, (size_t)h->L * sizeof(float2),
@@ -1633,7 +1658,9 @@ static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, 
     // of rotating streams together (carry, completion) cost more than their overlap gives -- per 1 M-sample buffer
     // 16.3 against 12.0 us in order at 1024 points, 17.0 against 10.2 at 256, 25.7 against 15.4 at 1230
     // (profiles/r03_pfb_api_ab.log)
-    const bool overlap = h->sw.pipe_overlap && h->mfma && !h->pfb_lds && ddc;
+    // ... and so does a handle that averages frames (gsdr_demod_set_frame_average): its accumulators pass from call to
+    // call in stream order
+    const bool overlap = h->sw.pipe_overlap && h->mfma && !h->pfb_lds && ddc && h->avg_k <= 1;
     hipStream_t cs = overlap ? h->s_main[h->pipe_seq % (unsigned)h->sw.pipe_streams] : h->stream;
     if (up) HIPCHK(h, hipStreamWaitEvent(cs, up, 0));
     if (overlap) {
@@ -1685,6 +1712,13 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     // first use of a stream (its hardware queue), of the copy engines in both directions and of
     // the code object costs milliseconds: pay them here, not on the first packets
     HIPCHK(h, gsdr::launch_warm(h->stream));
+    // the averaging kernel's first launch, on a frame of zeros; nothing has gone through the handle yet (otherwise the
+    // kernel has run already), so no group is open and the sums it leaves in the other accumulator are never read
+    if (h->avg_k > 1 && h->win_seq == 0) {
+        HIPCHK(h, hipMemsetAsync(h->d_avg_frames, 0, (size_t)h->ddc_channels * sizeof(float2), h->stream));
+        HIPCHK(h, gsdr::launch_pfb_average(h->d_avg_frames, 1, h->ddc_channels, h->avg_k, h->avg_kind, 0, h->d_avg_acc[0],
+                                           h->d_avg_acc[1], h->d_avg_frames, h->stream));
+    }
     if (h->pipe_ready) {
         for (int i = 0; i < kPipeStreams; ++i) HIPCHK(h, gsdr::launch_warm(h->s_main[i]));
         float2 *pin = nullptr;
@@ -1706,6 +1740,7 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
         gsdr_demod *twin = demod_create(&h->pc, h->sw);
         gsdr_c64 *pin_in = nullptr, *pin_out = nullptr;
         bool ok = twin != nullptr;
+        ok = ok && (h->avg_k <= 1 || gsdr_demod_set_frame_average(twin, h->avg_k, h->avg_kind) == 0);
         ok = ok && hipHostMalloc((void **)&pin_in, (size_t)h->L * sizeof(gsdr_c64)) == hipSuccess;
         ok = ok && hipHostMalloc((void **)&pin_out, (size_t)(h->capacity > 0 ? h->capacity : 1) * sizeof(gsdr_c64)) == hipSuccess;
         if (ok) {
@@ -1909,6 +1944,9 @@ void gsdr_demod_close(gsdr_demod *h) {
     if (h->d_pfb_sel) (void)hipFree(h->d_pfb_sel);
     for (int i = 0; i < kStageSets; ++i)
         if (h->d_pfb_carry[i]) (void)hipFree(h->d_pfb_carry[i]);
+    if (h->d_avg_frames) (void)hipFree(h->d_avg_frames);
+    for (float2 *p : h->d_avg_acc)
+        if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);  // ref: 03_implement.md:58-63
     delete h;
 }
@@ -1924,6 +1962,83 @@ int gsdr_demod_set_sc16_scale(gsdr_demod *h, float scale) {
 }
 
 float gsdr_demod_sc16_scale(const gsdr_demod *h) { return h ? h->sc16_scale : 0.f; }
+
+int gsdr_demod_set_frame_average(gsdr_demod *h, int k, int kind) {
+    if (!h) return -1;
+    if (h->mode != GSDR_TONES && h->mode != GSDR_NOISE) {
+        h->err = "frame average: only TONES and NOISE handles have frames to average";
+        return -1;
+    }
+    if (k < 1 || k > GSDR_FRAME_AVERAGE_MAX) {
+        h->err = "frame average: k must be in [1, " + std::to_string(GSDR_FRAME_AVERAGE_MAX) + "]";
+        return -1;
+    }
+    if (kind != GSDR_AVERAGE_COMPLEX && kind != GSDR_AVERAGE_POWER) {
+        h->err = "frame average: kind must be GSDR_AVERAGE_COMPLEX (0) or GSDR_AVERAGE_POWER (1)";
+        return -1;
+    }
+    if (h->win_seq > 0 || h->pipe_count > 0) {
+        h->err = "frame average: must be set before the first buffer goes through the handle";
+        return -1;
+    }
+    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
+    if (k > 1) {
+        // everything the averaging needs, now (nothing is allocated by the first packets); kept when k changes again
+        if (!h->d_avg_frames) HIPCHK(h, dev_alloc(&h->d_avg_frames, (size_t)h->ddc_channels * (size_t)h->batching));
+        for (auto &p : h->d_avg_acc) {
+            if (!p) HIPCHK(h, dev_alloc(&p, (size_t)h->ddc_channels));
+            HIPCHK(h, hipMemset(p, 0, (size_t)h->ddc_channels * sizeof(float2)));
+        }
+    }
+    const long long capacity = (long long)h->ddc_channels * ((h->batching + k - 1) / k);
+    if (capacity > h->capacity) {
+        // output staging that gsdr_demod_prepare sized for a larger k: nothing has used it yet, the entries make it anew
+        if (h->d_out) (void)hipFree(h->d_out);
+        if (h->d_in) (void)hipFree(h->d_in);
+        h->d_in = h->d_out = nullptr;     // (the host entry allocates the two together)
+        for (auto &sl : h->slot) {
+            if (sl.d_out) (void)hipFree(sl.d_out);
+            sl.d_out = nullptr;
+        }
+    }
+    h->avg_k = k;
+    h->avg_kind = kind;
+    h->avg_count = 0;
+    h->capacity = capacity;
+    return 0;
+}
+
+int gsdr_demod_frame_average(const gsdr_demod *h, int *kind) {
+    if (kind) *kind = h ? h->avg_kind : GSDR_AVERAGE_COMPLEX;
+    return h ? h->avg_k : 0;
+}
+
+int gsdr_frame_average_device(const gsdr_c64 *frames_dev, int n_frames, int n_ch, int k, int kind, int count,
+                              const gsdr_c64 *acc_in_dev, gsdr_c64 *acc_out_dev, gsdr_c64 *out_dev, void *hip_stream) {
+    const char *bad = nullptr;
+    if (n_frames < 0 || n_ch < 1) bad = "n_frames must be >= 0 and n_ch >= 1";
+    else if (k < 1 || k > GSDR_FRAME_AVERAGE_MAX) bad = "k must be in [1, 1048576]";
+    else if (kind != GSDR_AVERAGE_COMPLEX && kind != GSDR_AVERAGE_POWER) bad = "kind must be GSDR_AVERAGE_COMPLEX or GSDR_AVERAGE_POWER";
+    else if (count < 0 || count >= k) bad = "count must be in [0, k)";
+    else if (!acc_out_dev || (n_frames > 0 && !frames_dev) || (count > 0 && !acc_in_dev) ||
+             (((long long)count + n_frames) / k > 0 && !out_dev)) bad = "null buffer";
+    else if (((uintptr_t)frames_dev | (uintptr_t)acc_in_dev | (uintptr_t)acc_out_dev | (uintptr_t)out_dev) & 7) bad = "pointers must be 8-byte aligned";
+    if (bad) {
+        g_create_error = std::string("gsdr_frame_average_device: ") + bad;
+        return -1;
+    }
+    const hipError_t e = gsdr::launch_pfb_average(reinterpret_cast<const float2 *>(frames_dev), n_frames, n_ch, k, kind, count,
+                                                  reinterpret_cast<const float2 *>(acc_in_dev), reinterpret_cast<float2 *>(acc_out_dev),
+                                                  reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_frame_average_device: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return (int)(((long long)count + n_frames) / k);
+}
+
+// gsdr_frame_average_host (host_logic.cpp) leaves its message here
+void gsdr_note_error_(const char *msg) { g_create_error = msg ? msg : ""; }
 
 int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream) {
     if (n < 0 || (n > 0 && (!in_dev || !out_dev))) {
@@ -2024,6 +2139,8 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"rotation_blocks\": " + std::to_string(h->mfma && h->mac3 && h->rot2 ? 2 : 1);
     s += ", \"rotation_min_blocks\": " + std::to_string(kRot2MinBlocks);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
+    s += ", \"frame_average\": " + std::to_string(h->avg_k);
+    s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";
     s += ", \"timing_build\": ";
 #ifdef GSDR_TIMING_BUILD
     s += "1";

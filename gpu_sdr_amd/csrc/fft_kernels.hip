@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../../include/gsdr.h"
 #include "ddc_kernels.h"
 
 namespace gsdr {
@@ -1485,6 +1486,86 @@ hipError_t launch_pfb_select(const float2 *spectra, int nfft, int frames_n, cons
     if (nfft < 1 || frames_n < 1 || n_out < 1 || !spectra || !sel || !out) return hipErrorInvalidValue;
     const long long total = (long long)frames_n * n_out;
     hipLaunchKernelGGL(pfb_select_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, spectra, nfft, sel, n_out, total, out);
+    return hipGetLastError();
+}
+
+// ---- mean of k consecutive frames per channel (gsdr_demod_set_frame_average, gsdr_frame_average_device) ----
+// frames: [n_frames][n_ch], behind `count` (< k) frames of the open group that are already summed in acc_in.  Group
+// slot s holds the stream positions [s*k, (s+1)*k) (position = count + frame index); slots 0 .. rows-1 complete in
+// this call and go to out[s][ch], slot `rows` is the group left open and goes to acc_out (zeros when it is empty).
+// One work item per (slot, channel), channel fastest: the lanes of a wave read one contiguous segment of a frame row
+// per step (two or more segments k rows apart when n_ch is below the wave), and write one.  A work item walks its
+// frames in order -- acc = t_0, acc = fl32(acc + t_j), out = fl32(acc * fl32(1 / k)), include/gsdr.h -- four loads
+// in flight per step, the adds being the only dependent chain; nothing is contracted into an FMA.  No work item
+// reads what another writes (acc_in and acc_out are different buffers), so head, body and tail are one launch.
+template <int KIND>
+__device__ __forceinline__ float2 average_term(float2 v) {
+#pragma clang fp contract(off)
+    // plain operators: the pragma covers what is written here, not the bodies of __fmul_rn / __fadd_rn, whose
+    // operations carry the translation unit's contraction default and were fused into v_fmac_f32
+    if (KIND == GSDR_AVERAGE_POWER) {
+        const float rr = v.x * v.x, ii = v.y * v.y;
+        return make_float2(rr + ii, 0.f);
+    }
+    return v;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) GSDR_NO_PK void pfb_average_kernel(const float2 *__restrict__ frames, long long n_frames, int n_ch,
+                                                                     int k, int count, const float2 *__restrict__ acc_in,
+                                                                     float2 *__restrict__ acc_out, float2 *__restrict__ out,
+                                                                     long long rows, long long total, float inv_k) {
+#pragma clang fp contract(off)
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= total) return;
+    const long long s = g / n_ch;
+    const int ch = (int)(g - s * n_ch);
+    long long f0 = s * k - count, f1 = f0 + k;
+    if (f0 < 0) f0 = 0;
+    if (f1 > n_frames) f1 = n_frames;
+    float2 acc = make_float2(0.f, 0.f);
+    long long f = f0;
+    if (s == 0 && count > 0) {
+        acc = acc_in[ch];
+    } else if (f < f1) {
+        acc = average_term<KIND>(frames[(size_t)f * n_ch + ch]);
+        ++f;
+    }
+    const float2 *p = frames + (size_t)f * n_ch + ch;
+    for (; f + 4 <= f1; f += 4, p += (size_t)4 * n_ch) {
+        const float2 a = p[0], b = p[(size_t)n_ch], c = p[(size_t)2 * n_ch], d = p[(size_t)3 * n_ch];
+        const float2 ta = average_term<KIND>(a), tb = average_term<KIND>(b), tc = average_term<KIND>(c), td = average_term<KIND>(d);
+        acc.x = (((acc.x + ta.x) + tb.x) + tc.x) + td.x;
+        acc.y = (((acc.y + ta.y) + tb.y) + tc.y) + td.y;
+    }
+    for (; f < f1; ++f, p += n_ch) {
+        const float2 t = average_term<KIND>(*p);
+        acc.x = acc.x + t.x;
+        acc.y = acc.y + t.y;
+    }
+    if (s < rows)
+        out[g] = make_float2(acc.x * inv_k, acc.y * inv_k);
+    else
+        acc_out[ch] = acc;
+}
+
+hipError_t launch_pfb_average(const float2 *frames, long long n_frames, int n_ch, int k, int kind, int count, const float2 *acc_in,
+                              float2 *acc_out, float2 *out, hipStream_t st) {
+    if (n_frames < 0 || n_ch < 1 || k < 1 || count < 0 || count >= k || !acc_out || (n_frames > 0 && !frames) ||
+        (count > 0 && !acc_in) || (kind != GSDR_AVERAGE_COMPLEX && kind != GSDR_AVERAGE_POWER))
+        return hipErrorInvalidValue;
+    const long long rows = ((long long)count + n_frames) / k;
+    if (rows > 0 && !out) return hipErrorInvalidValue;
+    const long long total = (rows + 1) * n_ch;
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const float inv_k = 1.0f / (float)k;
+    if (kind == GSDR_AVERAGE_POWER)
+        hipLaunchKernelGGL(pfb_average_kernel<GSDR_AVERAGE_POWER>, dim3((unsigned)blocks), dim3(256), 0, st, frames, n_frames, n_ch, k,
+                           count, acc_in, acc_out, out, rows, total, inv_k);
+    else
+        hipLaunchKernelGGL(pfb_average_kernel<GSDR_AVERAGE_COMPLEX>, dim3((unsigned)blocks), dim3(256), 0, st, frames, n_frames, n_ch, k,
+                           count, acc_in, acc_out, out, rows, total, inv_k);
     return hipGetLastError();
 }
 

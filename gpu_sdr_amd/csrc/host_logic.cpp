@@ -218,4 +218,74 @@ void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float
     }
 }
 
+// Mean of k consecutive frames per channel on the host, the arithmetic of include/gsdr.h operation for operation: what
+// pfb_average_kernel (fft_kernels.hip) computes on the device, bit for bit.  Every sum and product is stored to a float
+// before it is used again, and the function is compiled without contraction, so no compiler fuses a product into a sum.
+// demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (this file without demod.cpp) has nobody to tell
+void gsdr_note_error_(const char *msg) __attribute__((weak));
+
+#if defined(__clang__)
+#define GSDR_NO_CONTRACT
+#elif defined(__GNUC__)
+#define GSDR_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define GSDR_NO_CONTRACT
+#endif
+
+GSDR_NO_CONTRACT
+int gsdr_frame_average_host(const gsdr_c64 *frames, int n_frames, int n_ch, int k, int kind, int count,
+                            const gsdr_c64 *acc_in, gsdr_c64 *acc_out, gsdr_c64 *out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const char *bad = nullptr;
+    if (n_frames < 0 || n_ch < 1) bad = "gsdr_frame_average: n_frames must be >= 0 and n_ch >= 1";
+    else if (k < 1 || k > GSDR_FRAME_AVERAGE_MAX) bad = "gsdr_frame_average: k must be in [1, 1048576]";
+    else if (kind != GSDR_AVERAGE_COMPLEX && kind != GSDR_AVERAGE_POWER) bad = "gsdr_frame_average: kind must be GSDR_AVERAGE_COMPLEX or GSDR_AVERAGE_POWER";
+    else if (count < 0 || count >= k) bad = "gsdr_frame_average: count must be in [0, k)";
+    else if (!acc_out || (n_frames > 0 && !frames) || (count > 0 && !acc_in)) bad = "gsdr_frame_average: null buffer";
+    const long long rows = bad ? 0 : ((long long)count + n_frames) / k;
+    if (!bad && rows > 0 && !out) bad = "gsdr_frame_average: null buffer";
+    if (bad) {
+        if (gsdr_note_error_) gsdr_note_error_(bad);
+        return -1;
+    }
+    const float inv_k = 1.0f / (float)k;
+    std::vector<gsdr_c64> acc((size_t)n_ch);
+    int have = count;                                  // frames summed in acc
+    for (int c = 0; c < n_ch; ++c) acc[(size_t)c] = count > 0 ? acc_in[c] : gsdr_c64{0.f, 0.f};
+    long long row = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const gsdr_c64 *fr = frames + (size_t)f * (size_t)n_ch;
+        for (int c = 0; c < n_ch; ++c) {
+            gsdr_c64 t = fr[c];
+            if (kind == GSDR_AVERAGE_POWER) {
+                const float rr = t.x * t.x;
+                const float ii = t.y * t.y;
+                t.x = rr + ii;
+                t.y = 0.f;
+            }
+            if (have == 0) {
+                acc[(size_t)c] = t;
+            } else {
+                const float sx = acc[(size_t)c].x + t.x;
+                const float sy = acc[(size_t)c].y + t.y;
+                acc[(size_t)c].x = sx;
+                acc[(size_t)c].y = sy;
+            }
+        }
+        if (++have == k) {
+            gsdr_c64 *o = out + (size_t)row * (size_t)n_ch;
+            for (int c = 0; c < n_ch; ++c) {
+                o[c].x = acc[(size_t)c].x * inv_k;
+                o[c].y = acc[(size_t)c].y * inv_k;
+            }
+            ++row;
+            have = 0;
+        }
+    }
+    for (int c = 0; c < n_ch; ++c) acc_out[c] = have > 0 ? acc[(size_t)c] : gsdr_c64{0.f, 0.f};
+    return (int)rows;
+}
+
 }  // extern "C"

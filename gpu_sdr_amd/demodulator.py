@@ -103,6 +103,15 @@ def _is_torch(x) -> bool:
 
 
 SC16_DEFAULT_SCALE = 2.0 ** -15
+AVERAGE_KINDS = ("complex", "power")       # GSDR_AVERAGE_COMPLEX, GSDR_AVERAGE_POWER
+
+
+def _average_kind(kind) -> int:
+    if kind in AVERAGE_KINDS:
+        return AVERAGE_KINDS.index(kind)
+    if isinstance(kind, int) and not isinstance(kind, bool):
+        return kind                        # the library checks the value
+    raise ValueError('kind must be "complex" or "power"')
 
 
 def _is_sc16(x) -> bool:
@@ -194,6 +203,26 @@ class RX_buffer_demodulator:
     @sc16_scale.setter
     def sc16_scale(self, scale: float) -> None:
         if self._L.gsdr_demod_set_sc16_scale(self._h, C.c_float(scale)) != 0:
+            raise GsdrError(self._L.gsdr_last_error(self._h).decode())
+
+    @property
+    def frame_average(self) -> int:
+        """k of the frame averaging (gsdr_demod_frame_average): frames per returned row; 1 is off."""
+        return int(self._L.gsdr_demod_frame_average(self._h, None))
+
+    @property
+    def frame_average_kind(self) -> str:
+        """"complex" or "power" (set_frame_average)."""
+        kind = C.c_int(0)
+        self._L.gsdr_demod_frame_average(self._h, C.byref(kind))
+        return AVERAGE_KINDS[kind.value]
+
+    def set_frame_average(self, k: int, kind="complex") -> None:
+        """TONES / NOISE: return the mean of every k consecutive frames per channel instead of the frames
+        (gsdr_demod_set_frame_average; rows [group][channel], ``out_capacity`` shrinks to channels * ceil(batching / k),
+        a call returns the groups that complete in it, possibly none).  kind "complex": mean of the complex frames;
+        "power": mean of |X|^2 in the real part.  Only before the first buffer; k = 1 switches it off."""
+        if self._L.gsdr_demod_set_frame_average(self._h, int(k), _average_kind(kind)) != 0:
             raise GsdrError(self._L.gsdr_last_error(self._h).decode())
 
     def prepare(self, host: bool = True, pipeline: bool = True, pipeline_host: bool = True, rehearse: bool = True,
@@ -367,6 +396,50 @@ def widen_sc16(in_buffer, out=None, scale: float = SC16_DEFAULT_SCALE, stream=No
         raise ValueError("out is shorter than the input")
     L.gsdr_widen_sc16_host(in_buffer.ctypes.data, out.ctypes.data, n, C.c_float(scale))
     return out
+
+
+def frame_average(frames, k: int, kind="complex", count: int = 0, acc=None, stream=None):
+    """The frame averaging on its own (gsdr_frame_average_device / _host, bit-identical): ``frames`` is complex64 of
+    shape (n_frames, n_ch) -- a CUDA tensor (one kernel on `stream` / the current torch stream, not synchronised) or a
+    numpy array (host, needs no GPU) --, ``count`` < k frames of the open group are already summed in ``acc`` (n_ch).
+    Returns ``(out, acc_out, count_out)``: the groups that completed, (rows, n_ch); the sums of the group left open
+    (zeros when none is); and its frame count, to be passed to the next call."""
+    kind_c = _average_kind(kind)
+    if len(frames.shape) != 2 or frames.shape[1] < 1:
+        raise ValueError("frames must have shape (n_frames, n_ch) with n_ch >= 1")
+    n_frames, n_ch = int(frames.shape[0]), int(frames.shape[1])
+    k, count = int(k), int(count)
+    if k < 1 or not 0 <= count < k:
+        raise ValueError("need k >= 1 and 0 <= count < k")
+    if count > 0 and acc is None:
+        raise ValueError("count > 0 needs the accumulator of the call before")
+    rows = (count + n_frames) // k
+    L = _lib.lib()
+    if _is_torch(frames):
+        import torch
+        def ok(t, n):
+            return _is_torch(t) and t.is_cuda and t.dtype == torch.complex64 and t.is_contiguous() and t.numel() == n
+        if not ok(frames, n_frames * n_ch) or (acc is not None and not ok(acc, n_ch)):
+            raise TypeError("need contiguous complex64 CUDA tensors; acc holds n_ch samples")
+        out = torch.empty((rows, n_ch), dtype=torch.complex64, device=frames.device)
+        acc_out = torch.empty(n_ch, dtype=torch.complex64, device=frames.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        r = L.gsdr_frame_average_device(frames.data_ptr(), n_frames, n_ch, k, kind_c, count,
+                                        acc.data_ptr() if acc is not None else None, acc_out.data_ptr(), out.data_ptr(),
+                                        C.c_void_p(stream.cuda_stream))
+    else:
+        def ok(a, n):
+            return isinstance(a, np.ndarray) and a.dtype == np.complex64 and a.flags.c_contiguous and a.size == n
+        if not ok(frames, n_frames * n_ch) or (acc is not None and not ok(acc, n_ch)):
+            raise TypeError("need contiguous complex64 arrays; acc holds n_ch samples")
+        out = np.empty((rows, n_ch), dtype=np.complex64)
+        acc_out = np.empty(n_ch, dtype=np.complex64)
+        r = L.gsdr_frame_average_host(frames.ctypes.data, n_frames, n_ch, k, kind_c, count,
+                                      acc.ctypes.data if acc is not None else None, acc_out.ctypes.data, out.ctypes.data)
+    if r != rows:
+        raise GsdrError(L.gsdr_last_error(None).decode())
+    return out, acc_out, (count + n_frames) % k
 
 
 # ---- host-side helpers of the path, straight from the library --------------

@@ -181,6 +181,20 @@ class RX_buffer_demodulator {
         return gsdr_demod_prepare(handle_, GSDR_PREPARE_HOST | GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST |
                                                GSDR_PREPARE_REHEARSE | GSDR_PREPARE_SC16) == 0;
     }
+    //! TONES / NOISE (extension, see "mean of k consecutive frames" in gsdr.h): process() / wait() return one row per
+    //! group of k consecutive frames, and out_capacity() shrinks accordingly; only before the first buffer.  The
+    //! constructor keeps refusing param::decim > 0 for these modes: a server maps the client's decim to this call.
+    bool set_frame_average(int k, int kind = GSDR_AVERAGE_COMPLEX) {
+        if (gsdr_demod_set_frame_average(handle_, k, kind) != 0) {
+            std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(handle_));
+            return false;
+        }
+        // the first launch of the averaging kernel now, not with the first packet
+        if (k > 1 && gsdr_demod_prepare(handle_, GSDR_PREPARE_HOST | GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST) != 0)
+            std::fprintf(stderr, "WARNING: demodulator: %s\n", gsdr_last_error(handle_));
+        return true;
+    }
+    int frame_average() const { return gsdr_demod_frame_average(handle_, nullptr); }
     int process(const gsdr_sc16* in, float2** out) {
         const int n = gsdr_demod_process_sc16(handle_, in, reinterpret_cast<gsdr_c64*>(*out));
         if (n < 0) {

@@ -178,6 +178,38 @@ int gsdr_demod_submit_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c
 int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream);
 void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float scale);
 
+/* ---- mean of k consecutive frames, TONES and NOISE (an extension: what the reference's decimate_spectra /
+ * decimate_pfb intend and do not deliver, ref: cpp/kernels.cu:704-790, cpp/USRP_demodulator.cpp:511-534,593-624;
+ * gsdr_demod_create() keeps refusing param::decim > 0 for these modes) ------------------------------------------
+ * A property of the handle like the sc16 scale: with k > 1 every RX entry returns, instead of one row per frame, one
+ * row per GROUP of k consecutive frames -- group g is frames [g*k, (g+1)*k) counted from the creation of the handle --
+ * and a call returns channels x the number of groups that complete in it (possibly 0), rows [group][channel].  The
+ * open group is carried to the next call, on whatever entry or stream that call is made.
+ * Arithmetic, per channel, real and imaginary part separately, every operation one IEEE single-precision operation
+ * rounded to nearest and nothing fused:  acc = t_0 (not 0 + t_0);  acc = acc + t_j in frame order;  when the k-th
+ * frame is in, the row is acc * (1.0f / k).  GSDR_AVERAGE_COMPLEX: t_j is the frame value.  GSDR_AVERAGE_POWER:
+ * t_j.x = re*re + im*im (two products, one sum), t_j.y = 0.  The result does not depend on where the stream is cut
+ * into buffers, and an Inf or NaN reaches exactly the groups that hold it.
+ * gsdr_demod_set_frame_average: TONES and NOISE handles, 1 <= k <= GSDR_FRAME_AVERAGE_MAX, before the first buffer
+ * has gone through the handle and with nothing outstanding; otherwise -1, a message in gsdr_last_error(h), and the
+ * old setting stays.  It allocates what it needs at once, and gsdr_demod_out_capacity() becomes
+ * channels * ceil(batching / k).  k == 1 is "off": the handle runs launch for launch as if the setter had never been
+ * called.  gsdr_demod_frame_average returns k (1 = off; 0 for a NULL handle) and the kind through *kind. */
+#define GSDR_AVERAGE_COMPLEX 0   /* mean of the complex frames */
+#define GSDR_AVERAGE_POWER   1   /* mean of |X|^2 in .x, 0 in .y: what a noise spectrum needs (a complex mean of noise tends to 0) */
+#define GSDR_FRAME_AVERAGE_MAX 1048576
+int gsdr_demod_set_frame_average(gsdr_demod *h, int k, int kind);
+int gsdr_demod_frame_average(const gsdr_demod *h, int *kind /* may be NULL */);
+/* The averaging on its own.  frames: [n_frames][n_ch]; count (0 <= count < k) frames of the open group are already
+ * summed in acc_in[n_ch] (not read when count == 0); writes the completed groups to out ([rows][n_ch]) and the new open
+ * group's partial sums to acc_out[n_ch] (zeros when none is open); acc_in and acc_out must not overlap.  Returns
+ * rows = (count + n_frames) / k, or -1 (gsdr_last_error(NULL)).  _device: device pointers, 8-byte aligned, one kernel
+ * enqueued on hip_stream and not synchronised; _host: the same bits on the CPU (needs no GPU). */
+int gsdr_frame_average_device(const gsdr_c64 *frames_dev, int n_frames, int n_ch, int k, int kind, int count,
+                              const gsdr_c64 *acc_in_dev, gsdr_c64 *acc_out_dev, gsdr_c64 *out_dev, void *hip_stream);
+int gsdr_frame_average_host(const gsdr_c64 *frames, int n_frames, int n_ch, int k, int kind, int count,
+                            const gsdr_c64 *acc_in, gsdr_c64 *acc_out, gsdr_c64 *out);
+
 /* ref: RX_buffer_demodulator::close, cpp/USRP_demodulator.cpp:333 (+ :466-698).
  * Frees every device allocation and the stream, then the handle itself. */
 void gsdr_demod_close(gsdr_demod *h);

@@ -20,6 +20,10 @@
 //     thread draining the stream queue (cpp/USRP_server_network.cpp:195-308); the demodulators run through the
 //     overlapped entry, gsdr_demod_submit() / gsdr_demod_wait();
 //   * burst mode's buffer length, buffer_len = burst_on * rate (link_threads.cpp:99-102).
+//   * decim > 0 of a TONES / NOISE command (pyUSRP's Get_full_spec(decimation=...)): the mean of `decim` consecutive
+//     frames, through gsdr_demod_set_frame_average() on a demodulator created with decim = 0 -- what the reference's
+//     decimate_spectra / decimate_pfb intend (cpp/USRP_demodulator.cpp:511-534,593-624); a buffer in which no group of
+//     frames completes sends no packet.
 // What it drops: UHD, HDF5 writer, reconnect threads, burst timing, delays, logging.
 //
 //   hipcc -O2 -std=c++17 -Iinclude tools/gsdr_server.cpp -Lgpu_sdr_amd -lgsdr \
@@ -158,6 +162,7 @@ struct FrontEnd {              // one RX demodulator fed by its TX generator (or
     gsdr_param_c rx{}, tx{};
     gsdr_antenna_info rxi{}, txi{};
     bool has_tx = false;
+    int frame_average = 1;            // TONES / NOISE commands with decim > 0: frames per streamed row (run_measurement)
     char code = 'B';
     int usrp = 0;
     long long n_buffers = 0;          // ceil(samples / buffer_len): rx_single_link counts INPUT samples (:660)
@@ -202,6 +207,10 @@ static void rx_link(FrontEnd *F, BlockingQueue<Packet> *stream_queue, int device
             n = 0;
         }
         F->in_pool.trash(f.in);                                                   // input_memory->trash (:669)
+        if (n == 0 && F->frame_average > 1) {   // no group of frames completed in this buffer: nothing to send
+            F->out_pool.trash(f.out);
+            return;
+        }
         Packet p{f.out, &F->out_pool, gsdr_rx_header{F->usrp, F->code, packet++, n, 0, gsdr_demod_channels(F->dem)}};
         stream_queue->push(p);                                                    // :676
     };
@@ -268,10 +277,23 @@ static bool run_measurement(const gsdr_command *cmd, int data_fd, int device) {
             ok = false;
             break;
         }
+        // TONES / NOISE with decim > 0 (pyUSRP's Get_full_spec(decimation=...)): the mean of `decim` consecutive
+        // frames.  The library refuses decim > 0 for these modes (it means the reference's own, broken, path there);
+        // the demodulator is created with decim = 0 and averages its frames instead, see gsdr_demod_set_frame_average
+        const int wave0 = F.rx.n_wave_type > 0 ? F.rx.wave_type[0] : -1;
+        if ((wave0 == GSDR_TONES || wave0 == GSDR_NOISE) && F.rx.decim > 0) {
+            F.frame_average = F.rx.decim > GSDR_FRAME_AVERAGE_MAX ? GSDR_FRAME_AVERAGE_MAX : (int)F.rx.decim;
+            F.rx.decim = 0;
+        }
         F.dem = gsdr_demod_create(&F.rx);                       // TXRX::set: new RX_buffer_demodulator (:121,:136)
         if (!F.dem) {
             std::fprintf(stderr, "ERROR: %s\n", gsdr_last_error(nullptr));
             continue;
+        }
+        if (F.frame_average > 1 && gsdr_demod_set_frame_average(F.dem, F.frame_average, GSDR_AVERAGE_COMPLEX) != 0) {
+            std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(F.dem));
+            ok = false;
+            break;
         }
         if (gsdr_demod_prepare(F.dem, GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST) != 0)
             std::fprintf(stderr, "WARNING: demodulator: %s\n", gsdr_last_error(F.dem));

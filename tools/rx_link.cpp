@@ -25,7 +25,8 @@
 // (with "sc16" the input file holds whole buffers of int16 I, Q pairs instead of complex64)
 // The same loop over a recorded stream (tests/test_gpu_rxlink.py): config.txt holds
 // "key value..." lines (mode DIRECT|TONES|CHIRP|NOISE|NODSP, rate, buffer_len, decim,
-// pf_average, fft_tones, freq ..., chirp_f ..., swipe_s ..., chirp_t ...); in.c64 holds
+// pf_average, fft_tones, freq ..., chirp_f ..., swipe_s ..., chirp_t ...; TONES / NOISE: frame_average K [power],
+// the mean of every K consecutive frames through RX_buffer_demodulator::set_frame_average); in.c64 holds
 // whole buffers of complex64; every packet's payload is appended to out.c64 and the
 // valid lengths are printed, as the streamer would put them into the packet headers.
 #include <hip/hip_runtime.h>
@@ -154,6 +155,7 @@ static int file_mode(int argc, char **argv) {
     p.buffer_len = 0; p.tuning_mode = false; p.decim = 0; p.data_mem_mult = 1; p.fft_tones = 0; p.pf_average = 4;
     w_type mode = NODSP;
     int channels = -1;
+    int frame_average = 1, frame_average_kind = GSDR_AVERAGE_COMPLEX;
     std::ifstream cfg(argv[2]);
     if (!cfg) { std::fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
     std::string line;
@@ -166,6 +168,11 @@ static int file_mode(int argc, char **argv) {
         else if (key == "rate") is >> p.rate;
         else if (key == "buffer_len") is >> p.buffer_len;
         else if (key == "decim") is >> p.decim;
+        else if (key == "frame_average") {
+            std::string kind;
+            is >> frame_average;
+            if (is >> kind) frame_average_kind = kind == "power" ? GSDR_AVERAGE_POWER : GSDR_AVERAGE_COMPLEX;
+        }
         else if (key == "pf_average") is >> p.pf_average;
         else if (key == "fft_tones") is >> p.fft_tones;
         else if (key == "freq") { int v; while (is >> v) p.freq.push_back(v); }
@@ -185,8 +192,9 @@ static int file_mode(int argc, char **argv) {
 
     RX_buffer_demodulator::device_index() = 0;
     RX_buffer_demodulator *demodulator = new RX_buffer_demodulator(&p);  // link_threads.cpp:121
+    if (frame_average != 1 && !demodulator->set_frame_average(frame_average, frame_average_kind)) return 1;
     if (sc16 && !demodulator->prepare_sc16()) { std::fprintf(stderr, "prepare_sc16 failed\n"); return 1; }
-    const size_t out_len = (size_t)gsdr_demod_out_capacity_of(demodulator);
+    const size_t out_len = (size_t)gsdr_demod_out_capacity_of(demodulator);   // (after set_frame_average: it shrinks)
     const int pool = GSDR_PIPELINE_DEPTH + 1;
     std::vector<float2 *> in_pool(pool), out_pool(pool);     // sc16: the input buffers hold gsdr_sc16, half the bytes
     for (int i = 0; i < pool; ++i)
