@@ -6,7 +6,7 @@ synthetic IQ source used for benchmarking.
 """
 from .demodulator import (GsdrError, RX_buffer_demodulator, RX_wrapper,  # noqa: F401
                           VNA_decimator_helper, buffer_helper, chirp_derive, frame_average,
-                          make_flat_window, make_sinc_window, param, pfb_batching,
+                          make_flat_window, make_sinc_window, narrow_sc16, param, pfb_batching,
                           pfb_tone_bins, string_to_w_type, w_type, w_type_to_str, widen_sc16)
 
 from .generator import TX_buffer_generator  # noqa: E402,F401
@@ -14,6 +14,6 @@ from .generator import TX_buffer_generator  # noqa: E402,F401
 __all__ = [
     "TX_buffer_generator",
     "GsdrError", "RX_buffer_demodulator", "RX_wrapper", "VNA_decimator_helper",
-    "buffer_helper", "chirp_derive", "frame_average", "make_flat_window", "make_sinc_window", "param",
+    "buffer_helper", "chirp_derive", "frame_average", "make_flat_window", "make_sinc_window", "narrow_sc16", "param",
     "pfb_batching", "pfb_tone_bins", "string_to_w_type", "w_type", "w_type_to_str", "widen_sc16",
 ]

@@ -90,6 +90,8 @@ SIGNATURES = [
     ("gsdr_demod_submit_device_sc16", C.c_int, [_vp, _vp, _vp]),
     ("gsdr_widen_sc16_device", C.c_int, [_vp, _vp, C.c_longlong, C.c_float, _vp]),
     ("gsdr_widen_sc16_host", None, [_vp, _vp, C.c_longlong, C.c_float]),
+    ("gsdr_narrow_sc16_device", C.c_int, [_vp, _vp, C.c_longlong, C.c_float, _vp, _vp]),
+    ("gsdr_narrow_sc16_host", C.c_longlong, [_vp, _vp, C.c_longlong, C.c_float]),
     ("gsdr_demod_set_frame_average", C.c_int, [_vp, C.c_int, C.c_int]),
     ("gsdr_demod_frame_average", C.c_int, [_vp, _ip]),
     ("gsdr_frame_average_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
@@ -128,6 +130,16 @@ SIGNATURES = [
     ("gsdr_txgen_get_ptr", C.c_void_p, [C.c_void_p]),
     ("gsdr_txgen_prepare_host", C.c_int, [C.c_void_p]),
     ("gsdr_txgen_mode", C.c_int, [C.c_void_p]),
+    ("gsdr_txgen_set_sc16_gain", C.c_int, [C.c_void_p, C.c_float]),
+    ("gsdr_txgen_sc16_gain", C.c_float, [C.c_void_p]),
+    ("gsdr_txgen_tones_fill_sc16", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
+    ("gsdr_txgen_get_device_sc16", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsdr_txgen_get_sc16", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gsdr_txgen_prepare_host_sc16", C.c_int, [C.c_void_p]),
+    ("gsdr_txgen_get_ptr_sc16", C.c_void_p, [C.c_void_p]),
+    ("gsdr_txgen_sc16_clipped", C.c_longlong, [C.c_void_p]),
+    ("gsdr_source_chirp_sc16", C.c_int, [_vp, C.c_longlong, C.c_ulonglong, C.POINTER(ChirpParamC), C.c_float,
+                                         C.c_float, _vp, _vp]),
     ("gsdr_chirp_derive", None, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                  C.POINTER(ChirpParamC)]),
     ("gsdr_chirp_derive_tx", None, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,

@@ -12,6 +12,7 @@
 // HBM-bound: 8 B read per sample, 8/ppt B written.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 
 #include "ddc_kernels.h"
@@ -497,17 +498,44 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void source_tones_kernel(
     }
 }
 
-__global__ __launch_bounds__(256) GSDR_NO_PK void source_chirp_kernel(float2 *__restrict__ out, long long n,
+// Where a finished TX sample goes: complex64 as it is, or narrowed to sc16 (include/gsdr.h, "sc16 output") in the
+// lane that holds it -- one dword per sample, no complex64 copy in memory and no second pass.  The two generator
+// kernels below are templates on the store; `extra` is what the store needs beyond the pointer (nothing for
+// complex64, whose instantiation has the argument list and the instructions the kernel had before there was a
+// second store).  What is computed in front of the store is the same expression, so the sc16 form is bit for bit
+// the narrowed complex64 form.
+struct StoreC64 {
+    typedef float2 Elem;
+    float2 *__restrict__ out;
+    __device__ __forceinline__ void put(long long s, float re, float im) { store_c64(out + s, re, im); }
+    __device__ __forceinline__ void finish(int) {}
+};
+struct StoreSc16 {
+    typedef int Elem;                            // a gsdr_sc16 as one dword
+    int *__restrict__ out;
+    float gain;
+    unsigned long long *__restrict__ clipped;    // may be null
+    int clips = 0;
+    __device__ __forceinline__ void put(long long s, float re, float im) { out[s] = narrow_sample(re, im, gain, clips); }
+    __device__ __forceinline__ void finish(int lane) { add_clips(clipped, clips, lane); }
+};
+
+// (sc16: s * scale is rounded to float32 before the gain multiplies it -- two roundings, as narrowing the complex64
+//  output does)
+template <typename Store, typename... Extra>
+__global__ __launch_bounds__(256) GSDR_NO_PK void source_chirp_kernel(typename Store::Elem *__restrict__ out, long long n,
                                                            unsigned long long index0,
-                                                           ChirpShape cs, float scale) {
+                                                           ChirpShape cs, float scale, Extra... extra) {
+    Store st{out, extra...};
     const bool small = cs.period < 0xffffffffull && cs.num_steps < 0xfffffffeull;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += stride) {
         const unsigned long long e = (index0 + (unsigned long long)o) % cs.period;
         float s, c;
         sincos_index(chirp_index(e, cs, small), s, c);
-        store_c64(out + o, s * scale, -c * scale);  // ref: kernels.cu:367-368
+        st.put(o, s * scale, -c * scale);  // ref: kernels.cu:367-368
     }
+    st.finish((int)(threadIdx.x & 63));
 }
 
 // ---------------------------------------------------------------------------
@@ -524,10 +552,14 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void source_chirp_kernel(float2 *__
 //   multiply-adds acc[j] += T C[k][j] with scalar second operands.  ~80 vector instructions per tone and
 //   1024 samples; the per-sample sincos of source_tones_kernel (bench.py's noisy input) is 70 x that.
 // ---------------------------------------------------------------------------
+template <typename Store, typename... Extra>
 __global__ __launch_bounds__(256) GSDR_NO_PK void tones_synth_kernel(
-    float2 *__restrict__ out, long long n, unsigned long long start, unsigned rate, unsigned long long rate_magic,
+    typename Store::Elem *__restrict__ out, long long n, unsigned long long start, unsigned rate, unsigned long long rate_magic,
     double inv_rate, const unsigned *__restrict__ fmod, const float2 *__restrict__ q0,
-    const float2 *__restrict__ btab, const float2 *__restrict__ ctab, int n_tones) {
+    const float2 *__restrict__ btab, const float2 *__restrict__ ctab, int n_tones, Extra... extra) {
+    // the store of a finished sample is the template parameter: with StoreSc16 the lane that holds (sx, sy) of sample
+    // base + 64 j + lane narrows both and writes one dword, a wave 256 contiguous bytes per stretch
+    Store st{out, extra...};
     // a workgroup makes 1024 consecutive samples; its four waves share the tones (chunks of 64 tones go
     // round the waves) and add their partial sums through the LDS: four times the waves of a wave-per-
     // stretch layout, which at one wave per SIMD was a bare latency chain (2048 tones: 708 us per buffer)
@@ -576,8 +608,9 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void tones_synth_kernel(
             sy += v.y;
         }
         const long long s = base + 64 * j + lane;
-        if (s < n) out[s] = mk2c(sx, sy);
+        if (s < n) st.put(s, sx, sy);
     }
+    st.finish(lane);
 }
 
 hipError_t launch_tones_synth(float2 *out, long long n, unsigned long long start, unsigned rate, const unsigned *fmod,
@@ -587,8 +620,23 @@ hipError_t launch_tones_synth(float2 *out, long long n, unsigned long long start
         return hipErrorInvalidValue;
     const unsigned long long magic = ~0ULL / rate;
     const long long groups = (n + 1023) / 1024;
-    hipLaunchKernelGGL(tones_synth_kernel, dim3((unsigned)groups), dim3(256), 0, st, out, n, start, rate, magic,
+    hipLaunchKernelGGL((tones_synth_kernel<StoreC64>), dim3((unsigned)groups), dim3(256), 0, st, out, n, start, rate, magic,
                        1.0 / (double)rate, fmod, q0, btab, ctab, n_tones);
+    return hipGetLastError();
+}
+
+hipError_t launch_tones_synth_sc16(void *out, long long n, unsigned long long start, unsigned rate, const unsigned *fmod,
+                                   const float2 *q0, const float2 *btab, const float2 *ctab, int n_tones, float gain,
+                                   unsigned long long *clipped, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!out || ((uintptr_t)out & 3) || ((uintptr_t)clipped & 7) || rate < 1 || start >= rate || n_tones < 0 ||
+        (n_tones > 0 && (!fmod || !q0 || !btab || !ctab)))
+        return hipErrorInvalidValue;
+    const unsigned long long magic = ~0ULL / rate;
+    const long long groups = (n + 1023) / 1024;
+    hipLaunchKernelGGL((tones_synth_kernel<StoreSc16, float, unsigned long long *>), dim3((unsigned)groups), dim3(256), 0, st,
+                       reinterpret_cast<int *>(out), n, start, rate, magic, 1.0 / (double)rate, fmod, q0, btab, ctab, n_tones, gain,
+                       clipped);
     return hipGetLastError();
 }
 
@@ -609,8 +657,19 @@ hipError_t launch_source_chirp(float2 *out, long long n, unsigned long long inde
     if (n <= 0) return hipSuccess;
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(source_chirp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, out, n,
+    hipLaunchKernelGGL((source_chirp_kernel<StoreC64>), dim3((unsigned)blocks), dim3(256), 0, st, out, n,
                        index0, cs, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_source_chirp_sc16(void *out, long long n, unsigned long long index0, const ChirpShape &cs, float scale,
+                                    float gain, unsigned long long *clipped, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!out || ((uintptr_t)out & 3) || ((uintptr_t)clipped & 7)) return hipErrorInvalidValue;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL((source_chirp_kernel<StoreSc16, float, unsigned long long *>), dim3((unsigned)blocks), dim3(256), 0, st,
+                       reinterpret_cast<int *>(out), n, index0, cs, scale, gain, clipped);
     return hipGetLastError();
 }
 

@@ -58,4 +58,47 @@ __device__ __forceinline__ void exact_phasor(unsigned long long ph, double inv_r
     im = -sn;
 }
 
+// ---- sc16 output: a float32 component narrowed to int16 (include/gsdr.h, "sc16 output") ------------------
+// v = c * gain (one IEEE multiply: the callers are compiled without contraction), r = v rounded to the nearest
+// integer, ties to even (v_rndne_f32), saturated to [-32768, 32767], NaN -> 0.  The clamp comes before the
+// conversion, so the conversion only ever sees an integer it can represent.  `clips` counts the components
+// that did not fit (NaN included; r == -32768 fits).
+__device__ __forceinline__ int narrow_component(float c, float gain, int &clips) {
+#pragma clang fp contract(off)
+    const float v = c * gain;
+    const float r = __builtin_rintf(v);
+    const bool nan = v != v, hi = r > 32767.0f, lo = r < -32768.0f;
+    clips += (nan || hi || lo) ? 1 : 0;
+    const float cl = nan ? 0.0f : hi ? 32767.0f : lo ? -32768.0f : r;
+    return (int)cl;
+}
+
+// one sample as the dword a gsdr_sc16 is: I in the low half, Q in the high half (little endian: I first)
+__device__ __forceinline__ int narrow_sample(float re, float im, float gain, int &clips) {
+    const int i = narrow_component(re, gain, clips), q = narrow_component(im, gain, clips);
+    return (i & 0xffff) | (int)((unsigned)q << 16);
+}
+
+// Integer sum over the 64 lanes of a wave with DPP row operations; the total arrives in lane 63.  Every lane of
+// the wave must be active.
+__device__ __forceinline__ int wave_isum_to_lane63(int x) {
+#define GSDR_DPP_IADD(ctrl, row_mask) x += __builtin_amdgcn_update_dpp(0, x, ctrl, row_mask, 0xf, false)
+    GSDR_DPP_IADD(0xB1, 0xf);    // quad_perm [1,0,3,2]
+    GSDR_DPP_IADD(0x4E, 0xf);    // quad_perm [2,3,0,1]
+    GSDR_DPP_IADD(0x141, 0xf);   // row_half_mirror
+    GSDR_DPP_IADD(0x140, 0xf);   // row_mirror: every lane holds the sum of its row of 16
+    GSDR_DPP_IADD(0x142, 0xa);   // row_bcast:15 into rows 1 and 3
+    GSDR_DPP_IADD(0x143, 0xc);   // row_bcast:31 into rows 2 and 3
+#undef GSDR_DPP_IADD
+    return x;
+}
+
+// The clipped components of a wave added to the caller's counter: one vector atomic from lane 63, none when the
+// wave clipped nothing (or no counter was given).  Called by whole waves, outside divergent control flow.
+__device__ __forceinline__ void add_clips(unsigned long long *__restrict__ clipped, int clips, int lane) {
+    const int total = wave_isum_to_lane63(clips);
+    if (clipped && lane == 63 && total > 0)
+        (void)__hip_atomic_fetch_add(clipped, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace gsdr

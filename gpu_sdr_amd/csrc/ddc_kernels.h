@@ -116,6 +116,10 @@ const char *mix_kernel_name(int n_tones, int tw, long long total, int K, int mix
 // sc16 input: out[k] = (float(in[k].i) * scale, float(in[k].q) * scale), k < n; `in` holds n interleaved int16 pairs
 // (4-byte aligned), `out` is 8-byte aligned; cus = compute units the grid is sized to.  n <= 0 launches nothing.
 hipError_t launch_widen_sc16(const void *in, float2 *out, long long n, float scale, int cus, hipStream_t st);
+// sc16 output: out[k] = narrowed in[k] (include/gsdr.h, "sc16 output"); `in` 8-byte, `out` 4-byte aligned device
+// pointers to n samples, `clipped` (may be null, 8-byte aligned) gets the number of clipped components added.
+hipError_t launch_narrow_sc16(const float2 *in, void *out, long long n, float gain, unsigned long long *clipped, int cus,
+                              hipStream_t st);
 
 // ---- DDC on the matrix cores (ddc_mfma.hip) --------------------------------
 struct MfmaShape {
@@ -287,6 +291,10 @@ hipError_t launch_warm(hipStream_t st);
 // ctab[k][16] = w_k^(64 j), w_k = e^(+2 pi i f_k / rate) (ref: tone_gen, cpp/kernels.cu:589-684)
 hipError_t launch_tones_synth(float2 *out, long long n, unsigned long long start, unsigned rate, const unsigned *fmod,
                               const float2 *q0, const float2 *btab, const float2 *ctab, int n_tones, hipStream_t st);
+// the same samples narrowed to sc16 in the lane that holds them (out: 4-byte aligned, gsdr_sc16)
+hipError_t launch_tones_synth_sc16(void *out, long long n, unsigned long long start, unsigned rate, const unsigned *fmod,
+                                   const float2 *q0, const float2 *btab, const float2 *ctab, int n_tones, float gain,
+                                   unsigned long long *clipped, hipStream_t st);
 const char *chirp_demod_kernel_name();
 const char *chirp_lockin_kernel_name();
 
@@ -297,5 +305,7 @@ hipError_t launch_source_tones(float2 *out, long long n, long long start, unsign
                                unsigned long long seed, hipStream_t st);
 hipError_t launch_source_chirp(float2 *out, long long n, unsigned long long index0,
                                const ChirpShape &cs, float scale, hipStream_t st);
+hipError_t launch_source_chirp_sc16(void *out, long long n, unsigned long long index0, const ChirpShape &cs, float scale,
+                                    float gain, unsigned long long *clipped, hipStream_t st);
 
 }  // namespace gsdr

@@ -644,6 +644,65 @@ hipError_t launch_widen_sc16(const void *in, float2 *out, long long n, float sca
     return hipGetLastError();
 }
 
+// ---- sc16 output: float2 narrowed to interleaved int16 I/Q -----------------------------------------------
+// The mirror of widen_sc16_kernel, arithmetic in narrow_component (ddc_device.h).  12 bytes per sample:
+//   * a lane takes four samples per step: two 16-byte loads (declared 8-byte aligned, all a float2 view
+//     guarantees), one 16-byte store; a wave reads 2 KiB and writes 1 KiB contiguous per step;
+//   * `head` (0 .. 3) samples in front go one by one, so that the 16-byte STORES are aligned whatever 4-byte
+//     boundary the destination starts at; up to three samples behind the last whole group likewise;
+//   * the grid is sized to the compute units (launch_narrow_sc16), the groups are walked in a grid-stride loop;
+//   * a thread counts the components it clipped, the wave adds its counts (DPP) behind the loop: one atomic per
+//     wave that clipped anything, none otherwise.
+typedef float narrow_f2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256) GSDR_NO_PK void narrow_sc16_kernel(const float2 *__restrict__ in, int *__restrict__ out, int head,
+                                                                     long long ngroups, int tail, float gain,
+                                                                     unsigned long long *__restrict__ clipped) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long body = (long long)head + 4 * ngroups;
+    const narrow_f2 *one = reinterpret_cast<const narrow_f2 *>(in);
+    int clips = 0;
+    if (gid < head) {
+        const narrow_f2 v = one[gid];
+        out[gid] = narrow_sample(v.x, v.y, gain, clips);
+    }
+    if (gid < tail) {
+        const narrow_f2 v = one[body + gid];
+        out[body + gid] = narrow_sample(v.x, v.y, gain, clips);
+    }
+    const widen_f4 *src = reinterpret_cast<const widen_f4 *>(in + head);
+    widen_i4 *dst = reinterpret_cast<widen_i4 *>(out + head);
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long g = gid; g < ngroups; g += stride) {
+        const widen_f4 lo = src[2 * g], hi = src[2 * g + 1];
+        widen_i4 o;
+        o.x = narrow_sample(lo.x, lo.y, gain, clips);
+        o.y = narrow_sample(lo.z, lo.w, gain, clips);
+        o.z = narrow_sample(hi.x, hi.y, gain, clips);
+        o.w = narrow_sample(hi.z, hi.w, gain, clips);
+        dst[g] = o;
+    }
+    add_clips(clipped, clips, (int)(threadIdx.x & 63));
+}
+
+hipError_t launch_narrow_sc16(const float2 *in, void *out, long long n, float gain, unsigned long long *clipped, int cus,
+                              hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (((uintptr_t)in & 7) || ((uintptr_t)out & 3) || ((uintptr_t)clipped & 7)) return hipErrorInvalidValue;
+    long long head = (long long)((16 - ((uintptr_t)out & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const long long ngroups = (n - head) / 4;
+    const int tail = (int)(n - head - 4 * ngroups);
+    // eight workgroups of four waves per compute unit hold every wave slot the kernel can use; fewer groups: fewer blocks
+    long long blocks = (ngroups + 255) / 256;
+    const long long cap = (long long)(cus > 0 ? cus : 256) * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(narrow_sc16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, reinterpret_cast<int *>(out), (int)head,
+                       ngroups, tail, gain, clipped);
+    return hipGetLastError();
+}
+
 const char *ddc_kernel_name() { return "ddc_kernel"; }
 const char *ddc_few_kernel_name() { return "ddc_few_kernel"; }
 const char *mix_kernel_name(int n_tones, int tw, long long total, int K, int mix_few) {

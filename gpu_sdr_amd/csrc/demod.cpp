@@ -2222,7 +2222,21 @@ struct gsdr_txgen {
     // (the reference's base_buffer, cpp/USRP_buffer_generator.cpp:77-95)
     float2 *h_period = nullptr;
     bool h_period_pinned = false;
+    // sc16 output (gsdr_txgen_*_sc16): the gain of the narrowing, the counter of clipped components (device memory,
+    // zeroed at creation), the staging buffer of get_sc16() (4 bytes per sample) and a period buffer of its own
+    float sc16_gain = 32767.0f;
+    unsigned long long *d_clipped = nullptr;
+    gsdr_sc16 *d_stage16 = nullptr;
+    size_t stage16_n = 0;
+    gsdr_sc16 *h_period16 = nullptr;
+    bool h_period16_pinned = false;
 };
+
+// the generator's counter of clipped components: 8 bytes of device memory, zero (the creating call has set the device)
+static bool txgen_make_counter(gsdr_txgen *g) {
+    return hipMalloc((void **)&g->d_clipped, sizeof(unsigned long long)) == hipSuccess &&
+           hipMemset(g->d_clipped, 0, sizeof(unsigned long long)) == hipSuccess;
+}
 
 gsdr_txgen *gsdr_txgen_tones_create(int rate, const int *freq, const float *ampl, const float *phase, int n_tones,
                                     int device_index) {
@@ -2259,7 +2273,7 @@ gsdr_txgen *gsdr_txgen_tones_create(int rate, const int *freq, const float *ampl
     }
     const bool ok = upload(&g->d_fmod, fm) == hipSuccess && upload(&g->d_q0, q0) == hipSuccess &&
                     upload(&g->d_btab, bt) == hipSuccess && upload(&g->d_ctab, ct) == hipSuccess &&
-                    hipStreamSynchronize(nullptr) == hipSuccess;
+                    txgen_make_counter(g) && hipStreamSynchronize(nullptr) == hipSuccess;
     if (!ok) {
         g_create_error = "gsdr_txgen_tones_create: device allocation failed";
         gsdr_txgen_close(g);
@@ -2292,11 +2306,16 @@ void gsdr_txgen_close(gsdr_txgen *g) {
     if (!g) return;
     if (g->device >= 0) (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (void *p : {(void *)g->d_fmod, (void *)g->d_q0, (void *)g->d_btab, (void *)g->d_ctab, (void *)g->d_stage})
+    for (void *p : {(void *)g->d_fmod, (void *)g->d_q0, (void *)g->d_btab, (void *)g->d_ctab, (void *)g->d_stage,
+                    (void *)g->d_clipped, (void *)g->d_stage16})
         if (p) (void)hipFree(p);
     if (g->h_period) {
         if (g->h_period_pinned) (void)hipHostFree(g->h_period);
         else std::free(g->h_period);
+    }
+    if (g->h_period16) {
+        if (g->h_period16_pinned) (void)hipHostFree(g->h_period16);
+        else std::free(g->h_period16);
     }
     delete g;
 }
@@ -2356,6 +2375,10 @@ gsdr_txgen *gsdr_txgen_create(const gsdr_param_c *p, const float *ampl, int n_am
         }
         g->period = g->cp.num_steps * g->cp.length;
         g->scale = n_ampl > 0 && ampl ? ampl[0] : 1.f;
+        if (!txgen_make_counter(g) || hipStreamSynchronize(nullptr) != hipSuccess) {
+            gsdr_txgen_close(g);
+            return fail("device allocation failed");
+        }
     } else {
         return fail("Void TX generation operation has not been implemented yet!");
     }
@@ -2495,6 +2518,220 @@ int gsdr_source_chirp(gsdr_c64 *out_dev, long long n, unsigned long long last_in
                                              (hipStream_t)hip_stream);
     if (e != hipSuccess) {
         g_create_error = std::string("gsdr_source_chirp: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return 0;
+}
+
+// ---- sc16 output of the TX generators (include/gsdr.h, "sc16 output") -----------------------------------------
+static bool sc16_gain_ok(float gain) { return std::isfinite(gain) && gain > 0.f; }
+
+int gsdr_txgen_set_sc16_gain(gsdr_txgen *g, float gain) {
+    const char *bad = nullptr;
+    if (!g) bad = "gsdr_txgen_set_sc16_gain: null handle";
+    else if (!sc16_gain_ok(gain)) bad = "gsdr_txgen_set_sc16_gain: the gain must be finite and > 0";
+    else if (g->h_period16) bad = "gsdr_txgen_set_sc16_gain: the sc16 period buffer exists already (it was made with the gain of that time)";
+    if (bad) {
+        g_create_error = bad;
+        return -1;
+    }
+    g->sc16_gain = gain;
+    return 0;
+}
+
+float gsdr_txgen_sc16_gain(const gsdr_txgen *g) { return g ? g->sc16_gain : 0.f; }
+
+int gsdr_txgen_tones_fill_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, long long n, long long start, void *hip_stream) {
+    if (!g || n < 0 || (n > 0 && !out_dev)) {
+        g_create_error = "gsdr_txgen_tones_fill_sc16: bad arguments";
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
+        g_create_error = "gsdr_txgen_tones_fill_sc16: hipSetDevice failed";
+        return -1;
+    }
+    long long sm = start % (long long)g->rate;
+    if (sm < 0) sm += g->rate;
+    const hipError_t e = gsdr::launch_tones_synth_sc16(out_dev, n, (unsigned long long)sm, g->rate, g->d_fmod, g->d_q0, g->d_btab,
+                                                       g->d_ctab, g->n_tones, g->sc16_gain, g->d_clipped, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_txgen_tones_fill_sc16: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return 0;
+}
+
+int gsdr_txgen_get_device_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, void *hip_stream) {
+    if (!g || !out_dev || g->mode < 0) {
+        g_create_error = "gsdr_txgen_get_sc16: bad arguments";
+        return -1;
+    }
+    int rc;
+    if (g->mode == GSDR_TONES) {
+        rc = gsdr_txgen_tones_fill_sc16(g, out_dev, g->buffer_len, (long long)(g->last % g->rate), hip_stream);
+    } else {
+        if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
+            g_create_error = "gsdr_txgen_get_sc16: hipSetDevice failed";
+            return -1;
+        }
+        rc = gsdr_source_chirp_sc16(out_dev, g->buffer_len, g->last, &g->cp, g->scale, g->sc16_gain, g->d_clipped, hip_stream);
+    }
+    if (rc == 0) g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
+    return rc;
+}
+
+// the staging buffer of the sc16 host entries: at least `samples` of gsdr_sc16 in device memory
+static bool txgen_stage16(gsdr_txgen *g, size_t samples) {
+    if (g->d_stage16 && g->stage16_n < samples) {
+        (void)hipFree(g->d_stage16);
+        g->d_stage16 = nullptr;
+        g->stage16_n = 0;
+    }
+    if (!g->d_stage16) {
+        if (hipMalloc((void **)&g->d_stage16, (samples ? samples : 1) * sizeof(gsdr_sc16)) != hipSuccess) {
+            (void)hipGetLastError();
+            g->d_stage16 = nullptr;
+            return false;
+        }
+        g->stage16_n = samples;
+    }
+    return true;
+}
+
+int gsdr_txgen_get_sc16(gsdr_txgen *g, gsdr_sc16 *out_host) {
+    if (!g || !out_host || g->mode < 0) {
+        g_create_error = "gsdr_txgen_get_sc16: bad arguments";
+        return -1;
+    }
+    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
+        g_create_error = "gsdr_txgen_get_sc16: hipSetDevice failed";
+        return -1;
+    }
+    if (!txgen_stage16(g, (size_t)g->buffer_len)) {
+        g_create_error = "gsdr_txgen_get_sc16: device allocation failed";
+        return -1;
+    }
+    if (gsdr_txgen_get_device_sc16(g, g->d_stage16, nullptr) != 0) return -1;
+    const hipError_t e = hipMemcpy(out_host, g->d_stage16, (size_t)g->buffer_len * sizeof(gsdr_sc16), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_txgen_get_sc16: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return 0;
+}
+
+// The sc16 twin of gsdr_txgen_prepare_host: one period plus one buffer, 4 bytes per sample, made once in pieces through
+// the sc16 staging buffer.  The complex64 period buffer is neither needed nor made.
+int gsdr_txgen_prepare_host_sc16(gsdr_txgen *g) {
+    if (!g || g->mode != GSDR_TONES) {
+        g_create_error = "gsdr_txgen_prepare_host_sc16: a TONES generator is needed";
+        return -1;
+    }
+    if (g->h_period16) return 0;
+    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
+        g_create_error = "gsdr_txgen_prepare_host_sc16: hipSetDevice failed";
+        return -1;
+    }
+    const unsigned long long total = g->period + (unsigned long long)g->buffer_len;
+    gsdr_sc16 *hp = nullptr;
+    bool pinned = hipHostMalloc((void **)&hp, (size_t)total * sizeof(gsdr_sc16)) == hipSuccess;
+    if (!pinned) {
+        (void)hipGetLastError();
+        hp = (gsdr_sc16 *)std::malloc((size_t)total * sizeof(gsdr_sc16));
+    }
+    if (!hp) {
+        g_create_error = "gsdr_txgen_prepare_host_sc16: cannot allocate the period buffer in host memory";
+        return -1;
+    }
+    const size_t piece = (size_t)(total < (8u << 20) ? total : (8u << 20));
+    bool ok = txgen_stage16(g, piece);
+    for (unsigned long long off = 0; ok && off < total; off += piece) {
+        const long long n = (long long)(total - off < piece ? total - off : piece);
+        ok = gsdr_txgen_tones_fill_sc16(g, g->d_stage16, n, (long long)(off % g->rate), nullptr) == 0 &&
+             hipMemcpy(hp + off, g->d_stage16, (size_t)n * sizeof(gsdr_sc16), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) {
+        if (pinned) (void)hipHostFree(hp);
+        else std::free(hp);
+        if (g_create_error.empty()) g_create_error = "gsdr_txgen_prepare_host_sc16: generating the period failed";
+        return -1;
+    }
+    g->h_period16 = hp;
+    g->h_period16_pinned = pinned;
+    return 0;
+}
+
+const gsdr_sc16 *gsdr_txgen_get_ptr_sc16(gsdr_txgen *g) {
+    if (!g || g->mode != GSDR_TONES) {
+        g_create_error = "gsdr_txgen_get_ptr_sc16: a TONES generator is needed";
+        return nullptr;
+    }
+    if (!g->h_period16 && gsdr_txgen_prepare_host_sc16(g) != 0) return nullptr;
+    const gsdr_sc16 *p = g->h_period16 + g->last;
+    g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
+    return p;
+}
+
+// a diagnostic: waits for everything the device has been given
+long long gsdr_txgen_sc16_clipped(gsdr_txgen *g) {
+    if (!g || !g->d_clipped) {
+        g_create_error = "gsdr_txgen_sc16_clipped: null handle";
+        return -1;
+    }
+    unsigned long long c = 0;
+    hipError_t e = g->device >= 0 ? hipSetDevice(g->device) : hipSuccess;
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&c, g->d_clipped, sizeof(c), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_txgen_sc16_clipped: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return (long long)c;
+}
+
+int gsdr_source_chirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index, const gsdr_chirp_param *cp,
+                           float scale, float gain, unsigned long long *clipped_dev, void *hip_stream) {
+    if (n == 0) return 0;
+    const char *bad = nullptr;
+    if (!out_dev || !cp || n < 0 || cp->num_steps < 1 || cp->length < 1) bad = "bad arguments";
+    else if (!sc16_gain_ok(gain)) bad = "the gain must be finite and > 0";
+    else if (((uintptr_t)out_dev & 3) || ((uintptr_t)clipped_dev & 7)) bad = "out_dev must be 4-byte, clipped_dev 8-byte aligned";
+    if (bad) {
+        g_create_error = std::string("gsdr_source_chirp_sc16: ") + bad;
+        return -1;
+    }
+    ChirpShape cs{};
+    cs.num_steps = cp->num_steps;
+    cs.length = cp->length;
+    cs.period = cp->num_steps * cp->length;
+    cs.chirpness = cp->chirpness;
+    cs.f0 = cp->f0;
+    const hipError_t e = gsdr::launch_source_chirp_sc16(out_dev, n, last_index % cs.period, cs, scale, gain, clipped_dev,
+                                                        (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_source_chirp_sc16: ") + hipGetErrorString(e);
+        return -1;
+    }
+    return 0;
+}
+
+int gsdr_narrow_sc16_device(const gsdr_c64 *in_dev, gsdr_sc16 *out_dev, long long n, float gain,
+                            unsigned long long *clipped_dev, void *hip_stream) {
+    if (n == 0) return 0;
+    const char *bad = nullptr;
+    if (n < 0 || !in_dev || !out_dev) bad = "null buffer";
+    else if (!sc16_gain_ok(gain)) bad = "the gain must be finite and > 0";
+    else if (((uintptr_t)in_dev & 7) || ((uintptr_t)out_dev & 3) || ((uintptr_t)clipped_dev & 7))
+        bad = "in_dev and clipped_dev must be 8-byte, out_dev 4-byte aligned";
+    if (bad) {
+        g_create_error = std::string("gsdr_narrow_sc16_device: ") + bad;
+        return -1;
+    }
+    const hipError_t e = gsdr::launch_narrow_sc16(reinterpret_cast<const float2 *>(in_dev), out_dev, n, gain, clipped_dev,
+                                                  device_cus(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        g_create_error = std::string("gsdr_narrow_sc16_device: ") + hipGetErrorString(e);
         return -1;
     }
     return 0;

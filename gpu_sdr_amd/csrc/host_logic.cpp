@@ -288,4 +288,41 @@ int gsdr_frame_average_host(const gsdr_c64 *frames, int n_frames, int n_ch, int 
     return (int)rows;
 }
 
+// sc16 output narrowed on the host, the arithmetic of include/gsdr.h step for step: what narrow_component
+// (ddc_device.h) computes on the device, bit for bit.  The range is tested on the rounded FLOAT and the conversion
+// only sees a value it can represent (converting a NaN or an out-of-range float is undefined behaviour).
+// std::nearbyintf rounds in the current rounding mode: to nearest, ties to even, unless the caller changed it.
+namespace {
+GSDR_NO_CONTRACT
+inline int16_t narrow_one_host(float c, float gain, long long &clipped) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float v = c * gain;
+    if (v != v) {
+        ++clipped;
+        return 0;
+    }
+    const float r = std::nearbyintf(v);
+    if (r > 32767.0f) {
+        ++clipped;
+        return 32767;
+    }
+    if (r < -32768.0f) {
+        ++clipped;
+        return -32768;
+    }
+    return (int16_t)(int)r;
+}
+}  // namespace
+
+long long gsdr_narrow_sc16_host(const gsdr_c64 *in, gsdr_sc16 *out, long long n, float gain) {
+    long long clipped = 0;
+    for (long long k = 0; k < n; ++k) {
+        out[k].i = narrow_one_host(in[k].x, gain, clipped);
+        out[k].q = narrow_one_host(in[k].y, gain, clipped);
+    }
+    return clipped;
+}
+
 }  // extern "C"

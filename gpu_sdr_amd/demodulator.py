@@ -398,6 +398,65 @@ def widen_sc16(in_buffer, out=None, scale: float = SC16_DEFAULT_SCALE, stream=No
     return out
 
 
+SC16_DEFAULT_GAIN = 32767.0
+
+
+def _check_sc16_gain(gain) -> float:
+    gain = float(np.float32(gain))
+    if not (np.isfinite(gain) and gain > 0):
+        raise ValueError("the sc16 gain must be finite and > 0")
+    return gain
+
+
+def narrow_sc16(in_buffer, out=None, gain: float = SC16_DEFAULT_GAIN, stream=None, clipped=None, return_clipped: bool = False):
+    """complex64 -> sc16 on its own (include/gsdr.h, "sc16 output"): per component ``v = float32(c * gain)``, rounded to
+    the nearest integer (ties to even), saturated to [-32768, 32767], NaN -> 0.  ``in_buffer``: contiguous complex64; a
+    CUDA tensor is narrowed on the device (gsdr_narrow_sc16_device, enqueued on `stream` / the current torch stream,
+    not synchronised), a numpy array on the host (gsdr_narrow_sc16_host, needs no GPU) -- bit-identical results.
+    ``out``: contiguous int16 of shape (..., 2) with at least as many samples (created when None).
+    ``clipped`` (device path): a one-element int64 CUDA tensor the kernel ADDS the number of clipped components to.
+    Returns ``out``; the host path returns ``(out, count)`` with ``return_clipped=True``."""
+    gain = _check_sc16_gain(gain)
+    L = _lib.lib()
+    if _is_torch(in_buffer):
+        import torch
+        if not (in_buffer.is_cuda and in_buffer.dtype == torch.complex64 and in_buffer.is_contiguous()):
+            raise TypeError("need a contiguous complex64 CUDA tensor (pass a numpy array for the host path)")
+        if return_clipped:
+            raise ValueError("return_clipped is for the host path: pass a `clipped` tensor on the device path")
+        n = int(in_buffer.numel())
+        if out is None:
+            out = torch.empty(tuple(in_buffer.shape) + (2,), dtype=torch.int16, device=in_buffer.device)
+        if not (_is_sc16(out) and _is_torch(out) and out.is_cuda):
+            raise TypeError("out must be a contiguous int16 CUDA tensor of shape (..., 2)")
+        if _sc16_rows(out) < n:
+            raise ValueError("out is shorter than the input")
+        cptr = None
+        if clipped is not None:
+            if not (_is_torch(clipped) and clipped.is_cuda and clipped.dtype == torch.int64 and clipped.numel() == 1):
+                raise TypeError("clipped must be a one-element int64 CUDA tensor")
+            cptr = clipped.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream(in_buffer.device)
+        if L.gsdr_narrow_sc16_device(in_buffer.data_ptr(), out.data_ptr(), n, C.c_float(gain), cptr,
+                                     C.c_void_p(stream.cuda_stream)) != 0:
+            raise GsdrError(L.gsdr_last_error(None).decode())
+        return out
+    if not (isinstance(in_buffer, np.ndarray) and in_buffer.dtype == np.complex64 and in_buffer.flags.c_contiguous):
+        raise TypeError("need a contiguous complex64 array or tensor")
+    if clipped is not None:
+        raise ValueError("clipped is for the device path: use return_clipped=True on the host path")
+    n = int(in_buffer.size)
+    if out is None:
+        out = np.empty(in_buffer.shape + (2,), dtype=np.int16)
+    if not (_is_sc16(out) and isinstance(out, np.ndarray)):
+        raise TypeError("out must be a contiguous int16 array of shape (..., 2)")
+    if _sc16_rows(out) < n:
+        raise ValueError("out is shorter than the input")
+    count = int(L.gsdr_narrow_sc16_host(in_buffer.ctypes.data, out.ctypes.data, n, C.c_float(gain)))
+    return (out, count) if return_clipped else out
+
+
 def frame_average(frames, k: int, kind="complex", count: int = 0, acc=None, stream=None):
     """The frame averaging on its own (gsdr_frame_average_device / _host, bit-identical): ``frames`` is complex64 of
     shape (n_frames, n_ch) -- a CUDA tensor (one kernel on `stream` / the current torch stream, not synchronised) or a

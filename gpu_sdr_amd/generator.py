@@ -48,7 +48,13 @@ class TX_buffer_generator:
 
     ``get(out)`` fills a torch complex64 CUDA tensor (gsdr_txgen_get_device, asynchronous on the current or
     the given stream) or a numpy complex64 array (gsdr_txgen_get, as the reference's get() to host memory)
-    of ``buffer_len`` samples with the next TX buffer; ``close()`` frees the device tables."""
+    of ``buffer_len`` samples with the next TX buffer; ``close()`` frees the device tables.
+
+    sc16 output (include/gsdr.h, "sc16 output"): ``get_sc16(out)`` and ``get_view_sc16()`` are the same calls for int16
+    buffers of shape (buffer_len, 2) -- exactly ``narrow_sc16`` of what ``get`` / ``get_view`` would have returned, made
+    by the generator kernel itself; they advance the same running index and may be mixed with the complex64 calls.
+    ``sc16_gain`` (32767 by default) is the factor of the narrowing, ``sc16_clipped()`` the number of components that
+    did not fit since the generator was created (a diagnostic: it waits for the device)."""
 
     def __init__(self, init_parameters: param, device_index: int = 0):
         import ctypes as C
@@ -110,6 +116,65 @@ class TX_buffer_generator:
             if stream is None:
                 stream = torch.cuda.current_stream(out.device)
             rc = self._L.gsdr_txgen_get_device(self._h, out.data_ptr(), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise GsdrError(self._L.gsdr_last_error(None).decode())
+
+    @property
+    def sc16_gain(self) -> float:
+        if not self._h:
+            raise GsdrError("generator is closed")
+        return float(self._L.gsdr_txgen_sc16_gain(self._h))
+
+    @sc16_gain.setter
+    def sc16_gain(self, gain: float) -> None:
+        import ctypes as C
+        if not self._h:
+            raise GsdrError("generator is closed")
+        if self._L.gsdr_txgen_set_sc16_gain(self._h, C.c_float(gain)) != 0:
+            raise GsdrError(self._L.gsdr_last_error(None).decode())
+
+    def sc16_clipped(self) -> int:
+        """Components clipped by the sc16 entries since creation (gsdr_txgen_sc16_clipped; synchronises the device)."""
+        if not self._h:
+            raise GsdrError("generator is closed")
+        n = int(self._L.gsdr_txgen_sc16_clipped(self._h))
+        if n < 0:
+            raise GsdrError(self._L.gsdr_last_error(None).decode())
+        return n
+
+    def get_view_sc16(self) -> np.ndarray:
+        """``get_view()`` in sc16: the next buffer_len samples as a read-only (buffer_len, 2) int16 VIEW of the
+        generator's own sc16 period buffer (gsdr_txgen_get_ptr_sc16; TONES only); valid until close()."""
+        import ctypes as C
+        if not self._h:
+            raise GsdrError("generator is closed")
+        ptr = self._L.gsdr_txgen_get_ptr_sc16(self._h)
+        if not ptr:
+            raise GsdrError(self._L.gsdr_last_error(None).decode())
+        buf = (C.c_int16 * (2 * self.buffer_len)).from_address(ptr)
+        v = np.frombuffer(buf, dtype=np.int16, count=2 * self.buffer_len).reshape(self.buffer_len, 2)
+        v.flags.writeable = False
+        return v
+
+    def get_sc16(self, out, stream=None) -> None:
+        """``get()`` in sc16: ``out`` is a contiguous int16 CUDA tensor (gsdr_txgen_get_device_sc16, asynchronous) or
+        numpy array (gsdr_txgen_get_sc16: 4 bytes per sample come back from the device) of shape (..., 2) with at
+        least buffer_len samples."""
+        import ctypes as C
+        from .demodulator import _is_sc16, _is_torch, _sc16_rows
+        if not self._h:
+            raise GsdrError("generator is closed")
+        if not _is_sc16(out) or _sc16_rows(out) < self.buffer_len:
+            raise TypeError("need a contiguous int16 array or tensor of shape (..., 2) with buffer_len samples")
+        if _is_torch(out):
+            import torch
+            if not out.is_cuda:
+                raise TypeError("a tensor must live on the GPU (pass a numpy array for the host path)")
+            if stream is None:
+                stream = torch.cuda.current_stream(out.device)
+            rc = self._L.gsdr_txgen_get_device_sc16(self._h, out.data_ptr(), C.c_void_p(stream.cuda_stream))
+        else:
+            rc = self._L.gsdr_txgen_get_sc16(self._h, out.ctypes.data)
         if rc != 0:
             raise GsdrError(self._L.gsdr_last_error(None).decode())
 

@@ -81,6 +81,34 @@ class TX_buffer_generator {
         }
     }
 
+    //! get() in the format a radio takes on the wire (an extension, gsdr.h "sc16 output"): the next buffer_len samples
+    //! as interleaved int16 I/Q, exactly the narrowed samples get() would have handed out, made by the generator
+    //! kernel itself.  The same two conventions: TONES replaces *in by a pointer into the generator's sc16 period
+    //! buffer (made at the first call, 4 bytes per sample; the gain is fixed from then on), CHIRP fills the
+    //! buffer_len samples *in points to.  get() and get_sc16() advance the same running index.
+    void get_sc16(gsdr_sc16** in) {
+        if (tones_) {
+            const gsdr_sc16* p = gsdr_txgen_get_ptr_sc16(handle_);
+            if (!p) {
+                std::fprintf(stderr, "ERROR: %s\n", gsdr_last_error(nullptr));
+                std::exit(-1);
+            }
+            *in = const_cast<gsdr_sc16*>(p);
+            return;
+        }
+        if (gsdr_txgen_get_sc16(handle_, *in) != 0) {
+            std::fprintf(stderr, "ERROR: %s\n", gsdr_last_error(nullptr));
+            std::exit(-1);
+        }
+    }
+
+    //! the factor of the narrowing (32767 by default).  false, with the old value kept, when the gain is not finite
+    //! and > 0 or the TONES period buffer of get_sc16() exists already (gsdr_last_error(NULL) has the reason)
+    bool set_sc16_gain(float gain) { return gsdr_txgen_set_sc16_gain(handle_, gain) == 0; }
+    float sc16_gain() const { return gsdr_txgen_sc16_gain(handle_); }
+    //! components that did not fit into int16 since the generator was made; a diagnostic, it waits for the device
+    long long sc16_clipped() { return gsdr_txgen_sc16_clipped(handle_); }
+
     //! (ref: cpp/USRP_buffer_generator.cpp:172-178)
     void close() {
         if (handle_) gsdr_txgen_close(handle_);

@@ -128,7 +128,11 @@ int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *ou
  *    what lies around the buffers.
  * (What tests/test_gpu_extents.py can and cannot see of this: DESIGN.md section 3.)
  * The writers further down (gsdr_txgen_get_device, gsdr_txgen_tones_fill, gsdr_source_tones, gsdr_source_chirp)
- * write exactly the n (gsdr_txgen_get_device: buffer_len) samples they are asked for, to an 8-byte aligned out_dev. */
+ * write exactly the n (gsdr_txgen_get_device: buffer_len) samples they are asked for, to an 8-byte aligned out_dev.
+ * Their sc16 forms (gsdr_txgen_get_device_sc16, gsdr_txgen_tones_fill_sc16, gsdr_source_chirp_sc16) and
+ * gsdr_narrow_sc16_device write exactly n (buffer_len) samples of gsdr_sc16 to an out_dev that needs 4-byte alignment
+ * only and may point anywhere into a larger allocation: nothing in front of it or behind it is written, and the output
+ * does not depend on where it points. */
 
 /* Creates now what the entries above would otherwise create on first use (device
  * staging buffers of the host-pointer entries, the streams, events and per-slot
@@ -177,6 +181,29 @@ int gsdr_demod_submit_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c
  * gsdr_last_error(NULL).  _host: the same arithmetic on the CPU, bit for bit (needs no GPU). */
 int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream);
 void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float scale);
+
+/* ---- sc16 output (an extension: the reference hands fc32 to UHD, which converts on the host) -----------------
+ * A radio takes sc16 on the wire.  Every TX generator entry further down has a form that writes gsdr_sc16 (I first,
+ * 4 bytes per sample) straight from the kernel that made the sample: half the bytes to store and to copy, and no
+ * conversion pass on the host.  Each is exactly "the complex64 entry, then narrow", bit for bit, for any start and n.
+ * Narrowing a float32 component c with a float32 gain is three steps, every one a single IEEE single-precision
+ * operation, nothing fused:
+ *   1. v = fl32(c * gain);
+ *   2. r = v rounded to the nearest integer, ties to even;
+ *   3. q = 0 if v is NaN;  32767 if r > 32767 (+Inf included);  -32768 if r < -32768 (-Inf included);  else (int16) r.
+ * (Round to nearest even plus saturation is what UHD's SIMD fc32 -> sc16 converters do.)  A component is CLIPPED when
+ * v is NaN, r > 32767 or r < -32768; r == -32768 is representable and no clip.  In numpy terms:
+ * np.rint(x.view(float32) * float32(gain)), clipped to [-32768, 32767], NaN -> 0, .astype(int16).
+ * The narrowing on its own.  _device: in_dev (8-byte aligned) and out_dev (4-byte aligned, anywhere in a larger
+ * allocation) are device pointers to n samples; exactly n samples are written; gain must be finite and > 0; when
+ * clipped_dev is given (8-byte aligned device memory) the kernel ADDS the number of clipped components of the call to
+ * it -- at most one atomic per wave, none for a wave that clipped nothing.  Enqueued on hip_stream, not synchronised;
+ * returns 0, or -1 with the reason in gsdr_last_error(NULL).  _host: the same arithmetic on the CPU, bit for bit (needs
+ * no GPU; any gain is taken as it is); returns the number of clipped components.  n == 0 touches nothing, not even
+ * the pointers. */
+int gsdr_narrow_sc16_device(const gsdr_c64 *in_dev, gsdr_sc16 *out_dev, long long n, float gain,
+                            unsigned long long *clipped_dev, void *hip_stream);
+long long gsdr_narrow_sc16_host(const gsdr_c64 *in, gsdr_sc16 *out, long long n, float gain);
 
 /* ---- mean of k consecutive frames, TONES and NOISE (an extension: what the reference's decimate_spectra /
  * decimate_pfb intend and do not deliver, ref: cpp/kernels.cu:704-790, cpp/USRP_demodulator.cpp:511-534,593-624;
@@ -425,6 +452,35 @@ long long gsdr_txgen_buffer_len(const gsdr_txgen *g);
 /* TX chirp law (ref: chirp_gen, cpp/kernels.cu:335-372) written to device. */
 int gsdr_source_chirp(gsdr_c64 *out_dev, long long n, unsigned long long last_index,
                       const gsdr_chirp_param *cp, float scale, void *hip_stream);
+
+/* ---- sc16 output of the TX generators (the contract: "sc16 output" further up) ------------------------------
+ * Every entry writes exactly the bits that narrowing the output of its complex64 entry gives.  The sc16 and the
+ * complex64 entries of one handle advance the same running index and may be mixed freely.
+ * The gain is a property of the handle: 32767 by default; it must be finite and > 0, otherwise
+ * gsdr_txgen_set_sc16_gain returns -1, leaves a message in gsdr_last_error(NULL) and keeps the old value.  It is
+ * refused in the same way once the handle's sc16 period buffer exists (the buffer was made with the old gain and
+ * stays unchanged until close).
+ * gsdr_txgen_get_sc16: through a device staging buffer of 4 bytes per sample, 4 bytes per sample copied to the host.
+ * gsdr_txgen_get_ptr_sc16 / gsdr_txgen_prepare_host_sc16: TONES only, like the complex64 pair, on a host buffer of
+ * their own -- period + buffer_len samples of gsdr_sc16, pinned when possible, made once in pieces through the device,
+ * valid and unchanged until gsdr_txgen_close(); the complex64 period buffer is not allocated for it.
+ * Clipped components: a generator owns one counter in device memory, zeroed at creation; all its sc16 entries add to
+ * it (the period + buffer_len samples generated for the period buffer once).  gsdr_txgen_sc16_clipped synchronises the
+ * generator's device and returns the total since creation (-1: device error).  It is a diagnostic -- look at it after
+ * a run or while setting a level -- and not meant for the per-buffer loop: it stalls the device.
+ * gsdr_source_chirp_sc16: the TX chirp law narrowed; s * scale is rounded to float32 before the gain multiplies it.
+ * n == 0 touches nothing, not even the pointers. */
+int gsdr_txgen_set_sc16_gain(gsdr_txgen *g, float gain);
+float gsdr_txgen_sc16_gain(const gsdr_txgen *g);
+int gsdr_txgen_tones_fill_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, long long n, long long start, void *hip_stream);
+int gsdr_txgen_get_device_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, void *hip_stream);
+int gsdr_txgen_get_sc16(gsdr_txgen *g, gsdr_sc16 *out_host);
+int gsdr_txgen_prepare_host_sc16(gsdr_txgen *g);
+const gsdr_sc16 *gsdr_txgen_get_ptr_sc16(gsdr_txgen *g);
+long long gsdr_txgen_sc16_clipped(gsdr_txgen *g);
+int gsdr_source_chirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index,
+                           const gsdr_chirp_param *cp, float scale, float gain,
+                           unsigned long long *clipped_dev, void *hip_stream);
 
 #ifdef __cplusplus
 }

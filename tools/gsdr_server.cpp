@@ -24,11 +24,15 @@
 //     frames, through gsdr_demod_set_frame_average() on a demodulator created with decim = 0 -- what the reference's
 //     decimate_spectra / decimate_pfb intend (cpp/USRP_demodulator.cpp:511-534,593-624); a buffer in which no group of
 //     frames completes sends no packet.
+//   * --wire sc16 (an extension): the loop-back runs in the format a real link carries.  tx_single_link fills pool
+//     buffers of 4 bytes per sample through gsdr_txgen_get_sc16() (silence is zeros), rx_single_link submits them through
+//     gsdr_demod_submit_sc16(); the demodulator's sc16 scale is 1 / the generator's sc16 gain.  The packets on the data
+//     socket are complex64 as ever.
 // What it drops: UHD, HDF5 writer, reconnect threads, burst timing, delays, logging.
 //
 //   hipcc -O2 -std=c++17 -Iinclude tools/gsdr_server.cpp -Lgpu_sdr_amd -lgsdr \
 //         -Wl,-rpath,$PWD/gpu_sdr_amd -o gpu_sdr_amd/gsdr_server
-//   gpu_sdr_amd/gsdr_server [--async 22001] [--data 61360] [--device 0] [--once]
+//   gpu_sdr_amd/gsdr_server [--async 22001] [--data 61360] [--device 0] [--once] [--wire fc32|sc16]
 #include <arpa/inet.h>
 #include <hip/hip_runtime.h>
 #include <netinet/in.h>
@@ -49,6 +53,8 @@
 #include <vector>
 
 #include "gsdr.h"
+
+static bool g_wire_sc16 = false;    // --wire sc16: TX -> RX buffers are gsdr_sc16 (4 bytes per sample)
 
 static bool read_all(int fd, void *buf, size_t n) {
     char *p = (char *)buf;
@@ -175,16 +181,18 @@ struct FrontEnd {              // one RX demodulator fed by its TX generator (or
 // tx_single_link (:568-584) + software_tx/rx_thread: generator->get() into a pool buffer, which becomes an RX buffer
 static void tx_link(FrontEnd *F, int device) {
     (void)hipSetDevice(device);
+    const size_t bytes = (size_t)F->rx.buffer_len * (g_wire_sc16 ? sizeof(gsdr_sc16) : sizeof(gsdr_c64));
     for (long long k = 0; k < F->n_buffers; ++k) {
         gsdr_c64 *buf = F->in_pool.get();
         if (F->gen) {
-            if (gsdr_txgen_get(F->gen, buf) != 0) {
+            const int rc = g_wire_sc16 ? gsdr_txgen_get_sc16(F->gen, reinterpret_cast<gsdr_sc16 *>(buf)) : gsdr_txgen_get(F->gen, buf);
+            if (rc != 0) {
                 std::fprintf(stderr, "ERROR: TX generator: %s\n", gsdr_last_error(nullptr));
                 F->ok = false;
-                std::memset(buf, 0, (size_t)F->rx.buffer_len * sizeof(gsdr_c64));
+                std::memset(buf, 0, bytes);
             }
         } else {
-            std::memset(buf, 0, (size_t)F->rx.buffer_len * sizeof(gsdr_c64));     // RX without TX: silence
+            std::memset(buf, 0, bytes);                                           // RX without TX: silence
         }
         F->rx_queue.push(buf);
     }
@@ -219,7 +227,9 @@ static void rx_link(FrontEnd *F, BlockingQueue<Packet> *stream_queue, int device
         if (!F->rx_queue.pop(in)) break;
         gsdr_c64 *out = F->out_pool.get();                                        // output_memory->get() (:663)
         if ((int)pending.size() == GSDR_PIPELINE_DEPTH) finish_oldest();
-        if (gsdr_demod_submit(F->dem, in, out) != 0) {
+        const int rc = g_wire_sc16 ? gsdr_demod_submit_sc16(F->dem, reinterpret_cast<const gsdr_sc16 *>(in), out)
+                                   : gsdr_demod_submit(F->dem, in, out);
+        if (rc != 0) {
             std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(F->dem));
             F->ok = false;
             F->in_pool.trash(in);
@@ -295,7 +305,7 @@ static bool run_measurement(const gsdr_command *cmd, int data_fd, int device) {
             ok = false;
             break;
         }
-        if (gsdr_demod_prepare(F.dem, GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST) != 0)
+        if (gsdr_demod_prepare(F.dem, GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST | (g_wire_sc16 ? GSDR_PREPARE_SC16 : 0)) != 0)
             std::fprintf(stderr, "WARNING: demodulator: %s\n", gsdr_last_error(F.dem));
         if (F.has_tx && F.tx.n_wave_type > 0) {
             // software loop-back: the TX buffer IS the RX buffer, so the generator makes RX-sized buffers
@@ -303,12 +313,19 @@ static bool run_measurement(const gsdr_command *cmd, int data_fd, int device) {
             txp.buffer_len = F.rx.buffer_len;
             F.gen = gsdr_txgen_create(&txp, F.txi.ampl, F.txi.n_ampl);
             if (!F.gen) std::fprintf(stderr, "WARNING: TX generator: %s (RX runs on silence)\n", gsdr_last_error(nullptr));
+            // sc16 wire: the receiver undoes the gain of the transmitter
+            if (F.gen && g_wire_sc16 && gsdr_demod_set_sc16_scale(F.dem, 1.0f / gsdr_txgen_sc16_gain(F.gen)) != 0) {
+                std::fprintf(stderr, "ERROR: demodulator: %s\n", gsdr_last_error(F.dem));
+                ok = false;
+                break;
+            }
         }
         const long long L = F.rx.buffer_len;
         F.n_buffers = F.rxi.samples > 0 ? (F.rxi.samples + L - 1) / L : 0;
         const size_t cap = (size_t)gsdr_demod_out_capacity(F.dem);
         // pools: RX buffers (preallocator(A_rx_buffer_len, RX_QUEUE_LENGTH), :114) and outputs (:143-150)
-        if (!F.in_pool.init((size_t)L, GSDR_PIPELINE_DEPTH + 3) || !F.out_pool.init(cap, GSDR_PIPELINE_DEPTH + 5)) {
+        // (sc16 wire: half-size RX buffers, L samples of 4 bytes)
+        if (!F.in_pool.init(g_wire_sc16 ? (size_t)(L + 1) / 2 : (size_t)L, GSDR_PIPELINE_DEPTH + 3) || !F.out_pool.init(cap, GSDR_PIPELINE_DEPTH + 5)) {
             std::fprintf(stderr, "ERROR: allocation failed\n");
             ok = false;
             break;
@@ -350,6 +367,14 @@ int main(int argc, char **argv) {
         else if (a == "--data" && i + 1 < argc) data_port = std::atoi(argv[++i]);
         else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (a == "--once") once = true;
+        else if (a == "--wire" && i + 1 < argc) {
+            const std::string w = argv[++i];
+            if (w != "sc16" && w != "fc32") {
+                std::fprintf(stderr, "ERROR: --wire takes fc32 or sc16\n");
+                return 1;
+            }
+            g_wire_sc16 = w == "sc16";
+        }
         else if (a == "--sw_loop" || a == "--no_net" || a == "--fw") {}  // accepted for script compatibility
     }
     if (hipSetDevice(device) != hipSuccess) {
@@ -357,7 +382,8 @@ int main(int argc, char **argv) {
         return 1;
     }
     const int data_l = listen_on(data_port), async_l = listen_on(async_port);
-    std::printf("gsdr_server: data :%d, async :%d, device %d (software loop-back)\n", data_port, async_port, device);
+    std::printf("gsdr_server: data :%d, async :%d, device %d (software loop-back%s)\n", data_port, async_port, device,
+                g_wire_sc16 ? ", sc16 wire" : "");
     std::fflush(stdout);
     // the reference blocks on the data connection first (Sync_server::connect), then on the async one
     const int data_fd = ::accept(data_l, nullptr, nullptr);
