@@ -20,18 +20,27 @@
 
 #include <unistd.h>
 
-#include "../../include/gsdr.h"
-#include "ddc_kernels.h"
+#include "host_util.h"
 
 extern char **environ;
 
 using gsdr::ChirpShape;
+using gsdr::chirp_shape;
+using gsdr::create_error;
 using gsdr::DdcLaunch;
 using gsdr::DdcShape;
+using gsdr::dev_alloc;
+using gsdr::device_cus;
+using gsdr::mod_rate;
+using gsdr::phasor;
+using gsdr::upload;
+
+std::string &gsdr::create_error() {
+    thread_local std::string msg;
+    return msg;
+}
 
 namespace {
-
-thread_local std::string g_create_error;
 
 constexpr int kMaxF = 8;           // tap phases the DDC kernel is instantiated for
 constexpr int kMaxEvents = 8192;   // profiling ring
@@ -266,40 +275,9 @@ namespace {
     } while (0)
 
 int fail_create(gsdr_demod *h, const std::string &msg) {
-    g_create_error = msg;
+    create_error() = msg;
     if (h) gsdr_demod_close(h);
     return -1;
-}
-
-template <typename T>
-hipError_t dev_alloc(T **p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-}
-
-template <typename T>
-hipError_t upload(T **dst, const std::vector<T> &src) {
-    hipError_t e = dev_alloc(dst, src.size());
-    if (e != hipSuccess) return e;
-    if (src.empty()) return hipSuccess;
-    return hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
-// compute units of the current device (256 when it cannot be asked)
-int device_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    return cus;
-}
-
-// exp(-2*pi*i * ph/rate) for an exact integer phase, in double.
-inline void phasor(unsigned long long ph, unsigned rate, double &re, double &im) {
-    const double a = 2.0 * M_PI * ((double)ph / (double)rate);
-    re = std::cos(a);
-    im = -std::sin(a);
 }
 
 // Builds the per-tone NCO tables of the DDC kernel (see ddc_kernels.hip):
@@ -310,12 +288,7 @@ int build_nco_tables(gsdr_demod *h, const std::vector<long long> &tone, unsigned
     std::vector<float2> btab((size_t)K * Npad);
     std::vector<double2> wk(Npad), wrem(Npad);
     for (int n = 0; n < Npad; ++n) {
-        unsigned long long fm = 0;
-        if (n < h->ddc_channels) {
-            long long r = tone[n] % (long long)rate;
-            if (r < 0) r += rate;
-            fm = (unsigned long long)r;
-        }
+        const unsigned long long fm = n < h->ddc_channels ? mod_rate(tone[n], rate) : 0u;
         fmod[n] = (unsigned)fm;
         for (int lo = 0; lo < K; ++lo) {
             double re, im;
@@ -454,6 +427,18 @@ int setup_ddc_common(gsdr_demod *h, int F, int M, unsigned rate,
     return 0;
 }
 
+// the tables and launch switches of the handle that every DdcLaunch carries
+void set_tables(const gsdr_demod *h, DdcLaunch &a) {
+    a.taps_t = h->d_taps_t;
+    a.taps_p = h->d_taps_p;
+    a.btab = h->d_btab;
+    a.wk = h->d_wk;
+    a.wrem = h->d_wrem;
+    a.fmod = h->d_fmod;
+    a.lds_bytes = h->sw.ddc_lds;
+    a.sh.prefetch = h->sw.ddc_prefetch;
+}
+
 // fields of DdcShape the kernels derive nothing from on the device
 void finish_shape(DdcShape &sh) {
     sh.cbase = sh.nblk / (sh.nch > 0 ? sh.nch : 1);
@@ -531,11 +516,7 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
     const int nt32 = (h->ddc_channels + 31) / 32;
     pl.ntg = (nt32 + pl.TT - 1) / pl.TT;
     std::vector<unsigned> fmod_in(h->ddc_channels);
-    for (int n = 0; n < h->ddc_channels; ++n) {
-        long long r = tone[n] % (long long)rate;
-        if (r < 0) r += rate;
-        fmod_in[n] = (unsigned)r;
-    }
+    for (int n = 0; n < h->ddc_channels; ++n) fmod_in[n] = mod_rate(tone[n], rate);
     std::vector<uint4> bfrag;
     std::vector<float2> ptab, dtab;
     std::vector<float> taps;
@@ -700,17 +681,11 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
         h->waves_ratio = r;
         DdcLaunch a{};
         a.x = x;
-        a.taps_t = h->d_taps_t;
-        a.taps_p = h->d_taps_p;
-        a.btab = h->d_btab;
-        a.wk = h->d_wk;
-        a.wrem = h->d_wrem;
-        a.fmod = h->d_fmod;
+        set_tables(h, a);
         a.out = y;
         a.tails = h->d_tails;
         a.tails_nch = h->tails_nch;
         a.pipe = true;
-        a.lds_bytes = h->sw.ddc_lds;
         a.sh.N = h->ddc_channels;
         a.sh.Npad = h->Npad;
         a.sh.TW = h->TW;
@@ -719,7 +694,6 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
         a.sh.nblk = nblk;
         a.sh.nch = pick_chunks(h, nblk);
         a.sh.xlast = (long long)nblk * h->M + h->pad - 4;
-        a.sh.prefetch = h->sw.ddc_prefetch;
         finish_shape(a.sh);
         float ms = 0.f;
         for (int it = 0; it < 4 && !rc; ++it) {  // first iteration warms up
@@ -867,16 +841,9 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
 int enqueue_direct(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     DdcLaunch a{};
     a.x = in;
-    a.taps_t = h->d_taps_t;
-    a.taps_p = h->d_taps_p;
+    set_tables(h, a);
     a.pipe = h->pipe && h->decim > 0 && h->L >= 4;
     a.few = h->few;
-    a.lds_bytes = h->sw.ddc_lds;
-    a.sh.prefetch = h->sw.ddc_prefetch;
-    a.btab = h->d_btab;
-    a.wk = h->d_wk;
-    a.wrem = h->d_wrem;
-    a.fmod = h->d_fmod;
     a.out = out;
     a.sh.N = h->N;
     a.sh.Npad = h->Npad;
@@ -1016,12 +983,7 @@ int enqueue_pfb(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     } else if (cb > 0) {
         DdcLaunch a{};
         a.x = win;
-        a.taps_t = h->d_taps_t;
-        a.taps_p = h->d_taps_p;
-        a.btab = h->d_btab;
-        a.wk = h->d_wk;
-        a.wrem = h->d_wrem;
-        a.fmod = h->d_fmod;
+        set_tables(h, a);
         a.out = out;
         a.tails = h->d_tails;
         a.tails_nch = h->tails_nch;
@@ -1035,8 +997,6 @@ int enqueue_pfb(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
         a.sh.M = h->M;
         a.sh.nblk = cb + h->F - 1;  // frame r spans blocks r .. r+F-1
         a.pipe = h->pipe;
-        a.lds_bytes = h->sw.ddc_lds;
-        a.sh.prefetch = h->sw.ddc_prefetch;
         a.sh.xlast = (long long)a.sh.nblk * h->M + h->pad - 4;  // a window is allocated twice as long
         a.sh.g_off = h->F - 1;      // DDC output G <-> frame r = G-(F-1)
         const int nch = pick_chunks(h, a.sh.nblk);
@@ -1121,9 +1081,9 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
 
 // gsdr_demod_create with the switches given (gsdr_demod_prepare's rehearsal twin takes its parent's)
 gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
-    g_create_error.clear();
+    create_error().clear();
     if (!p) {
-        g_create_error = "null parameters";
+        create_error() = "null parameters";
         return nullptr;
     }
     gsdr_demod *h = new gsdr_demod();
@@ -1386,11 +1346,7 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
             if (!need(cp.num_steps >= 1 && cp.length >= 1 &&
                           cp.num_steps <= 0x7fffffffffffffffULL / cp.length,
                       "chirp period overflows")) return nullptr;
-            h->cs.num_steps = cp.num_steps;
-            h->cs.length = cp.length;
-            h->cs.period = cp.num_steps * cp.length;
-            h->cs.chirpness = cp.chirpness;
-            h->cs.f0 = cp.f0;
+            h->cs = chirp_shape(cp);
             if (h->decim > 0) {
                 const unsigned long long ppt = cp.length * (unsigned long long)h->decim;  // :231
                 if (!need(ppt >= 1 && ppt <= (unsigned long long)h->L,
@@ -1442,7 +1398,7 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
 extern "C" {
 
 const char *gsdr_last_error(const gsdr_demod *h) {
-    return h ? h->err.c_str() : g_create_error.c_str();
+    return h ? h->err.c_str() : create_error().c_str();
 }
 
 gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gsdr::read_switches()); }
@@ -1454,28 +1410,33 @@ gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gs
 static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 *in16, float2 *wide, float2 *out,
                                hipStream_t st);
 
-int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev,
-                              void *hip_stream) {
+// What every entry that takes a buffer starts with: -1 without a handle, "null buffer" into the handle without a buffer
+static int refuse_null(gsdr_demod *h, const void *in, const void *out) {
     if (!h) return -1;
-    if (!in_dev || !out_dev) {
+    if (!in || !out) {
         h->err = "null buffer";
         return -1;
     }
+    return 0;
+}
+
+// gsdr_demod_process_device and gsdr_demod_process_device_sc16 (in16_dev != nullptr)
+static int process_device(gsdr_demod *h, const gsdr_c64 *in_dev, const gsdr_sc16 *in16_dev, gsdr_c64 *out_dev,
+                          void *hip_stream) {
+    if (refuse_null(h, in16_dev ? (const void *)in16_dev : in_dev, out_dev)) return -1;
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
+    if (in16_dev && h->mode != GSDR_NODSP && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
     // NULL is HIP's null stream, as everywhere in HIP
-    return process_device_body(h, reinterpret_cast<const float2 *>(in_dev), nullptr, nullptr,
+    return process_device_body(h, reinterpret_cast<const float2 *>(in_dev), in16_dev, in16_dev ? h->d_wide : nullptr,
                                reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
 }
 
+int gsdr_demod_process_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev, void *hip_stream) {
+    return process_device(h, in_dev, nullptr, out_dev, hip_stream);
+}
+
 int gsdr_demod_process_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, void *hip_stream) {
-    if (!h) return -1;
-    if (!in_dev || !out_dev) {
-        h->err = "null buffer";
-        return -1;
-    }
-    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (h->mode != GSDR_NODSP && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
-    return process_device_body(h, nullptr, in_dev, h->d_wide, reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
+    return process_device(h, nullptr, in_dev, out_dev, hip_stream);
 }
 
 static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 *in16, float2 *wide, float2 *out,
@@ -1508,14 +1469,12 @@ static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 
     return n;
 }
 
-int gsdr_demod_process(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host) {
-    if (!h) return -1;
-    if (!in_host || !out_host) {
-        h->err = "null buffer";
-        return -1;
-    }
-    if (h->mode == GSDR_NODSP) {  // ref: :335-339, a host memcpy
-        std::memcpy(out_host, in_host, (size_t)h->L * sizeof(gsdr_c64));
+// gsdr_demod_process and gsdr_demod_process_sc16 (in16_host != nullptr)
+static int process_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *in16_host, gsdr_c64 *out_host) {
+    if (refuse_null(h, in16_host ? (const void *)in16_host : in_host, out_host)) return -1;
+    if (h->mode == GSDR_NODSP) {  // ref: :335-339, a host memcpy; sc16 samples are widened on the host instead
+        if (in16_host) gsdr_widen_sc16_host(in16_host, out_host, h->L, h->sc16_scale);
+        else std::memcpy(out_host, in_host, (size_t)h->L * sizeof(gsdr_c64));
         return (int)h->L;
     }
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
@@ -1523,10 +1482,16 @@ int gsdr_demod_process(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_hos
         HIPCHK(h, dev_alloc(&h->d_in, (size_t)h->L));
         HIPCHK(h, dev_alloc(&h->d_out, (size_t)h->capacity));
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_in, in_host, (size_t)h->L * sizeof(float2),
-                             hipMemcpyHostToDevice, h->stream));
-    const int ret = gsdr_demod_process_device(h, reinterpret_cast<gsdr_c64 *>(h->d_in),
-                                              reinterpret_cast<gsdr_c64 *>(h->d_out), h->stream);
+    if (in16_host) {
+        // half the bytes over the host link; widened into the staging buffer of the complex64 entry
+        if (!h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
+        HIPCHK(h, hipMemcpyAsync(h->d_in16, in16_host, (size_t)h->L * sizeof(gsdr_sc16), hipMemcpyHostToDevice, h->stream));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->d_in, in_host, (size_t)h->L * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    }
+    // complex64: the samples are in d_in; sc16: they are in d_in16 and the body widens them into d_in
+    const int ret = in16_host ? process_device_body(h, nullptr, h->d_in16, h->d_in, h->d_out, h->stream)
+                              : process_device_body(h, h->d_in, nullptr, nullptr, h->d_out, h->stream);
     if (ret < 0) return ret;
     if (ret > 0)
         HIPCHK(h, hipMemcpyAsync(out_host, h->d_out, (size_t)ret * sizeof(float2),
@@ -1535,31 +1500,12 @@ int gsdr_demod_process(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_hos
     return ret;
 }
 
+int gsdr_demod_process(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host) {
+    return process_host(h, in_host, nullptr, out_host);
+}
+
 int gsdr_demod_process_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *out_host) {
-    if (!h) return -1;
-    if (!in_host || !out_host) {
-        h->err = "null buffer";
-        return -1;
-    }
-    if (h->mode == GSDR_NODSP) {  // the complex64 entry copies on the host, this one widens there
-        gsdr_widen_sc16_host(in_host, out_host, h->L, h->sc16_scale);
-        return (int)h->L;
-    }
-    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_in) {
-        HIPCHK(h, dev_alloc(&h->d_in, (size_t)h->L));
-        HIPCHK(h, dev_alloc(&h->d_out, (size_t)h->capacity));
-    }
-    if (!h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
-    // half the bytes over the host link; widened into the staging buffer of the complex64 entry
-    HIPCHK(h, hipMemcpyAsync(h->d_in16, in_host, (size_t)h->L * sizeof(gsdr_sc16), hipMemcpyHostToDevice, h->stream));
-    const int ret = process_device_body(h, nullptr, h->d_in16, h->d_in, h->d_out, h->stream);
-    if (ret < 0) return ret;
-    if (ret > 0)
-        HIPCHK(h, hipMemcpyAsync(out_host, h->d_out, (size_t)ret * sizeof(float2),
-                                 hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ret;
+    return process_host(h, nullptr, in_host, out_host);
 }
 
 static void pipeline_teardown(gsdr_demod *h) {
@@ -1748,37 +1694,30 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
             ok = gsdr_demod_prepare(twin, what & ~GSDR_PREPARE_REHEARSE) == 0;
             if (ok && (what & GSDR_PREPARE_HOST))
                 for (int k = 0; k < 2 && ok; ++k) ok = gsdr_demod_process(twin, pin_in, pin_out) >= 0;
-            if (ok && (what & GSDR_PREPARE_PIPELINE_HOST)) {
+            // `count` buffers through a submit entry of the twin, waiting whenever the pipeline is full
+            auto rehearse_submit = [&](auto submit, int count) {
                 int pending = 0;
-                for (int k = 0; k < 2 * GSDR_PIPELINE_DEPTH + 2 && ok; ++k) {
+                for (int k = 0; k < count && ok; ++k) {
                     if (pending == GSDR_PIPELINE_DEPTH) {
                         ok = gsdr_demod_wait(twin) >= 0;
                         --pending;
                     }
-                    ok = ok && gsdr_demod_submit(twin, pin_in, pin_out) == 0;
+                    ok = ok && submit() == 0;
                     ++pending;
                 }
                 while (ok && pending-- > 0) ok = gsdr_demod_wait(twin) >= 0;
-            }
+            };
+            if (ok && (what & GSDR_PREPARE_PIPELINE_HOST))
+                rehearse_submit([&] { return gsdr_demod_submit(twin, pin_in, pin_out); }, 2 * GSDR_PIPELINE_DEPTH + 2);
             // the sc16 forms of the same entries (first launch of the widening kernel, on both streams it runs on);
             // the zeros of pin_in serve as L sc16 samples too
             const gsdr_sc16 *pin_in16 = reinterpret_cast<const gsdr_sc16 *>(pin_in);
             if (ok && sc16 && (what & GSDR_PREPARE_HOST))
                 for (int k = 0; k < 2 && ok; ++k) ok = gsdr_demod_process_sc16(twin, pin_in16, pin_out) >= 0;
-            if (ok && sc16 && (what & GSDR_PREPARE_PIPELINE_HOST)) {
-                int pending = 0;
-                for (int k = 0; k < GSDR_PIPELINE_DEPTH + 2 && ok; ++k) {
-                    if (pending == GSDR_PIPELINE_DEPTH) {
-                        ok = gsdr_demod_wait(twin) >= 0;
-                        --pending;
-                    }
-                    ok = ok && gsdr_demod_submit_sc16(twin, pin_in16, pin_out) == 0;
-                    ++pending;
-                }
-                while (ok && pending-- > 0) ok = gsdr_demod_wait(twin) >= 0;
-            }
+            if (ok && sc16 && (what & GSDR_PREPARE_PIPELINE_HOST))
+                rehearse_submit([&] { return gsdr_demod_submit_sc16(twin, pin_in16, pin_out); }, GSDR_PIPELINE_DEPTH + 2);
         }
-        if (!ok) h->err = std::string("rehearsal failed: ") + (twin ? twin->err : g_create_error);
+        if (!ok) h->err = std::string("rehearsal failed: ") + (twin ? twin->err : create_error());
         if (pin_in) (void)hipHostFree(pin_in);
         if (pin_out) (void)hipHostFree(pin_out);
         if (twin) gsdr_demod_close(twin);
@@ -1787,22 +1726,34 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     return 0;
 }
 
-// gsdr_demod_submit and gsdr_demod_submit_sc16 (in16_host != nullptr)
-static int submit_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *in16_host, gsdr_c64 *out_host) {
-    if (!h) return -1;
-    if (!(in_host || in16_host) || !out_host) {
-        h->err = "null buffer";
-        return -1;
-    }
+// What every submit entry starts with: the refusals, the device, the pipeline, and the slot the buffer goes to.  The slot
+// is free: its previous download (or kernels) were waited for in gsdr_demod_wait().
+static int submit_begin(gsdr_demod *h, const void *in, const void *out, gsdr_demod::Slot **slot) {
+    if (refuse_null(h, in, out)) return -1;
     if (h->pipe_count >= GSDR_PIPELINE_DEPTH) {
         h->err = "pipeline full: call gsdr_demod_wait() first";
         return -1;
     }
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
     if (pipeline_init(h)) return -1;
-    auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
+    *slot = &h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
+    return 0;
+}
+
+// ... and ends with: the n samples of the slot are there when wait_ev has happened
+static int submit_end(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t wait_ev, int n) {
+    sl.wait_ev = wait_ev;
+    sl.n = n;
+    h->pipe_count++;
+    return 0;
+}
+
+// gsdr_demod_submit and gsdr_demod_submit_sc16 (in16_host != nullptr)
+static int submit_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *in16_host, gsdr_c64 *out_host) {
+    gsdr_demod::Slot *slot = nullptr;
+    if (submit_begin(h, in16_host ? (const void *)in16_host : in_host, out_host, &slot)) return -1;
+    auto &sl = *slot;
     if (slot_buffers(h, sl, true, true, in16_host != nullptr)) return -1;
-    // the slot is free: its previous download was waited for in gsdr_demod_wait()
     if (in16_host) {
         // half the bytes, then the widening, both on the upload stream in front of sl.up: it overlaps the kernels of
         // the buffer before and does not lengthen the compute stream
@@ -1818,10 +1769,7 @@ static int submit_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *
     if (n > 0)
         HIPCHK(h, hipMemcpyAsync(out_host, sl.d_out, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->s_down));
     HIPCHK(h, hipEventRecord(sl.down, h->s_down));
-    sl.wait_ev = sl.down;
-    sl.n = n;
-    h->pipe_count++;
-    return 0;
+    return submit_end(h, sl, sl.down, n);
 }
 
 int gsdr_demod_submit(gsdr_demod *h, const gsdr_c64 *in_host, gsdr_c64 *out_host) {
@@ -1832,57 +1780,35 @@ int gsdr_demod_submit_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *ou
     return submit_host(h, nullptr, in_host, out_host);
 }
 
-int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev) {
-    if (!h) return -1;
-    if (!in_dev || !out_dev) {
-        h->err = "null buffer";
-        return -1;
+// gsdr_demod_submit_device and gsdr_demod_submit_device_sc16 (in16_dev != nullptr)
+static int submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, const gsdr_sc16 *in16_dev, gsdr_c64 *out_dev) {
+    gsdr_demod::Slot *slot = nullptr;
+    if (submit_begin(h, in16_dev ? (const void *)in16_dev : in_dev, out_dev, &slot)) return -1;
+    auto &sl = *slot;
+    float2 *out = reinterpret_cast<float2 *>(out_dev);
+    int n;
+    if (!in16_dev) {
+        n = pipeline_compute(h, sl, nullptr, reinterpret_cast<const float2 *>(in_dev), out);
+    } else if (h->mode == GSDR_NODSP) {
+        n = pipeline_compute(h, sl, nullptr, nullptr, out, in16_dev);
+    } else {
+        // in16_dev is complete (the contract of the complex64 entry): widened into the slot's input buffer -- free, its last
+        // reader was waited for in gsdr_demod_wait() -- on the upload stream, beside the kernels of the buffer before
+        if (slot_buffers(h, sl, true, false, false)) return -1;
+        HIPCHK(h, gsdr::launch_widen_sc16(in16_dev, sl.d_in, h->L, h->sc16_scale, h->cus, h->s_up));
+        HIPCHK(h, hipEventRecord(sl.up, h->s_up));
+        n = pipeline_compute(h, sl, sl.up, sl.d_in, out);
     }
-    if (h->pipe_count >= GSDR_PIPELINE_DEPTH) {
-        h->err = "pipeline full: call gsdr_demod_wait() first";
-        return -1;
-    }
-    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (pipeline_init(h)) return -1;
-    auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
-    const int n = pipeline_compute(h, sl, nullptr, reinterpret_cast<const float2 *>(in_dev),
-                                   reinterpret_cast<float2 *>(out_dev));
     if (n < 0) return -1;
-    sl.wait_ev = sl.done;
-    sl.n = n;
-    h->pipe_count++;
-    return 0;
+    return submit_end(h, sl, sl.done, n);
+}
+
+int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *out_dev) {
+    return submit_device(h, in_dev, nullptr, out_dev);
 }
 
 int gsdr_demod_submit_device_sc16(gsdr_demod *h, const gsdr_sc16 *in_dev, gsdr_c64 *out_dev) {
-    if (!h) return -1;
-    if (!in_dev || !out_dev) {
-        h->err = "null buffer";
-        return -1;
-    }
-    if (h->pipe_count >= GSDR_PIPELINE_DEPTH) {
-        h->err = "pipeline full: call gsdr_demod_wait() first";
-        return -1;
-    }
-    if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (pipeline_init(h)) return -1;
-    auto &sl = h->slot[(h->pipe_head + h->pipe_count) % GSDR_PIPELINE_DEPTH];
-    int n;
-    if (h->mode == GSDR_NODSP) {
-        n = pipeline_compute(h, sl, nullptr, nullptr, reinterpret_cast<float2 *>(out_dev), in_dev);
-    } else {
-        // in_dev is complete (the contract of the complex64 entry): widened into the slot's input buffer -- free, its last
-        // reader was waited for in gsdr_demod_wait() -- on the upload stream, beside the kernels of the buffer before
-        if (slot_buffers(h, sl, true, false, false)) return -1;
-        HIPCHK(h, gsdr::launch_widen_sc16(in_dev, sl.d_in, h->L, h->sc16_scale, h->cus, h->s_up));
-        HIPCHK(h, hipEventRecord(sl.up, h->s_up));
-        n = pipeline_compute(h, sl, sl.up, sl.d_in, reinterpret_cast<float2 *>(out_dev));
-    }
-    if (n < 0) return -1;
-    sl.wait_ev = sl.done;
-    sl.n = n;
-    h->pipe_count++;
-    return 0;
+    return submit_device(h, nullptr, in_dev, out_dev);
 }
 
 int gsdr_demod_wait(gsdr_demod *h) {
@@ -2024,31 +1950,31 @@ int gsdr_frame_average_device(const gsdr_c64 *frames_dev, int n_frames, int n_ch
              (((long long)count + n_frames) / k > 0 && !out_dev)) bad = "null buffer";
     else if (((uintptr_t)frames_dev | (uintptr_t)acc_in_dev | (uintptr_t)acc_out_dev | (uintptr_t)out_dev) & 7) bad = "pointers must be 8-byte aligned";
     if (bad) {
-        g_create_error = std::string("gsdr_frame_average_device: ") + bad;
+        create_error() = std::string("gsdr_frame_average_device: ") + bad;
         return -1;
     }
     const hipError_t e = gsdr::launch_pfb_average(reinterpret_cast<const float2 *>(frames_dev), n_frames, n_ch, k, kind, count,
                                                   reinterpret_cast<const float2 *>(acc_in_dev), reinterpret_cast<float2 *>(acc_out_dev),
                                                   reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
     if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_frame_average_device: ") + hipGetErrorString(e);
+        create_error() = std::string("gsdr_frame_average_device: ") + hipGetErrorString(e);
         return -1;
     }
     return (int)(((long long)count + n_frames) / k);
 }
 
 // gsdr_frame_average_host (host_logic.cpp) leaves its message here
-void gsdr_note_error_(const char *msg) { g_create_error = msg ? msg : ""; }
+void gsdr_note_error_(const char *msg) { create_error() = msg ? msg : ""; }
 
 int gsdr_widen_sc16_device(const gsdr_sc16 *in_dev, gsdr_c64 *out_dev, long long n, float scale, void *hip_stream) {
     if (n < 0 || (n > 0 && (!in_dev || !out_dev))) {
-        g_create_error = "gsdr_widen_sc16_device: null buffer";
+        create_error() = "gsdr_widen_sc16_device: null buffer";
         return -1;
     }
     const hipError_t e = gsdr::launch_widen_sc16(in_dev, reinterpret_cast<float2 *>(out_dev), n, scale, device_cus(),
                                                  (hipStream_t)hip_stream);
     if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_widen_sc16_device: ") + hipGetErrorString(e);
+        create_error() = std::string("gsdr_widen_sc16_device: ") + hipGetErrorString(e);
         return -1;
     }
     return 0;
@@ -2164,577 +2090,6 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     std::memcpy(buf, s.data(), (size_t)n);
     buf[n] = 0;
     return n;
-}
-
-// ---- synthetic sources -----------------------------------------------------
-int gsdr_source_tones(gsdr_c64 *out_dev, long long n, long long start, int rate, const int *freq,
-                      const float *ampl, const float *phase, int n_tones, float sigma,
-                      unsigned long long seed, void *hip_stream) {
-    if (!out_dev || n < 0 || rate <= 0 || n_tones < 0) return -1;
-    std::vector<unsigned> fm(n_tones > 0 ? n_tones : 1, 0u);
-    for (int k = 0; k < n_tones; ++k) {
-        long long r = (long long)freq[k] % rate;
-        if (r < 0) r += rate;
-        fm[k] = (unsigned)r;
-    }
-    unsigned *d_f = nullptr;
-    float *d_a = nullptr, *d_p = nullptr;
-    const size_t cnt = fm.size();
-    hipError_t e = hipMalloc((void **)&d_f, cnt * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_a, cnt * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_p, cnt * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_f, fm.data(), cnt * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_tones > 0) e = hipMemcpy(d_a, ampl, n_tones * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_tones > 0) e = hipMemcpy(d_p, phase, n_tones * sizeof(float), hipMemcpyHostToDevice);
-    hipStream_t st = (hipStream_t)hip_stream;
-    long long start_mod = start % rate;
-    if (start_mod < 0) start_mod += rate;
-    if (e == hipSuccess)
-        e = gsdr::launch_source_tones(reinterpret_cast<float2 *>(out_dev), n, start_mod, (unsigned)rate,
-                                      d_f, d_a, d_p, n_tones, sigma, seed, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_f) (void)hipFree(d_f);
-    if (d_a) (void)hipFree(d_a);
-    if (d_p) (void)hipFree(d_p);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_source_tones: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-// ---- TX tone comb at scale (row f3) ------------------------------------------
-struct gsdr_txgen {
-    int device = -1;
-    unsigned rate = 1;
-    int n_tones = 0;
-    unsigned *d_fmod = nullptr;
-    float2 *d_q0 = nullptr, *d_btab = nullptr, *d_ctab = nullptr;
-    // the TX_buffer_generator state (gsdr_txgen_create)
-    int mode = -1;                     // GSDR_TONES / GSDR_CHIRP, -1: a bare tone comb (gsdr_txgen_tones_create)
-    long long buffer_len = 0;
-    unsigned long long period = 1, last = 0;
-    gsdr_chirp_param cp{};
-    float scale = 1.f;
-    float2 *d_stage = nullptr;         // get() to host memory goes through here
-    size_t stage_n = 0;                // samples d_stage holds
-    // TONES through gsdr_txgen_get_ptr: one period + one buffer of the comb in host memory, made once
-    // (the reference's base_buffer, cpp/USRP_buffer_generator.cpp:77-95)
-    float2 *h_period = nullptr;
-    bool h_period_pinned = false;
-    // sc16 output (gsdr_txgen_*_sc16): the gain of the narrowing, the counter of clipped components (device memory,
-    // zeroed at creation), the staging buffer of get_sc16() (4 bytes per sample) and a period buffer of its own
-    float sc16_gain = 32767.0f;
-    unsigned long long *d_clipped = nullptr;
-    gsdr_sc16 *d_stage16 = nullptr;
-    size_t stage16_n = 0;
-    gsdr_sc16 *h_period16 = nullptr;
-    bool h_period16_pinned = false;
-};
-
-// the generator's counter of clipped components: 8 bytes of device memory, zero (the creating call has set the device)
-static bool txgen_make_counter(gsdr_txgen *g) {
-    return hipMalloc((void **)&g->d_clipped, sizeof(unsigned long long)) == hipSuccess &&
-           hipMemset(g->d_clipped, 0, sizeof(unsigned long long)) == hipSuccess;
-}
-
-gsdr_txgen *gsdr_txgen_tones_create(int rate, const int *freq, const float *ampl, const float *phase, int n_tones,
-                                    int device_index) {
-    g_create_error.clear();
-    if (rate <= 0 || n_tones < 0 || (n_tones > 0 && (!freq || !ampl))) {
-        g_create_error = "gsdr_txgen_tones_create: bad arguments";
-        return nullptr;
-    }
-    if (device_index >= 0 && hipSetDevice(device_index) != hipSuccess) {
-        g_create_error = "gsdr_txgen_tones_create: hipSetDevice failed (no such GPU?)";
-        return nullptr;
-    }
-    gsdr_txgen *g = new gsdr_txgen();
-    g->device = device_index;
-    g->rate = (unsigned)rate;
-    g->n_tones = n_tones;
-    const size_t N = (size_t)(n_tones > 0 ? n_tones : 1);
-    std::vector<unsigned> fm(N, 0u);
-    std::vector<float2> q0(N, make_float2(0.f, 0.f)), bt(N * 64), ct(N * 16);
-    for (int k = 0; k < n_tones; ++k) {
-        long long r = (long long)freq[k] % rate;
-        if (r < 0) r += rate;
-        fm[(size_t)k] = (unsigned)r;
-        const double ph0 = phase ? (double)phase[k] : 0.0;
-        q0[(size_t)k] = make_float2((float)((double)ampl[k] * std::cos(ph0)), (float)((double)ampl[k] * std::sin(ph0)));
-        // w^m for the exact integer phase (f m) mod rate, TX sign: e^(+2 pi i ...)
-        auto w = [&](unsigned long long m) {
-            double re, im;
-            phasor(((unsigned long long)r * m) % (unsigned long long)rate, (unsigned)rate, re, im);   // e^(-...)
-            return make_float2((float)re, (float)-im);
-        };
-        for (int lo = 0; lo < 64; ++lo) bt[(size_t)k * 64 + lo] = w((unsigned long long)lo);
-        for (int j = 0; j < 16; ++j) ct[(size_t)k * 16 + j] = w(64ULL * (unsigned long long)j);
-    }
-    const bool ok = upload(&g->d_fmod, fm) == hipSuccess && upload(&g->d_q0, q0) == hipSuccess &&
-                    upload(&g->d_btab, bt) == hipSuccess && upload(&g->d_ctab, ct) == hipSuccess &&
-                    txgen_make_counter(g) && hipStreamSynchronize(nullptr) == hipSuccess;
-    if (!ok) {
-        g_create_error = "gsdr_txgen_tones_create: device allocation failed";
-        gsdr_txgen_close(g);
-        return nullptr;
-    }
-    return g;
-}
-
-int gsdr_txgen_tones_fill(gsdr_txgen *g, gsdr_c64 *out_dev, long long n, long long start, void *hip_stream) {
-    if (!g || !out_dev || n < 0) {
-        g_create_error = "gsdr_txgen_tones_fill: bad arguments";
-        return -1;
-    }
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_tones_fill: hipSetDevice failed";
-        return -1;
-    }
-    long long sm = start % (long long)g->rate;
-    if (sm < 0) sm += g->rate;
-    const hipError_t e = gsdr::launch_tones_synth(reinterpret_cast<float2 *>(out_dev), n, (unsigned long long)sm, g->rate,
-                                                  g->d_fmod, g->d_q0, g->d_btab, g->d_ctab, g->n_tones, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_txgen_tones_fill: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-void gsdr_txgen_close(gsdr_txgen *g) {
-    if (!g) return;
-    if (g->device >= 0) (void)hipSetDevice(g->device);
-    (void)hipDeviceSynchronize();
-    for (void *p : {(void *)g->d_fmod, (void *)g->d_q0, (void *)g->d_btab, (void *)g->d_ctab, (void *)g->d_stage,
-                    (void *)g->d_clipped, (void *)g->d_stage16})
-        if (p) (void)hipFree(p);
-    if (g->h_period) {
-        if (g->h_period_pinned) (void)hipHostFree(g->h_period);
-        else std::free(g->h_period);
-    }
-    if (g->h_period16) {
-        if (g->h_period16_pinned) (void)hipHostFree(g->h_period16);
-        else std::free(g->h_period16);
-    }
-    delete g;
-}
-
-// ref: TX_buffer_generator::TX_buffer_generator, cpp/USRP_buffer_generator.cpp:10-160
-gsdr_txgen *gsdr_txgen_create(const gsdr_param_c *p, const float *ampl, int n_ampl) {
-    g_create_error.clear();
-    auto fail = [](const char *msg) {
-        g_create_error = msg;
-        return (gsdr_txgen *)nullptr;
-    };
-    if (!p) return fail("null parameters");
-    if (p->buffer_len < 1) return fail("buffer_len must be positive");
-    if (p->rate < 1) return fail("rate must be positive");
-    if (p->n_wave_type < 1 || !p->wave_type) return fail("TX buffer generation needs at least one wave_type");
-    const int last = p->wave_type[0];
-    int chirps = 0;
-    bool mixed = false;
-    for (int i = 0; i < p->n_wave_type; ++i) {
-        chirps += p->wave_type[i] == GSDR_CHIRP;
-        mixed |= p->wave_type[i] != last;
-    }
-    if (chirps > 1)      // :26-29
-        return fail("Multiple chirp TX buffer generation has been requested. This feature is not implemented yet.");
-    if (mixed)           // :31-34
-        return fail("Mixed TX buffer generation has been requested. This feature is not implemented yet.");
-    if (last == GSDR_NODSP || last == GSDR_SWONLY) return fail("NODSP CASE NOT IMPLEMENTED.");   // :41-44
-    if (last == GSDR_RAMP || last == GSDR_DIRECT) return fail("RAMP CASE NOT IMPLEMENTED.");      // :46-49
-    gsdr_txgen *g = nullptr;
-    // NOISE: the reference's `case NOISE:` (:52-58) has no break and falls through into TONES, which overwrites its
-    // get/close pointers: a TX NOISE request generates the tone comb of freq[] / ampl[] there, and so it does here
-    if (last == GSDR_TONES || last == GSDR_NOISE) {
-        const int n = p->n_wave_type;
-        if (p->n_freq < n || !p->freq || n_ampl < n || !ampl) return fail("TONES needs freq[] and ampl[] for every wave_type entry");
-        std::vector<int> tf((size_t)n);
-        std::vector<float> ta((size_t)n);
-        const int nt = gsdr_tx_tone_bins(p->rate, p->freq, ampl, n, tf.data(), ta.data());
-        g = gsdr_txgen_tones_create(p->rate, tf.data(), ta.data(), nullptr, nt > 0 ? nt : 0, p->device_index);
-        if (!g) return nullptr;
-        // TONES_buffer_len: rate, or the multiple of it that holds one buffer (:60-75)
-        g->period = (unsigned long long)p->rate * (unsigned long long)((p->buffer_len + p->rate - 1) / p->rate);
-    } else if (last == GSDR_CHIRP) {
-        if (p->n_freq < 1 || p->n_chirp_f < 1 || p->n_swipe_s < 1 || p->n_chirp_t < 1 || !p->freq || !p->chirp_f ||
-            !p->swipe_s || !p->chirp_t)
-            return fail("CHIRP needs freq[0], chirp_f[0], swipe_s[0] and chirp_t[0]");
-        if (p->device_index >= 0 && hipSetDevice(p->device_index) != hipSuccess)
-            return fail("hipSetDevice failed (no such GPU?)");
-        g = new gsdr_txgen();
-        g->device = p->device_index;
-        g->rate = (unsigned)p->rate;
-        // the TX side's own derivation: a step shorter than one sample also resets num_steps, and the slope
-        // follows the reset value (:107-129)
-        gsdr_chirp_derive_tx(p->rate, p->freq[0], p->chirp_f[0], p->swipe_s[0], p->chirp_t[0], &g->cp);
-        if (g->cp.num_steps < 1 || g->cp.length < 1 || g->cp.num_steps > 0x7fffffffffffffffULL / g->cp.length) {
-            delete g;
-            return fail("chirp period overflows");
-        }
-        g->period = g->cp.num_steps * g->cp.length;
-        g->scale = n_ampl > 0 && ampl ? ampl[0] : 1.f;
-        if (!txgen_make_counter(g) || hipStreamSynchronize(nullptr) != hipSuccess) {
-            gsdr_txgen_close(g);
-            return fail("device allocation failed");
-        }
-    } else {
-        return fail("Void TX generation operation has not been implemented yet!");
-    }
-    g->mode = last == GSDR_NOISE ? GSDR_TONES : last;
-    g->buffer_len = p->buffer_len;
-    g->last = 0;
-    return g;
-}
-
-long long gsdr_txgen_buffer_len(const gsdr_txgen *g) { return g ? g->buffer_len : 0; }
-
-// ref: get_from_tones :226-229, get_from_chirp :208-221
-int gsdr_txgen_get_device(gsdr_txgen *g, gsdr_c64 *out_dev, void *hip_stream) {
-    if (!g || !out_dev || g->mode < 0) {
-        g_create_error = "gsdr_txgen_get: bad arguments";
-        return -1;
-    }
-    int rc;
-    if (g->mode == GSDR_TONES) {
-        rc = gsdr_txgen_tones_fill(g, out_dev, g->buffer_len, (long long)(g->last % g->rate), hip_stream);
-    } else {
-        if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-            g_create_error = "gsdr_txgen_get: hipSetDevice failed";
-            return -1;
-        }
-        rc = gsdr_source_chirp(out_dev, g->buffer_len, g->last, &g->cp, g->scale, hip_stream);
-    }
-    if (rc == 0) g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
-    return rc;
-}
-
-int gsdr_txgen_get(gsdr_txgen *g, gsdr_c64 *out_host) {
-    if (!g || !out_host || g->mode < 0) {
-        g_create_error = "gsdr_txgen_get: bad arguments";
-        return -1;
-    }
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_get: hipSetDevice failed";
-        return -1;
-    }
-    if (g->d_stage && g->stage_n < (size_t)g->buffer_len) {
-        (void)hipFree(g->d_stage);
-        g->d_stage = nullptr;
-    }
-    if (!g->d_stage) {
-        if (dev_alloc(&g->d_stage, (size_t)g->buffer_len) != hipSuccess) {
-            g_create_error = "gsdr_txgen_get: device allocation failed";
-            return -1;
-        }
-        g->stage_n = (size_t)g->buffer_len;
-    }
-    if (gsdr_txgen_get_device(g, reinterpret_cast<gsdr_c64 *>(g->d_stage), nullptr) != 0) return -1;
-    const hipError_t e = hipMemcpy(out_host, g->d_stage, (size_t)g->buffer_len * sizeof(float2), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_txgen_get: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-// ref: the TONES branch of the constructor (:77-95): base_buffer = one period (TONES_buffer_len samples) plus
-// buffer_len more (a copy of its beginning), in host memory.  Made once, in pieces through a device buffer.
-int gsdr_txgen_prepare_host(gsdr_txgen *g) {
-    if (!g || g->mode != GSDR_TONES) {
-        g_create_error = "gsdr_txgen_prepare_host: a TONES generator is needed";
-        return -1;
-    }
-    if (g->h_period) return 0;
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_prepare_host: hipSetDevice failed";
-        return -1;
-    }
-    const unsigned long long total = g->period + (unsigned long long)g->buffer_len;
-    float2 *hp = nullptr;
-    bool pinned = hipHostMalloc((void **)&hp, (size_t)total * sizeof(float2)) == hipSuccess;
-    if (!pinned) {
-        (void)hipGetLastError();
-        hp = (float2 *)std::malloc((size_t)total * sizeof(float2));
-    }
-    if (!hp) {
-        g_create_error = "gsdr_txgen_prepare_host: cannot allocate the period buffer in host memory";
-        return -1;
-    }
-    const size_t piece = (size_t)(total < (8u << 20) ? total : (8u << 20));
-    if (g->d_stage && g->stage_n < piece) {
-        (void)hipFree(g->d_stage);
-        g->d_stage = nullptr;
-    }
-    bool ok = true;
-    if (!g->d_stage) {
-        ok = dev_alloc(&g->d_stage, piece) == hipSuccess;
-        g->stage_n = ok ? piece : 0;
-    }
-    for (unsigned long long off = 0; ok && off < total; off += piece) {
-        const long long n = (long long)(total - off < piece ? total - off : piece);
-        ok = gsdr_txgen_tones_fill(g, reinterpret_cast<gsdr_c64 *>(g->d_stage), n, (long long)(off % g->rate), nullptr) == 0 &&
-             hipMemcpy(hp + off, g->d_stage, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (!ok) {
-        if (pinned) (void)hipHostFree(hp);
-        else std::free(hp);
-        if (g_create_error.empty()) g_create_error = "gsdr_txgen_prepare_host: generating the period failed";
-        return -1;
-    }
-    g->h_period = hp;
-    g->h_period_pinned = pinned;
-    return 0;
-}
-
-// ref: get_from_tones (:226-229): *target = base_buffer + TONES_last_sample -- the caller's pointer is REPLACED by one
-// into the generator's own period buffer (tx_single_link hands in an unallocated pointer for TONES,
-// cpp/USRP_server_link_threads.cpp:568-584, and never frees what it gets back).
-const gsdr_c64 *gsdr_txgen_get_ptr(gsdr_txgen *g) {
-    if (!g || g->mode != GSDR_TONES) {
-        g_create_error = "gsdr_txgen_get_ptr: a TONES generator is needed";
-        return nullptr;
-    }
-    if (!g->h_period && gsdr_txgen_prepare_host(g) != 0) return nullptr;
-    const gsdr_c64 *p = reinterpret_cast<const gsdr_c64 *>(g->h_period + g->last);
-    g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
-    return p;
-}
-
-int gsdr_txgen_mode(const gsdr_txgen *g) { return g ? g->mode : -1; }
-
-int gsdr_source_chirp(gsdr_c64 *out_dev, long long n, unsigned long long last_index,
-                      const gsdr_chirp_param *cp, float scale, void *hip_stream) {
-    if (!out_dev || !cp || n < 0 || cp->num_steps < 1 || cp->length < 1) return -1;
-    ChirpShape cs{};
-    cs.num_steps = cp->num_steps;
-    cs.length = cp->length;
-    cs.period = cp->num_steps * cp->length;
-    cs.chirpness = cp->chirpness;
-    cs.f0 = cp->f0;
-    hipError_t e = gsdr::launch_source_chirp(reinterpret_cast<float2 *>(out_dev), n,
-                                             last_index % cs.period, cs, scale,
-                                             (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_source_chirp: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-// ---- sc16 output of the TX generators (include/gsdr.h, "sc16 output") -----------------------------------------
-static bool sc16_gain_ok(float gain) { return std::isfinite(gain) && gain > 0.f; }
-
-int gsdr_txgen_set_sc16_gain(gsdr_txgen *g, float gain) {
-    const char *bad = nullptr;
-    if (!g) bad = "gsdr_txgen_set_sc16_gain: null handle";
-    else if (!sc16_gain_ok(gain)) bad = "gsdr_txgen_set_sc16_gain: the gain must be finite and > 0";
-    else if (g->h_period16) bad = "gsdr_txgen_set_sc16_gain: the sc16 period buffer exists already (it was made with the gain of that time)";
-    if (bad) {
-        g_create_error = bad;
-        return -1;
-    }
-    g->sc16_gain = gain;
-    return 0;
-}
-
-float gsdr_txgen_sc16_gain(const gsdr_txgen *g) { return g ? g->sc16_gain : 0.f; }
-
-int gsdr_txgen_tones_fill_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, long long n, long long start, void *hip_stream) {
-    if (!g || n < 0 || (n > 0 && !out_dev)) {
-        g_create_error = "gsdr_txgen_tones_fill_sc16: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_tones_fill_sc16: hipSetDevice failed";
-        return -1;
-    }
-    long long sm = start % (long long)g->rate;
-    if (sm < 0) sm += g->rate;
-    const hipError_t e = gsdr::launch_tones_synth_sc16(out_dev, n, (unsigned long long)sm, g->rate, g->d_fmod, g->d_q0, g->d_btab,
-                                                       g->d_ctab, g->n_tones, g->sc16_gain, g->d_clipped, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_txgen_tones_fill_sc16: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-int gsdr_txgen_get_device_sc16(gsdr_txgen *g, gsdr_sc16 *out_dev, void *hip_stream) {
-    if (!g || !out_dev || g->mode < 0) {
-        g_create_error = "gsdr_txgen_get_sc16: bad arguments";
-        return -1;
-    }
-    int rc;
-    if (g->mode == GSDR_TONES) {
-        rc = gsdr_txgen_tones_fill_sc16(g, out_dev, g->buffer_len, (long long)(g->last % g->rate), hip_stream);
-    } else {
-        if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-            g_create_error = "gsdr_txgen_get_sc16: hipSetDevice failed";
-            return -1;
-        }
-        rc = gsdr_source_chirp_sc16(out_dev, g->buffer_len, g->last, &g->cp, g->scale, g->sc16_gain, g->d_clipped, hip_stream);
-    }
-    if (rc == 0) g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
-    return rc;
-}
-
-// the staging buffer of the sc16 host entries: at least `samples` of gsdr_sc16 in device memory
-static bool txgen_stage16(gsdr_txgen *g, size_t samples) {
-    if (g->d_stage16 && g->stage16_n < samples) {
-        (void)hipFree(g->d_stage16);
-        g->d_stage16 = nullptr;
-        g->stage16_n = 0;
-    }
-    if (!g->d_stage16) {
-        if (hipMalloc((void **)&g->d_stage16, (samples ? samples : 1) * sizeof(gsdr_sc16)) != hipSuccess) {
-            (void)hipGetLastError();
-            g->d_stage16 = nullptr;
-            return false;
-        }
-        g->stage16_n = samples;
-    }
-    return true;
-}
-
-int gsdr_txgen_get_sc16(gsdr_txgen *g, gsdr_sc16 *out_host) {
-    if (!g || !out_host || g->mode < 0) {
-        g_create_error = "gsdr_txgen_get_sc16: bad arguments";
-        return -1;
-    }
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_get_sc16: hipSetDevice failed";
-        return -1;
-    }
-    if (!txgen_stage16(g, (size_t)g->buffer_len)) {
-        g_create_error = "gsdr_txgen_get_sc16: device allocation failed";
-        return -1;
-    }
-    if (gsdr_txgen_get_device_sc16(g, g->d_stage16, nullptr) != 0) return -1;
-    const hipError_t e = hipMemcpy(out_host, g->d_stage16, (size_t)g->buffer_len * sizeof(gsdr_sc16), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_txgen_get_sc16: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-// The sc16 twin of gsdr_txgen_prepare_host: one period plus one buffer, 4 bytes per sample, made once in pieces through
-// the sc16 staging buffer.  The complex64 period buffer is neither needed nor made.
-int gsdr_txgen_prepare_host_sc16(gsdr_txgen *g) {
-    if (!g || g->mode != GSDR_TONES) {
-        g_create_error = "gsdr_txgen_prepare_host_sc16: a TONES generator is needed";
-        return -1;
-    }
-    if (g->h_period16) return 0;
-    if (g->device >= 0 && hipSetDevice(g->device) != hipSuccess) {
-        g_create_error = "gsdr_txgen_prepare_host_sc16: hipSetDevice failed";
-        return -1;
-    }
-    const unsigned long long total = g->period + (unsigned long long)g->buffer_len;
-    gsdr_sc16 *hp = nullptr;
-    bool pinned = hipHostMalloc((void **)&hp, (size_t)total * sizeof(gsdr_sc16)) == hipSuccess;
-    if (!pinned) {
-        (void)hipGetLastError();
-        hp = (gsdr_sc16 *)std::malloc((size_t)total * sizeof(gsdr_sc16));
-    }
-    if (!hp) {
-        g_create_error = "gsdr_txgen_prepare_host_sc16: cannot allocate the period buffer in host memory";
-        return -1;
-    }
-    const size_t piece = (size_t)(total < (8u << 20) ? total : (8u << 20));
-    bool ok = txgen_stage16(g, piece);
-    for (unsigned long long off = 0; ok && off < total; off += piece) {
-        const long long n = (long long)(total - off < piece ? total - off : piece);
-        ok = gsdr_txgen_tones_fill_sc16(g, g->d_stage16, n, (long long)(off % g->rate), nullptr) == 0 &&
-             hipMemcpy(hp + off, g->d_stage16, (size_t)n * sizeof(gsdr_sc16), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (!ok) {
-        if (pinned) (void)hipHostFree(hp);
-        else std::free(hp);
-        if (g_create_error.empty()) g_create_error = "gsdr_txgen_prepare_host_sc16: generating the period failed";
-        return -1;
-    }
-    g->h_period16 = hp;
-    g->h_period16_pinned = pinned;
-    return 0;
-}
-
-const gsdr_sc16 *gsdr_txgen_get_ptr_sc16(gsdr_txgen *g) {
-    if (!g || g->mode != GSDR_TONES) {
-        g_create_error = "gsdr_txgen_get_ptr_sc16: a TONES generator is needed";
-        return nullptr;
-    }
-    if (!g->h_period16 && gsdr_txgen_prepare_host_sc16(g) != 0) return nullptr;
-    const gsdr_sc16 *p = g->h_period16 + g->last;
-    g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
-    return p;
-}
-
-// a diagnostic: waits for everything the device has been given
-long long gsdr_txgen_sc16_clipped(gsdr_txgen *g) {
-    if (!g || !g->d_clipped) {
-        g_create_error = "gsdr_txgen_sc16_clipped: null handle";
-        return -1;
-    }
-    unsigned long long c = 0;
-    hipError_t e = g->device >= 0 ? hipSetDevice(g->device) : hipSuccess;
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(&c, g->d_clipped, sizeof(c), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_txgen_sc16_clipped: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return (long long)c;
-}
-
-int gsdr_source_chirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index, const gsdr_chirp_param *cp,
-                           float scale, float gain, unsigned long long *clipped_dev, void *hip_stream) {
-    if (n == 0) return 0;
-    const char *bad = nullptr;
-    if (!out_dev || !cp || n < 0 || cp->num_steps < 1 || cp->length < 1) bad = "bad arguments";
-    else if (!sc16_gain_ok(gain)) bad = "the gain must be finite and > 0";
-    else if (((uintptr_t)out_dev & 3) || ((uintptr_t)clipped_dev & 7)) bad = "out_dev must be 4-byte, clipped_dev 8-byte aligned";
-    if (bad) {
-        g_create_error = std::string("gsdr_source_chirp_sc16: ") + bad;
-        return -1;
-    }
-    ChirpShape cs{};
-    cs.num_steps = cp->num_steps;
-    cs.length = cp->length;
-    cs.period = cp->num_steps * cp->length;
-    cs.chirpness = cp->chirpness;
-    cs.f0 = cp->f0;
-    const hipError_t e = gsdr::launch_source_chirp_sc16(out_dev, n, last_index % cs.period, cs, scale, gain, clipped_dev,
-                                                        (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_source_chirp_sc16: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-int gsdr_narrow_sc16_device(const gsdr_c64 *in_dev, gsdr_sc16 *out_dev, long long n, float gain,
-                            unsigned long long *clipped_dev, void *hip_stream) {
-    if (n == 0) return 0;
-    const char *bad = nullptr;
-    if (n < 0 || !in_dev || !out_dev) bad = "null buffer";
-    else if (!sc16_gain_ok(gain)) bad = "the gain must be finite and > 0";
-    else if (((uintptr_t)in_dev & 7) || ((uintptr_t)out_dev & 3) || ((uintptr_t)clipped_dev & 7))
-        bad = "in_dev and clipped_dev must be 8-byte, out_dev 4-byte aligned";
-    if (bad) {
-        g_create_error = std::string("gsdr_narrow_sc16_device: ") + bad;
-        return -1;
-    }
-    const hipError_t e = gsdr::launch_narrow_sc16(reinterpret_cast<const float2 *>(in_dev), out_dev, n, gain, clipped_dev,
-                                                  device_cus(), (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        g_create_error = std::string("gsdr_narrow_sc16_device: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
 }
 
 }  // extern "C"

@@ -1,0 +1,233 @@
+"""Every refusal of the TX generator, the synthetic sources and the RX entries that returns before the first HIP
+call, for both wire formats (complex64 and sc16): the return value and the exact bytes gsdr_last_error(NULL) gives
+afterwards.  The two formats differ in a few of these on purpose (include/gsdr.h); this file pins each difference.
+No GPU call is made: no pointer below passes every check of its entry, so no launcher is reached."""
+import ctypes as C
+
+import pytest
+
+from gpu_sdr_amd._lib import ChirpParamC, ParamC
+
+TONES, CHIRP, NOISE, RAMP, NODSP, SWONLY, DIRECT = range(7)
+PLANTED = b"null parameters"
+# never dereferenced: each is used only where an earlier check refuses the call
+ALIGNED, OFF2, OFF4 = 0x1000, 0x1002, 0x1004
+
+
+def last_error(lib):
+    return lib.gsdr_last_error(None)
+
+
+def plant(lib):
+    """Leaves a known message behind: the next refusal must replace it (or, where it is silent, keep it)."""
+    assert lib.gsdr_txgen_create(None, None, 0) is None
+    assert last_error(lib) == PLANTED
+
+
+def chirp_param(num_steps=10, length=35):
+    return ChirpParamC(num_steps, length, 1000, 0)
+
+
+def make_param(wave_type, rate=1000, buffer_len=300, freq=(), chirp_t=(), chirp_f=(), swipe_s=()):
+    """A gsdr_param_c and the arrays it points to (returned so that they outlive the call)."""
+    keep = [(C.c_int * max(len(wave_type), 1))(*wave_type), (C.c_int * max(len(freq), 1))(*freq),
+            (C.c_float * max(len(chirp_t), 1))(*chirp_t), (C.c_int * max(len(chirp_f), 1))(*chirp_f),
+            (C.c_int * max(len(swipe_s), 1))(*swipe_s)]
+    p = ParamC()
+    p.rate, p.decim, p.fft_tones, p.pf_average, p.buffer_len, p.device_index = rate, 0, 0, 1, buffer_len, 0
+    p.wave_type, p.n_wave_type = C.cast(keep[0], C.POINTER(C.c_int)), len(wave_type)
+    p.freq, p.n_freq = C.cast(keep[1], C.POINTER(C.c_int)), len(freq)
+    p.chirp_t, p.n_chirp_t = C.cast(keep[2], C.POINTER(C.c_float)), len(chirp_t)
+    p.chirp_f, p.n_chirp_f = C.cast(keep[3], C.POINTER(C.c_int)), len(chirp_f)
+    p.swipe_s, p.n_swipe_s = C.cast(keep[4], C.POINTER(C.c_int)), len(swipe_s)
+    return p, keep
+
+
+# ---- NULL generator ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("sfx", ["", "_sc16"])
+def test_null_generator_tones_fill(gsdr_lib, sfx):
+    # Without a generator both formats refuse alike.  Where they differ -- out_dev == NULL at n == 0: sc16 returns 0,
+    # complex64 refuses -- takes a real generator, that is a GPU: the sc16 half is pinned by
+    # test_gpu_sc16_tx.py::test_tones_fill_sc16_small_gain_no_tones_and_refusals ("n == 0 touches nothing"), the complex64
+    # half by no test so far.
+    fill = getattr(gsdr_lib, "gsdr_txgen_tones_fill" + sfx)
+    for out, n in ((ALIGNED, 4), (None, 4), (None, 0), (ALIGNED, 0), (ALIGNED, -1)):
+        plant(gsdr_lib)
+        assert fill(None, out, n, 0, None) == -1
+        assert last_error(gsdr_lib) == b"gsdr_txgen_tones_fill%s: bad arguments" % sfx.encode()
+
+
+@pytest.mark.parametrize("sfx", ["", "_sc16"])
+def test_null_generator_get(gsdr_lib, sfx):
+    """get_device and get share one prefix per format: gsdr_txgen_get / gsdr_txgen_get_sc16."""
+    msg = b"gsdr_txgen_get%s: bad arguments" % sfx.encode()
+    plant(gsdr_lib)
+    assert getattr(gsdr_lib, "gsdr_txgen_get_device" + sfx)(None, ALIGNED, None) == -1
+    assert last_error(gsdr_lib) == msg
+    plant(gsdr_lib)
+    assert getattr(gsdr_lib, "gsdr_txgen_get" + sfx)(None, ALIGNED) == -1
+    assert last_error(gsdr_lib) == msg
+
+
+@pytest.mark.parametrize("sfx", ["", "_sc16"])
+def test_null_generator_period_buffer(gsdr_lib, sfx):
+    plant(gsdr_lib)
+    assert getattr(gsdr_lib, "gsdr_txgen_prepare_host" + sfx)(None) == -1
+    assert last_error(gsdr_lib) == b"gsdr_txgen_prepare_host%s: a TONES generator is needed" % sfx.encode()
+    plant(gsdr_lib)
+    assert getattr(gsdr_lib, "gsdr_txgen_get_ptr" + sfx)(None) is None
+    assert last_error(gsdr_lib) == b"gsdr_txgen_get_ptr%s: a TONES generator is needed" % sfx.encode()
+
+
+def test_null_generator_sc16_gain_and_counter(gsdr_lib):
+    plant(gsdr_lib)
+    assert gsdr_lib.gsdr_txgen_set_sc16_gain(None, 1000.0) == -1
+    assert last_error(gsdr_lib) == b"gsdr_txgen_set_sc16_gain: null handle"
+    plant(gsdr_lib)
+    assert gsdr_lib.gsdr_txgen_sc16_clipped(None) == -1
+    assert last_error(gsdr_lib) == b"gsdr_txgen_sc16_clipped: null handle"
+
+
+def test_null_generator_getters_and_close(gsdr_lib):
+    plant(gsdr_lib)
+    assert gsdr_lib.gsdr_txgen_buffer_len(None) == 0
+    assert gsdr_lib.gsdr_txgen_mode(None) == -1
+    assert gsdr_lib.gsdr_txgen_sc16_gain(None) == 0.0
+    gsdr_lib.gsdr_txgen_close(None)
+    assert last_error(gsdr_lib) == PLANTED
+
+
+# ---- gsdr_source_chirp: refuses without a message ------------------------------------------------------------------
+
+def test_source_chirp_refuses_silently(gsdr_lib):
+    cp, cp0 = chirp_param(), chirp_param(num_steps=0)
+    plant(gsdr_lib)
+    for out, n, c in ((None, 1, cp), (ALIGNED, 1, None), (ALIGNED, -1, cp), (ALIGNED, 1, cp0),
+                      (None, 0, cp), (ALIGNED, 0, None)):     # n == 0 is no excuse here (it is for the sc16 entry)
+        assert gsdr_lib.gsdr_source_chirp(out, n, 0, C.byref(c) if c else None, 1.0, None) == -1
+        assert last_error(gsdr_lib) == PLANTED
+
+
+# ---- gsdr_source_chirp_sc16, gsdr_narrow_sc16_device ---------------------------------------------------------------
+
+BAD_GAINS = [0.0, -1.0, float("nan"), float("inf")]
+
+
+def test_source_chirp_sc16_empty_is_no_error(gsdr_lib):
+    plant(gsdr_lib)
+    assert gsdr_lib.gsdr_source_chirp_sc16(None, 0, 0, None, 1.0, 0.0, None, None) == 0
+    assert last_error(gsdr_lib) == PLANTED
+
+
+def test_source_chirp_sc16_refusals_in_order(gsdr_lib):
+    lib = gsdr_lib
+    cp, cp0, cp_len0 = chirp_param(), chirp_param(num_steps=0), chirp_param(length=0)
+
+    def call(out, n, c, gain, clipped):
+        plant(lib)
+        rc = lib.gsdr_source_chirp_sc16(out, n, 0, C.byref(c) if c else None, 1.0, gain, clipped, None)
+        return rc, last_error(lib)
+
+    # bad arguments come first: a bad gain and a misaligned pointer behind them do not change the message
+    for out, n, c in ((None, 1, cp), (OFF2, 1, None), (OFF2, -1, cp), (OFF2, 1, cp0), (OFF2, 1, cp_len0)):
+        assert call(out, n, c, 0.0, OFF4) == (-1, b"gsdr_source_chirp_sc16: bad arguments")
+    # then the gain, whatever the alignment
+    for gain in BAD_GAINS:
+        assert call(OFF2, 1, cp, gain, OFF4) == (-1, b"gsdr_source_chirp_sc16: the gain must be finite and > 0")
+    # then the alignment: out_dev 4 bytes, clipped_dev 8 bytes (NULL counts as aligned)
+    msg = b"gsdr_source_chirp_sc16: out_dev must be 4-byte, clipped_dev 8-byte aligned"
+    assert call(OFF2, 1, cp, 32767.0, None) == (-1, msg)
+    assert call(OFF2, 1, cp, 32767.0, ALIGNED) == (-1, msg)
+    assert call(ALIGNED, 1, cp, 32767.0, OFF4) == (-1, msg)
+
+
+def test_narrow_sc16_device_refusals_in_order(gsdr_lib):
+    lib = gsdr_lib
+
+    def call(src, out, n, gain, clipped):
+        plant(lib)
+        return lib.gsdr_narrow_sc16_device(src, out, n, gain, clipped, None), last_error(lib)
+
+    plant(lib)
+    assert lib.gsdr_narrow_sc16_device(None, None, 0, 0.0, None, None) == 0
+    assert last_error(lib) == PLANTED
+    for src, out, n in ((None, OFF2, 1), (OFF4, None, 1), (OFF4, OFF2, -1)):
+        assert call(src, out, n, 0.0, OFF4) == (-1, b"gsdr_narrow_sc16_device: null buffer")
+    for gain in BAD_GAINS:
+        assert call(OFF4, OFF2, 1, gain, OFF4) == (-1, b"gsdr_narrow_sc16_device: the gain must be finite and > 0")
+    msg = b"gsdr_narrow_sc16_device: in_dev and clipped_dev must be 8-byte, out_dev 4-byte aligned"
+    assert call(OFF4, ALIGNED, 1, 32767.0, None) == (-1, msg)
+    assert call(ALIGNED, OFF2, 1, 32767.0, None) == (-1, msg)
+    assert call(ALIGNED, ALIGNED, 1, 32767.0, OFF4) == (-1, msg)
+
+
+def test_widen_sc16_device_null_buffer(gsdr_lib):
+    for src, out, n in ((None, ALIGNED, 1), (ALIGNED, None, 1), (ALIGNED, ALIGNED, -1)):
+        plant(gsdr_lib)
+        assert gsdr_lib.gsdr_widen_sc16_device(src, out, n, 1.0, None) == -1
+        assert last_error(gsdr_lib) == b"gsdr_widen_sc16_device: null buffer"
+
+
+# ---- gsdr_txgen_create / gsdr_txgen_tones_create: what is refused before the device is chosen ---------------------
+
+CHIRP_ARRAYS = dict(freq=(10,), chirp_t=(0.01,), chirp_f=(100,), swipe_s=(10,))
+CREATE_REFUSALS = [
+    ("buffer_len", dict(wave_type=[TONES], buffer_len=0), b"buffer_len must be positive"),
+    ("rate", dict(wave_type=[TONES], rate=0), b"rate must be positive"),
+    ("no_wave_type", dict(wave_type=[]), b"TX buffer generation needs at least one wave_type"),
+    ("two_chirps", dict(wave_type=[CHIRP, CHIRP], **CHIRP_ARRAYS),
+     b"Multiple chirp TX buffer generation has been requested. This feature is not implemented yet."),
+    ("mixed", dict(wave_type=[TONES, CHIRP], **CHIRP_ARRAYS),
+     b"Mixed TX buffer generation has been requested. This feature is not implemented yet."),
+    ("nodsp", dict(wave_type=[NODSP]), b"NODSP CASE NOT IMPLEMENTED."),
+    ("swonly", dict(wave_type=[SWONLY]), b"NODSP CASE NOT IMPLEMENTED."),
+    ("ramp", dict(wave_type=[RAMP]), b"RAMP CASE NOT IMPLEMENTED."),
+    ("direct", dict(wave_type=[DIRECT]), b"RAMP CASE NOT IMPLEMENTED."),
+    ("tones_without_ampl", dict(wave_type=[TONES, TONES], freq=(10, 20)),
+     b"TONES needs freq[] and ampl[] for every wave_type entry"),
+    ("noise_without_freq", dict(wave_type=[NOISE]), b"TONES needs freq[] and ampl[] for every wave_type entry"),
+    ("chirp_without_chirp_t", dict(wave_type=[CHIRP], freq=(10,), chirp_f=(100,), swipe_s=(10,)),
+     b"CHIRP needs freq[0], chirp_f[0], swipe_s[0] and chirp_t[0]"),
+    ("unknown_type", dict(wave_type=[7]), b"Void TX generation operation has not been implemented yet!"),
+]
+
+
+def test_txgen_create_null_parameters(gsdr_lib):
+    assert gsdr_lib.gsdr_txgen_tones_create(0, None, None, None, 0, 0) is None      # leaves another message
+    assert gsdr_lib.gsdr_txgen_create(None, None, 0) is None
+    assert last_error(gsdr_lib) == b"null parameters"
+
+
+@pytest.mark.parametrize("kwargs,msg", [c[1:] for c in CREATE_REFUSALS], ids=[c[0] for c in CREATE_REFUSALS])
+def test_txgen_create_refusals(gsdr_lib, kwargs, msg):
+    p, keep = make_param(**kwargs)
+    plant(gsdr_lib)
+    # "tones_without_ampl" hands in freq[] but no ampl[]; the other cases are refused before ampl is looked at
+    assert gsdr_lib.gsdr_txgen_create(C.byref(p), None, 0) is None
+    assert last_error(gsdr_lib) == msg
+    del keep
+
+
+def test_txgen_tones_create_bad_arguments(gsdr_lib):
+    one_f, one_a = (C.c_int * 1)(10), (C.c_float * 1)(0.5)
+    for rate, freq, ampl, n in ((0, one_f, one_a, 1), (1000, one_f, one_a, -1), (1000, None, one_a, 1), (1000, one_f, None, 1)):
+        plant(gsdr_lib)
+        assert gsdr_lib.gsdr_txgen_tones_create(rate, freq, ampl, None, n, 0) is None
+        assert last_error(gsdr_lib) == b"gsdr_txgen_tones_create: bad arguments"
+
+
+# ---- RX: a NULL handle ---------------------------------------------------------------------------------------------
+
+def test_rx_entries_refuse_a_null_handle(gsdr_lib):
+    lib = gsdr_lib
+    plant(lib)
+    for sfx in ("", "_sc16"):
+        assert getattr(lib, "gsdr_demod_process" + sfx)(None, ALIGNED, ALIGNED) == -1
+        assert getattr(lib, "gsdr_demod_process_device" + sfx)(None, ALIGNED, ALIGNED, None) == -1
+        assert getattr(lib, "gsdr_demod_submit" + sfx)(None, ALIGNED, ALIGNED) == -1
+        assert getattr(lib, "gsdr_demod_submit_device" + sfx)(None, ALIGNED, ALIGNED) == -1
+    assert lib.gsdr_demod_wait(None) == -1
+    assert lib.gsdr_demod_prepare(None, 0) == -1
+    # a call without a handle has nowhere to leave a message, and leaves the creation message alone
+    assert last_error(lib) == PLANTED
