@@ -4,6 +4,8 @@
 
 #include <vector>
 
+#include "dev_owner.h"
+
 // No packed FP32 (v_pk_*_f32) in a kernel that may share a SIMD with the matrix-core DDC loop of another
 // launch -- another handle on the same GPU, or the neighbouring buffer of this one: a v_pk_*_f32 with a
 // high-half broadcast returned stale values in some lanes while another wave of the SIMD ran an MFMA loop
@@ -221,12 +223,11 @@ struct FftPlan {
     int m = 0;                 // 0: mixed-radix Stockham stages over n; else Bluestein through length m = 2^k
     int n_radices = 0;
     int radices[32] = {};      // stages of n (m == 0) or of m
-    float2 *d_tw = nullptr;    // w_len^k, len = n or m
-    float2 *d_chirp = nullptr; // Bluestein: exp(+i pi k^2 / n), k < n
-    float2 *d_bhat = nullptr;  // Bluestein: transform of the wrapped chirp, length m
+    DevBuf<float2> d_tw;       // w_len^k, len = n or m
+    DevBuf<float2> d_chirp;    // Bluestein: exp(+i pi k^2 / n), k < n
+    DevBuf<float2> d_bhat;     // Bluestein: transform of the wrapped chirp, length m
 };
-int fft_plan_build(FftPlan &pl, int n);
-void fft_plan_free(FftPlan &pl);
+int fft_plan_build(FftPlan &pl, int n);   // (a plan releases its tables when it is destroyed or built anew)
 // [batch][n] in src -> [batch][n] in dst; src and tmp are scratch of batch * max(n, m) each (src is destroyed)
 hipError_t fft_forward(const FftPlan &pl, float2 *src, float2 *dst, float2 *tmp, int batch, hipStream_t st);
 // frames[r][k] = sum_{i<avg} raw[(r+i)*nfft + k] * window[i*nfft + k], r < frames_n (ref: cpp/kernels.cu:474-516)

@@ -29,11 +29,9 @@ using gsdr::chirp_shape;
 using gsdr::create_error;
 using gsdr::DdcLaunch;
 using gsdr::DdcShape;
-using gsdr::dev_alloc;
 using gsdr::device_cus;
 using gsdr::mod_rate;
 using gsdr::phasor;
-using gsdr::upload;
 
 std::string &gsdr::create_error() {
     thread_local std::string msg;
@@ -112,8 +110,16 @@ struct gsdr_demod {
     gsdr::Switches sw;      // the GSDR_* switches, read when the handle was created
     int mode = GSDR_NODSP;
     int device = -1;
-    hipStream_t stream = nullptr;
     std::string err;
+    // Every d_* buffer, stream and event below is an owner (dev_owner.h) and is released by `delete`.  gsdr_demod_close
+    // synchronises the streams first -- the one ordering that matters -- so the order among the releases is not
+    // observable; the streams are declared in front of everything else all the same, so that the buffers and events go
+    // before them and `stream` goes last.  (The caller's streams in `dirty` are not the handle's and stay raw.)
+    gsdr::Stream stream;
+    gsdr::Stream s_up, s_down;                  // pipelined host-pointer entry: upload and download
+    // pipelined entries (gsdr_demod_submit*): consecutive DIRECT calls go to these compute streams in turn, so that
+    // their kernels overlap (see pipeline_compute)
+    gsdr::Stream s_main[kPipeStreams];
 
     int N = 0;              // channels = wave_type.size()
     int ddc_channels = 0;   // tones the DDC kernels run (== N except NOISE: fft_tones)
@@ -123,22 +129,21 @@ struct gsdr_demod {
     float fcut = 0.f;
 
     // host-pointer entry staging
-    float2 *d_in = nullptr, *d_out = nullptr;
+    gsdr::DevBuf<float2> d_in, d_out;           // allocated together: both set or both empty (staging_pair)
     // sc16 input (gsdr_demod_*_sc16): the scale of the widening; the half-size upload buffer of the host-pointer
     // entry (widened into d_in); the buffer gsdr_demod_process_device_sc16 widens the caller's samples into
     float sc16_scale = 1.0f / 32768.0f;
-    gsdr_sc16 *d_in16 = nullptr;
-    float2 *d_wide = nullptr;
+    gsdr::DevBuf<gsdr_sc16> d_in16;
+    gsdr::DevBuf<float2> d_wide;
     int cus = 256;                     // compute units of the device (grid of the widening kernel)
     // pipelined host-pointer entry (gsdr_demod_submit / _wait)
     struct Slot {
-        float2 *d_in = nullptr, *d_out = nullptr;
-        gsdr_sc16 *d_in16 = nullptr;       // gsdr_demod_submit_sc16: upload target, widened into d_in
-        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-        hipEvent_t wait_ev = nullptr;      // what gsdr_demod_wait() waits for: down (host) / done (device)
+        gsdr::DevBuf<float2> d_in, d_out;
+        gsdr::DevBuf<gsdr_sc16> d_in16;    // gsdr_demod_submit_sc16: upload target, widened into d_in
+        gsdr::Event up, done, down;
+        hipEvent_t wait_ev = nullptr;      // what gsdr_demod_wait() waits for: down (host) / done (device); not owned
         int n = 0;
     } slot[GSDR_PIPELINE_DEPTH];
-    hipStream_t s_up = nullptr, s_down = nullptr;
     bool pipe_ready = false;             // pipeline_init() succeeded
     int pipe_head = 0, pipe_count = 0;   // oldest outstanding slot, number outstanding
 
@@ -152,16 +157,16 @@ struct gsdr_demod {
     int tails_nch = 0;                 // chunk count the tails buffer was sized for (0: not yet)
     double waves_ratio = 1.3;          // grid waves / resident waves (autotuned in create)
     std::vector<float> window;         // taps (DIRECT) / PFB window / VNA profile, real part
-    float *d_taps_t = nullptr;
-    float *d_taps_p = nullptr;         // zero-padded [nsub*K+2][FP] copy for ddc_flat_kernel
+    gsdr::DevBuf<float> d_taps_t;
+    gsdr::DevBuf<float> d_taps_p;      // zero-padded [nsub*K+2][FP] copy for ddc_flat_kernel
     bool pipe = false;                 // ddc_flat_kernel (F <= 4) instead of ddc_kernel
     int pad = 0;                       // samples the flat kernel reads past a block (nsub*K - M)
-    float2 *d_stage = nullptr;         // padded copy of the input when pad > 0 (DIRECT only)
-    float2 *d_btab = nullptr;
-    double2 *d_wk = nullptr, *d_wrem = nullptr;
-    unsigned *d_fmod = nullptr;
-    float2 *d_tails = nullptr;
-    float2 *d_carry[2] = {nullptr, nullptr};
+    gsdr::DevBuf<float2> d_stage;      // padded copy of the input when pad > 0 (DIRECT only)
+    gsdr::DevBuf<float2> d_btab;
+    gsdr::DevBuf<double2> d_wk, d_wrem;
+    gsdr::DevBuf<unsigned> d_fmod;
+    gsdr::DevBuf<float2> d_tails;
+    gsdr::DevBuf<float2> d_carry[2];
     int parity = 0;
     // ---- DDC on the matrix cores (ddc_mfma.hip) ----
     bool mfma = false;
@@ -173,29 +178,26 @@ struct gsdr_demod {
     // pre-converted operands (ddc_convert_kernel + ddc_mfma_ring16p_kernel) for launches of many
     // rounds: one image set per staging set (the main kernels of the calls in flight read theirs)
     bool prec = false;                 // image sets allocated: the path may be chosen
-    uint4 *d_img[kStageSets] = {};
+    gsdr::DevBuf<uint4> d_img[kStageSets];
     // three real products per complex multiply (ddc_convert3_kernel + ddc_mfma_ring16p3_kernel, DESIGN.md section
     // 4.1d): decided once, in setup_mfma; such a handle sends EVERY matrix-core launch through that pair
     bool mac3 = false;
     bool rot2 = false;                 // ... through ddc_mfma_ring16p3r2_kernel: one rotation per pair of blocks (section 4.1e)
-    uint4 *d_bfrag3 = nullptr;
-    float4 *d_ptab3 = nullptr;
-    uint4 *d_bfrag = nullptr;
-    float2 *d_ptab = nullptr, *d_dtab = nullptr;
-    float *d_mtaps = nullptr;
-    unsigned *d_mfmod = nullptr;
+    gsdr::DevBuf<uint4> d_bfrag3;
+    gsdr::DevBuf<float4> d_ptab3;
+    gsdr::DevBuf<uint4> d_bfrag;
+    gsdr::DevBuf<float2> d_ptab, d_dtab;
+    gsdr::DevBuf<float> d_mtaps;
+    gsdr::DevBuf<unsigned> d_mfmod;
     // kScaleSlots tables of segment maxima (absmax_kernel), one per call in turn; seg_k blocks of M samples per segment
-    unsigned *d_segmax = nullptr;
+    gsdr::DevBuf<unsigned> d_segmax;
     int seg_k = 1, nseg_alloc = 0;
     // [carry | first rows' samples | zeros] and [last rows' samples | zeros], see absmax_kernel.
     // kStageSets of each, used in turn: the staging pass of call j writes set j (and the carry
     // part of head j+1) while the main kernels of calls j-1 .. j-kPipeStreams+1 may still read theirs.
-    float2 *d_head[kStageSets] = {};
-    float2 *d_tail[kStageSets] = {};
-    // pipelined entries (gsdr_demod_submit*): consecutive DIRECT calls go to two compute
-    // streams in turn, so that their kernels overlap (see pipeline_compute)
-    hipStream_t s_main[kPipeStreams] = {};
-    hipEvent_t ev_abs[4] = {nullptr, nullptr, nullptr, nullptr};    // staging pass of call j done
+    gsdr::DevBuf<float2> d_head[kStageSets];
+    gsdr::DevBuf<float2> d_tail[kStageSets];
+    gsdr::Event ev_abs[4];             // pipelined entries: staging pass of call j done
     // Streams that carry work of this handle nobody has been ordered behind yet.  The carry, the
     // scale slots, the raw windows and the head/tail copies pass from one call to the next ON THE
     // DEVICE: a call that runs on another stream than its predecessors first joins them (an event
@@ -207,7 +209,7 @@ struct gsdr_demod {
     // If recording on a remembered stream returns an error, the entry is dropped and the call goes on.  (A stream
     // destroyed before that is beyond help: HIP faults inside hipEventRecord, tests/test_gpu_parity.py.)
     std::vector<hipStream_t> dirty;
-    hipEvent_t ev_join = nullptr;
+    gsdr::Event ev_join;
     bool pipe_overlap = false;         // set around the compute of an overlapped call
     unsigned long long pipe_seq = 0;   // overlapped calls so far
     unsigned long long call_no = 0;    // absmax slot rotation
@@ -218,15 +220,15 @@ struct gsdr_demod {
     // raw_input (ref :143): kStageSets windows used in turn.  The staging of call j copies the
     // unconsumed end of window j-1 to the front of window j and appends the new buffer, so the
     // kernels of call j-1 may still read their window (the reference moves it in place, :504-509).
-    float2 *d_win[kStageSets] = {};
+    gsdr::DevBuf<float2> d_win[kStageSets];
     unsigned long long win_seq = 0;    // TONES/NOISE calls so far
     long long prev_spare_begin = 0, prev_spare_samples = 0;
     // ---- NOISE through the FFT stage (fft_kernels.hip) ----
     bool noise_fft = false;
     gsdr::FftPlan fft{};
-    float2 *d_fft_a = nullptr, *d_fft_b = nullptr;   // frames / scratch, batching * max(nfft, m) each
-    float2 *d_fft_c = nullptr;                       // TONES through these stages: the spectra the bins are picked from
-    float *d_fft_win = nullptr;                      // the PFB window on the device
+    gsdr::DevBuf<float2> d_fft_a, d_fft_b;           // frames / scratch, batching * max(nfft, m) each
+    gsdr::DevBuf<float2> d_fft_c;                    // TONES through these stages: the spectra the bins are picked from
+    gsdr::DevBuf<float> d_fft_win;                   // the PFB window on the device
     // ---- the parameters this handle was created with (gsdr_demod_prepare's rehearsal builds a twin) ----
     gsdr_param_c pc{};
     std::vector<int> pc_wave_type, pc_freq, pc_chirp_f, pc_swipe_s;
@@ -234,22 +236,22 @@ struct gsdr_demod {
     // ---- TONES / NOISE, a frame per workgroup: filter + in-LDS transform + bin selection (fft_kernels.hip) ----
     bool pfb_lds = false;
     bool pfb_blue = false;                           // ... through Bluestein's identity (h->fft holds chirp, transform, twiddles)
-    float2 *d_pfb_tw = nullptr;                      // w_nfft^k
-    int *d_pfb_sel = nullptr;                        // TONES: bin of every output column
-    float2 *d_pfb_carry[kStageSets] = {};            // the samples a call leaves over (at most F*nfft)
+    gsdr::DevBuf<float2> d_pfb_tw;                   // w_nfft^k
+    gsdr::DevBuf<int> d_pfb_sel;                     // TONES: bin of every output column
+    gsdr::DevBuf<float2> d_pfb_carry[kStageSets];    // the samples a call leaves over (at most F*nfft)
     // ---- TONES / NOISE, mean of avg_k consecutive frames (gsdr_demod_set_frame_average; 1: off, nothing below is used) ----
     int avg_k = 1, avg_kind = GSDR_AVERAGE_COMPLEX;
     int avg_count = 0;                               // frames of the open group, summed in d_avg_acc[avg_seq % 2]
     unsigned long long avg_seq = 0;                  // launches of pfb_average_kernel so far: they read one accumulator, write the other
-    float2 *d_avg_frames = nullptr;                  // [batching][ddc_channels]: where the PFB writes its frames instead of `out`
-    float2 *d_avg_acc[2] = {nullptr, nullptr};       // [ddc_channels] each
+    gsdr::DevBuf<float2> d_avg_frames;               // [batching][ddc_channels]: where the PFB writes its frames instead of `out`
+    gsdr::DevBuf<float2> d_avg_acc[2];               // [ddc_channels] each
     // ---- CHIRP ----
     ChirpShape cs{};
     int ppt = 0;
     gsdr_vna_helper vh{};
-    float *d_profile = nullptr;
-    float2 *d_chirp_part = nullptr;    // partial sums of chirp_lockin_split_kernel (kChirpPartials float2)
-    float2 *d_ccarry[2] = {nullptr, nullptr};
+    gsdr::DevBuf<float> d_profile;
+    gsdr::DevBuf<float2> d_chirp_part; // partial sums of chirp_lockin_split_kernel (kChirpPartials float2)
+    gsdr::DevBuf<float2> d_ccarry[2];
     int cparity = 0;
     int carry_len = 0;                 // spare_size (ref :54,:369)
     unsigned long long last_index = 0; // ref :217,:355
@@ -258,7 +260,7 @@ struct gsdr_demod {
     bool prof = false;
     int prof_every = 1;                // time every n-th launch (an event pair costs ~3 us of stream time)
     unsigned long long prof_seen = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<gsdr::Event, gsdr::Event>> ev_pool;
     size_t ev_used = 0;
     const char *kernel_name = "none";
 };
@@ -301,10 +303,10 @@ int build_nco_tables(gsdr_demod *h, const std::vector<long long> &tone, unsigned
         phasor((fm * (unsigned long long)h->R) % rate, rate, re, im);
         wrem[n] = make_double2(re, im);
     }
-    HIPCHK(h, upload(&h->d_fmod, fmod));
-    HIPCHK(h, upload(&h->d_btab, btab));
-    HIPCHK(h, upload(&h->d_wk, wk));
-    HIPCHK(h, upload(&h->d_wrem, wrem));
+    HIPCHK(h, h->d_fmod.upload(fmod));
+    HIPCHK(h, h->d_btab.upload(btab));
+    HIPCHK(h, h->d_wk.upload(wk));
+    HIPCHK(h, h->d_wrem.upload(wrem));
     return 0;
 }
 
@@ -313,13 +315,13 @@ int upload_taps_transposed(gsdr_demod *h) {
     std::vector<float> t((size_t)h->M * h->F);
     for (int j = 0; j < h->F; ++j)
         for (int m = 0; m < h->M; ++m) t[(size_t)m * h->F + j] = h->window[(size_t)j * h->M + m];
-    HIPCHK(h, upload(&h->d_taps_t, t));
+    HIPCHK(h, h->d_taps_t.upload(t));
     if (h->pipe) {
         const int FP = h->F == 3 ? 4 : h->F;
         std::vector<float> p((size_t)(h->M + h->pad + 2) * FP, 0.f);
         for (int j = 0; j < h->F; ++j)
             for (int m = 0; m < h->M; ++m) p[(size_t)m * FP + j] = h->window[(size_t)j * h->M + m];
-        HIPCHK(h, upload(&h->d_taps_p, p));
+        HIPCHK(h, h->d_taps_p.upload(p));
     }
     return 0;
 }
@@ -422,8 +424,7 @@ int setup_ddc_common(gsdr_demod *h, int F, int M, unsigned rate,
     if (build_nco_tables(h, tone, rate)) return -1;
     if (upload_taps_transposed(h)) return -1;
     const size_t tail_elems = (size_t)(h->tails_nch + 1) * (size_t)(F > 1 ? F - 1 : 1) * h->Npad;
-    HIPCHK(h, dev_alloc(&h->d_tails, tail_elems));
-    HIPCHK(h, hipMemset(h->d_tails, 0, tail_elems * sizeof(float2)));
+    HIPCHK(h, h->d_tails.alloc_zeroed(tail_elems));
     return 0;
 }
 
@@ -523,11 +524,11 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
     std::vector<unsigned> fmod;
     float unscale = 1.f;
     gsdr::mfma_build_tables(pl, fmod_in, h->window.data(), bfrag, ptab, dtab, taps, fmod, unscale);
-    HIPCHK(h, upload(&h->d_bfrag, bfrag));
-    HIPCHK(h, upload(&h->d_ptab, ptab));
-    HIPCHK(h, upload(&h->d_dtab, dtab));
-    HIPCHK(h, upload(&h->d_mtaps, taps));
-    HIPCHK(h, upload(&h->d_mfmod, fmod));
+    HIPCHK(h, h->d_bfrag.upload(bfrag));
+    HIPCHK(h, h->d_ptab.upload(ptab));
+    HIPCHK(h, h->d_dtab.upload(dtab));
+    HIPCHK(h, h->d_mtaps.upload(taps));
+    HIPCHK(h, h->d_mfmod.upload(fmod));
     {
         // maxima per segment of the call's logical stream [carry | buffer] (TONES: the raw window, allocated
         // 2 * nfft * batching long): a segment is one block of M samples, several when blocks are short
@@ -535,8 +536,7 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const long long t_max = direct ? (long long)(F - 1) * M + h->L : 2LL * h->nfft * h->batching;
         const long long seg_len = (long long)h->seg_k * M;
         h->nseg_alloc = (int)((t_max + seg_len - 1) / seg_len) + 2;
-        HIPCHK(h, dev_alloc(&h->d_segmax, (size_t)kScaleSlots * h->nseg_alloc));
-        HIPCHK(h, hipMemset(h->d_segmax, 0, (size_t)kScaleSlots * h->nseg_alloc * sizeof(unsigned)));
+        HIPCHK(h, h->d_segmax.alloc_zeroed((size_t)kScaleSlots * h->nseg_alloc));
     }
     gsdr::MfmaShape &sh = h->mf;
     sh.N = h->ddc_channels;
@@ -567,10 +567,8 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const size_t head_n = (size_t)sh.carry_len + 32u * (size_t)M + reach + 8;
         const size_t tail_n = (size_t)(32 + F) * (size_t)M + reach + 8;
         for (int i = 0; i < kStageSets; ++i) {
-            HIPCHK(h, dev_alloc(&h->d_head[i], head_n));
-            HIPCHK(h, hipMemset(h->d_head[i], 0, head_n * sizeof(float2)));
-            HIPCHK(h, dev_alloc(&h->d_tail[i], tail_n));
-            HIPCHK(h, hipMemset(h->d_tail[i], 0, tail_n * sizeof(float2)));
+            HIPCHK(h, h->d_head[i].alloc_zeroed(head_n));
+            HIPCHK(h, h->d_tail[i].alloc_zeroed(tail_n));
         }
     }
     // pre-converted operands: allocated when a launch of this handle may use them (the largest row count, in an
@@ -583,7 +581,7 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const bool mac3 = mac3_chosen(h, want, nhi);
         const size_t img_n = (size_t)ngt_max * (size_t)nhi * (mac3 ? 768 : 512);   // uint4 per image set: 12 / 8 KiB per block
         if (want && img_n * sizeof(uint4) > (size_t)8 << 30) want = false;
-        for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, dev_alloc(&h->d_img[i], img_n));
+        for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, h->d_img[i].alloc(img_n));
         h->prec = want;
         h->mac3 = want && mac3;
         h->rot2 = rot2_chosen(h, h->mac3, nhi);
@@ -591,8 +589,8 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
             gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
-            HIPCHK(h, upload(&h->d_bfrag3, bfrag3));
-            HIPCHK(h, upload(&h->d_ptab3, ptab3));
+            HIPCHK(h, h->d_bfrag3.upload(bfrag3));
+            HIPCHK(h, h->d_ptab3.upload(ptab3));
         }
     }
     h->mfma = true;
@@ -617,7 +615,7 @@ int join_streams(gsdr_demod *h, hipStream_t st, Keep keep) {
             h->dirty[w++] = s;
             continue;
         }
-        if (!h->ev_join) HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        if (!h->ev_join) HIPCHK(h, hipEventCreateWithFlags(h->ev_join.out(), hipEventDisableTiming));
         if (hipEventRecord(h->ev_join, s) != hipSuccess) {
             // nothing that could still be waited for: forget the stream rather than fail every later call
             (void)hipGetLastError();
@@ -637,10 +635,10 @@ int record_begin(gsdr_demod *h, hipStream_t st, hipEvent_t *stop) {
     if (!h->prof || h->ev_used >= (size_t)kMaxEvents) return 0;
     if (h->prof_seen++ % (unsigned long long)h->prof_every != 0) return 0;
     if (h->ev_used == h->ev_pool.size()) {
-        hipEvent_t a, b;
-        HIPCHK(h, hipEventCreate(&a));
-        HIPCHK(h, hipEventCreate(&b));
-        h->ev_pool.emplace_back(a, b);
+        gsdr::Event a, b;
+        HIPCHK(h, hipEventCreate(a.out()));
+        HIPCHK(h, hipEventCreate(b.out()));
+        h->ev_pool.emplace_back(std::move(a), std::move(b));
     }
     HIPCHK(h, hipEventRecord(h->ev_pool[h->ev_used].first, st));
     *stop = h->ev_pool[h->ev_used].second;
@@ -663,17 +661,16 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
     }
     const size_t n_in = (size_t)nblk * h->M + h->pad + 8;
     const size_t n_out = (size_t)nblk * h->ddc_channels;
-    float2 *x = nullptr, *y = nullptr;
-    HIPCHK(h, dev_alloc(&x, n_in));
-    if (dev_alloc(&y, n_out) != hipSuccess) {
-        (void)hipFree(x);
+    gsdr::DevBuf<float2> x, y;
+    HIPCHK(h, x.alloc(n_in));
+    if (y.alloc(n_out) != hipSuccess) {
         h->err = "autotune scratch allocation failed";
         return -1;
     }
     (void)hipMemset(x, 0x3c, n_in * sizeof(float2));  // 0.0115f everywhere: finite, non-zero
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    gsdr::Event e0, e1;
+    (void)hipEventCreate(e0.out());
+    (void)hipEventCreate(e1.out());
     const double cand[] = {0.8, 1.0, 1.3, 1.7};
     double best_ms = 1e30, best_ratio = 1.3;
     int rc = 0;
@@ -711,10 +708,6 @@ int autotune_chunks(gsdr_demod *h, int nblk) {
             best_ratio = r;
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(x);
-    (void)hipFree(y);
     if (rc) {
         h->err = "autotune launch failed";
         return -1;
@@ -1079,6 +1072,211 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
     return ret;
 }
 
+// ---------------------------------------------------------------------------
+// creation: one setup function per mode and engine; each returns 0, or -1 with the message in h->err
+// ---------------------------------------------------------------------------
+
+int refuse(gsdr_demod *h, const char *msg) {
+    h->err = msg;
+    return -1;
+}
+
+// ref: :59-119
+int setup_direct(gsdr_demod *h, const gsdr_param_c *p) {
+    const gsdr::Switches &sw = h->sw;
+    if (p->rate <= 0) return refuse(h, "rate must be positive");
+    if (!(p->n_freq >= h->N && p->freq)) return refuse(h, "DIRECT needs one frequency per wave_type entry");
+    const std::vector<long long> tone(p->freq, p->freq + h->N);
+    if (h->decim <= 0) {
+        // undecimated: only the NCO tables are needed
+        h->F = 1;
+        h->M = 1;
+        h->window.assign(1, 1.f);
+        if (setup_ddc_common(h, 1, 1, (unsigned)p->rate, tone, 1, /*allow_flat=*/false)) return -1;
+        h->kernel_name = gsdr::mix_kernel_name(h->N, h->TW, h->L, h->K, sw.mix_few);
+        h->capacity = (long long)h->N * h->L;
+        return 0;
+    }
+    if (h->L % h->decim != 0) return refuse(h, "buffer_len must be a multiple of decim (ref: fir.cu:20)");
+    if (p->pf_average < 1 || p->pf_average > kMaxF) return refuse(h, "pf_average must be in [1,8] for DIRECT with decimation");
+    if (h->decim > 0x7fffffffLL / p->pf_average) return refuse(h, "decim*pf_average overflows");
+    const int F = (int)p->pf_average, M = (int)h->decim;
+    h->window.resize((size_t)M * F);
+    // ref: :99 taps, cut-off 0.75/(2*decim) narrowed to float
+    gsdr_make_sinc_window(M * F, (float)(0.75 / (M * 2)), h->window.data());
+    if (setup_ddc_common(h, F, M, (unsigned)p->rate, tone, (int)(h->L / M))) return -1;
+    if (h->pipe && h->pad > 0 && h->d_stage.alloc_zeroed((size_t)h->L + h->pad) != hipSuccess)
+        return refuse(h, "staging allocation failed");
+    h->kernel_name = h->pipe ? gsdr::ddc_flat_kernel_name() : gsdr::ddc_kernel_name();
+    for (auto &c : h->d_carry)
+        if (c.alloc_zeroed((size_t)(F > 1 ? F - 1 : 1) * h->Npad) != hipSuccess) return refuse(h, "carry allocation failed");
+    // (rows read whole 32-sample phasor blocks: the padding behind a window must stay
+    //  within the next block, or middle rows would read past the buffer)
+    // A handful of tones at a long decimation: every engine below walks a block's samples in sequence per
+    // tone lane / matrix column, and a launch is as long as one workgroup's walk (72 us per 1 M-sample
+    // buffer for 1 ... 256 tones at decim 1000).  ddc_few_kernel splits the block over the lanes of a wave
+    // per (chunk, tone): 16 tones at decim 1000 in 15 us (profiles/r03_shape_sweep.log).  GSDR_DDC_FEW=0: off.
+    h->few = sw.ddc_mfma && sw.ddc_few && !h->pipe && M >= 512 && h->N <= 32 && h->TW == 1;
+    if (h->few) h->kernel_name = gsdr::ddc_few_kernel_name();
+    if (!h->few && sw.ddc_mfma && h->L / M >= F - 1 && h->L >= 4 && F <= 33 && (M * F + 31) / 32 * 32 - M * F <= M &&
+        setup_mfma(h, /*direct=*/true, tone))
+        return -1;
+    if (!h->mfma && autotune_chunks(h, (int)(h->L / M))) return -1;
+    h->capacity = (long long)h->N * (h->L / M);
+    return 0;
+}
+
+// TONES / NOISE, a frame per workgroup -- polyphase filter, transform inside the LDS, bin selection: the
+// reference's own algorithm (:486-565, :568-649) at one read of the window and one write of the selected bins per
+// buffer.  blue_m > 0: through Bluestein's identity at that padded length.
+int setup_pfb_lds(gsdr_demod *h, bool noise, int F, const std::vector<long long> &tone, long long blue_m) {
+    h->pfb_lds = true;
+    h->pfb_blue = blue_m > 0;
+    h->F = F;
+    h->M = h->nfft;
+    std::vector<float2> tw((size_t)h->nfft);
+    for (int k = 0; k < h->nfft; ++k) {
+        const double a = -2.0 * M_PI * (double)k / (double)h->nfft;
+        tw[(size_t)k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    const std::vector<int> sel(tone.begin(), tone.end());
+    bool ok = h->d_pfb_tw.upload(tw) == hipSuccess && h->d_fft_win.upload(h->window) == hipSuccess &&
+              (noise || h->d_pfb_sel.upload(sel) == hipSuccess);
+    // Bluestein: the chirp, its transform and the twiddles of length m (fft_plan_build makes exactly these)
+    if (ok && h->pfb_blue) ok = gsdr::fft_plan_build(h->fft, h->nfft) == 0 && h->fft.m == (int)blue_m;
+    for (int i = 0; i < kStageSets && ok; ++i) ok = h->d_pfb_carry[i].alloc_zeroed((size_t)h->nfft * F + 8) == hipSuccess;
+    if (!ok) return refuse(h, "PFB allocation failed");
+    // the kernel of a call of L / nfft frames (each launch reports its own, enqueue_pfb_lds)
+    h->kernel_name = gsdr::pfb_kernel_name(gsdr::pfb_choose(h->nfft, F, h->pfb_blue ? &h->fft : nullptr,
+                                                            (int)(h->L / h->nfft), h->ddc_channels, device_cus(), h->sw));
+    return 0;
+}
+
+// Frames the LDS kernel does not take: the polyphase filter and one launch per radix stage through memory (§4.5) --
+// NOISE keeps every bin, TONES (tones_global) picks its bins out of a scratch spectrum.  For TONES this replaces one
+// DDC per bin when the frame is long (above 8192 points a frame is a window of 32 768+ samples: the DDC rows become
+// thousand-block loops on a handful of workgroups)
+int setup_pfb_global(gsdr_demod *h, bool tones_global, int F, const std::vector<long long> &tone) {
+    h->noise_fft = true;
+    h->F = F;
+    h->M = h->nfft;
+    h->kernel_name = gsdr::fft_kernel_name();
+    if (tones_global) {
+        const std::vector<int> sel(tone.begin(), tone.end());
+        if (h->d_pfb_sel.upload(sel) != hipSuccess || h->d_fft_c.alloc((size_t)h->nfft * (size_t)h->batching) != hipSuccess)
+            return refuse(h, "TONES allocation failed");
+    }
+    if (gsdr::fft_plan_build(h->fft, h->nfft) != 0) return refuse(h, "cannot plan an FFT of fft_tones points");
+    const size_t len = (size_t)(h->fft.m > h->nfft ? h->fft.m : h->nfft) * (size_t)h->batching;
+    bool ok = h->d_fft_a.alloc(len) == hipSuccess && h->d_fft_b.alloc(len) == hipSuccess &&
+              h->d_fft_win.upload(h->window) == hipSuccess;
+    for (int i = 0; i < kStageSets && ok; ++i) ok = h->d_win[i].alloc_zeroed((size_t)h->nfft * h->batching * 2) == hipSuccess;
+    return ok ? 0 : refuse(h, "NOISE allocation failed");
+}
+
+// Every selected bin as a tone of the DDC kernels (GSDR_PFB_LDS=0 with GSDR_TONES_FFT=0 / GSDR_NOISE_FFT=0)
+int setup_pfb_ddc(gsdr_demod *h, int F, const std::vector<long long> &tone) {
+    const int rc = setup_ddc_common(h, F, h->nfft, (unsigned)h->nfft, tone, (int)(h->L / h->nfft) + F + 6);
+    h->kernel_name = h->pipe ? gsdr::ddc_flat_kernel_name() : gsdr::ddc_kernel_name();
+    if (rc) return -1;
+    // raw_input (:143) plus an equally long half of padding behind it, kStageSets times
+    for (auto &w : h->d_win)
+        if (w.alloc_zeroed((size_t)h->nfft * h->batching * 2) != hipSuccess) return refuse(h, "raw_input allocation failed");
+    // every carried sample of the raw window must come from the previous buffer
+    // (absmax covers this buffer and the one before)
+    // and the padding behind the last window must stay inside the raw buffer's spare half
+    if (h->sw.ddc_mfma && (long long)h->nfft * (F + 1) <= h->L && (long long)h->nfft * h->batching >= 40 &&
+        setup_mfma(h, /*direct=*/false, tone))
+        return -1;
+    if (!h->mfma && autotune_chunks(h, (int)(h->L / h->nfft) + F - 1)) return -1;
+    return 0;
+}
+
+// TONES, ref: :121-175, :702-768; NOISE, ref: :264-313 (full spectrum: every FFT bin is a channel)
+int setup_pfb(gsdr_demod *h, const gsdr_param_c *p) {
+    const gsdr::Switches &sw = h->sw;
+    const bool noise = (h->mode == GSDR_NOISE);
+    if (p->rate <= 0) return refuse(h, "rate must be positive");
+    if (p->fft_tones < 1) return refuse(h, "fft_tones must be >= 1");
+    if (p->pf_average < 1 || p->pf_average > kMaxF) return refuse(h, "pf_average must be in [1,8] for TONES/NOISE");
+    if (!(noise || (p->n_freq >= h->N && p->freq))) return refuse(h, "TONES needs one frequency per wave_type entry");
+    if (h->decim > 0)
+        return refuse(h, "TONES/NOISE with decim > 0 is not supported: the reference path is broken "
+                         "(ref: kernels.cu:718-719,747,779, USRP_demodulator.cpp:172,516)");
+    if ((long long)p->fft_tones * p->pf_average > 0x7fffffffLL) return refuse(h, "fft_tones*pf_average overflows");
+    // NOISE: polyphase filter + batched FFT of every frame (fft_kernels.hip), any fft_tones.
+    // GSDR_NOISE_FFT=0 evaluates every bin as a DDC tone instead (round 1's path: O(fft_tones)
+    // per sample, kept for A/B runs and refused above 16384 bins)
+    const bool noise_fft = noise && sw.noise_fft;
+    if (noise && !noise_fft && p->fft_tones > 16384)
+        return refuse(h, "NOISE without the FFT stage (GSDR_NOISE_FFT=0) supports fft_tones <= 16384");
+    h->nfft = p->fft_tones;
+    const int F = (int)p->pf_average;
+    h->fcut = (float)(1. / (2 * h->nfft));                     // :131, :274
+    h->window.resize((size_t)h->nfft * F);
+    gsdr_make_sinc_window(h->nfft * F, h->fcut, h->window.data());  // :134, :277
+    h->batching = gsdr_pfb_batching(h->L, h->nfft, F);         // :706
+    const int n_ch = noise ? h->nfft : h->N;                   // channels of the DDC launch
+    h->bins.resize(n_ch);
+    if (noise) {
+        for (int u = 0; u < n_ch; ++u) h->bins[u] = u;         // process_pfb_spec keeps every bin
+    } else {
+        gsdr_pfb_tone_bins(p->rate, h->nfft, p->freq, h->N, h->bins.data());  // :722-733
+    }
+    std::vector<long long> tone(n_ch);
+    for (int u = 0; u < n_ch; ++u) tone[u] = h->bins[u] < 0 ? 0 : h->bins[u];
+    // buffer_helper(n_tones, buffer_len, average, n_eff_tones): :159 / :301
+    gsdr_buffer_helper_init(&h->bh, h->nfft, (int)h->L, F, n_ch);
+    h->ddc_channels = n_ch;
+    h->capacity = (long long)n_ch * h->batching;               // :147 / :288
+    // The engine.  In the LDS: frames of up to 8192 points without a prime factor above 127;
+    // GSDR_PFB_LDS=0, GSDR_TONES_FFT=0 (TONES only) or such a length leave TONES to the DDC
+    // kernels (every selected bin as a tone) and NOISE to the global-memory FFT stages.
+    int radices16[16];
+    const bool direct_ok = gsdr::pfb_lds_plan(h->nfft, radices16, sw.pfb_radix8) >= 0;
+    // a prime factor above 127 (or GSDR_PFB_BLUESTEIN=1: any length, for tests): Bluestein's identity inside
+    // the workgroup, when a frame at the padded length m = 2^ceil(log2(2 nfft - 1)) fits the LDS
+    long long blue_m = 1;
+    while (blue_m < 2LL * h->nfft - 1) blue_m <<= 1;
+    const bool blue_ok = (sw.pfb_bluestein < 0 ? !direct_ok : sw.pfb_bluestein != 0) &&
+                         blue_m <= gsdr::kPfbLdsMaxN && gsdr::pfb_cu_fits(h->nfft, F, (int)blue_m, sw);
+    if (sw.pfb_lds && (direct_ok || blue_ok) && (noise ? noise_fft : sw.tones_fft))
+        return setup_pfb_lds(h, noise, F, tone, blue_ok ? blue_m : 0);
+    const bool tones_global = !noise && sw.tones_fft;
+    if (noise_fft || tones_global) return setup_pfb_global(h, tones_global, F, tone);
+    return setup_pfb_ddc(h, F, tone);
+}
+
+// ref: :177-262
+int setup_chirp(gsdr_demod *h, const gsdr_param_c *p) {
+    if (p->rate <= 0) return refuse(h, "rate must be positive");
+    if (!(p->n_freq >= 1 && p->n_chirp_f >= 1 && p->n_swipe_s >= 1 && p->n_chirp_t >= 1 && p->freq && p->chirp_f &&
+          p->swipe_s && p->chirp_t))
+        return refuse(h, "CHIRP needs freq[0], chirp_f[0], swipe_s[0] and chirp_t[0]");
+    gsdr_chirp_param cp;
+    gsdr_chirp_derive(p->rate, p->freq[0], p->chirp_f[0], p->swipe_s[0], p->chirp_t[0], &cp);
+    if (!(cp.num_steps >= 1 && cp.length >= 1 && cp.num_steps <= 0x7fffffffffffffffULL / cp.length))
+        return refuse(h, "chirp period overflows");
+    h->cs = chirp_shape(cp);
+    if (h->decim <= 0) {
+        h->kernel_name = gsdr::chirp_demod_kernel_name();
+        h->capacity = h->L;
+        return 0;
+    }
+    const unsigned long long ppt = cp.length * (unsigned long long)h->decim;  // :231
+    if (!(ppt >= 1 && ppt <= (unsigned long long)h->L)) return refuse(h, "chirp lock-in needs length*decim <= buffer_len");
+    h->ppt = (int)ppt;
+    gsdr_vna_helper_init(&h->vh, h->ppt, (int)h->L);       // :235
+    h->window.resize(h->ppt);
+    gsdr_make_flat_window(h->ppt, h->ppt / 10, h->window.data());  // :246
+    h->kernel_name = gsdr::chirp_lockin_kernel_name();
+    h->capacity = h->L / h->ppt + 1;
+    if (h->d_profile.upload(h->window) != hipSuccess || h->d_ccarry[0].alloc((size_t)h->ppt) != hipSuccess ||
+        h->d_ccarry[1].alloc((size_t)h->ppt) != hipSuccess || h->d_chirp_part.alloc((size_t)kChirpPartials) != hipSuccess)
+        return refuse(h, "chirp allocation failed");
+    return 0;
+}
+
 // gsdr_demod_create with the switches given (gsdr_demod_prepare's rehearsal twin takes its parent's)
 gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
     create_error().clear();
@@ -1137,239 +1335,22 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         // ref: :41-44 low priority stream for tone modes, :186-189 high for chirp
-        hipError_t e = hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking,
-                                                   last == GSDR_CHIRP ? hi : lo);
+        // (into a local first: the owner takes the stream only when the call has succeeded, whatever a failed one wrote)
+        hipStream_t s = nullptr;
+        hipError_t e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, last == GSDR_CHIRP ? hi : lo);
         if (e != hipSuccess) {
-            h->stream = nullptr;
             fail_create(h, std::string("cannot create a HIP stream: ") + hipGetErrorString(e));
             return nullptr;
         }
+        *h->stream.out() = s;
     }
-
-    auto need = [&](bool ok, const char *msg) {
-        if (!ok) fail_create(h, msg);
-        return ok;
-    };
 
     int rc = 0;
     switch (last) {
-        case GSDR_DIRECT: {  // ref: :59-119
-            if (!need(p->rate > 0, "rate must be positive")) return nullptr;
-            if (!need(p->n_freq >= h->N && p->freq, "DIRECT needs one frequency per wave_type entry")) return nullptr;
-            std::vector<long long> tone(p->freq, p->freq + h->N);
-            if (h->decim > 0) {
-                if (!need(h->L % h->decim == 0, "buffer_len must be a multiple of decim (ref: fir.cu:20)")) return nullptr;
-                if (!need(p->pf_average >= 1 && p->pf_average <= kMaxF, "pf_average must be in [1,8] for DIRECT with decimation")) return nullptr;
-                if (!need(h->decim <= 0x7fffffffLL / p->pf_average, "decim*pf_average overflows")) return nullptr;
-                const int F = (int)p->pf_average, M = (int)h->decim;
-                h->window.resize((size_t)M * F);
-                // ref: :99 taps, cut-off 0.75/(2*decim) narrowed to float
-                gsdr_make_sinc_window(M * F, (float)(0.75 / (M * 2)), h->window.data());
-                rc = setup_ddc_common(h, F, M, (unsigned)p->rate, tone, (int)(h->L / M));
-                if (!rc && h->pipe && h->pad > 0) {
-                    const size_t n = (size_t)h->L + h->pad;
-                    if (dev_alloc(&h->d_stage, n) != hipSuccess ||
-                        hipMemset(h->d_stage, 0, n * sizeof(float2)) != hipSuccess) {
-                        h->err = "staging allocation failed";
-                        rc = -1;
-                    }
-                }
-                h->kernel_name = h->pipe ? gsdr::ddc_flat_kernel_name() : gsdr::ddc_kernel_name();
-                if (!rc) {
-                    for (int i = 0; i < 2 && !rc; ++i) {
-                        const size_t n = (size_t)(F > 1 ? F - 1 : 1) * h->Npad;
-                        if (dev_alloc(&h->d_carry[i], n) != hipSuccess ||
-                            hipMemset(h->d_carry[i], 0, n * sizeof(float2)) != hipSuccess) {
-                            h->err = "carry allocation failed";
-                            rc = -1;
-                        }
-                    }
-                }
-                // (rows read whole 32-sample phasor blocks: the padding behind a window must stay
-                //  within the next block, or middle rows would read past the buffer)
-                // A handful of tones at a long decimation: every engine below walks a block's samples in sequence per
-                // tone lane / matrix column, and a launch is as long as one workgroup's walk (72 us per 1 M-sample
-                // buffer for 1 ... 256 tones at decim 1000).  ddc_few_kernel splits the block over the lanes of a wave
-                // per (chunk, tone): 16 tones at decim 1000 in 15 us (profiles/r03_shape_sweep.log).  GSDR_DDC_FEW=0: off.
-                h->few = !rc && sw.ddc_mfma && sw.ddc_few && !h->pipe &&
-                         M >= 512 && h->N <= 32 && h->TW == 1;
-                if (h->few) h->kernel_name = gsdr::ddc_few_kernel_name();
-                if (!rc && !h->few && sw.ddc_mfma && h->L / M >= F - 1 && h->L >= 4 && F <= 33 &&
-                    (M * F + 31) / 32 * 32 - M * F <= M)
-                    rc = setup_mfma(h, /*direct=*/true, tone);
-                if (!rc && !h->mfma) rc = autotune_chunks(h, (int)(h->L / M));
-                h->capacity = (long long)h->N * (h->L / M);
-            } else {
-                // undecimated: only the NCO tables are needed
-                h->F = 1;
-                h->M = 1;
-                h->window.assign(1, 1.f);
-                rc = setup_ddc_common(h, 1, 1, (unsigned)p->rate, tone, 1, /*allow_flat=*/false);
-                h->kernel_name = gsdr::mix_kernel_name(h->N, h->TW, h->L, h->K, sw.mix_few);
-                h->capacity = (long long)h->N * h->L;
-            }
-            break;
-        }
-        case GSDR_TONES:    // ref: :121-175, :702-768
-        case GSDR_NOISE: {  // ref: :264-313 (full spectrum: every FFT bin is a channel)
-            const bool noise = (last == GSDR_NOISE);
-            if (!need(p->rate > 0, "rate must be positive")) return nullptr;
-            if (!need(p->fft_tones >= 1, "fft_tones must be >= 1")) return nullptr;
-            if (!need(p->pf_average >= 1 && p->pf_average <= kMaxF, "pf_average must be in [1,8] for TONES/NOISE")) return nullptr;
-            if (!need(noise || (p->n_freq >= h->N && p->freq), "TONES needs one frequency per wave_type entry")) return nullptr;
-            if (!need(h->decim <= 0,
-                      "TONES/NOISE with decim > 0 is not supported: the reference path is broken "
-                      "(ref: kernels.cu:718-719,747,779, USRP_demodulator.cpp:172,516)")) return nullptr;
-            if (!need((long long)p->fft_tones * p->pf_average <= 0x7fffffffLL, "fft_tones*pf_average overflows")) return nullptr;
-            // NOISE: polyphase filter + batched FFT of every frame (fft_kernels.hip), any fft_tones.
-            // GSDR_NOISE_FFT=0 evaluates every bin as a DDC tone instead (round 1's path: O(fft_tones)
-            // per sample, kept for A/B runs and refused above 16384 bins)
-            const bool noise_fft = noise && sw.noise_fft;
-            if (!need(!noise || noise_fft || p->fft_tones <= 16384,
-                      "NOISE without the FFT stage (GSDR_NOISE_FFT=0) supports fft_tones <= 16384")) return nullptr;
-            h->nfft = p->fft_tones;
-            const int F = (int)p->pf_average;
-            h->fcut = (float)(1. / (2 * h->nfft));                     // :131, :274
-            h->window.resize((size_t)h->nfft * F);
-            gsdr_make_sinc_window(h->nfft * F, h->fcut, h->window.data());  // :134, :277
-            h->batching = gsdr_pfb_batching(h->L, h->nfft, F);         // :706
-            const int n_ch = noise ? h->nfft : h->N;                   // channels of the DDC launch
-            h->bins.resize(n_ch);
-            if (noise) {
-                for (int u = 0; u < n_ch; ++u) h->bins[u] = u;         // process_pfb_spec keeps every bin
-            } else {
-                gsdr_pfb_tone_bins(p->rate, h->nfft, p->freq, h->N, h->bins.data());  // :722-733
-            }
-            std::vector<long long> tone(n_ch);
-            for (int u = 0; u < n_ch; ++u) tone[u] = h->bins[u] < 0 ? 0 : h->bins[u];
-            // buffer_helper(n_tones, buffer_len, average, n_eff_tones): :159 / :301
-            gsdr_buffer_helper_init(&h->bh, h->nfft, (int)h->L, F, n_ch);
-            h->ddc_channels = n_ch;
-            // A frame per workgroup -- polyphase filter, transform inside the LDS, bin selection: the
-            // reference's own algorithm (:486-565, :568-649) at one read of the window and one write of
-            // the selected bins per buffer.  Frames of up to 8192 points without a prime factor above 127;
-            // GSDR_PFB_LDS=0, GSDR_TONES_FFT=0 (TONES only) or such a length leave TONES to the DDC
-            // kernels (every selected bin as a tone) and NOISE to the global-memory FFT stages.
-            int radices16[16];
-            const bool direct_ok = gsdr::pfb_lds_plan(h->nfft, radices16, sw.pfb_radix8) >= 0;
-            // a prime factor above 127 (or GSDR_PFB_BLUESTEIN=1: any length, for tests): Bluestein's identity inside
-            // the workgroup, when a frame at the padded length m = 2^ceil(log2(2 nfft - 1)) fits the LDS
-            long long blue_m = 1;
-            while (blue_m < 2LL * h->nfft - 1) blue_m <<= 1;
-            const bool blue_ok = (sw.pfb_bluestein < 0 ? !direct_ok : sw.pfb_bluestein != 0) &&
-                                 blue_m <= gsdr::kPfbLdsMaxN && gsdr::pfb_cu_fits(h->nfft, F, (int)blue_m, sw);
-            const bool lds_path = sw.pfb_lds && (direct_ok || blue_ok) && (noise ? noise_fft : sw.tones_fft);
-            if (lds_path) {
-                h->pfb_lds = true;
-                h->pfb_blue = blue_ok;
-                h->F = F;
-                h->M = h->nfft;
-                std::vector<float2> tw((size_t)h->nfft);
-                for (int k = 0; k < h->nfft; ++k) {
-                    const double a = -2.0 * M_PI * (double)k / (double)h->nfft;
-                    tw[(size_t)k] = make_float2((float)std::cos(a), (float)std::sin(a));
-                }
-                std::vector<int> sel(tone.begin(), tone.end());
-                bool ok = upload(&h->d_pfb_tw, tw) == hipSuccess && upload(&h->d_fft_win, h->window) == hipSuccess &&
-                          (noise || upload(&h->d_pfb_sel, sel) == hipSuccess);
-                // Bluestein: the chirp, its transform and the twiddles of length m (fft_plan_build makes exactly these)
-                if (ok && blue_ok) ok = gsdr::fft_plan_build(h->fft, h->nfft) == 0 && h->fft.m == (int)blue_m;
-                const size_t ncarry = (size_t)h->nfft * F + 8;
-                for (int i = 0; i < kStageSets && ok; ++i)
-                    ok = dev_alloc(&h->d_pfb_carry[i], ncarry) == hipSuccess &&
-                         hipMemset(h->d_pfb_carry[i], 0, ncarry * sizeof(float2)) == hipSuccess;
-                if (!need(ok, "PFB allocation failed")) return nullptr;
-                // the kernel of a call of L / nfft frames (each launch reports its own, enqueue_pfb_lds)
-                h->kernel_name = gsdr::pfb_kernel_name(gsdr::pfb_choose(h->nfft, F, blue_ok ? &h->fft : nullptr,
-                                                                        (int)(h->L / h->nfft), n_ch, device_cus(), sw));
-                h->capacity = (long long)n_ch * h->batching;               // :147 / :288
-                break;
-            }
-            // frames the LDS kernel does not take: the polyphase filter and one launch per radix stage through
-            // memory (§4.5) -- NOISE keeps every bin, TONES picks its bins out of a scratch spectrum.  For
-            // TONES this replaces one DDC per bin when the frame is long (above 8192 points a frame is a
-            // window of 32 768+ samples: the DDC rows become thousand-block loops on a handful of workgroups)
-            const bool tones_global = !noise && sw.tones_fft;
-            if (noise_fft || tones_global) {
-                h->noise_fft = true;
-                h->F = F;
-                h->M = h->nfft;
-                h->kernel_name = gsdr::fft_kernel_name();
-                if (tones_global) {
-                    std::vector<int> sel(tone.begin(), tone.end());
-                    if (!need(upload(&h->d_pfb_sel, sel) == hipSuccess &&
-                                  dev_alloc(&h->d_fft_c, (size_t)h->nfft * (size_t)h->batching) == hipSuccess,
-                              "TONES allocation failed")) return nullptr;
-                }
-                if (!need(gsdr::fft_plan_build(h->fft, h->nfft) == 0, "cannot plan an FFT of fft_tones points")) return nullptr;
-                const size_t len = (size_t)(h->fft.m > h->nfft ? h->fft.m : h->nfft) * (size_t)h->batching;
-                const size_t nwin = (size_t)h->nfft * h->batching * 2;
-                bool ok = dev_alloc(&h->d_fft_a, len) == hipSuccess && dev_alloc(&h->d_fft_b, len) == hipSuccess &&
-                          upload(&h->d_fft_win, h->window) == hipSuccess;
-                for (int i = 0; i < kStageSets && ok; ++i)
-                    ok = dev_alloc(&h->d_win[i], nwin) == hipSuccess &&
-                         hipMemset(h->d_win[i], 0, nwin * sizeof(float2)) == hipSuccess;
-                if (!need(ok, "NOISE allocation failed")) return nullptr;
-                h->capacity = (long long)n_ch * h->batching;               // :288
-                break;
-            }
-            rc = setup_ddc_common(h, F, h->nfft, (unsigned)h->nfft, tone,
-                                  (int)(h->L / h->nfft) + F + 6);
-            h->kernel_name = h->pipe ? gsdr::ddc_flat_kernel_name() : gsdr::ddc_kernel_name();
-            if (!rc) {
-                // raw_input (:143) plus an equally long half of padding behind it, kStageSets times
-                const size_t n = (size_t)h->nfft * h->batching * 2;
-                for (int i = 0; i < kStageSets && !rc; ++i)
-                    if (dev_alloc(&h->d_win[i], n) != hipSuccess ||
-                        hipMemset(h->d_win[i], 0, n * sizeof(float2)) != hipSuccess) {
-                        h->err = "raw_input allocation failed";
-                        rc = -1;
-                    }
-            }
-            // every carried sample of the raw window must come from the previous buffer
-            // (absmax covers this buffer and the one before)
-            // and the padding behind the last window must stay inside the raw buffer's spare half
-            if (!rc && sw.ddc_mfma && (long long)h->nfft * (F + 1) <= h->L &&
-                (long long)h->nfft * h->batching >= 40)
-                rc = setup_mfma(h, /*direct=*/false, tone);
-            if (!rc && !h->mfma) rc = autotune_chunks(h, (int)(h->L / h->nfft) + F - 1);
-            h->capacity = (long long)n_ch * h->batching;               // :147 / :288
-            break;
-        }
-        case GSDR_CHIRP: {  // ref: :177-262
-            if (!need(p->rate > 0, "rate must be positive")) return nullptr;
-            if (!need(p->n_freq >= 1 && p->n_chirp_f >= 1 && p->n_swipe_s >= 1 && p->n_chirp_t >= 1 &&
-                          p->freq && p->chirp_f && p->swipe_s && p->chirp_t,
-                      "CHIRP needs freq[0], chirp_f[0], swipe_s[0] and chirp_t[0]")) return nullptr;
-            gsdr_chirp_param cp;
-            gsdr_chirp_derive(p->rate, p->freq[0], p->chirp_f[0], p->swipe_s[0], p->chirp_t[0], &cp);
-            if (!need(cp.num_steps >= 1 && cp.length >= 1 &&
-                          cp.num_steps <= 0x7fffffffffffffffULL / cp.length,
-                      "chirp period overflows")) return nullptr;
-            h->cs = chirp_shape(cp);
-            if (h->decim > 0) {
-                const unsigned long long ppt = cp.length * (unsigned long long)h->decim;  // :231
-                if (!need(ppt >= 1 && ppt <= (unsigned long long)h->L,
-                          "chirp lock-in needs length*decim <= buffer_len")) return nullptr;
-                h->ppt = (int)ppt;
-                gsdr_vna_helper_init(&h->vh, h->ppt, (int)h->L);       // :235
-                h->window.resize(h->ppt);
-                gsdr_make_flat_window(h->ppt, h->ppt / 10, h->window.data());  // :246
-                h->kernel_name = gsdr::chirp_lockin_kernel_name();
-                if (upload(&h->d_profile, h->window) != hipSuccess ||
-                    dev_alloc(&h->d_ccarry[0], (size_t)h->ppt) != hipSuccess ||
-                    dev_alloc(&h->d_ccarry[1], (size_t)h->ppt) != hipSuccess ||
-                    dev_alloc(&h->d_chirp_part, (size_t)kChirpPartials) != hipSuccess) {
-                    h->err = "chirp allocation failed";
-                    rc = -1;
-                }
-                h->capacity = h->L / h->ppt + 1;
-            } else {
-                h->kernel_name = gsdr::chirp_demod_kernel_name();
-                h->capacity = h->L;
-            }
-            break;
-        }
+        case GSDR_DIRECT: rc = setup_direct(h, p); break;
+        case GSDR_TONES:
+        case GSDR_NOISE: rc = setup_pfb(h, p); break;
+        case GSDR_CHIRP: rc = setup_chirp(h, p); break;
         case GSDR_NODSP:  // ref: :315-321
             h->capacity = h->L;
             h->kernel_name = "memcpy";
@@ -1425,7 +1406,7 @@ static int process_device(gsdr_demod *h, const gsdr_c64 *in_dev, const gsdr_sc16
                           void *hip_stream) {
     if (refuse_null(h, in16_dev ? (const void *)in16_dev : in_dev, out_dev)) return -1;
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (in16_dev && h->mode != GSDR_NODSP && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
+    if (in16_dev && h->mode != GSDR_NODSP && !h->d_wide) HIPCHK(h, h->d_wide.alloc((size_t)h->L));
     // NULL is HIP's null stream, as everywhere in HIP
     return process_device_body(h, reinterpret_cast<const float2 *>(in_dev), in16_dev, in16_dev ? h->d_wide : nullptr,
                                reinterpret_cast<float2 *>(out_dev), (hipStream_t)hip_stream);
@@ -1469,6 +1450,18 @@ static int process_device_body(gsdr_demod *h, const float2 *in, const gsdr_sc16 
     return n;
 }
 
+// The staging buffers of the host-pointer entry are made as a pair: both set or both empty.  (Were d_in kept when d_out
+// cannot be had, the next call would skip the allocation and hand a null d_out to the kernels.)
+static int staging_pair(gsdr_demod *h) {
+    if (h->d_in) return 0;
+    hipError_t e = h->d_in.alloc((size_t)h->L);
+    if (e == hipSuccess) e = h->d_out.alloc((size_t)h->capacity);
+    if (e == hipSuccess) return 0;
+    h->d_in.reset(), h->d_out.reset();
+    h->err = std::string("staging allocation of the host entry: ") + hipGetErrorString(e);
+    return -1;
+}
+
 // gsdr_demod_process and gsdr_demod_process_sc16 (in16_host != nullptr)
 static int process_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 *in16_host, gsdr_c64 *out_host) {
     if (refuse_null(h, in16_host ? (const void *)in16_host : in_host, out_host)) return -1;
@@ -1478,13 +1471,10 @@ static int process_host(gsdr_demod *h, const gsdr_c64 *in_host, const gsdr_sc16 
         return (int)h->L;
     }
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_in) {
-        HIPCHK(h, dev_alloc(&h->d_in, (size_t)h->L));
-        HIPCHK(h, dev_alloc(&h->d_out, (size_t)h->capacity));
-    }
+    if (staging_pair(h)) return -1;
     if (in16_host) {
         // half the bytes over the host link; widened into the staging buffer of the complex64 entry
-        if (!h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
+        if (!h->d_in16) HIPCHK(h, h->d_in16.alloc((size_t)h->L));
         HIPCHK(h, hipMemcpyAsync(h->d_in16, in16_host, (size_t)h->L * sizeof(gsdr_sc16), hipMemcpyHostToDevice, h->stream));
     } else {
         HIPCHK(h, hipMemcpyAsync(h->d_in, in_host, (size_t)h->L * sizeof(float2), hipMemcpyHostToDevice, h->stream));
@@ -1508,24 +1498,16 @@ int gsdr_demod_process_sc16(gsdr_demod *h, const gsdr_sc16 *in_host, gsdr_c64 *o
     return process_host(h, nullptr, in_host, out_host);
 }
 
+// what pipeline_init's all-or-nothing rule needs: nothing of the pipeline is left
 static void pipeline_teardown(gsdr_demod *h) {
     for (auto &sl : h->slot) {
-        if (sl.up) (void)hipEventDestroy(sl.up);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.down) (void)hipEventDestroy(sl.down);
-        sl.up = sl.done = sl.down = sl.wait_ev = nullptr;
+        sl.up.reset(), sl.done.reset(), sl.down.reset();
+        sl.wait_ev = nullptr;
     }
-    for (int i = 0; i < kPipeStreams; ++i) {
-        if (h->s_main[i]) (void)hipStreamDestroy(h->s_main[i]);
-        h->s_main[i] = nullptr;
-    }
-    for (int i = 0; i < 4; ++i) {
-        if (h->ev_abs[i]) (void)hipEventDestroy(h->ev_abs[i]);
-        h->ev_abs[i] = nullptr;
-    }
-    if (h->s_up) (void)hipStreamDestroy(h->s_up);
-    if (h->s_down) (void)hipStreamDestroy(h->s_down);
-    h->s_up = h->s_down = nullptr;
+    for (auto &st : h->s_main) st.reset();
+    for (auto &e : h->ev_abs) e.reset();
+    h->s_up.reset(), h->s_down.reset();
+    h->pipe_ready = false;
 }
 
 static int pipeline_init_parts(gsdr_demod *h);
@@ -1545,12 +1527,12 @@ static int pipeline_init(gsdr_demod *h) {
 }
 
 static int pipeline_init_parts(gsdr_demod *h) {
-    HIPCHK(h, hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->s_down, hipStreamNonBlocking));
+    HIPCHK(h, hipStreamCreateWithFlags(h->s_up.out(), hipStreamNonBlocking));
+    HIPCHK(h, hipStreamCreateWithFlags(h->s_down.out(), hipStreamNonBlocking));
     for (auto &sl : h->slot) {
-        HIPCHK(h, hipEventCreateWithFlags(&sl.up, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&sl.down, hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(sl.up.out(), hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(sl.done.out(), hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(sl.down.out(), hipEventDisableTiming));
     }
     // The compute streams must sit on different hardware queues to overlap.  HIP deals the
     // streams of one priority class out to few queues (4 by default) that every other stream
@@ -1569,13 +1551,15 @@ static int pipeline_init_parts(gsdr_demod *h) {
     std::vector<uint32_t> all_units((size_t)(prop.multiProcessorCount + 31) / 32, 0xffffffffu);
     if (prop.multiProcessorCount % 32) all_units.back() = (1u << (prop.multiProcessorCount % 32)) - 1u;
     for (int i = 0; i < kPipeStreams; ++i) {
-        if (h->sw.pipe_queues &&
-            hipExtStreamCreateWithCUMask(&h->s_main[i], (uint32_t)all_units.size(), all_units.data()) == hipSuccess)
+        hipStream_t s = nullptr;      // (the owner takes it only when the call has succeeded)
+        if (h->sw.pipe_queues && hipExtStreamCreateWithCUMask(&s, (uint32_t)all_units.size(), all_units.data()) == hipSuccess) {
+            *h->s_main[i].out() = s;
             continue;
+        }
         (void)hipGetLastError();
-        HIPCHK(h, hipStreamCreateWithPriority(&h->s_main[i], hipStreamNonBlocking, prio_least));
+        HIPCHK(h, hipStreamCreateWithPriority(h->s_main[i].out(), hipStreamNonBlocking, prio_least));
     }
-    for (int i = 0; i < 4; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_abs[i], hipEventDisableTiming));
+    for (int i = 0; i < 4; ++i) HIPCHK(h, hipEventCreateWithFlags(h->ev_abs[i].out(), hipEventDisableTiming));
     return 0;
 }
 
@@ -1631,9 +1615,9 @@ static int pipeline_compute(gsdr_demod *h, gsdr_demod::Slot &sl, hipEvent_t up, 
 
 // the device buffers of a pipeline slot, each created when the first entry that needs it asks for it
 static int slot_buffers(gsdr_demod *h, gsdr_demod::Slot &sl, bool in, bool out, bool in16) {
-    if (in && !sl.d_in) HIPCHK(h, dev_alloc(&sl.d_in, (size_t)h->L));
-    if (out && !sl.d_out) HIPCHK(h, dev_alloc(&sl.d_out, (size_t)h->capacity));
-    if (in16 && !sl.d_in16) HIPCHK(h, dev_alloc(&sl.d_in16, (size_t)h->L));
+    if (in && !sl.d_in) HIPCHK(h, sl.d_in.alloc((size_t)h->L));
+    if (out && !sl.d_out) HIPCHK(h, sl.d_out.alloc((size_t)h->capacity));
+    if (in16 && !sl.d_in16) HIPCHK(h, sl.d_in16.alloc((size_t)h->L));
     return 0;
 }
 
@@ -1641,16 +1625,13 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     if (!h) return -1;
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
     if (h->mode == GSDR_NODSP) return 0;
-    if ((what & GSDR_PREPARE_HOST) && !h->d_in) {
-        HIPCHK(h, dev_alloc(&h->d_in, (size_t)h->L));
-        HIPCHK(h, dev_alloc(&h->d_out, (size_t)h->capacity));
-    }
+    if ((what & GSDR_PREPARE_HOST) && staging_pair(h)) return -1;
     if (what & (GSDR_PREPARE_PIPELINE | GSDR_PREPARE_PIPELINE_HOST)) {
         if (pipeline_init(h)) return -1;
     }
     const bool sc16 = (what & GSDR_PREPARE_SC16) != 0;
-    if (sc16 && (what & GSDR_PREPARE_HOST) && !h->d_in16) HIPCHK(h, dev_alloc(&h->d_in16, (size_t)h->L));
-    if (sc16 && !h->d_wide) HIPCHK(h, dev_alloc(&h->d_wide, (size_t)h->L));
+    if (sc16 && (what & GSDR_PREPARE_HOST) && !h->d_in16) HIPCHK(h, h->d_in16.alloc((size_t)h->L));
+    if (sc16 && !h->d_wide) HIPCHK(h, h->d_wide.alloc((size_t)h->L));
     for (auto &sl : h->slot) {
         const bool host = (what & GSDR_PREPARE_PIPELINE_HOST) != 0;
         if (slot_buffers(h, sl, host || (sc16 && (what & GSDR_PREPARE_PIPELINE)), host, host && sc16)) return -1;
@@ -1827,6 +1808,7 @@ int gsdr_demod_wait(gsdr_demod *h) {
     return sl.n;
 }
 
+// Nothing may be released while a stream of the handle can still run a kernel that reads it: wait for them, then delete
 void gsdr_demod_close(gsdr_demod *h) {
     if (!h) return;
     if (h->device >= 0) (void)hipSetDevice(h->device);
@@ -1835,45 +1817,6 @@ void gsdr_demod_close(gsdr_demod *h) {
         if (h->s_main[i]) (void)hipStreamSynchronize(h->s_main[i]);
     if (h->s_up) (void)hipStreamSynchronize(h->s_up);
     if (h->s_down) (void)hipStreamSynchronize(h->s_down);
-    for (auto &sl : h->slot) {
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.d_in16) (void)hipFree(sl.d_in16);
-    }
-    pipeline_teardown(h);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (auto &e : h->ev_pool) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    if (h->d_chirp_part) (void)hipFree(h->d_chirp_part);
-    void *ptrs[] = {h->d_in16,    h->d_wide,
-                    h->d_in,      h->d_out,     h->d_taps_t,   h->d_taps_p,   h->d_stage,    h->d_btab,     h->d_wk,
-                    h->d_wrem,    h->d_fmod,    h->d_tails,    h->d_carry[0], h->d_carry[1],
-                    h->d_profile, h->d_ccarry[0], h->d_ccarry[1],
-                    h->d_bfrag,   h->d_ptab,    h->d_dtab,     h->d_mtaps,    h->d_mfmod,
-                    h->d_segmax,  h->d_bfrag3,  h->d_ptab3};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < kStageSets; ++i) {
-        if (h->d_img[i]) (void)hipFree(h->d_img[i]);
-        if (h->d_win[i]) (void)hipFree(h->d_win[i]);
-        if (h->d_head[i]) (void)hipFree(h->d_head[i]);
-        if (h->d_tail[i]) (void)hipFree(h->d_tail[i]);
-    }
-    gsdr::fft_plan_free(h->fft);
-    if (h->d_fft_a) (void)hipFree(h->d_fft_a);
-    if (h->d_fft_b) (void)hipFree(h->d_fft_b);
-    if (h->d_fft_c) (void)hipFree(h->d_fft_c);
-    if (h->d_fft_win) (void)hipFree(h->d_fft_win);
-    if (h->d_pfb_tw) (void)hipFree(h->d_pfb_tw);
-    if (h->d_pfb_sel) (void)hipFree(h->d_pfb_sel);
-    for (int i = 0; i < kStageSets; ++i)
-        if (h->d_pfb_carry[i]) (void)hipFree(h->d_pfb_carry[i]);
-    if (h->d_avg_frames) (void)hipFree(h->d_avg_frames);
-    for (float2 *p : h->d_avg_acc)
-        if (p) (void)hipFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);  // ref: 03_implement.md:58-63
     delete h;
 }
 
@@ -1910,22 +1853,18 @@ int gsdr_demod_set_frame_average(gsdr_demod *h, int k, int kind) {
     if (h->device >= 0) HIPCHK(h, hipSetDevice(h->device));
     if (k > 1) {
         // everything the averaging needs, now (nothing is allocated by the first packets); kept when k changes again
-        if (!h->d_avg_frames) HIPCHK(h, dev_alloc(&h->d_avg_frames, (size_t)h->ddc_channels * (size_t)h->batching));
+        if (!h->d_avg_frames) HIPCHK(h, h->d_avg_frames.alloc((size_t)h->ddc_channels * (size_t)h->batching));
         for (auto &p : h->d_avg_acc) {
-            if (!p) HIPCHK(h, dev_alloc(&p, (size_t)h->ddc_channels));
+            if (!p) HIPCHK(h, p.alloc((size_t)h->ddc_channels));
             HIPCHK(h, hipMemset(p, 0, (size_t)h->ddc_channels * sizeof(float2)));
         }
     }
     const long long capacity = (long long)h->ddc_channels * ((h->batching + k - 1) / k);
     if (capacity > h->capacity) {
         // output staging that gsdr_demod_prepare sized for a larger k: nothing has used it yet, the entries make it anew
-        if (h->d_out) (void)hipFree(h->d_out);
-        if (h->d_in) (void)hipFree(h->d_in);
-        h->d_in = h->d_out = nullptr;     // (the host entry allocates the two together)
-        for (auto &sl : h->slot) {
-            if (sl.d_out) (void)hipFree(sl.d_out);
-            sl.d_out = nullptr;
-        }
+        h->d_out.reset();
+        h->d_in.reset();                  // (the host entry allocates the two together)
+        for (auto &sl : h->slot) sl.d_out.reset();
     }
     h->avg_k = k;
     h->avg_kind = kind;

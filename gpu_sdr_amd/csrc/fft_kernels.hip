@@ -1346,14 +1346,6 @@ void host_fft_pow2(std::vector<double> &re, std::vector<double> &im) {
     }
 }
 
-template <typename T>
-hipError_t to_device(T **dst, const std::vector<T> &src) {
-    *dst = nullptr;
-    hipError_t e = hipMalloc((void **)dst, (src.empty() ? 1 : src.size()) * sizeof(T));
-    if (e != hipSuccess) return e;
-    return src.empty() ? hipSuccess : hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 }  // namespace
 
 #ifdef GSDR_STAMP_BUILD
@@ -1377,7 +1369,7 @@ int fft_plan_build(FftPlan &pl, int n) {
         pl.n_radices = (int)rad.size();
         for (size_t i = 0; i < rad.size() && i < 32; ++i) pl.radices[i] = rad[i];
         host_twiddles(n, tw);
-        if (to_device(&pl.d_tw, tw) != hipSuccess) return -1;
+        if (pl.d_tw.upload(tw) != hipSuccess) return -1;
         return 0;
     }
     // Bluestein: m = 2^ceil(log2(2n-1))
@@ -1389,7 +1381,7 @@ int fft_plan_build(FftPlan &pl, int n) {
     pl.n_radices = (int)rad.size();
     for (size_t i = 0; i < rad.size() && i < 32; ++i) pl.radices[i] = rad[i];
     host_twiddles(pl.m, tw);
-    if (to_device(&pl.d_tw, tw) != hipSuccess) return -1;
+    if (pl.d_tw.upload(tw) != hipSuccess) return -1;
     std::vector<float2> chirp((size_t)n);
     std::vector<double> br((size_t)m, 0.0), bi((size_t)m, 0.0);
     for (long long j = 0; j < n; ++j) {
@@ -1403,15 +1395,8 @@ int fft_plan_build(FftPlan &pl, int n) {
     host_fft_pow2(br, bi);
     std::vector<float2> bhat((size_t)m);
     for (long long k = 0; k < m; ++k) bhat[(size_t)k] = make_float2((float)br[(size_t)k], (float)bi[(size_t)k]);
-    if (to_device(&pl.d_chirp, chirp) != hipSuccess || to_device(&pl.d_bhat, bhat) != hipSuccess) return -1;
+    if (pl.d_chirp.upload(chirp) != hipSuccess || pl.d_bhat.upload(bhat) != hipSuccess) return -1;
     return 0;
-}
-
-void fft_plan_free(FftPlan &pl) {
-    if (pl.d_tw) (void)hipFree(pl.d_tw);
-    if (pl.d_chirp) (void)hipFree(pl.d_chirp);
-    if (pl.d_bhat) (void)hipFree(pl.d_bhat);
-    pl = FftPlan{};
 }
 
 // Stockham stages of one length-`len` transform set: src -> ... -> dst, ping-ponging through tmp

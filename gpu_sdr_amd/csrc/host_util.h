@@ -11,27 +11,13 @@
 
 #include "../../include/gsdr.h"
 #include "ddc_kernels.h"
+#include "dev_owner.h"
 
 namespace gsdr {
 
 // The message gsdr_last_error(NULL) returns: what the last call without a handle of its own (a creation, a TX or
 // source entry, gsdr_note_error_) left on this thread.  One thread-local object, in demod.cpp.
 std::string &create_error();
-
-template <typename T>
-hipError_t dev_alloc(T **p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-}
-
-template <typename T>
-hipError_t upload(T **dst, const std::vector<T> &src) {
-    hipError_t e = dev_alloc(dst, src.size());
-    if (e != hipSuccess) return e;
-    if (src.empty()) return hipSuccess;
-    return hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-}
 
 // compute units of the current device (256 when it cannot be asked)
 inline int device_cus() {

@@ -15,18 +15,16 @@
 using gsdr::ChirpShape;
 using gsdr::chirp_shape;
 using gsdr::create_error;
-using gsdr::dev_alloc;
 using gsdr::device_cus;
 using gsdr::mod_rate;
 using gsdr::phasor;
-using gsdr::upload;
 
 namespace gsdr {
 
 // What a generator keeps per wire format.
 template <typename T>
 struct TxBuffers {
-    T *d_stage = nullptr;      // get() to host memory goes through here
+    DevBuf<T> d_stage;         // get() to host memory goes through here
     size_t stage_n = 0;        // samples d_stage holds
     // TONES through get_ptr: one period + one buffer of the comb in host memory, made once
     // (the reference's base_buffer, cpp/USRP_buffer_generator.cpp:77-95)
@@ -41,8 +39,8 @@ struct gsdr_txgen {
     int device = -1;
     unsigned rate = 1;
     int n_tones = 0;
-    unsigned *d_fmod = nullptr;
-    float2 *d_q0 = nullptr, *d_btab = nullptr, *d_ctab = nullptr;
+    gsdr::DevBuf<unsigned> d_fmod;
+    gsdr::DevBuf<float2> d_q0, d_btab, d_ctab;
     // the TX_buffer_generator state (gsdr_txgen_create)
     int mode = -1;                     // GSDR_TONES / GSDR_CHIRP, -1: a bare tone comb (gsdr_txgen_tones_create)
     long long buffer_len = 0;
@@ -53,7 +51,7 @@ struct gsdr_txgen {
     // sc16 output (gsdr_txgen_*_sc16): the gain of the narrowing, the counter of clipped components (device memory,
     // zeroed at creation), and a staging buffer (4 bytes per sample) and a period buffer of its own
     float sc16_gain = 32767.0f;
-    unsigned long long *d_clipped = nullptr;
+    gsdr::DevBuf<unsigned long long> d_clipped;
     gsdr::TxBuffers<gsdr_sc16> sc16;
 };
 
@@ -118,27 +116,18 @@ int refuse(const char *entry, const char *what) {
 bool set_device(const gsdr_txgen *g) { return g->device < 0 || hipSetDevice(g->device) == hipSuccess; }
 
 // the generator's counter of clipped components: 8 bytes of device memory, zero (the creating call has set the device)
-bool txgen_make_counter(gsdr_txgen *g) {
-    return hipMalloc((void **)&g->d_clipped, sizeof(unsigned long long)) == hipSuccess &&
-           hipMemset(g->d_clipped, 0, sizeof(unsigned long long)) == hipSuccess;
-}
+bool txgen_make_counter(gsdr_txgen *g) { return g->d_clipped.alloc_zeroed(1) == hipSuccess; }
 
 // the staging buffer of the host entries: at least `samples` elements in device memory, grown on demand
 template <typename T>
 bool stage_reserve(gsdr::TxBuffers<T> &b, size_t samples) {
-    if (b.d_stage && b.stage_n < samples) {
-        (void)hipFree(b.d_stage);
-        b.d_stage = nullptr;
-        b.stage_n = 0;
+    if (b.d_stage && b.stage_n >= samples) return true;
+    b.stage_n = 0;
+    if (b.d_stage.alloc(samples) != hipSuccess) {   // (frees the shorter one first)
+        (void)hipGetLastError();
+        return false;
     }
-    if (!b.d_stage) {
-        if (dev_alloc(&b.d_stage, samples) != hipSuccess) {
-            (void)hipGetLastError();
-            b.d_stage = nullptr;
-            return false;
-        }
-        b.stage_n = samples;
-    }
+    b.stage_n = samples;
     return true;
 }
 
@@ -159,12 +148,6 @@ void period_free(T *p, bool pinned) {
     if (!p) return;
     if (pinned) (void)hipHostFree(p);
     else std::free(p);
-}
-
-template <typename T>
-void buffers_free(gsdr::TxBuffers<T> &b) {
-    if (b.d_stage) (void)hipFree(b.d_stage);
-    period_free(b.h_period, b.h_period_pinned);
 }
 
 template <typename Fmt>
@@ -277,12 +260,12 @@ int gsdr_source_tones(gsdr_c64 *out_dev, long long n, long long start, int rate,
     if (!out_dev || n < 0 || rate <= 0 || n_tones < 0) return -1;
     std::vector<unsigned> fm(n_tones > 0 ? n_tones : 1, 0u);
     for (int k = 0; k < n_tones; ++k) fm[k] = mod_rate(freq[k], rate);
-    unsigned *d_f = nullptr;
-    float *d_a = nullptr, *d_p = nullptr;
+    gsdr::DevBuf<unsigned> d_f;
+    gsdr::DevBuf<float> d_a, d_p;
     const size_t cnt = fm.size();
-    hipError_t e = hipMalloc((void **)&d_f, cnt * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_a, cnt * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_p, cnt * sizeof(float));
+    hipError_t e = d_f.alloc(cnt);
+    if (e == hipSuccess) e = d_a.alloc(cnt);
+    if (e == hipSuccess) e = d_p.alloc(cnt);
     if (e == hipSuccess) e = hipMemcpy(d_f, fm.data(), cnt * sizeof(unsigned), hipMemcpyHostToDevice);
     if (e == hipSuccess && n_tones > 0) e = hipMemcpy(d_a, ampl, n_tones * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && n_tones > 0) e = hipMemcpy(d_p, phase, n_tones * sizeof(float), hipMemcpyHostToDevice);
@@ -291,9 +274,6 @@ int gsdr_source_tones(gsdr_c64 *out_dev, long long n, long long start, int rate,
         e = gsdr::launch_source_tones(reinterpret_cast<float2 *>(out_dev), n, mod_rate(start, rate), (unsigned)rate,
                                       d_f, d_a, d_p, n_tones, sigma, seed, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_f) (void)hipFree(d_f);
-    if (d_a) (void)hipFree(d_a);
-    if (d_p) (void)hipFree(d_p);
     if (e != hipSuccess) {
         create_error() = std::string("gsdr_source_tones: ") + hipGetErrorString(e);
         return -1;
@@ -365,8 +345,8 @@ gsdr_txgen *gsdr_txgen_tones_create(int rate, const int *freq, const float *ampl
         for (int lo = 0; lo < 64; ++lo) bt[(size_t)k * 64 + lo] = w((unsigned long long)lo);
         for (int j = 0; j < 16; ++j) ct[(size_t)k * 16 + j] = w(64ULL * (unsigned long long)j);
     }
-    const bool ok = upload(&g->d_fmod, fm) == hipSuccess && upload(&g->d_q0, q0) == hipSuccess &&
-                    upload(&g->d_btab, bt) == hipSuccess && upload(&g->d_ctab, ct) == hipSuccess &&
+    const bool ok = g->d_fmod.upload(fm) == hipSuccess && g->d_q0.upload(q0) == hipSuccess &&
+                    g->d_btab.upload(bt) == hipSuccess && g->d_ctab.upload(ct) == hipSuccess &&
                     txgen_make_counter(g) && hipStreamSynchronize(nullptr) == hipSuccess;
     if (!ok) {
         create_error() = "gsdr_txgen_tones_create: device allocation failed";
@@ -380,10 +360,8 @@ void gsdr_txgen_close(gsdr_txgen *g) {
     if (!g) return;
     if (g->device >= 0) (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (void *p : {(void *)g->d_fmod, (void *)g->d_q0, (void *)g->d_btab, (void *)g->d_ctab, (void *)g->d_clipped})
-        if (p) (void)hipFree(p);
-    buffers_free(g->c64);
-    buffers_free(g->sc16);
+    period_free(g->c64.h_period, g->c64.h_period_pinned);
+    period_free(g->sc16.h_period, g->sc16.h_period_pinned);
     delete g;
 }
 

@@ -231,3 +231,38 @@ def test_rx_entries_refuse_a_null_handle(gsdr_lib):
     assert lib.gsdr_demod_prepare(None, 0) == -1
     # a call without a handle has nowhere to leave a message, and leaves the creation message alone
     assert last_error(lib) == PLANTED
+
+
+# ---- gsdr_demod_create: what is refused before the first HIP call ----------------------------------------------------
+
+RX_MULTI = b"Multiple chirp RX buffer demodulation has been requested. This feature is not implemented yet."
+RX_MIXED = b"Mixed RX buffer demodulation has been requested. This feature is not implemented yet."
+RX_CREATE_REFUSALS = [
+    ("two_chirps", dict(wave_type=[CHIRP, CHIRP], **CHIRP_ARRAYS), RX_MULTI),
+    ("mixed", dict(wave_type=[TONES, DIRECT], freq=(10, 20)), RX_MIXED),
+    ("mixed_nodsp_first", dict(wave_type=[NODSP, TONES], freq=(10, 20)), RX_MIXED),
+    ("buffer_len_zero", dict(wave_type=[DIRECT], freq=(10,), buffer_len=0), b"buffer_len must be positive"),
+    ("buffer_len_negative", dict(wave_type=[NODSP], buffer_len=-5), b"buffer_len must be positive"),
+    ("buffer_len_zero_no_wave_type", dict(wave_type=[], buffer_len=0), b"buffer_len must be positive"),
+    # the order of the checks decides the message of a doubly wrong request: chirps, then mixed, then the length
+    ("two_chirps_and_mixed_and_length", dict(wave_type=[CHIRP, TONES, CHIRP], buffer_len=0, **CHIRP_ARRAYS), RX_MULTI),
+    ("mixed_and_length", dict(wave_type=[TONES, CHIRP], buffer_len=0, **CHIRP_ARRAYS), RX_MIXED),
+]
+
+
+def test_demod_create_null_parameters(gsdr_lib):
+    assert gsdr_lib.gsdr_txgen_tones_create(0, None, None, None, 0, 0) is None      # leaves another message
+    assert last_error(gsdr_lib) != b"null parameters"
+    assert gsdr_lib.gsdr_demod_create(None) is None
+    assert last_error(gsdr_lib) == b"null parameters"
+
+
+@pytest.mark.parametrize("kwargs,msg", [c[1:] for c in RX_CREATE_REFUSALS], ids=[c[0] for c in RX_CREATE_REFUSALS])
+def test_demod_create_refusals(gsdr_lib, kwargs, msg):
+    """None of these has created a stream or allocated anything yet: the half-made handle is released without a HIP
+    call (its owners are empty)."""
+    p, keep = make_param(**kwargs)
+    plant(gsdr_lib)
+    assert gsdr_lib.gsdr_demod_create(C.byref(p)) is None
+    assert last_error(gsdr_lib) == msg
+    del keep
