@@ -35,6 +35,9 @@
 //   ddc_mfma_ring16p3r2_kernel  that loop with phasor images of 64 samples: the partial sums are rotated into the
 //                             accumulators once per pair of blocks (tools/gen_ddc_mfma_ring16p3r2.py,
 //                             tests/test_gpu_mfma3r2.py; GSDR_MFMA_3M_ROT)
+//   ddc_mfma_ring16p3f_kernel three products over 64-sample spans folded about their centre: four operand units of
+//                             K = 32 per span, 48 instead of 72 MFMAs (tools/gen_ddc_mfma_ring16p3f.py, fed by
+//                             ddc_convert3f_kernel; tests/test_gpu_fold.py; GSDR_MFMA_FOLD)
 //   ddc_mfma_ring16w8_kernel  the same loop for workgroups of eight waves
 //                             (tools/gen_ddc_mfma_ring16w8.py): single launches of one round
 //   ddc_mfma_ring_kernel      round 1's production kernel, the ring loop on v_mfma_f32_32x32x16_f16
@@ -55,6 +58,7 @@
 #include "ddc_mfma_ring16p_gen.h"
 #include "ddc_mfma_ring16p3_gen.h"
 #include "ddc_mfma_ring16p3r2_gen.h"
+#include "ddc_mfma_ring16p3f_gen.h"
 
 namespace gsdr {
 
@@ -1014,6 +1018,118 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     ring16p3_tile<true>(a, lds, gt0, tg, wave, active);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The folded three-product loop (tools/gen_ddc_mfma_ring16p3f.py).  The phase of a 64-sample
+// span is taken from its centre: sample j (t = j - 31.5) and its partner j' = 63 - j have c(j') = c(j), d(j') = -d(j),
+// so that two of Gauss's three sums fold to half length:
+//     P1 = sum a*c = sum_{j<32} (a_j + a_j')*c_j            P2 = sum b*d = sum_{j<32} (b_j - b_j')*d_j
+//     P3 = sum (a+b)*(c+d) = sum_{j<32} (a_j + b_j)*(c_j + d_j) + (a_j' + b_j')*(c_j - d_j)
+//     Re = P1 - P2      Im = P3 - P1 - P2
+// ddc_convert3f_kernel writes the 16-KiB slot image of a (row tile, span): piece 4*unit + 2*sp + rh of 1 KiB, unit
+// 0..3 = U1 = a_j + a_j', U2 = b_j - b_j', U3 = a_j + b_j, U4 = a_j' + b_j'; sp 0 = fp16 hi, 1 = lo; lane l of a piece =
+// row 16*rh + (l & 15), j = 8*(l >> 4) .. +7.  a and b are the products of split_pair bit for bit, every U one fp32 add
+// or subtract of two of them (no contraction).  A window of an odd number of blocks ends in a half span: its partners
+// are exact zeros and nothing of the missing block is loaded (the pass reads what ddc_convert3_kernel reads).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert3f_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
+    const MfmaShape &sh = a.sh;
+    const int l = threadIdx.x & 63, rh = threadIdx.x >> 6;
+    const int r = 16 * rh + (l & 15), g = l >> 4;
+    const int gt = blockIdx.x / nspan, sp = blockIdx.x - gt * nspan;
+    const int o = gt * 32 + r;
+    const float S = exp2_bits(row_scale_exp(a, o));
+    const int oc = o < sh.nout ? o : sh.nout - 1;
+    const float2 *xbase = gt == 0 ? a.head + sh.carry_len : (gt == sh.ngt - 1 ? a.tail - sh.tail0 : a.x);
+    const float2 *xrow = xbase + (long long)(oc + sh.woff) * sh.M;
+    const int k0 = sp * 64 + 8 * g;          // sample of j = 8*g; j + jj at k0 + jj
+    const int k1 = sp * 64 + 56 - 8 * g;     // the partner of j + jj at k1 + 7 - jj
+    const bool whole = 2 * sp + 1 < nhi;     // the span's second block lies inside the window's extent
+    const float4u *px = reinterpret_cast<const float4u *>(xrow + k0);
+    const float4v x0 = px[0], x1 = px[1], x2 = px[2], x3 = px[3];
+    const float4v h0 = *reinterpret_cast<const float4v *>(a.taps + k0) * S;
+    const float4v h1 = *reinterpret_cast<const float4v *>(a.taps + k0 + 4) * S;
+    const float4v zero = {0.f, 0.f, 0.f, 0.f};
+    float4v y0 = zero, y1 = zero, y2 = zero, y3 = zero, g0 = zero, g1 = zero;
+    if (whole) {
+        const float4u *py = reinterpret_cast<const float4u *>(xrow + k1);
+        y0 = py[0], y1 = py[1], y2 = py[2], y3 = py[3];
+        g0 = *reinterpret_cast<const float4v *>(a.taps + k1) * S;
+        g1 = *reinterpret_cast<const float4v *>(a.taps + k1 + 4) * S;
+    }
+    const float xr[8] = {x0.x, x0.z, x1.x, x1.z, x2.x, x2.z, x3.x, x3.z};
+    const float xi[8] = {x0.y, x0.w, x1.y, x1.w, x2.y, x2.w, x3.y, x3.w};
+    const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+    const float yr[8] = {y0.x, y0.z, y1.x, y1.z, y2.x, y2.z, y3.x, y3.z};
+    const float yi[8] = {y0.y, y0.w, y1.y, y1.w, y2.y, y2.w, y3.y, y3.w};
+    const float gs[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    half8 hi[4], lo[4];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma clang fp contract(off)
+        const float pa = mul_legacy(xr[j], hs[j]), pb = mul_legacy(xi[j], hs[j]);
+        // a half span: exact zeros, whatever the registers would multiply to
+        const float qa = whole ? mul_legacy(yr[7 - j], gs[7 - j]) : 0.f, qb = whole ? mul_legacy(yi[7 - j], gs[7 - j]) : 0.f;
+        const float u[4] = {pa + qa, pb - qb, pa + pb, qa + qb};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            _Float16 h, w;
+            split_one(u[c], h, w);
+            hi[c][j] = h;
+            lo[c][j] = w;
+        }
+    }
+    uint4 *dst = img + (size_t)blockIdx.x * (GSDR_MFMA_RING16P3F_SLOT / 16) + rh * 64 + l;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        dst[(4 * c) * 64] = __builtin_bit_cast(uint4, hi[c]);
+        dst[(4 * c + 2) * 64] = __builtin_bit_cast(uint4, lo[c]);
+    }
+}
+
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3f_tile(
+    const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
+    const MfmaShape &sh = a.sh;
+    const int Np = sh.NT32 * 32;
+    const int nspan = ((sh.nk8 + 3) / 4 + 1) / 2;
+    const int lane = (int)(fresh_tid() & 63u);
+    const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
+    const unsigned bo = (unsigned)tg * (16u * 1024u) + (unsigned)lane * 16u;      // 16 phasor images per 32-tone tile
+    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
+    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
+    // this wave copies pieces 4*wave .. 4*wave + 3 of every image
+    const unsigned io0 = (unsigned)wave * 4096u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u, io3 = io0 + 3072u;
+    const unsigned wrs = lds_base + (unsigned)wave * 4096u;
+    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nspan * (GSDR_MFMA_RING16P3F_SLOT / 16)),
+                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
+    asm volatile(GSDR_MFMA_RING16P3F_TEXT
+                 :
+                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [io3] "v"(io3), [po] "v"(po), [bo] "v"(bo),
+                   [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),
+                   GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),
+                   [nhi] GSDR_SGPR(nspan)
+                 : GSDR_MFMA_RING16P3F_CLOBBERS);
+    if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
+}
+
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3f_kernel(
+    const MfmaLaunch a) {
+    constexpr int W = 4;
+    // ring (4 slots of 16 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P3F_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P3F_BYTES >= 4 * 8192, "the accumulators fit");
+    static_assert(2 * GSDR_MFMA_RING16P3F_BYTES <= 160 * 1024, "two workgroups per compute unit");
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int gt0 = (q / sh.ntq) * 8 + xcd;
+    if (gt0 >= sh.ngt) return;
+    const int tg_raw = (q % sh.ntq) * W + wave;
+    const bool active = tg_raw < sh.ntg;
+    const int tg = active ? tg_raw : sh.ntg - 1;
+    ring16p3f_tile(a, lds, gt0, tg, wave, active);
+}
+
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
 // new buffer) or of region B (what the previous call left in front), a wave 512 of them: sixteen bytes per lane and
 // load, all four loads of a wave in flight at once -- one memory round trip per wave.  Maxima per segment:
@@ -1325,6 +1441,58 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
         }
 }
 
+// Tables of the folded three-product loop (ddc_mfma_ring16p3f_kernel).  Per 32-tone tile 16 B
+// images f = (unit*2 + th)*2 + sp of c_j, d_j, c_j + d_j, c_j - d_j, j < 32, where c_j + i*d_j = w^(j - 31.5): formed in
+// double from the exact integer phase in half samples (mod 2*rate), rounded once, split hi/lo; lane l holds tone
+// 16*th + (l & 15), element jj <-> j = 8*(l >> 4) + jj.  Per (span, tone) the phasor of the span's centre
+// w_n^(64*span + 31.5) as (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.
+void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                         std::vector<float4> &ptab3) {
+    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
+    const unsigned long long rate2 = 2ULL * pl.rate;
+    // w^(ph2 / 2), ph2 in half samples; host_phasor's sign: w = exp(-2 pi i / rate)
+    auto half_phasor = [&](unsigned long long ph2, double &re, double &im) {
+        const double ang = M_PI * ((double)ph2 / (double)pl.rate);
+        re = std::cos(ang);
+        im = -std::sin(ang);
+    };
+    bfrag3.assign((size_t)tiles * 16 * 64, uint4{0, 0, 0, 0});
+    for (int T = 0; T < tiles; ++T)
+        for (int th = 0; th < 2; ++th)
+            for (int lane = 0; lane < 64; ++lane) {
+                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
+                unsigned short img[4][2][8];
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int j = 8 * (lane >> 4) + jj;
+                    // t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
+                    double wr, wi;
+                    half_phasor((fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
+                    const double c = wr, d = -wi;
+                    const float v[4] = {(float)c, (float)d, (float)(c + d), (float)(c - d)};
+                    for (int u = 0; u < 4; ++u) {
+                        const unsigned short hb = to_half_bits(v[u]);
+                        img[u][0][jj] = hb;
+                        img[u][1][jj] = to_half_bits(v[u] - from_half_bits(hb));
+                    }
+                }
+                for (int u = 0; u < 4; ++u)
+                    for (int sp = 0; sp < 2; ++sp) {
+                        uint4 w;
+                        __builtin_memcpy(&w, img[u][sp], 16);
+                        bfrag3[((size_t)T * 16 + (u * 2 + th) * 2 + sp) * 64 + lane] = w;
+                    }
+            }
+    const int nrow = ((pl.nk8 + 3) / 4 + 1) / 2;
+    ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int row = 0; row < nrow; ++row)
+        for (int n = 0; n < Np; ++n) {
+            const unsigned long long t2 = (128ULL * (unsigned long long)row + 63ULL) % rate2;
+            double re, im;
+            half_phasor((unsigned long long)(((unsigned __int128)fmod[n] * t2) % rate2), re, im);
+            ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(im - re), (float)(re + im));
+        }
+}
+
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
     if (!s.x || s.n < 1 || s.nb < 0 || (s.nb > 0 && !s.b) || s.carry_len < 0 || s.carry_len > s.n || s.head_n < 0 ||
         s.head_n > s.n || s.tail0 < 0 || s.tail0 > s.n || !s.seg || !s.seg_clear || s.seg_len < 64 ||
@@ -1398,6 +1566,21 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
                 hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3(grid), dim3(256), 0, st, a);
             return hipGetLastError();
         }
+        case MfmaKernel::AsmRing16P3F: {
+            // the folded conversion pass and its loop (a.img: ngt * nspan images of 16 KiB; a.bfrag3 / a.ptab3: the
+            // tables of mfma_build_tables3f)
+            if (!a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
+            const int nhi = (sh.nk8 + 3) / 4, nspan = (nhi + 1) / 2;
+            const long long cgrid = (long long)sh.ngt * nspan;
+            grid = ring_grid(sh.ngt, sh.ntq, 1);
+            if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(ddc_convert3f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, const_cast<uint4 *>(a.img),
+                               nhi, nspan);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(ddc_mfma_ring16p3f_kernel, dim3(grid), dim3(256), 0, st, a);
+            return hipGetLastError();
+        }
         case MfmaKernel::AsmRing16W8:
             if (!(grid = ring_grid(sh.ngt, (sh.ntg + 7) / 8, 1))) return hipErrorInvalidValue;
             hipLaunchKernelGGL(ddc_mfma_ring16w8_kernel, dim3(grid), dim3(512), 0, st, a);
@@ -1421,7 +1604,8 @@ const char *ddc_mfma_kernel_name(MfmaKernel kind) {
     switch (kind) {
         case MfmaKernel::AsmRing16P:
         case MfmaKernel::AsmRing16P3:
-        case MfmaKernel::AsmRing16P3R2: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
+        case MfmaKernel::AsmRing16P3R2:
+        case MfmaKernel::AsmRing16P3F: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
         case MfmaKernel::AsmRing16W8: return "ddc_mfma_ring16w8_kernel";
         case MfmaKernel::AsmRing16: return "ddc_mfma_ring16_kernel";
         case MfmaKernel::AsmRing: return "ddc_mfma_ring_kernel";

@@ -83,6 +83,7 @@ gsdr::Switches gsdr::read_switches() {
     s.mfma_prec = env("GSDR_MFMA_PREC", -1);
     s.mfma_3m = env("GSDR_MFMA_3M", -1);
     s.mfma_3m_rot = env("GSDR_MFMA_3M_ROT", -1);
+    s.mfma_fold = env("GSDR_MFMA_FOLD", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -183,6 +184,7 @@ struct gsdr_demod {
     // 4.1d): decided once, in setup_mfma; such a handle sends EVERY matrix-core launch through that pair
     bool mac3 = false;
     bool rot2 = false;                 // ... through ddc_mfma_ring16p3r2_kernel: one rotation per pair of blocks (section 4.1e)
+    bool fold = false;                 // ... through ddc_mfma_ring16p3f_kernel: each pair folded about its centre (section 4.1f)
     gsdr::DevBuf<uint4> d_bfrag3;
     gsdr::DevBuf<float4> d_ptab3;
     gsdr::DevBuf<uint4> d_bfrag;
@@ -486,6 +488,19 @@ bool rot2_chosen(const gsdr_demod *h, bool mac3, long long nhi) {
     return mac3 && nhi >= 1 && (h->sw.mfma_3m_rot == 2 || (h->sw.mfma_3m_rot < 0 && nhi >= kRot2MinBlocks));
 }
 
+// A handle that rotates once per pair folds each 64-sample span about its centre (ddc_convert3f_kernel +
+// ddc_mfma_ring16p3f_kernel): the phasor of sample j and of its partner 63 - j are conjugates, so
+// two of the three sums run over 32 sums / differences of partners: 48 MFMAs per span instead of 72, still three real
+// products per complex multiply and one rotation per two blocks.  The folded operands are sums of two products, which
+// costs precision on the weakest tones of a 60 dB comb; kFoldMinBlocks is the shortest of the tested windows (94, 125,
+// 250 blocks) from which test_gpu_fold.py::test_hdr_comb_fold_keeps_the_rule measured the rule of kMac3MinBlocks kept at
+// it and every longer tested one (err / bound 0.84, 0.70, 0.51 at 94, 125, 250 blocks, against 0.84, 0.78, 0.56 not
+// folded; DESIGN.md section 4.1f, profiles/fold_parity_margins.json).  GSDR_MFMA_FOLD: 1 = every handle that rotates per pair, 0 (or anything else) = never.
+constexpr long long kFoldMinBlocks = 94;
+bool fold_chosen(const gsdr_demod *h, bool rot2, long long nhi) {
+    return rot2 && (h->sw.mfma_fold == 1 || (h->sw.mfma_fold < 0 && nhi >= kFoldMinBlocks));
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
@@ -579,16 +594,23 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const long long nhi = (pl.nk8 + 3) / 4;
         bool want = prec_pays(h, ngt_max, /*overlap=*/true);
         const bool mac3 = mac3_chosen(h, want, nhi);
-        const size_t img_n = (size_t)ngt_max * (size_t)nhi * (mac3 ? 768 : 512);   // uint4 per image set: 12 / 8 KiB per block
+        const bool fold = fold_chosen(h, rot2_chosen(h, mac3, nhi), nhi);
+        // uint4 per image set: 12 / 8 KiB per block, folded 16 KiB per pair of blocks
+        const size_t img_n = fold ? (size_t)ngt_max * (size_t)((nhi + 1) / 2) * 1024
+                                  : (size_t)ngt_max * (size_t)nhi * (mac3 ? 768 : 512);
         if (want && img_n * sizeof(uint4) > (size_t)8 << 30) want = false;
         for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, h->d_img[i].alloc(img_n));
         h->prec = want;
         h->mac3 = want && mac3;
         h->rot2 = rot2_chosen(h, h->mac3, nhi);
+        h->fold = fold_chosen(h, h->rot2, nhi);
         if (h->mac3) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
-            gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
+            if (h->fold)
+                gsdr::mfma_build_tables3f(pl, fmod, bfrag3, ptab3);
+            else
+                gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
             HIPCHK(h, h->d_bfrag3.upload(bfrag3));
             HIPCHK(h, h->d_ptab3.upload(ptab3));
         }
@@ -810,7 +832,8 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     gsdr::MfmaKernel kind = h->mf_kind;
     if (h->mac3) {
         // whatever the entry, the stream pattern or the row count: one arithmetic per handle
-        kind = h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3;
+        kind = h->fold ? gsdr::MfmaKernel::AsmRing16P3F
+                       : (h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3);
         a.img = h->d_img[hs];
         a.bfrag3 = h->d_bfrag3;
         a.ptab3 = h->d_ptab3;
@@ -2003,6 +2026,8 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"complex_mac_min_blocks\": " + std::to_string(kMac3MinBlocks);
     s += ", \"rotation_blocks\": " + std::to_string(h->mfma && h->mac3 && h->rot2 ? 2 : 1);
     s += ", \"rotation_min_blocks\": " + std::to_string(kRot2MinBlocks);
+    s += ", \"fold\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? 1 : 0);
+    s += ", \"fold_min_blocks\": " + std::to_string(kFoldMinBlocks);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"frame_average\": " + std::to_string(h->avg_k);
     s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";

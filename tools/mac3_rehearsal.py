@@ -13,10 +13,16 @@ own fp32 order (oracle/recipe_b.py, complex64) beside it; bound = max(1e-5, 3 x 
 one rotation per pair of blocks; the window padded with zero taps to whole pairs) beside the
 32-sample one, on the 60 dB comb at the three longest windows.
 
+--fold: the 64-sample arithmetic beside its folded form (phase from the centre of the span,
+P1 = sum (a_j + a_j')*c_j, P2 = sum (b_j - b_j')*d_j, P3 = sum (a_j+b_j)*(c_j+d_j) + (a_j'+b_j')*(c_j-d_j) over j < 32,
+j' = 63 - j; every operand one fp32 add, one rounding per sum), 60 dB comb at the three longest windows and the 40 dB
+comb at M 1000.
+
 Reads nothing but oracle/ and gpu_sdr_amd/source.py.
 
     python3 tools/mac3_rehearsal.py > profiles/mac3_rehearsal.log
     python3 tools/mac3_rehearsal.py --rot-span 64 > profiles/mac3r2_rehearsal.log
+    python3 tools/mac3_rehearsal.py --fold > profiles/fold_rehearsal.log
 """
 import os
 import sys
@@ -49,6 +55,13 @@ def gemm3(a, b):
     return (ah @ bh + ah @ bl + al @ bh).astype(f32)
 
 
+def split_sum(a, b):
+    """gemm3 without its rounding (a sum that goes on in the same accumulator)"""
+    ah, al = split(a)
+    bh, bl = split(b)
+    return ah @ bh + ah @ bl + al @ bh
+
+
 def fma(acc, p, k):
     return (acc.astype(f64) + p.astype(f64) * k.astype(f64)).astype(f32)
 
@@ -58,10 +71,12 @@ def phasor(ph, rate):
     return np.cos(ang), -np.sin(ang)
 
 
-def emulate(x, taps, freq, rate, M, F, products, span=32):
+def emulate(x, taps, freq, rate, M, F, products, span=32, fold=False):
     """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128.
-    span: samples per block sum and rotation (64: the pair rotation of section 4.1e, three products only)"""
+    span: samples per block sum and rotation (64: the pair rotation of section 4.1e, three products only);
+    fold: the 64-sample span folded about its centre (section 4.1f)"""
     assert span == 32 or products == 3
+    assert not fold or span == 64
     N, MF = len(freq), M * F
     nout = len(x) // M
     rows = np.arange(F - 1, nout)
@@ -86,10 +101,26 @@ def emulate(x, taps, freq, rate, M, F, products, span=32):
     lo = np.arange(span, dtype=np.int64)
     wr, wi = phasor((fm[None, :] * lo[:, None]) % rate, rate)            # [span][N]
     c, d = wr.astype(f32), wi.astype(f32)
+    if fold:
+        j = np.arange(32, dtype=np.int64)
+        ph2 = (fm[None, :] * (63 - 2 * j)[:, None]) % (2 * rate)          # w^(j - 31.5) = conj(w^(31.5 - j)), half samples
+        cc, dd = np.cos(np.pi * ph2 / rate), np.sin(np.pi * ph2 / rate)
     for blk in range(nhi):
         ab, bb = a[:, span * blk: span * blk + span], b[:, span * blk: span * blk + span]
         pr, pi = phasor((fm * ((blk * span) % rate)) % rate, rate)
-        if products == 4:
+        if fold:
+            aj, bj, ap, bp = ab[:, :32], bb[:, :32], ab[:, :31:-1], bb[:, :31:-1]
+            p1 = gemm3((aj + ap).astype(f32), cc.astype(f32))
+            p2 = gemm3((bj - bp).astype(f32), dd.astype(f32))
+            p3 = (split_sum((aj + bj).astype(f32), (cc + dd).astype(f32)) +
+                  split_sum((ap + bp).astype(f32), (cc - dd).astype(f32))).astype(f32)
+            ps2 = (fm * ((128 * blk + 63) % (2 * rate))) % (2 * rate)
+            pr, pi = np.cos(np.pi * ps2 / rate), -np.sin(np.pi * ps2 / rate)
+            prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
+            pm, pp = (pi - pr).astype(f32)[None, :], (pr + pi).astype(f32)[None, :]
+            accr = fma(fma(fma(accr, pp, p1), pm, p2), -pif, p3)
+            acci = fma(fma(fma(acci, pm, p1), -pp, p2), prf, p3)
+        elif products == 4:
             re = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([c, -d], axis=0)))
             im = (gemm3(np.concatenate([ab, bb], axis=1), np.concatenate([d, c], axis=0)))
             prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
@@ -148,7 +179,33 @@ def main_span(span):
               f"{errs[span].max():.3e} {(errs[span] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
 
 
+def main_fold():
+    N, rate, F = 64, 200_000_000, 4
+    print("span_dB  M  blocks | err32 (reference fp32 order) | 3 products, rotation per 64: worst err, worst err/bound | "
+          "folded: worst err, worst err/bound | median, max per-tone ratio folded/64")
+    for span_db, decims in ((60, (2000, 1000, 750)), (40, (1000,))):
+        for M in decims:
+            L = 200 * M
+            freq, x = comb(N, rate, L, span_db, np.random.default_rng(4242 + span_db))
+            ref = oracle.Direct(freq, rate, M, F, L)
+            taps = ref.taps()
+            yr = ref.process(x).astype(np.complex128)[F:]
+            y32 = recipe_b.Direct(freq, rate, M, F, L, acc=np.complex64).process(x).astype(np.complex128)[F:]
+            den = np.linalg.norm(yr, axis=0)
+            err32 = np.linalg.norm(y32 - yr, axis=0) / den
+            bound = np.maximum(1e-5, 3.0 * err32)
+            errs = {}
+            for fold in (False, True):
+                y = emulate(x, taps, freq, rate, M, F, 3, span=64, fold=fold)[1:]
+                errs[fold] = np.linalg.norm(y - yr, axis=0) / den
+            ratio = errs[True] / errs[False]
+            print(f"{span_db:3d} {M:5d} {(M * F + 31) // 32:4d} | {err32.max():.3e} | {errs[False].max():.3e} {(errs[False] / bound).max():.3f} | "
+                  f"{errs[True].max():.3e} {(errs[True] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
+
+
 def main():
+    if "--fold" in sys.argv:
+        return main_fold()
     if "--rot-span" in sys.argv:
         return main_span(int(sys.argv[sys.argv.index("--rot-span") + 1]))
     N, rate, F = 64, 200_000_000, 4
