@@ -44,6 +44,8 @@ struct Switches {
                                 // rotate their partial sums once per pair of blocks; 2: every three-product handle; else per block
     int mfma_fold = -1;         // GSDR_MFMA_FOLD, -1 unset: handles that rotate per pair and have a window of kFoldMinBlocks blocks or
                                 // more fold each 64-sample span about its centre (48 MFMAs per span for 72); 1: every such handle; else never
+    int mfma_fold_products = -1;    // GSDR_MFMA_FOLD_PRODUCTS, -1 unset: a folded handle sums the plain four products straight into Re and Im
+                                // (ddc_mfma_ring16p4f_kernel); 3: Gauss's three (ddc_mfma_ring16p3f_kernel); 4: the four
     int mfma_timing = 0;        // GSDR_MFMA_TIMING, 0: timing-only modes 1 - 3 (builds with -DGSDR_TIMING_BUILD only)
     bool noise_fft = true;      // GSDR_NOISE_FFT, 1: NOISE through the polyphase filter + FFT; 0: every bin a DDC tone
     bool tones_fft = true;      // GSDR_TONES_FFT, 1: TONES through filter + FFT + bin selection; 0: every bin a DDC tone
@@ -165,8 +167,9 @@ struct MfmaLaunch {
     float2 *out;
     const uint4 *img;          // AsmRing16P: [ngt][nhi] pre-converted ring-slot images of 8 KiB (ddc_convert_kernel);
                                // AsmRing16P3: of 12 KiB (ddc_convert3_kernel); AsmRing16P3F: [ngt][ceil(nhi/2)] of 16 KiB
-                               // (ddc_convert3f_kernel)
+                               // (ddc_convert3f_kernel); AsmRing16P4F: the same of ddc_convert4f_kernel
     const uint4 *bfrag3;       // AsmRing16P3 / AsmRing16P3R2: phasor images c, d-c, c+d of mfma_build_tables3, span 1 / 2
+                               // AsmRing16P3F: c, d, c+d, c-d of mfma_build_tables3f; AsmRing16P4F: c, d of mfma_build_tables4f
     const float4 *ptab3;       // AsmRing16P3: [ceil(nk8/4) + 1][NT32*32]  (Pr, Pi, Pr-Pi, Pr+Pi) of w_n^(hi*32);
                                // AsmRing16P3R2: [ceil(ceil(nk8/4) / 2) + 1][NT32*32] of w_n^(pair*64)
     MfmaShape sh;
@@ -188,6 +191,9 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
                         std::vector<float4> &ptab3);
 // the folded loop (AsmRing16P3F): images c, d, c+d, c-d of w^(j - 31.5), j < 32, and (Pr, Pi, Pi-Pr, Pr+Pi) of w_n^(64*span + 31.5)
 void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                         std::vector<float4> &ptab3);
+// the direct folded loop (AsmRing16P4F): images c, d of w^(j - 31.5), j < 32, and the span phasors of mfma_build_tables3f
+void mfma_build_tables4f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                          std::vector<float4> &ptab3);
 // The staging pass in front of the matrix-core kernels.  The logical stream of a call is T = [B | A]: A the new
 // buffer x[0 .. n), B what the previous call left in front of it (DIRECT: the raw-sample carry, read from the head
@@ -218,10 +224,11 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
 // operands, eight-wave workgroups); AsmRing16P3: the pre-converted loop with three real products per complex
 // multiply (chosen per handle, demod.cpp), AsmRing16P3R2: that loop rotating its partial sums once per pair of
 // blocks (tables of mfma_build_tables3 with span 2 in bfrag3 / ptab3), AsmRing16P3F: three products over 64-sample spans
-// folded about their centre (images of ddc_convert3f_kernel, tables of mfma_build_tables3f in bfrag3 / ptab3); AsmRing:
+// folded about their centre (images of ddc_convert3f_kernel, tables of mfma_build_tables3f in bfrag3 / ptab3), AsmRing16P4F: that fold with the plain four products (images of
+// ddc_convert4f_kernel, tables of mfma_build_tables4f); AsmRing:
 // round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled (TT, PK, W apply to it only; the assembly kernels are
 // TT = 1, PK = 32, W = 4).
-enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F };
+enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F };
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);
 const char *ddc_mfma_kernel_name(MfmaKernel kind);
 

@@ -38,6 +38,10 @@
 //   ddc_mfma_ring16p3f_kernel three products over 64-sample spans folded about their centre: four operand units of
 //                             K = 32 per span, 48 instead of 72 MFMAs (tools/gen_ddc_mfma_ring16p3f.py, fed by
 //                             ddc_convert3f_kernel; tests/test_gpu_fold.py; GSDR_MFMA_FOLD)
+//   ddc_mfma_ring16p4f_kernel the folded loop with the plain four products: the same four units of K = 32 and 48
+//                             MFMAs per span summed straight into Re and Im, 64 instead of 96 rotation FMAs
+//                             (tools/gen_ddc_mfma_ring16p4f.py, fed by ddc_convert4f_kernel;
+//                             tests/test_gpu_fold4.py; GSDR_MFMA_FOLD_PRODUCTS)
 //   ddc_mfma_ring16w8_kernel  the same loop for workgroups of eight waves
 //                             (tools/gen_ddc_mfma_ring16w8.py): single launches of one round
 //   ddc_mfma_ring_kernel      round 1's production kernel, the ring loop on v_mfma_f32_32x32x16_f16
@@ -59,6 +63,7 @@
 #include "ddc_mfma_ring16p3_gen.h"
 #include "ddc_mfma_ring16p3r2_gen.h"
 #include "ddc_mfma_ring16p3f_gen.h"
+#include "ddc_mfma_ring16p4f_gen.h"
 
 namespace gsdr {
 
@@ -1030,8 +1035,15 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
 // row 16*rh + (l & 15), j = 8*(l >> 4) .. +7.  a and b are the products of split_pair bit for bit, every U one fp32 add
 // or subtract of two of them (no contraction).  A window of an odd number of blocks ends in a half span: its partners
 // are exact zeros and nothing of the missing block is loaded (the pass reads what ddc_convert3_kernel reads).
+//
+// The direct fold (kDirect, ddc_convert4f_kernel; tools/gen_ddc_mfma_ring16p4f.py) folds the
+// plain four products instead:
+//     Re = sum a*c - sum b*d = sum_{j<32} (a_j + a_j')*c_j + (b_j' - b_j)*d_j
+//     Im = sum a*d + sum b*c = sum_{j<32} (a_j - a_j')*d_j + (b_j + b_j')*c_j
+// Same a, b, a', b', same piece layout; units V1 = a_j + a_j', V2 = b_j' - b_j, V3 = a_j - a_j', V4 = b_j + b_j'.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert3f_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
+template <bool kDirect>
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void convert_fold(const MfmaLaunch &a, uint4 *__restrict__ img, int nhi, int nspan) {
     const MfmaShape &sh = a.sh;
     const int l = threadIdx.x & 63, rh = threadIdx.x >> 6;
     const int r = 16 * rh + (l & 15), g = l >> 4;
@@ -1069,7 +1081,7 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
         const float pa = mul_legacy(xr[j], hs[j]), pb = mul_legacy(xi[j], hs[j]);
         // a half span: exact zeros, whatever the registers would multiply to
         const float qa = whole ? mul_legacy(yr[7 - j], gs[7 - j]) : 0.f, qb = whole ? mul_legacy(yi[7 - j], gs[7 - j]) : 0.f;
-        const float u[4] = {pa + qa, pb - qb, pa + pb, qa + qb};
+        const float u[4] = {pa + qa, kDirect ? qb - pb : pb - qb, kDirect ? pa - qa : pa + pb, kDirect ? pb + qb : qa + qb};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             _Float16 h, w;
@@ -1086,14 +1098,29 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
     }
 }
 
+__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert3f_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
+    convert_fold<false>(a, img, nhi, nspan);
+}
+
+__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert4f_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
+    convert_fold<true>(a, img, nhi, nspan);
+}
+
+// The direct fold is the same tile with another asm statement: 8 phasor images (c, d) per 32-tone tile instead of 16,
+// the same ring, slot size, operands, grid and epilogue.
+static_assert(GSDR_MFMA_RING16P4F_SLOT == GSDR_MFMA_RING16P3F_SLOT && GSDR_MFMA_RING16P4F_BYTES == GSDR_MFMA_RING16P3F_BYTES,
+              "one image format and one ring for both folded loops");
+
+template <bool kDirect>
 __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3f_tile(
     const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
+    constexpr unsigned kImages = kDirect ? 8 : 16;      // 1-KiB phasor images per 32-tone tile
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
     const int nspan = ((sh.nk8 + 3) / 4 + 1) / 2;
     const int lane = (int)(fresh_tid() & 63u);
     const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
-    const unsigned bo = (unsigned)tg * (16u * 1024u) + (unsigned)lane * 16u;      // 16 phasor images per 32-tone tile
+    const unsigned bo = (unsigned)tg * (kImages * 1024u) + (unsigned)lane * 16u;
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
     const unsigned rd16 = lds_base + (unsigned)lane * 16u;
     // this wave copies pieces 4*wave .. 4*wave + 3 of every image
@@ -1102,13 +1129,16 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
     const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nspan * (GSDR_MFMA_RING16P3F_SLOT / 16)),
                              ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
-    asm volatile(GSDR_MFMA_RING16P3F_TEXT
-                 :
-                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [io3] "v"(io3), [po] "v"(po), [bo] "v"(bo),
-                   [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),
-                   GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),
-                   [nhi] GSDR_SGPR(nspan)
-                 : GSDR_MFMA_RING16P3F_CLOBBERS);
+#define GSDR_RING16P3F_OPERANDS                                                                                    \
+    [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [io3] "v"(io3), [po] "v"(po), [bo] "v"(bo),                    \
+        [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),                 \
+        GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),                 \
+        [nhi] GSDR_SGPR(nspan)
+    if constexpr (kDirect)
+        asm volatile(GSDR_MFMA_RING16P4F_TEXT : : GSDR_RING16P3F_OPERANDS : GSDR_MFMA_RING16P4F_CLOBBERS);
+    else
+        asm volatile(GSDR_MFMA_RING16P3F_TEXT : : GSDR_RING16P3F_OPERANDS : GSDR_MFMA_RING16P3F_CLOBBERS);
+#undef GSDR_RING16P3F_OPERANDS
     if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
 }
 
@@ -1127,7 +1157,25 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     const int tg_raw = (q % sh.ntq) * W + wave;
     const bool active = tg_raw < sh.ntg;
     const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3f_tile(a, lds, gt0, tg, wave, active);
+    ring16p3f_tile<false>(a, lds, gt0, tg, wave, active);
+}
+
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p4f_kernel(
+    const MfmaLaunch a) {
+    constexpr int W = 4;
+    // ring (4 slots of 16 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P4F_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P4F_BYTES >= 4 * 8192, "the accumulators fit");
+    static_assert(2 * GSDR_MFMA_RING16P4F_BYTES <= 160 * 1024, "two workgroups per compute unit");
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int gt0 = (q / sh.ntq) * 8 + xcd;
+    if (gt0 >= sh.ngt) return;
+    const int tg_raw = (q % sh.ntq) * W + wave;
+    const bool active = tg_raw < sh.ntg;
+    const int tg = active ? tg_raw : sh.ntg - 1;
+    ring16p3f_tile<true>(a, lds, gt0, tg, wave, active);
 }
 
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
@@ -1441,6 +1489,29 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
         }
 }
 
+// w^(ph2 / 2), ph2 in half samples; host_phasor's sign: w = exp(-2 pi i / rate)
+static void half_phasor(unsigned rate, unsigned long long ph2, double &re, double &im) {
+    const double ang = M_PI * ((double)ph2 / (double)rate);
+    re = std::cos(ang);
+    im = -std::sin(ang);
+}
+
+// Span phasors of the folded loops: per (span, tone) the phasor of the span's centre w_n^(64*span + 31.5) as
+// (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.
+static void fold_span_phasors(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<float4> &ptab3) {
+    const int Np = pl.ntg * pl.TT * 32;
+    const unsigned long long rate2 = 2ULL * pl.rate;
+    const int nrow = ((pl.nk8 + 3) / 4 + 1) / 2;
+    ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int row = 0; row < nrow; ++row)
+        for (int n = 0; n < Np; ++n) {
+            const unsigned long long t2 = (128ULL * (unsigned long long)row + 63ULL) % rate2;
+            double re, im;
+            half_phasor(pl.rate, (unsigned long long)(((unsigned __int128)fmod[n] * t2) % rate2), re, im);
+            ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(im - re), (float)(re + im));
+        }
+}
+
 // Tables of the folded three-product loop (ddc_mfma_ring16p3f_kernel).  Per 32-tone tile 16 B
 // images f = (unit*2 + th)*2 + sp of c_j, d_j, c_j + d_j, c_j - d_j, j < 32, where c_j + i*d_j = w^(j - 31.5): formed in
 // double from the exact integer phase in half samples (mod 2*rate), rounded once, split hi/lo; lane l holds tone
@@ -1448,14 +1519,8 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
 // w_n^(64*span + 31.5) as (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.
 void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                          std::vector<float4> &ptab3) {
-    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
+    const int tiles = pl.ntg * pl.TT;
     const unsigned long long rate2 = 2ULL * pl.rate;
-    // w^(ph2 / 2), ph2 in half samples; host_phasor's sign: w = exp(-2 pi i / rate)
-    auto half_phasor = [&](unsigned long long ph2, double &re, double &im) {
-        const double ang = M_PI * ((double)ph2 / (double)pl.rate);
-        re = std::cos(ang);
-        im = -std::sin(ang);
-    };
     bfrag3.assign((size_t)tiles * 16 * 64, uint4{0, 0, 0, 0});
     for (int T = 0; T < tiles; ++T)
         for (int th = 0; th < 2; ++th)
@@ -1466,7 +1531,7 @@ void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, 
                     const int j = 8 * (lane >> 4) + jj;
                     // t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
                     double wr, wi;
-                    half_phasor((fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
+                    half_phasor(pl.rate, (fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
                     const double c = wr, d = -wi;
                     const float v[4] = {(float)c, (float)d, (float)(c + d), (float)(c - d)};
                     for (int u = 0; u < 4; ++u) {
@@ -1482,15 +1547,43 @@ void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, 
                         bfrag3[((size_t)T * 16 + (u * 2 + th) * 2 + sp) * 64 + lane] = w;
                     }
             }
-    const int nrow = ((pl.nk8 + 3) / 4 + 1) / 2;
-    ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int row = 0; row < nrow; ++row)
-        for (int n = 0; n < Np; ++n) {
-            const unsigned long long t2 = (128ULL * (unsigned long long)row + 63ULL) % rate2;
-            double re, im;
-            half_phasor((unsigned long long)(((unsigned __int128)fmod[n] * t2) % rate2), re, im);
-            ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(im - re), (float)(re + im));
-        }
+    fold_span_phasors(pl, fmod, ptab3);
+}
+
+// Tables of the direct folded loop (ddc_mfma_ring16p4f_kernel).  Per 32-tone tile 8 B images
+// f = (u01*2 + th)*2 + sp of c_j (u01 = 0) and d_j (1), j < 32, c_j + i*d_j = w^(j - 31.5), formed, rounded and split as
+// in mfma_build_tables3f; lane l holds tone 16*th + (l & 15), element jj <-> j = 8*(l >> 4) + jj.  The span phasors are
+// those of mfma_build_tables3f (the loop reads Pr and Pi of a row).
+void mfma_build_tables4f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                         std::vector<float4> &ptab3) {
+    const int tiles = pl.ntg * pl.TT;
+    const unsigned long long rate2 = 2ULL * pl.rate;
+    bfrag3.assign((size_t)tiles * 8 * 64, uint4{0, 0, 0, 0});
+    for (int T = 0; T < tiles; ++T)
+        for (int th = 0; th < 2; ++th)
+            for (int lane = 0; lane < 64; ++lane) {
+                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
+                unsigned short img[2][2][8];
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int j = 8 * (lane >> 4) + jj;
+                    // t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
+                    double wr, wi;
+                    half_phasor(pl.rate, (fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
+                    const float v[2] = {(float)wr, (float)-wi};
+                    for (int u = 0; u < 2; ++u) {
+                        const unsigned short hb = to_half_bits(v[u]);
+                        img[u][0][jj] = hb;
+                        img[u][1][jj] = to_half_bits(v[u] - from_half_bits(hb));
+                    }
+                }
+                for (int u = 0; u < 2; ++u)
+                    for (int sp = 0; sp < 2; ++sp) {
+                        uint4 w;
+                        __builtin_memcpy(&w, img[u][sp], 16);
+                        bfrag3[((size_t)T * 8 + (u * 2 + th) * 2 + sp) * 64 + lane] = w;
+                    }
+            }
+    fold_span_phasors(pl, fmod, ptab3);
 }
 
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
@@ -1566,19 +1659,27 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
                 hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3(grid), dim3(256), 0, st, a);
             return hipGetLastError();
         }
-        case MfmaKernel::AsmRing16P3F: {
+        case MfmaKernel::AsmRing16P3F:
+        case MfmaKernel::AsmRing16P4F: {
             // the folded conversion pass and its loop (a.img: ngt * nspan images of 16 KiB; a.bfrag3 / a.ptab3: the
-            // tables of mfma_build_tables3f)
+            // tables of mfma_build_tables3f, or of mfma_build_tables4f for the direct fold)
+            const bool direct = kind == MfmaKernel::AsmRing16P4F;
             if (!a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
             const int nhi = (sh.nk8 + 3) / 4, nspan = (nhi + 1) / 2;
             const long long cgrid = (long long)sh.ngt * nspan;
             grid = ring_grid(sh.ngt, sh.ntq, 1);
             if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
-            hipLaunchKernelGGL(ddc_convert3f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, const_cast<uint4 *>(a.img),
-                               nhi, nspan);
+            uint4 *img = const_cast<uint4 *>(a.img);
+            if (direct)
+                hipLaunchKernelGGL(ddc_convert4f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nspan);
+            else
+                hipLaunchKernelGGL(ddc_convert3f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nspan);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(ddc_mfma_ring16p3f_kernel, dim3(grid), dim3(256), 0, st, a);
+            if (direct)
+                hipLaunchKernelGGL(ddc_mfma_ring16p4f_kernel, dim3(grid), dim3(256), 0, st, a);
+            else
+                hipLaunchKernelGGL(ddc_mfma_ring16p3f_kernel, dim3(grid), dim3(256), 0, st, a);
             return hipGetLastError();
         }
         case MfmaKernel::AsmRing16W8:
@@ -1605,7 +1706,8 @@ const char *ddc_mfma_kernel_name(MfmaKernel kind) {
         case MfmaKernel::AsmRing16P:
         case MfmaKernel::AsmRing16P3:
         case MfmaKernel::AsmRing16P3R2:
-        case MfmaKernel::AsmRing16P3F: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
+        case MfmaKernel::AsmRing16P3F:
+        case MfmaKernel::AsmRing16P4F: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
         case MfmaKernel::AsmRing16W8: return "ddc_mfma_ring16w8_kernel";
         case MfmaKernel::AsmRing16: return "ddc_mfma_ring16_kernel";
         case MfmaKernel::AsmRing: return "ddc_mfma_ring_kernel";

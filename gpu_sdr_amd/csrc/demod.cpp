@@ -84,6 +84,7 @@ gsdr::Switches gsdr::read_switches() {
     s.mfma_3m = env("GSDR_MFMA_3M", -1);
     s.mfma_3m_rot = env("GSDR_MFMA_3M_ROT", -1);
     s.mfma_fold = env("GSDR_MFMA_FOLD", -1);
+    s.mfma_fold_products = env("GSDR_MFMA_FOLD_PRODUCTS", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -185,6 +186,8 @@ struct gsdr_demod {
     bool mac3 = false;
     bool rot2 = false;                 // ... through ddc_mfma_ring16p3r2_kernel: one rotation per pair of blocks (section 4.1e)
     bool fold = false;                 // ... through ddc_mfma_ring16p3f_kernel: each pair folded about its centre (section 4.1f)
+    int fold_products = 0;             // a folded handle's arithmetic: 3 = Gauss (ddc_mfma_ring16p3f_kernel), 4 = the plain four
+                                       // products (ddc_convert4f_kernel + ddc_mfma_ring16p4f_kernel, section 4.1g); 0: not folded
     gsdr::DevBuf<uint4> d_bfrag3;
     gsdr::DevBuf<float4> d_ptab3;
     gsdr::DevBuf<uint4> d_bfrag;
@@ -501,6 +504,19 @@ bool fold_chosen(const gsdr_demod *h, bool rot2, long long nhi) {
     return rot2 && (h->sw.mfma_fold == 1 || (h->sw.mfma_fold < 0 && nhi >= kFoldMinBlocks));
 }
 
+// The arithmetic of a folded handle.  The plain four products fold completely -- the same
+// four units of K = 32 and 48 MFMAs per span as the Gauss fold, whose third sum has no symmetry -- and need two
+// product tile sets, the images of c and d only and 64 rotation FMAs per span instead of 96.  complex_mac,
+// rotation_blocks and fold in describe() name the rule that selected the handle (mac3_chosen, rot2_chosen,
+// fold_chosen: unchanged); fold_products names what it computes.  GSDR_MFMA_FOLD_PRODUCTS: 3 = the Gauss fold, 4 = the
+// direct fold, unset = kFoldProductsDefault.
+constexpr int kFoldProductsDefault = 4;
+int fold_products_chosen(const gsdr_demod *h, bool fold) {
+    if (!fold) return 0;
+    const int p = h->sw.mfma_fold_products;
+    return p == 3 || p == 4 ? p : kFoldProductsDefault;
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
@@ -604,10 +620,13 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         h->mac3 = want && mac3;
         h->rot2 = rot2_chosen(h, h->mac3, nhi);
         h->fold = fold_chosen(h, h->rot2, nhi);
+        h->fold_products = fold_products_chosen(h, h->fold);
         if (h->mac3) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
-            if (h->fold)
+            if (h->fold_products == 4)
+                gsdr::mfma_build_tables4f(pl, fmod, bfrag3, ptab3);
+            else if (h->fold)
                 gsdr::mfma_build_tables3f(pl, fmod, bfrag3, ptab3);
             else
                 gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
@@ -832,7 +851,7 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     gsdr::MfmaKernel kind = h->mf_kind;
     if (h->mac3) {
         // whatever the entry, the stream pattern or the row count: one arithmetic per handle
-        kind = h->fold ? gsdr::MfmaKernel::AsmRing16P3F
+        kind = h->fold ? (h->fold_products == 4 ? gsdr::MfmaKernel::AsmRing16P4F : gsdr::MfmaKernel::AsmRing16P3F)
                        : (h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3);
         a.img = h->d_img[hs];
         a.bfrag3 = h->d_bfrag3;
@@ -2028,6 +2047,7 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"rotation_min_blocks\": " + std::to_string(kRot2MinBlocks);
     s += ", \"fold\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? 1 : 0);
     s += ", \"fold_min_blocks\": " + std::to_string(kFoldMinBlocks);
+    s += ", \"fold_products\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? h->fold_products : 0);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"frame_average\": " + std::to_string(h->avg_k);
     s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";

@@ -18,11 +18,16 @@ P1 = sum (a_j + a_j')*c_j, P2 = sum (b_j - b_j')*d_j, P3 = sum (a_j+b_j)*(c_j+d_
 j' = 63 - j; every operand one fp32 add, one rounding per sum), 60 dB comb at the three longest windows and the 40 dB
 comb at M 1000.
 
+--fold4: the folded three-product arithmetic beside the folded plain four products (DESIGN.md section 4.1g:
+Re = sum (a_j + a_j')*c_j + (b_j' - b_j)*d_j, Im = sum (a_j - a_j')*d_j + (b_j + b_j')*c_j over j < 32, two units summed
+into one fp32 result, acc += P*(Re + i*Im)), 60 dB comb at 250, 125, 94, 63 and 32 blocks and the 40 dB comb at M 1000.
+
 Reads nothing but oracle/ and gpu_sdr_amd/source.py.
 
     python3 tools/mac3_rehearsal.py > profiles/mac3_rehearsal.log
     python3 tools/mac3_rehearsal.py --rot-span 64 > profiles/mac3r2_rehearsal.log
     python3 tools/mac3_rehearsal.py --fold > profiles/fold_rehearsal.log
+    python3 tools/mac3_rehearsal.py --fold4 > profiles/fold4_rehearsal.log
 """
 import os
 import sys
@@ -74,8 +79,8 @@ def phasor(ph, rate):
 def emulate(x, taps, freq, rate, M, F, products, span=32, fold=False):
     """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128.
     span: samples per block sum and rotation (64: the pair rotation of section 4.1e, three products only);
-    fold: the 64-sample span folded about its centre (section 4.1f)"""
-    assert span == 32 or products == 3
+    fold: the 64-sample span folded about its centre (section 4.1f; products 4: the direct fold of section 4.1g)"""
+    assert span == 32 or products == 3 or fold
     assert not fold or span == 64
     N, MF = len(freq), M * F
     nout = len(x) // M
@@ -108,7 +113,16 @@ def emulate(x, taps, freq, rate, M, F, products, span=32, fold=False):
     for blk in range(nhi):
         ab, bb = a[:, span * blk: span * blk + span], b[:, span * blk: span * blk + span]
         pr, pi = phasor((fm * ((blk * span) % rate)) % rate, rate)
-        if fold:
+        if fold and products == 4:
+            aj, bj, ap, bp = ab[:, :32], bb[:, :32], ab[:, :31:-1], bb[:, :31:-1]
+            re = (split_sum((aj + ap).astype(f32), cc.astype(f32)) + split_sum((bp - bj).astype(f32), dd.astype(f32))).astype(f32)
+            im = (split_sum((aj - ap).astype(f32), dd.astype(f32)) + split_sum((bj + bp).astype(f32), cc.astype(f32))).astype(f32)
+            ps2 = (fm * ((128 * blk + 63) % (2 * rate))) % (2 * rate)
+            pr, pi = np.cos(np.pi * ps2 / rate), -np.sin(np.pi * ps2 / rate)
+            prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
+            accr = fma(fma(accr, prf, re), -pif, im)
+            acci = fma(fma(acci, pif, re), prf, im)
+        elif fold:
             aj, bj, ap, bp = ab[:, :32], bb[:, :32], ab[:, :31:-1], bb[:, :31:-1]
             p1 = gemm3((aj + ap).astype(f32), cc.astype(f32))
             p2 = gemm3((bj - bp).astype(f32), dd.astype(f32))
@@ -203,7 +217,33 @@ def main_fold():
                   f"{errs[True].max():.3e} {(errs[True] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
 
 
+def main_fold4():
+    N, rate, F = 64, 200_000_000, 4
+    print("span_dB  M  blocks | err32 (reference fp32 order) | Gauss fold: worst err, worst err/bound | "
+          "direct fold: worst err, worst err/bound | median, max per-tone ratio direct/Gauss")
+    for span_db, decims in ((60, (2000, 1000, 750, 500, 256)), (40, (1000,))):
+        for M in decims:
+            L = 200 * M
+            freq, x = comb(N, rate, L, span_db, np.random.default_rng(4242 + span_db))
+            ref = oracle.Direct(freq, rate, M, F, L)
+            taps = ref.taps()
+            yr = ref.process(x).astype(np.complex128)[F:]
+            y32 = recipe_b.Direct(freq, rate, M, F, L, acc=np.complex64).process(x).astype(np.complex128)[F:]
+            den = np.linalg.norm(yr, axis=0)
+            err32 = np.linalg.norm(y32 - yr, axis=0) / den
+            bound = np.maximum(1e-5, 3.0 * err32)
+            errs = {}
+            for products in (3, 4):
+                y = emulate(x, taps, freq, rate, M, F, products, span=64, fold=True)[1:]
+                errs[products] = np.linalg.norm(y - yr, axis=0) / den
+            ratio = errs[4] / errs[3]
+            print(f"{span_db:3d} {M:5d} {(M * F + 31) // 32:4d} | {err32.max():.3e} | {errs[3].max():.3e} {(errs[3] / bound).max():.3f} | "
+                  f"{errs[4].max():.3e} {(errs[4] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
+
+
 def main():
+    if "--fold4" in sys.argv:
+        return main_fold4()
     if "--fold" in sys.argv:
         return main_fold()
     if "--rot-span" in sys.argv:
