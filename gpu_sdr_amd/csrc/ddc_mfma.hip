@@ -877,20 +877,27 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ri
     if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
 }
 
+// The grid of the five pre-converted kernels, XCD-major: workgroup blockIdx.x takes row tile gt0 of XCD blockIdx.x & 7
+// and four 32-tone tiles, one per wave; it leaves where there is no such row tile (ring_grid rounds the row tiles up to
+// whole eights).  A wave past the last tone tile (not `active`) runs the loop on a copy of that tile -- it keeps the
+// barriers -- and stores nothing.  Declares wave, gt0, tg, active.  A macro: through a function's reference arguments
+// the compiler schedules the scalar code of all five kernels differently.
+#define GSDR_RINGP_GRID_DECODE(a)                                               \
+    const MfmaShape &sh = (a).sh;                                               \
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   \
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;                        \
+    const int gt0 = (q / sh.ntq) * 8 + xcd;                                     \
+    if (gt0 >= sh.ngt) return;                                                  \
+    const int tg_raw = (q % sh.ntq) * 4 + wave;                                 \
+    const bool active = tg_raw < sh.ntg;                                        \
+    const int tg = active ? tg_raw : sh.ntg - 1
+
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p_kernel(
     const MfmaLaunch a) {
-    constexpr int W = 4;
     // ring (4 slots of 8 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
     __shared__ uint4 lds[2048];
     static_assert(sizeof(uint4) * 2048 >= GSDR_MFMA_RING16P_BYTES, "ring fits");
-    const MfmaShape &sh = a.sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int gt0 = (q / sh.ntq) * 8 + xcd;
-    if (gt0 >= sh.ngt) return;
-    const int tg_raw = (q % sh.ntq) * W + wave;
-    const bool active = tg_raw < sh.ntg;
-    const int tg = active ? tg_raw : sh.ntg - 1;
+    GSDR_RINGP_GRID_DECODE(a);
     ring16p_tile(a, lds, gt0, 1, tg, wave, active);
 }
 
@@ -958,69 +965,77 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
 // mfma_build_tables3 for a span of one block or of two.
 static_assert(GSDR_MFMA_RING16P3R2_SLOT == GSDR_MFMA_RING16P3_SLOT, "one image format for both three-product loops");
 
-template <bool kPairs>
-__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3_tile(
+// Of the two folded loops (further down) the direct one is the same tile with another asm statement: 8 phasor images
+// (c, d) per 32-tone tile instead of 16, the same ring, slot size, operands, grid and epilogue.
+static_assert(GSDR_MFMA_RING16P4F_SLOT == GSDR_MFMA_RING16P3F_SLOT && GSDR_MFMA_RING16P4F_BYTES == GSDR_MFMA_RING16P3F_BYTES,
+              "one image format and one ring for both folded loops");
+
+// The tile of the four product loops (generated over one frame, tools/ddc_mfma_pframe.py, which names the operands):
+// one set of operands around one of four asm statements.  The three-product loops
+// take an image per block (slots of 12 KiB, three 1-KiB pieces per wave), the folded ones an image per span of two
+// blocks (16 KiB, four pieces: one operand more, io3).
+template <MfmaKernel kLoop>
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16px_tile(
     const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
-    constexpr int KS = 4;
-    constexpr unsigned kImages = kPairs ? 24 : 12;      // 1-KiB phasor images per 32-tone tile
+    constexpr bool kFold = kLoop == MfmaKernel::AsmRing16P3F || kLoop == MfmaKernel::AsmRing16P4F;
+    constexpr unsigned kPieces = kFold ? 4 : 3;
+    constexpr unsigned kSlot = kFold ? GSDR_MFMA_RING16P3F_SLOT : GSDR_MFMA_RING16P3_SLOT;
+    static_assert(kSlot == 4 * kPieces * 1024, "four waves copy an image");
+    // 1-KiB phasor images per 32-tone tile
+    constexpr unsigned kImages = kLoop == MfmaKernel::AsmRing16P3 ? 12 : kLoop == MfmaKernel::AsmRing16P3R2 ? 24 : kLoop == MfmaKernel::AsmRing16P3F ? 16 : 8;
     const MfmaShape &sh = a.sh;
     const int Np = sh.NT32 * 32;
-    const int nhi = (sh.nk8 + KS - 1) / KS;
+    const int nblk = (sh.nk8 + 3) / 4, nhi = kFold ? (nblk + 1) / 2 : nblk;      // images of a row tile
     const int lane = (int)(fresh_tid() & 63u);
     const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
     const unsigned bo = (unsigned)tg * (kImages * 1024u) + (unsigned)lane * 16u;
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
     const unsigned rd16 = lds_base + (unsigned)lane * 16u;
-    // this wave copies pieces 3*wave .. 3*wave + 2 of every image
-    const unsigned io0 = (unsigned)wave * 3072u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u;
-    const unsigned wrs = lds_base + (unsigned)wave * 3072u;
+    // this wave copies pieces kPieces*wave .. kPieces*wave + kPieces - 1 of every image
+    const unsigned io0 = (unsigned)wave * (kPieces * 1024u) + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u;
+    [[maybe_unused]] const unsigned io3 = io0 + 3072u;
+    const unsigned wrs = lds_base + (unsigned)wave * (kPieces * 1024u);
     const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
-    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P3_SLOT / 16)),
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (kSlot / 16)),
                              ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
-#define GSDR_RING16P3_OPERANDS                                                                                     \
-    [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [po] "v"(po), [bo] "v"(bo), [lane16] "v"(rd16),                \
-        [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs), GSDR_SGPR_PAIR(pp, ppb),            \
-        GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u), [nhi] GSDR_SGPR(nhi)
-    if constexpr (kPairs)
-        asm volatile(GSDR_MFMA_RING16P3R2_TEXT : : GSDR_RING16P3_OPERANDS : GSDR_MFMA_RING16P3R2_CLOBBERS);
+#define GSDR_RINGPX_IO3 [io3] "v"(io3),
+#define GSDR_RINGPX_ASM(LOOP, IO3)                                                                                 \
+    asm volatile(GSDR_MFMA_##LOOP##_TEXT                                                                           \
+                 :                                                                                                 \
+                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), IO3 [po] "v"(po), [bo] "v"(bo),                 \
+                   [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),      \
+                   GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),      \
+                   [nhi] GSDR_SGPR(nhi)                                                                            \
+                 : GSDR_MFMA_##LOOP##_CLOBBERS)
+    if constexpr (kLoop == MfmaKernel::AsmRing16P3)
+        GSDR_RINGPX_ASM(RING16P3, );
+    else if constexpr (kLoop == MfmaKernel::AsmRing16P3R2)
+        GSDR_RINGPX_ASM(RING16P3R2, );
+    else if constexpr (kLoop == MfmaKernel::AsmRing16P3F)
+        GSDR_RINGPX_ASM(RING16P3F, GSDR_RINGPX_IO3);
     else
-        asm volatile(GSDR_MFMA_RING16P3_TEXT : : GSDR_RING16P3_OPERANDS : GSDR_MFMA_RING16P3_CLOBBERS);
-#undef GSDR_RING16P3_OPERANDS
+        GSDR_RINGPX_ASM(RING16P4F, GSDR_RINGPX_IO3);
+#undef GSDR_RINGPX_ASM
+#undef GSDR_RINGPX_IO3
     if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3_kernel(
     const MfmaLaunch a) {
-    constexpr int W = 4;
     // ring (4 slots of 12 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
     __shared__ uint4 lds[GSDR_MFMA_RING16P3_BYTES / 16];
     static_assert(GSDR_MFMA_RING16P3_BYTES >= 4 * 8192, "the accumulators fit");
-    const MfmaShape &sh = a.sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int gt0 = (q / sh.ntq) * 8 + xcd;
-    if (gt0 >= sh.ngt) return;
-    const int tg_raw = (q % sh.ntq) * W + wave;
-    const bool active = tg_raw < sh.ntg;
-    const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3_tile<false>(a, lds, gt0, tg, wave, active);
+    GSDR_RINGP_GRID_DECODE(a);
+    ring16px_tile<MfmaKernel::AsmRing16P3>(a, lds, gt0, tg, wave, active);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3r2_kernel(
     const MfmaLaunch a) {
-    constexpr int W = 4;
     // ring (4 slots of 12 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
     __shared__ uint4 lds[GSDR_MFMA_RING16P3R2_BYTES / 16];
     static_assert(GSDR_MFMA_RING16P3R2_BYTES >= 4 * 8192, "the accumulators fit");
-    const MfmaShape &sh = a.sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int gt0 = (q / sh.ntq) * 8 + xcd;
-    if (gt0 >= sh.ngt) return;
-    const int tg_raw = (q % sh.ntq) * W + wave;
-    const bool active = tg_raw < sh.ntg;
-    const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3_tile<true>(a, lds, gt0, tg, wave, active);
+    GSDR_RINGP_GRID_DECODE(a);
+    ring16px_tile<MfmaKernel::AsmRing16P3R2>(a, lds, gt0, tg, wave, active);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1106,76 +1121,24 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
     convert_fold<true>(a, img, nhi, nspan);
 }
 
-// The direct fold is the same tile with another asm statement: 8 phasor images (c, d) per 32-tone tile instead of 16,
-// the same ring, slot size, operands, grid and epilogue.
-static_assert(GSDR_MFMA_RING16P4F_SLOT == GSDR_MFMA_RING16P3F_SLOT && GSDR_MFMA_RING16P4F_BYTES == GSDR_MFMA_RING16P3F_BYTES,
-              "one image format and one ring for both folded loops");
-
-template <bool kDirect>
-__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void ring16p3f_tile(
-    const MfmaLaunch &a, uint4 *lds, int gt, int tg, int wave, bool active) {
-    constexpr unsigned kImages = kDirect ? 8 : 16;      // 1-KiB phasor images per 32-tone tile
-    const MfmaShape &sh = a.sh;
-    const int Np = sh.NT32 * 32;
-    const int nspan = ((sh.nk8 + 3) / 4 + 1) / 2;
-    const int lane = (int)(fresh_tid() & 63u);
-    const unsigned po = (unsigned)(tg * 32 + (lane & 15)) * 16u;
-    const unsigned bo = (unsigned)tg * (kImages * 1024u) + (unsigned)lane * 16u;
-    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
-    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
-    // this wave copies pieces 4*wave .. 4*wave + 3 of every image
-    const unsigned io0 = (unsigned)wave * 4096u + (unsigned)lane * 16u, io1 = io0 + 1024u, io2 = io0 + 2048u, io3 = io0 + 3072u;
-    const unsigned wrs = lds_base + (unsigned)wave * 4096u;
-    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
-    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nspan * (GSDR_MFMA_RING16P3F_SLOT / 16)),
-                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
-#define GSDR_RING16P3F_OPERANDS                                                                                    \
-    [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [io3] "v"(io3), [po] "v"(po), [bo] "v"(bo),                    \
-        [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),                 \
-        GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),                 \
-        [nhi] GSDR_SGPR(nspan)
-    if constexpr (kDirect)
-        asm volatile(GSDR_MFMA_RING16P4F_TEXT : : GSDR_RING16P3F_OPERANDS : GSDR_MFMA_RING16P4F_CLOBBERS);
-    else
-        asm volatile(GSDR_MFMA_RING16P3F_TEXT : : GSDR_RING16P3F_OPERANDS : GSDR_MFMA_RING16P3F_CLOBBERS);
-#undef GSDR_RING16P3F_OPERANDS
-    if (active) ring16_epilogue(a, lds, gt, tg, wave, (int)(fresh_tid() & 63u), kScaleFromTable);
-}
-
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3f_kernel(
     const MfmaLaunch a) {
-    constexpr int W = 4;
     // ring (4 slots of 16 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
     __shared__ uint4 lds[GSDR_MFMA_RING16P3F_BYTES / 16];
     static_assert(GSDR_MFMA_RING16P3F_BYTES >= 4 * 8192, "the accumulators fit");
     static_assert(2 * GSDR_MFMA_RING16P3F_BYTES <= 160 * 1024, "two workgroups per compute unit");
-    const MfmaShape &sh = a.sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int gt0 = (q / sh.ntq) * 8 + xcd;
-    if (gt0 >= sh.ngt) return;
-    const int tg_raw = (q % sh.ntq) * W + wave;
-    const bool active = tg_raw < sh.ntg;
-    const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3f_tile<false>(a, lds, gt0, tg, wave, active);
+    GSDR_RINGP_GRID_DECODE(a);
+    ring16px_tile<MfmaKernel::AsmRing16P3F>(a, lds, gt0, tg, wave, active);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p4f_kernel(
     const MfmaLaunch a) {
-    constexpr int W = 4;
     // ring (4 slots of 16 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
     __shared__ uint4 lds[GSDR_MFMA_RING16P4F_BYTES / 16];
     static_assert(GSDR_MFMA_RING16P4F_BYTES >= 4 * 8192, "the accumulators fit");
     static_assert(2 * GSDR_MFMA_RING16P4F_BYTES <= 160 * 1024, "two workgroups per compute unit");
-    const MfmaShape &sh = a.sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int gt0 = (q / sh.ntq) * 8 + xcd;
-    if (gt0 >= sh.ngt) return;
-    const int tg_raw = (q % sh.ntq) * W + wave;
-    const bool active = tg_raw < sh.ntg;
-    const int tg = active ? tg_raw : sh.ntg - 1;
-    ring16p3f_tile<true>(a, lds, gt0, tg, wave, active);
+    GSDR_RINGP_GRID_DECODE(a);
+    ring16px_tile<MfmaKernel::AsmRing16P4F>(a, lds, gt0, tg, wave, active);
 }
 
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
@@ -1442,43 +1405,61 @@ void mfma_build_tables(const MfmaPlan &pl, const std::vector<unsigned> &fmod_in,
     for (int t = 0; t < pl.MF; ++t) taps[t] = std::ldexp(window[t], -eh);
 }
 
-// Tables of the three-product loops.  `span`: the blocks of 32 samples the loop rotates at a time, 1
-// (ddc_mfma_ring16p3_kernel) or 2 (ddc_mfma_ring16p3r2_kernel).  Per 32-tone tile 12 * span B images
-// f = half*12 + (comp*2 + th)*2 + sp of c, (d-c), (c+d) -- w = c + i*d, formed in double, rounded once, split hi/lo;
-// lane l holds tone 16*th + (l & 15), element j <-> sample 32*half + 8*(l >> 4) + j of the span -- and per (span, tone)
-// the phasor w_n^(32*span*row) as (Pr, Pi, Pr-Pi, Pr+Pi).  One row more than there are spans: the loop loads the
-// phasors of a span while it computes the one before.
-void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
-                        std::vector<float4> &ptab3) {
-    const int tiles = pl.ntg * pl.TT, Np = tiles * 32;
-    const unsigned rate = pl.rate;
-    const int nimg = 12 * span;
+// w^(ph2 / 2), ph2 in half samples; host_phasor's sign: w = exp(-2 pi i / rate)
+static void half_phasor(unsigned rate, unsigned long long ph2, double &re, double &im) {
+    const double ang = M_PI * ((double)ph2 / (double)rate);
+    re = std::cos(ang);
+    im = -std::sin(ang);
+}
+
+// B images of the product loops: per 32-tone tile `halves` groups of 4 * NV images f = half*4*NV + (c*2 + th)*2 + sp.
+// values(fm, s, v) gives the NV quantities v[c] of the tone of frequency word fm at sample s = 32*half + j of the span,
+// each formed in double and rounded once; here every one is split hi/lo into fp16 (sp 0, 1), eight of a lane packed
+// into a uint4: lane l holds tone 16*th + (l & 15), element jj <-> j = 8*(l >> 4) + jj.
+template <int NV, class Values>
+static void build_images3(const MfmaPlan &pl, const std::vector<unsigned> &fmod, int halves, std::vector<uint4> &bfrag3,
+                          Values values) {
+    const int tiles = pl.ntg * pl.TT, nimg = 4 * NV * halves;
     bfrag3.assign((size_t)tiles * nimg * 64, uint4{0, 0, 0, 0});
     for (int T = 0; T < tiles; ++T)
-        for (int half = 0; half < span; ++half)
+        for (int half = 0; half < halves; ++half)
             for (int th = 0; th < 2; ++th)
                 for (int lane = 0; lane < 64; ++lane) {
                     const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
-                    unsigned short img[3][2][8];
-                    for (int j = 0; j < 8; ++j) {
-                        const int lo = 32 * half + 8 * (lane >> 4) + j;
-                        double wr, wi;
-                        host_phasor((fm * (unsigned long long)lo) % rate, rate, wr, wi);
-                        const float v[3] = {(float)wr, (float)(wi - wr), (float)(wr + wi)};
-                        for (int c = 0; c < 3; ++c) {
+                    unsigned short img[NV][2][8];
+                    for (int jj = 0; jj < 8; ++jj) {
+                        float v[NV];
+                        values(fm, 32 * half + 8 * (lane >> 4) + jj, v);
+                        for (int c = 0; c < NV; ++c) {
                             const unsigned short hb = to_half_bits(v[c]);
-                            img[c][0][j] = hb;
-                            img[c][1][j] = to_half_bits(v[c] - from_half_bits(hb));
+                            img[c][0][jj] = hb;
+                            img[c][1][jj] = to_half_bits(v[c] - from_half_bits(hb));
                         }
                     }
-                    for (int c = 0; c < 3; ++c)
+                    for (int c = 0; c < NV; ++c)
                         for (int sp = 0; sp < 2; ++sp) {
                             uint4 w;
                             __builtin_memcpy(&w, img[c][sp], 16);
-                            const int f = half * 12 + (c * 2 + th) * 2 + sp;
+                            const int f = half * 4 * NV + (c * 2 + th) * 2 + sp;
                             bfrag3[((size_t)T * nimg + f) * 64 + lane] = w;
                         }
                 }
+}
+
+// Tables of the three-product loops.  `span`: the blocks of 32 samples the loop rotates at a time, 1
+// (ddc_mfma_ring16p3_kernel) or 2 (ddc_mfma_ring16p3r2_kernel).  Per 32-tone tile 12 * span B images (build_images3)
+// of c, (d-c), (c+d) -- w = c + i*d at sample 32*half + j of the span -- and per (span, tone) the phasor
+// w_n^(32*span*row) as (Pr, Pi, Pr-Pi, Pr+Pi).  One row more than there are spans: the loop loads the phasors of a
+// span while it computes the one before.
+void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                        std::vector<float4> &ptab3) {
+    const int Np = pl.ntg * pl.TT * 32;
+    const unsigned rate = pl.rate;
+    build_images3<3>(pl, fmod, span, bfrag3, [rate](unsigned long long fm, int s, float *v) {
+        double wr, wi;
+        host_phasor((fm * (unsigned long long)s) % rate, rate, wr, wi);
+        v[0] = (float)wr, v[1] = (float)(wi - wr), v[2] = (float)(wr + wi);
+    });
     const int nrow = ((pl.nk8 + 3) / 4 + span - 1) / span;
     ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
     for (int row = 0; row < nrow; ++row)
@@ -1487,13 +1468,6 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
             host_phasor(((unsigned long long)fmod[n] * (((unsigned long long)row * 32 * span) % rate)) % rate, rate, re, im);
             ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(re - im), (float)(re + im));
         }
-}
-
-// w^(ph2 / 2), ph2 in half samples; host_phasor's sign: w = exp(-2 pi i / rate)
-static void half_phasor(unsigned rate, unsigned long long ph2, double &re, double &im) {
-    const double ang = M_PI * ((double)ph2 / (double)rate);
-    re = std::cos(ang);
-    im = -std::sin(ang);
 }
 
 // Span phasors of the folded loops: per (span, tone) the phasor of the span's centre w_n^(64*span + 31.5) as
@@ -1512,77 +1486,38 @@ static void fold_span_phasors(const MfmaPlan &pl, const std::vector<unsigned> &f
         }
 }
 
+// c_j + i*d_j = w^(j - 31.5), j < 32, of the folded loops: from the exact integer phase in half samples (mod 2*rate);
+// t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
+static void fold_phasor(unsigned rate, unsigned long long fm, int j, double &c, double &d) {
+    double wr, wi;
+    half_phasor(rate, (fm * (unsigned long long)(63 - 2 * j)) % (2ULL * rate), wr, wi);
+    c = wr, d = -wi;
+}
+
 // Tables of the folded three-product loop (ddc_mfma_ring16p3f_kernel).  Per 32-tone tile 16 B
-// images f = (unit*2 + th)*2 + sp of c_j, d_j, c_j + d_j, c_j - d_j, j < 32, where c_j + i*d_j = w^(j - 31.5): formed in
-// double from the exact integer phase in half samples (mod 2*rate), rounded once, split hi/lo; lane l holds tone
-// 16*th + (l & 15), element jj <-> j = 8*(l >> 4) + jj.  Per (span, tone) the phasor of the span's centre
-// w_n^(64*span + 31.5) as (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.
+// images (build_images3, unit = c) of c_j, d_j, c_j + d_j, c_j - d_j (fold_phasor), and the span phasors.
 void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                          std::vector<float4> &ptab3) {
-    const int tiles = pl.ntg * pl.TT;
-    const unsigned long long rate2 = 2ULL * pl.rate;
-    bfrag3.assign((size_t)tiles * 16 * 64, uint4{0, 0, 0, 0});
-    for (int T = 0; T < tiles; ++T)
-        for (int th = 0; th < 2; ++th)
-            for (int lane = 0; lane < 64; ++lane) {
-                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
-                unsigned short img[4][2][8];
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int j = 8 * (lane >> 4) + jj;
-                    // t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
-                    double wr, wi;
-                    half_phasor(pl.rate, (fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
-                    const double c = wr, d = -wi;
-                    const float v[4] = {(float)c, (float)d, (float)(c + d), (float)(c - d)};
-                    for (int u = 0; u < 4; ++u) {
-                        const unsigned short hb = to_half_bits(v[u]);
-                        img[u][0][jj] = hb;
-                        img[u][1][jj] = to_half_bits(v[u] - from_half_bits(hb));
-                    }
-                }
-                for (int u = 0; u < 4; ++u)
-                    for (int sp = 0; sp < 2; ++sp) {
-                        uint4 w;
-                        __builtin_memcpy(&w, img[u][sp], 16);
-                        bfrag3[((size_t)T * 16 + (u * 2 + th) * 2 + sp) * 64 + lane] = w;
-                    }
-            }
+    const unsigned rate = pl.rate;
+    build_images3<4>(pl, fmod, 1, bfrag3, [rate](unsigned long long fm, int j, float *v) {
+        double c, d;
+        fold_phasor(rate, fm, j, c, d);
+        v[0] = (float)c, v[1] = (float)d, v[2] = (float)(c + d), v[3] = (float)(c - d);
+    });
     fold_span_phasors(pl, fmod, ptab3);
 }
 
 // Tables of the direct folded loop (ddc_mfma_ring16p4f_kernel).  Per 32-tone tile 8 B images
-// f = (u01*2 + th)*2 + sp of c_j (u01 = 0) and d_j (1), j < 32, c_j + i*d_j = w^(j - 31.5), formed, rounded and split as
-// in mfma_build_tables3f; lane l holds tone 16*th + (l & 15), element jj <-> j = 8*(l >> 4) + jj.  The span phasors are
-// those of mfma_build_tables3f (the loop reads Pr and Pi of a row).
+// of c_j and d_j, formed, rounded and split as in mfma_build_tables3f.  The span phasors are those of
+// mfma_build_tables3f (the loop reads Pr and Pi of a row).
 void mfma_build_tables4f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                          std::vector<float4> &ptab3) {
-    const int tiles = pl.ntg * pl.TT;
-    const unsigned long long rate2 = 2ULL * pl.rate;
-    bfrag3.assign((size_t)tiles * 8 * 64, uint4{0, 0, 0, 0});
-    for (int T = 0; T < tiles; ++T)
-        for (int th = 0; th < 2; ++th)
-            for (int lane = 0; lane < 64; ++lane) {
-                const unsigned long long fm = fmod[(size_t)T * 32 + 16 * th + (lane & 15)];
-                unsigned short img[2][2][8];
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int j = 8 * (lane >> 4) + jj;
-                    // t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
-                    double wr, wi;
-                    half_phasor(pl.rate, (fm * (unsigned long long)(63 - 2 * j)) % rate2, wr, wi);
-                    const float v[2] = {(float)wr, (float)-wi};
-                    for (int u = 0; u < 2; ++u) {
-                        const unsigned short hb = to_half_bits(v[u]);
-                        img[u][0][jj] = hb;
-                        img[u][1][jj] = to_half_bits(v[u] - from_half_bits(hb));
-                    }
-                }
-                for (int u = 0; u < 2; ++u)
-                    for (int sp = 0; sp < 2; ++sp) {
-                        uint4 w;
-                        __builtin_memcpy(&w, img[u][sp], 16);
-                        bfrag3[((size_t)T * 8 + (u * 2 + th) * 2 + sp) * 64 + lane] = w;
-                    }
-            }
+    const unsigned rate = pl.rate;
+    build_images3<2>(pl, fmod, 1, bfrag3, [rate](unsigned long long fm, int j, float *v) {
+        double c, d;
+        fold_phasor(rate, fm, j, c, d);
+        v[0] = (float)c, v[1] = (float)d;
+    });
     fold_span_phasors(pl, fmod, ptab3);
 }
 
@@ -1635,51 +1570,36 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
     switch (kind) {
         case MfmaKernel::AsmRing16P:
         case MfmaKernel::AsmRing16P3:
-        case MfmaKernel::AsmRing16P3R2: {
-            // the conversion pass, then the loop that copies its images (a.img: ngt * nhi images of 8 KiB, or of 12 KiB
-            // for the three-product loops, whose tables a.bfrag3 / a.ptab3 are those of the loop launched)
-            const bool three = kind != MfmaKernel::AsmRing16P;
-            if (!a.img || (three && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
-            const int nhi = (sh.nk8 + 3) / 4;
-            const long long cgrid = (long long)sh.ngt * nhi;
-            grid = ring_grid(sh.ngt, sh.ntq, 1);
-            if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
-            uint4 *img = const_cast<uint4 *>(a.img);
-            if (three)
-                hipLaunchKernelGGL(ddc_convert3_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi);
-            else
-                hipLaunchKernelGGL(ddc_convert_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, a, img, nhi);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            if (kind == MfmaKernel::AsmRing16P3R2)
-                hipLaunchKernelGGL(ddc_mfma_ring16p3r2_kernel, dim3(grid), dim3(256), 0, st, a);
-            else if (three)
-                hipLaunchKernelGGL(ddc_mfma_ring16p3_kernel, dim3(grid), dim3(256), 0, st, a);
-            else
-                hipLaunchKernelGGL(ddc_mfma_ring16p_kernel, dim3(grid), dim3(256), 0, st, a);
-            return hipGetLastError();
-        }
+        case MfmaKernel::AsmRing16P3R2:
         case MfmaKernel::AsmRing16P3F:
         case MfmaKernel::AsmRing16P4F: {
-            // the folded conversion pass and its loop (a.img: ngt * nspan images of 16 KiB; a.bfrag3 / a.ptab3: the
-            // tables of mfma_build_tables3f, or of mfma_build_tables4f for the direct fold)
-            const bool direct = kind == MfmaKernel::AsmRing16P4F;
-            if (!a.img || !a.bfrag3 || !a.ptab3) return hipErrorInvalidValue;
-            const int nhi = (sh.nk8 + 3) / 4, nspan = (nhi + 1) / 2;
-            const long long cgrid = (long long)sh.ngt * nspan;
+            // the conversion pass, then the loop that copies its images.  a.img: ngt * nimg images -- of 8 KiB per block,
+            // of 12 KiB per block for the three-product loops, of 16 KiB per span of two blocks for the folded ones;
+            // a.bfrag3 / a.ptab3: the tables of the product loop launched (mfma_build_tables3, 3f, 4f)
+            void (*conv)(const MfmaLaunch, uint4 *, int) = nullptr;             // an image per block
+            void (*convf)(const MfmaLaunch, uint4 *, int, int) = nullptr;       // an image per span
+            void (*loop)(const MfmaLaunch) = nullptr;
+            switch (kind) {
+                case MfmaKernel::AsmRing16P: conv = ddc_convert_kernel, loop = ddc_mfma_ring16p_kernel; break;
+                case MfmaKernel::AsmRing16P3: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3_kernel; break;
+                case MfmaKernel::AsmRing16P3R2: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3r2_kernel; break;
+                case MfmaKernel::AsmRing16P3F: convf = ddc_convert3f_kernel, loop = ddc_mfma_ring16p3f_kernel; break;
+                default: convf = ddc_convert4f_kernel, loop = ddc_mfma_ring16p4f_kernel;
+            }
+            const bool products = kind != MfmaKernel::AsmRing16P;
+            if (!a.img || (products && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
+            const int nhi = (sh.nk8 + 3) / 4, nimg = convf ? (nhi + 1) / 2 : nhi;
+            const long long cgrid = (long long)sh.ngt * nimg;
             grid = ring_grid(sh.ngt, sh.ntq, 1);
             if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
             uint4 *img = const_cast<uint4 *>(a.img);
-            if (direct)
-                hipLaunchKernelGGL(ddc_convert4f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nspan);
+            if (convf)
+                hipLaunchKernelGGL(convf, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nimg);
             else
-                hipLaunchKernelGGL(ddc_convert3f_kernel, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nspan);
+                hipLaunchKernelGGL(conv, dim3((unsigned)cgrid), dim3(products ? 128 : 256), 0, st, a, img, nhi);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
-            if (direct)
-                hipLaunchKernelGGL(ddc_mfma_ring16p4f_kernel, dim3(grid), dim3(256), 0, st, a);
-            else
-                hipLaunchKernelGGL(ddc_mfma_ring16p3f_kernel, dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(loop, dim3(grid), dim3(256), 0, st, a);
             return hipGetLastError();
         }
         case MfmaKernel::AsmRing16W8:

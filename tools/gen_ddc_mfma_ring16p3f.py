@@ -46,17 +46,10 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ddc_mfma_gen import Counters, ar, print_header, vr   # noqa: E402
-from gen_ddc_mfma_ring16p3 import (ABLATE, S_BF, S_K, S_M0, S_NHI1, S_NLEFT, S_PSTRIDE, S_RD, S_RD2, S_RDN,   # noqa: E402
-                                   S_T0, S_T1, S_WR, S_WRS, S_XB, SB, SGPR_CLOBBER, dma_ops, p_loads)
-from gen_ddc_mfma_ring16p3r2 import READ_AT, first_use, last_use, mfma_of   # noqa: E402
+from ddc_mfma_pframe import Loop, print_loop   # noqa: E402
 
 NU = 4                     # operand units U1..U4
-NP = 3                     # products P1, P2, P3
-SLOT = NU * 4 * 1024       # bytes of one ring slot
-NSLOT = 4                  # ring slots: images arrive three spans ahead
 NG = 12 * NU               # MFMAs per span
-PROD = (0, 1, 2, 2)        # the product a unit sums into
 
 # ---- register map ------------------------------------------------------------
 VB = 12                    # v0..v11 stay with the compiler
@@ -67,56 +60,15 @@ P = {"A": VB + 144, "B": VB + 152}   # (Pr, Pi, Pi-Pr, Pr+Pi) of tone half 0, of
 ADDR = {"A": (VB + 160, VB + 161), "B": (VB + 162, VB + 163)}
 V_LAST = VB + 163
 NAGPR = 16 * NU
-BF = [S_BF, 66, 68, 70]    # scalar bases of the 16 phasor images, 4 KiB apart (prologue)
+BF = [56, 66, 68, 70]      # scalar bases of the 16 phasor images, 4 KiB apart (prologue)
 ROT0, ROT1 = 2, 47         # the FMAs of a span lie in gaps ROT0..ROT1
 G_PLOAD = 28
-
-assert V_LAST + 1 + NAGPR <= 256 and not (set(BF) | {b + 1 for b in BF}) - set(SGPR_CLOBBER)
-
-
-def frag(unit, rh, sp):
-    return F0 + 16 * unit + 8 * sp + 4 * rh
-
-
-def piece(unit, rh, sp):
-    return 1024 * (4 * unit + 2 * sp + rh)
-
-
-def bfrag(unit, th, sp):
-    return ar(((unit * 2 + th) * 2 + sp) * 4)
-
-
-def image_pointer(par):
-    """SALU: s[SB[par].x] = image base + SLOT * min(S_K, spans-1), then S_K += 1"""
-    S_X = SB[par]["x"]
-    return [
-        f"s_min_u32 s{S_T0}, s{S_K}, s{S_NHI1}",
-        f"s_mul_i32 s{S_T1}, s{S_T0}, {SLOT}",
-        f"s_add_u32 s{S_X}, s{S_XB}, s{S_T1}",
-        f"s_addc_u32 s{S_X + 1}, s{S_XB + 1}, 0",
-        f"s_add_u32 s{S_K}, s{S_K}, 1",
-    ]
-
-
-def rotate_ops(prod, p):
-    """The two FMAs per accumulator element that product `prod` feeds: 32 v_fma_f32 in two sweeps
-    (an accumulator is read again 32 instructions after it was written)."""
-    ops = []
-    for part in range(2):                # 0: acc_r, 1: acc_i
-        for i in range(16):
-            th = (i >> 2) & 1            # register i belongs to tile (rh, th) = (i >> 3, (i >> 2) & 1)
-            pr, pi, pm, pp = (vr(p + 4 * th + j) for j in range(4))
-            acc = vr(ACC[part] + i)
-            k = vr(KB[prod] + i)
-            coef = ((pp, pm), (pm, "-" + pp), ("-" + pi, pr))[prod][part]
-            ops.append(f"v_fma_f32 {acc}, {coef}, {k}, {acc}")
-    return ops
 
 
 def rotation(p_cur, p_prev):
     """[(gap, kind, v_fma_f32)]: P3 of the span before, then P1 and P2 of this one."""
-    ops = [("rot", op) for op in rotate_ops(2, p_prev)] + \
-          [("rotp", op) for prod in (0, 1) for op in rotate_ops(prod, p_cur)]
+    ops = [("rot", op) for op in LOOP.rotate_ops(2, p_prev)] + \
+          [("rotp", op) for prod in (0, 1) for op in LOOP.rotate_ops(prod, p_cur)]
     n = len(ops)
     placed = [(ROT0 + (k * (ROT1 - ROT0 + 1)) // n, kind, op) for k, (kind, op) in enumerate(ops)]
     for k, (g, _, _) in enumerate(placed):
@@ -128,206 +80,19 @@ def rotation(p_cur, p_prev):
     return placed
 
 
-def span(cnt, out, label):
-    """One span of 64 samples: 48 MFMAs.  Span s computes from ring slot RD, prefetches span s+1's
-    first fragments from RDN and starts the copy of span s+3's image into slot WR (free since the
-    barrier that ended s-1)."""
-    out.append(f"; ---- span, parity {label}")
-    other = "B" if label == "A" else "A"
-    p_cur, p_prev = P[label], P[other]
-    S_P, N_P = SB[label]["p"], SB[other]["p"]
-    gaps = {g: [] for g in range(NG)}
-    V_RD, V_RDN = ADDR[label]
-    N_RD, N_RDN = ADDR[other]
-
-    last_rd = None
-    for unit in (1, 2, 3, 0):
-        for (rh, sp), rel in READ_AT.items():
-            g = (12 * unit if unit else NG) + rel
-            lu, fu = last_use(unit, rh, sp), first_use(unit, rh, sp)
-            if unit == 0:
-                assert g - lu >= 23 and NG + fu - g >= 8, (unit, rh, sp)
-            else:
-                assert NG + g - lu >= 23 and fu - g >= 8, (unit, rh, sp)
-                last_rd = f"f{unit}{rh}{sp}"
-            gaps[g].append(("lds", f"ds_read_b128 {vr(frag(unit, rh, sp), 4)}, {vr(V_RD if unit else V_RDN)} "
-                            f"offset:{piece(unit, rh, sp)}", f"f{unit}{rh}{sp}"))
-    # image of span s+3 -> slot WR: pointer (this parity's set) in gaps 0..1, the four pieces at
-    # gaps 2, 10, 18, 26
-    for i, sx in enumerate(image_pointer(label)):
-        gaps[i // 3].append(("salu", sx, None))
-    for which in range(4):
-        for tx in dma_ops(label, S_WR, which):
-            gaps[2 + 8 * which].append(("dma" if tx.startswith("global") else "salu", tx, f"d{which}{label}"))
-    # P of span s+1 into the other parity's registers
-    for tx in p_loads(p_prev, S_P):
-        gaps[G_PLOAD].append(("vm", tx, "p" + other))
-    gaps[G_PLOAD + 1].append(("salu", f"s_add_u32 s{N_P}, s{S_P}, s{S_PSTRIDE}", None))
-    gaps[G_PLOAD + 1].append(("salu", f"s_addc_u32 s{N_P + 1}, s{S_P + 1}, 0", None))
-    for g, kind, op in rotation(p_cur, p_prev):
-        gaps[g].append((kind, op, None))
-    # ring slot rotation (four slots) and the read addresses of the next span, once every ring
-    # access of this one has been issued (gap 46)
-    gaps[46].append(("salu", f"s_mov_b32 s{S_T0}, s{S_RD}", None))
-    gaps[46].append(("salu", f"s_mov_b32 s{S_RD}, s{S_RDN}", None))
-    gaps[46].append(("salu", f"s_mov_b32 s{S_RDN}, s{S_RD2}", None))
-    gaps[47].append(("salu", f"s_mov_b32 s{S_RD2}, s{S_WR}", None))
-    gaps[47].append(("salu", f"s_mov_b32 s{S_WR}, s{S_T0}", None))
-    gaps[47].append(("addr", f"v_add_u32 {vr(N_RD)}, s{S_RD}, %[lane16]", None))
-    gaps[47].append(("addr", f"v_add_u32 {vr(N_RDN)}, s{S_RDN}, %[lane16]", None))
-
-    waited_p = False
-    for g in range(NG):
-        unit, m = divmod(g, 12)
-        rh, th, sp_a, sp_b = mfma_of(m)
-        if first_use(unit, rh, sp_a) == g:
-            cnt.need_lgkm(f"f{unit}{rh}{sp_a}")
-        dst = KB[PROD[unit]] + 4 * (2 * rh + th)
-        src_c = "0" if unit < 3 and m < 4 else vr(dst, 4)
-        if "mfma" not in ABLATE:
-            out.append(f"v_mfma_f32_16x16x32_f16 {vr(dst, 4)}, {vr(frag(unit, rh, sp_a), 4)}, "
-                       f"{bfrag(unit, th, sp_b)}, {src_c}")
-        for kind, text, tag in gaps[g]:
-            if kind == "lds":
-                if "lds" not in ABLATE:
-                    out.append(text)
-                    cnt.issue_lgkm(tag)
-            elif kind == "vm":
-                out.append(text)
-                cnt.issue_vm(tag)
-            elif kind == "dma":
-                if "gload" not in ABLATE:
-                    out.append(text)
-                    cnt.issue_vm(tag)
-            elif kind in ("rot", "rotp"):
-                if kind == "rotp" and not waited_p:
-                    cnt.need_vm("p" + label)      # loaded one span ago
-                    waited_p = True
-                if "rot" not in ABLATE:
-                    out.append(text)
-            else:
-                out.append(text)
-    # the image this wave started one span ago (span s+2's) must have landed before the barrier
-    # publishes it: span s+1 prefetches from it (the wait for P has covered it already)
-    cnt.need_vm("d3" + other)
-    # every read of THIS span's slot has returned (the barrier frees it for the copy of span s+4); the
-    # prefetch of span s+1's first fragments (gaps 38..46, from the next slot) stays in flight across it
-    cnt.need_lgkm(last_rd)
-    if "bar" not in ABLATE:
-        out.append("s_barrier")
-
-
-def generate():
-    out = []
-    cnt = Counters(out)
-    o = out.append
-    o("; ===== prologue =====")
-    o(f"s_mov_b32 s{S_M0}, m0")
-    o(f"s_mov_b32 s{S_XB}, %[ib_lo]")          # image base of this row tile, span 0
-    o(f"s_mov_b32 s{S_XB + 1}, %[ib_hi]")
-    o(f"s_mov_b32 s{S_WRS}, %[wrs]")
-    o(f"s_mov_b32 s{SB['B']['p']}, %[pp_lo]")
-    o(f"s_mov_b32 s{SB['B']['p'] + 1}, %[pp_hi]")
-    o(f"s_mov_b32 s{S_BF}, %[bf_lo]")
-    o(f"s_mov_b32 s{S_BF + 1}, %[bf_hi]")
-    o(f"s_mov_b32 s{S_PSTRIDE}, %[pstride]")
-    o(f"s_mov_b32 s{S_NLEFT}, %[nhi]")
-    o(f"s_add_u32 s{S_NHI1}, %[nhi], -1")
-    o(f"s_mov_b32 s{S_K}, 0")
-    o(f"s_mov_b32 s{S_RD}, 0")
-    o(f"s_mov_b32 s{S_RDN}, {SLOT}")
-    o(f"s_mov_b32 s{S_RD2}, {2 * SLOT}")
-    o(f"s_mov_b32 s{S_WR}, {3 * SLOT}")
-    o("s_nop 4")
-    for j in range(1, len(BF)):
-        o(f"s_add_u32 s{BF[j]}, s{S_BF}, {4096 * j}")
-        o(f"s_addc_u32 s{BF[j] + 1}, s{S_BF + 1}, 0")
-    # P of span 0 (parity A) through parity B's pointer; parity A's pointer is span 1's
-    o(f"s_add_u32 s{SB['A']['p']}, s{SB['B']['p']}, s{S_PSTRIDE}")
-    o(f"s_addc_u32 s{SB['A']['p'] + 1}, s{SB['B']['p'] + 1}, 0")
-    o("s_nop 4")
-    out.extend(p_loads(P["A"], SB["B"]["p"]))
-    for f in range(4 * NU):
-        b = BF[f // 4]
-        if "bimg" not in ABLATE:
-            o(f"global_load_dwordx4 {ar(4 * f)}, %[bo], s[{b}:{b + 1}] offset:{(f % 4) * 1024}")
-    # the first span rotates "P3 of the span before": 0, with P = 0
-    for base in (KB[2], ACC[0], ACC[1]):
-        for i in range(16):
-            o(f"v_mov_b32 {vr(base + i)}, 0")
-    for i in range(8):
-        o(f"v_mov_b32 {vr(P['B'] + i)}, 0")
-    # images of spans 0, 1, 2 into slots 0, 1, 2 (pointer sets A, B, C: one per image)
-    for par, slot in (("A", S_RD), ("B", S_RDN), ("C", S_RD2)):
-        out.extend(image_pointer(par))
-        for which in range(4):
-            o("s_nop 4")
-            out.extend(dma_ops(par, slot, which))
-        o("s_nop 4")
-    V_RD, V_RDN = ADDR["A"]
-    o(f"v_add_u32 {vr(V_RD)}, s{S_RD}, %[lane16]")
-    o(f"v_add_u32 {vr(V_RDN)}, s{S_RDN}, %[lane16]")
-    o("s_waitcnt vmcnt(0)")          # P of span 0, the phasor images and the three slot images
-    o("s_barrier")
-    for rh, sp in ((0, 0), (1, 0), (0, 1), (1, 1)):
-        o(f"ds_read_b128 {vr(frag(0, rh, sp), 4)}, {vr(V_RD)} offset:{piece(0, rh, sp)}")
-    o("s_waitcnt lgkmcnt(0)")
-    cnt.lgkm = []
-
-    def trip(out_, cnt_):
-        span(cnt_, out_, "A")
-        out_.append(f"s_sub_u32 s{S_NLEFT}, s{S_NLEFT}, 1")
-        out_.append(f"s_cmp_eq_u32 s{S_NLEFT}, 0")
-        out_.append("s_cbranch_scc1 2f")
-        span(cnt_, out_, "B")
-        out_.append(f"s_sub_u32 s{S_NLEFT}, s{S_NLEFT}, 1")
-        out_.append(f"s_cmp_lg_u32 s{S_NLEFT}, 0")
-        out_.append("s_cbranch_scc1 1b")
-
-    # outstanding operations at the top of the loop in the steady state (on entry there are none:
-    # the waits derived from the steady state are then met at once)
-    state = ([], [])
-    for _ in range(4):
-        probe = Counters([])
-        probe.vm, probe.lgkm = list(state[0]), list(state[1])
-        trip(probe.out, probe)
-        if (probe.vm, probe.lgkm) == state:
-            break
-        state = (list(probe.vm), list(probe.lgkm))
-    else:
-        raise AssertionError("no steady state")
-    cnt.vm, cnt.lgkm = list(state[0]), list(state[1])
-    o(f"; ===== main loop, two spans per trip; vm, lgkm at the top: {state}")
-    o("1:")
-    trip(out, cnt)
-    assert (cnt.vm, cnt.lgkm) == state, (cnt.lgkm, cnt.vm, state)
-    # P3 of the last span is still to be rotated, with that span's P
-    o("s_waitcnt vmcnt(0)")
-    o("s_nop 15")
-    o("s_nop 15")
-    out.extend(rotate_ops(2, P["B"]))
-    o("s_branch 3f")
-    o("2:")
-    o("s_waitcnt vmcnt(0)")
-    o("s_nop 15")
-    o("s_nop 15")
-    out.extend(rotate_ops(2, P["A"]))
-    o("3:")
-    # every image copy has landed (vmcnt(0) above) and every wave is past the last barrier: the
-    # ring is idle, the accumulators go to the C++ epilogue through it
-    o("s_barrier")
-    for q in range(8):
-        base = (ACC[0] if q < 4 else ACC[1]) + 4 * (q & 3)
-        o(f"ds_write_b128 %[accaddr], {vr(base, 4)} offset:{q * 1024}")
-    o("s_waitcnt lgkmcnt(0)")
-    o(f"s_mov_b32 m0, s{S_M0}")
-    return out
+LOOP = Loop(noun="span", units=NU, prod=(0, 1, 2, 2), image=(0, 1, 2, 3),
+            split=((1, 0), (0, 1), (0, 0)),                  # lo*hi, hi*lo, hi*hi: small terms first
+            # the lo fragments (used by the first four MFMAs only) first, the hi fragments in the one gap that is
+            # 23 MFMAs behind their last use (R1) and 8 ahead of their first
+            read_at={(0, 1): -10, (1, 1): -8, (0, 0): -4, (1, 0): -2},
+            coef=(("p", "m"), ("m", "-p"), ("-i", "r")),     # P1, P2, P3; m = Pi-Pr, p = Pr+Pi
+            late=2, g_pload=G_PLOAD,
+            rotation=rotation, vb=VB, acc=ACC, kb=KB, f0=F0, p=P, addr=ADDR, v_last=V_LAST, nagpr=NAGPR, bf=BF)
 
 
 def main():
-    print_header("GSDR_MFMA_RING16P3F", __file__,
-                 "Main loop of ddc_mfma_ring16p3f_kernel (three real products per complex multiply over 64-sample spans folded about their centre: four K=32 operand units per span)",
-                 generate(), vb=VB, v_last=V_LAST, nagpr=NAGPR, sgprs=SGPR_CLOBBER, nbytes=NSLOT * SLOT, slot=SLOT)
+    print_loop(LOOP, "GSDR_MFMA_RING16P3F", __file__,
+               "Main loop of ddc_mfma_ring16p3f_kernel (three real products per complex multiply over 64-sample spans folded about their centre: four K=32 operand units per span)")
 
 
 if __name__ == "__main__":
