@@ -46,6 +46,8 @@ struct Switches {
                                 // more fold each 64-sample span about its centre (48 MFMAs per span for 72); 1: every such handle; else never
     int mfma_fold_products = -1;    // GSDR_MFMA_FOLD_PRODUCTS, -1 unset: a folded handle sums the plain four products straight into Re and Im
                                 // (ddc_mfma_ring16p4f_kernel); 3: Gauss's three (ddc_mfma_ring16p3f_kernel); 4: the four
+    int mfma_wave_tones = -1;   // GSDR_MFMA_WAVE_TONES, -1 unset: a handle that sums the plain four products takes the loop with wave tiles of
+                                // 16 rows x 64 tones (ddc_mfma_ring16p4fw_kernel) when that launches no more waves; 64: every such handle; 32: never
     int mfma_timing = 0;        // GSDR_MFMA_TIMING, 0: timing-only modes 1 - 3 (builds with -DGSDR_TIMING_BUILD only)
     bool noise_fft = true;      // GSDR_NOISE_FFT, 1: NOISE through the polyphase filter + FFT; 0: every bin a DDC tone
     bool tones_fft = true;      // GSDR_TONES_FFT, 1: TONES through filter + FFT + bin selection; 0: every bin a DDC tone
@@ -225,10 +227,10 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
 // multiply (chosen per handle, demod.cpp), AsmRing16P3R2: that loop rotating its partial sums once per pair of
 // blocks (tables of mfma_build_tables3 with span 2 in bfrag3 / ptab3), AsmRing16P3F: three products over 64-sample spans
 // folded about their centre (images of ddc_convert3f_kernel, tables of mfma_build_tables3f in bfrag3 / ptab3), AsmRing16P4F: that fold with the plain four products (images of
-// ddc_convert4f_kernel, tables of mfma_build_tables4f); AsmRing:
+// ddc_convert4f_kernel, tables of mfma_build_tables4f), AsmRing16P4FW: that loop, images and tables on wave tiles of 16 rows x 64 tones; AsmRing:
 // round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled (TT, PK, W apply to it only; the assembly kernels are
 // TT = 1, PK = 32, W = 4).
-enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F };
+enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F, AsmRing16P4FW };
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);
 const char *ddc_mfma_kernel_name(MfmaKernel kind);
 

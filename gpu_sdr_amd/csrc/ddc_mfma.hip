@@ -64,6 +64,7 @@
 #include "ddc_mfma_ring16p3r2_gen.h"
 #include "ddc_mfma_ring16p3f_gen.h"
 #include "ddc_mfma_ring16p4f_gen.h"
+#include "ddc_mfma_ring16p4fw_gen.h"
 
 namespace gsdr {
 
@@ -1141,6 +1142,130 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
     ring16px_tile<MfmaKernel::AsmRing16P4F>(a, lds, gt0, tg, wave, active);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The direct folded loop on a wave tile of 16 rows x 64 tones (tools/gen_ddc_mfma_ring16p4fw.py, DESIGN.md section
+// 4.1h).  Same images (ddc_convert4f_kernel), same tables (mfma_build_tables4f), per output element the same MFMAs,
+// rotation and epilogue arithmetic in the same order as ddc_mfma_ring16p4f_kernel: the same bits.  A workgroup takes
+// the 16-row tile g16 = 2*gt + rh and 256 tones, a wave two consecutive 32-tone tiles: an operand fragment feeds
+// twelve MFMAs instead of six, and the ring holds only the eight 1-KiB pieces of row half rh of every slot image
+// (8 KiB a span instead of 16).
+//     tile q = tone quarter, register j of lane l  <->  row 16*rh + 4*(l >> 4) + j of row tile gt,
+//                                                     tone 16*q + (l & 15) of the wave's 64.
+// ---------------------------------------------------------------------------------------------
+// store_tile16 for that tile: per element the same table entries, the same tile phasor (of the 32-row tile gt), the
+// same 1/S and the same FMAs.  tg0, tg1: the wave's two 32-tone tiles (one that does not exist is a copy of the last:
+// st0, st1 say which are stored).  Lane l computes the tile phasor of tone l of the 64 and the scale of row l & 15.
+__device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void store_tile16w(
+    const MfmaLaunch &a, int gt, int rh, int tg0, int tg1, bool st0, bool st1, int lane, const float16v &accr,
+    const float16v &acci) {
+    const MfmaShape &sh = a.sh;
+    const int Np = sh.NT32 * 32;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int tg_self = lane >> 5 ? tg1 : tg0;
+    const unsigned fm = a.fmod[tg_self * 32 + (lane & 31)];
+    const unsigned mbits = row_max_bits(a, gt * 32 + 16 * rh + l15);
+    float2 d[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            d[4 * q + j] = a.dtab[(size_t)(16 * rh + 4 * l4 + j) * Np + (q >> 1 ? tg1 : tg0) * 32 + 16 * (q & 1) + l15];
+    asm volatile("" ::: "memory");
+    const float2 base_self = tile_phasor(a, gt, fm);
+    asm volatile("" ::: "memory");
+    const int se_self = scale_exp_of(mbits);
+    // 1 / S of the lane's four rows (row 16*rh + 4*l4 + j lives in lane 4*l4 + j)
+    float inv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        inv[j] = exp2_bits(-__builtin_amdgcn_ds_bpermute((4 * l4 + j) << 2, se_self)) * sh.unscale;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // lane 16*q + l15 holds the tile phasor of tone 16*q + l15
+        const int src = (16 * q + l15) << 2;
+        const float bx = bits_to_float((unsigned)__builtin_amdgcn_ds_bpermute(src, (int)float_to_bits(base_self.x)));
+        const float by = bits_to_float((unsigned)__builtin_amdgcn_ds_bpermute(src, (int)float_to_bits(base_self.y)));
+        const int n = (q >> 1 ? tg1 : tg0) * 32 + 16 * (q & 1) + l15;
+        const bool stored = q >> 1 ? st1 : st0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // The FMAs that store_tile16 is compiled to in ddc_mfma_ring16p4f_kernel, spelled out: left to the compiler
+            // a sum of two products comes out with either product fused, and the last bit with it.  There the second
+            // product is rounded and the first fused, except in ri of the elements j = 1..3 of tile (rh 1, th 0), where
+            // it is the other way round (read from that kernel's code; test_gpu_widetile.py compares the bits).
+#pragma clang fp contract(off)
+            const int i = 4 * q + j;
+            const int row = 16 * rh + 4 * l4 + j;
+            const float dx = d[i].x * inv[j], dy = d[i].y * inv[j];
+            const float rr = __builtin_fmaf(bx, dx, -(by * dy));
+            const float ri = rh == 1 && (q & 1) == 0 && j >= 1 ? __builtin_fmaf(by, dx, bx * dy) : __builtin_fmaf(bx, dy, by * dx);
+            float2 y;
+            y.x = __builtin_fmaf(accr[i], rr, -(acci[i] * ri));
+            y.y = __builtin_fmaf(accr[i], ri, acci[i] * rr);
+            const int orow = gt * 32 + row;
+            if (stored && orow < sh.nout && n < sh.N) a.out[(size_t)orow * sh.N + n] = y;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p4fw_kernel(
+    const MfmaLaunch a) {
+    // ring (4 slots of 8 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P4FW_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P4FW_BYTES >= 4 * 8192, "the accumulators fit");
+    static_assert(2 * GSDR_MFMA_RING16P4FW_SLOT == GSDR_MFMA_RING16P4F_SLOT, "a ring slot is one row half of a slot image");
+    // the grid over 16-row tiles, XCD-major; four pairs of 32-tone tiles per workgroup, one pair per wave.  A wave whose
+    // second tile, or both, lie past the last runs the loop on a copy of the last tile -- it keeps the barriers -- and
+    // stores nothing of it
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int ntq = (sh.ntg + 7) >> 3;
+    const int g16 = (q / ntq) * 8 + xcd;
+    if (g16 * 16 >= sh.nout) return;          // no row in this tile
+    const int gt = g16 >> 1, rh = g16 & 1;
+    const int tg_raw = ((q % ntq) * 4 + wave) * 2;
+    const bool st0 = tg_raw < sh.ntg, st1 = tg_raw + 1 < sh.ntg;
+    const int tg0 = st0 ? tg_raw : sh.ntg - 1, tg1 = st1 ? tg_raw + 1 : sh.ntg - 1;
+
+    const int Np = sh.NT32 * 32;
+    const int nhi = ((sh.nk8 + 3) / 4 + 1) / 2;      // spans: slot images of a row tile
+    const int lane = (int)(fresh_tid() & 63u);
+    const unsigned po = (unsigned)(tg0 * 32 + (lane & 15)) * 16u, po1 = (unsigned)(tg1 * 32 + (lane & 15)) * 16u;
+    const unsigned bo = (unsigned)tg0 * 8192u + (unsigned)lane * 16u, bo1 = (unsigned)tg1 * 8192u + (unsigned)lane * 16u;
+    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
+    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
+    // this wave copies unit `wave` of row half rh of every image: pieces 4*wave + rh (hi) and 4*wave + 2 + rh (lo) of
+    // the image become pieces 2*wave and 2*wave + 1 of the ring slot
+    const unsigned io0 = (unsigned)(4 * wave + rh) * 1024u + (unsigned)lane * 16u, io1 = io0 + 2048u;
+    const unsigned wrs = lds_base + (unsigned)wave * 2048u;
+    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (GSDR_MFMA_RING16P4F_SLOT / 16)),
+                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
+    asm volatile(GSDR_MFMA_RING16P4FW_TEXT
+                 :
+                 : [io0] "v"(io0), [io1] "v"(io1), [po] "v"(po), [po1] "v"(po1), [bo] "v"(bo), [bo1] "v"(bo1),
+                   [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),
+                   GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),
+                   [nhi] GSDR_SGPR(nhi)
+                 : GSDR_MFMA_RING16P4FW_CLOBBERS);
+    if (!st0) return;
+    // the accumulators come back from this wave's 8 KiB: real parts of tone quarters 0..3, then the imaginary parts
+    const int lane2 = (int)(fresh_tid() & 63u);
+    float16v accr, acci;
+    const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            accr[qd * 4 + j] = vr[j];
+            acci[qd * 4 + j] = vi[j];
+        }
+    }
+    store_tile16w(a, gt, rh, tg0, tg1, st0, st1, lane2, accr, acci);
+}
+
 // The staging pass (StageLaunch in ddc_kernels.h).  A workgroup takes 2048 consecutive samples of region A (the
 // new buffer) or of region B (what the previous call left in front), a wave 512 of them: sixteen bytes per lane and
 // load, all four loads of a wave in flight at once -- one memory round trip per wave.  Maxima per segment:
@@ -1572,7 +1697,8 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
         case MfmaKernel::AsmRing16P3:
         case MfmaKernel::AsmRing16P3R2:
         case MfmaKernel::AsmRing16P3F:
-        case MfmaKernel::AsmRing16P4F: {
+        case MfmaKernel::AsmRing16P4F:
+        case MfmaKernel::AsmRing16P4FW: {
             // the conversion pass, then the loop that copies its images.  a.img: ngt * nimg images -- of 8 KiB per block,
             // of 12 KiB per block for the three-product loops, of 16 KiB per span of two blocks for the folded ones;
             // a.bfrag3 / a.ptab3: the tables of the product loop launched (mfma_build_tables3, 3f, 4f)
@@ -1584,13 +1710,16 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
                 case MfmaKernel::AsmRing16P3: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3_kernel; break;
                 case MfmaKernel::AsmRing16P3R2: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3r2_kernel; break;
                 case MfmaKernel::AsmRing16P3F: convf = ddc_convert3f_kernel, loop = ddc_mfma_ring16p3f_kernel; break;
+                case MfmaKernel::AsmRing16P4FW: convf = ddc_convert4f_kernel, loop = ddc_mfma_ring16p4fw_kernel; break;
                 default: convf = ddc_convert4f_kernel, loop = ddc_mfma_ring16p4f_kernel;
             }
             const bool products = kind != MfmaKernel::AsmRing16P;
             if (!a.img || (products && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
             const int nhi = (sh.nk8 + 3) / 4, nimg = convf ? (nhi + 1) / 2 : nhi;
             const long long cgrid = (long long)sh.ngt * nimg;
-            grid = ring_grid(sh.ngt, sh.ntq, 1);
+            // the wide loop: 16-row tiles, eight 32-tone tiles per workgroup
+            grid = kind == MfmaKernel::AsmRing16P4FW ? ring_grid((sh.nout + 15) / 16, (sh.ntg + 7) / 8, 1)
+                                                     : ring_grid(sh.ngt, sh.ntq, 1);
             if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
             uint4 *img = const_cast<uint4 *>(a.img);
             if (convf)
@@ -1627,7 +1756,8 @@ const char *ddc_mfma_kernel_name(MfmaKernel kind) {
         case MfmaKernel::AsmRing16P3:
         case MfmaKernel::AsmRing16P3R2:
         case MfmaKernel::AsmRing16P3F:
-        case MfmaKernel::AsmRing16P4F: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
+        case MfmaKernel::AsmRing16P4F:
+        case MfmaKernel::AsmRing16P4FW: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
         case MfmaKernel::AsmRing16W8: return "ddc_mfma_ring16w8_kernel";
         case MfmaKernel::AsmRing16: return "ddc_mfma_ring16_kernel";
         case MfmaKernel::AsmRing: return "ddc_mfma_ring_kernel";

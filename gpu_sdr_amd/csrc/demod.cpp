@@ -85,6 +85,7 @@ gsdr::Switches gsdr::read_switches() {
     s.mfma_3m_rot = env("GSDR_MFMA_3M_ROT", -1);
     s.mfma_fold = env("GSDR_MFMA_FOLD", -1);
     s.mfma_fold_products = env("GSDR_MFMA_FOLD_PRODUCTS", -1);
+    s.mfma_wave_tones = env("GSDR_MFMA_WAVE_TONES", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -188,6 +189,7 @@ struct gsdr_demod {
     bool fold = false;                 // ... through ddc_mfma_ring16p3f_kernel: each pair folded about its centre (section 4.1f)
     int fold_products = 0;             // a folded handle's arithmetic: 3 = Gauss (ddc_mfma_ring16p3f_kernel), 4 = the plain four
                                        // products (ddc_convert4f_kernel + ddc_mfma_ring16p4f_kernel, section 4.1g); 0: not folded
+    int wave_tones = 32;               // tones of a wave's tile: 64 = a handle of four products runs ddc_mfma_ring16p4fw_kernel (section 4.1h)
     gsdr::DevBuf<uint4> d_bfrag3;
     gsdr::DevBuf<float4> d_ptab3;
     gsdr::DevBuf<uint4> d_bfrag;
@@ -517,6 +519,19 @@ int fold_products_chosen(const gsdr_demod *h, bool fold) {
     return p == 3 || p == 4 ? p : kFoldProductsDefault;
 }
 
+// The wave tile of a handle that sums the plain four products: 16 rows x 64 tones
+// (ddc_mfma_ring16p4fw_kernel) copies and reads half the operand bytes of 32 x 32 (ddc_mfma_ring16p4f_kernel) for the
+// same MFMAs per wave and the same bits, but splits the rows over twice the workgroups and the tones over half of them.
+// It is taken where it launches no more waves for the handle's largest row count -- many tones; with 128 tones or
+// fewer it would run twice the workgroups, half of their waves idle.  GSDR_MFMA_WAVE_TONES: 64 = every such handle,
+// 32 = never, unset = by that rule.
+int wave_tones_chosen(const gsdr_demod *h, int fold_products, long long max_rows, long long ntg) {
+    if (fold_products != 4) return 32;
+    const int w = h->sw.mfma_wave_tones;
+    if (w == 32 || w == 64) return w;
+    return ((max_rows + 15) / 16) * ((ntg + 7) / 8) <= ((max_rows + 31) / 32) * ((ntg + 3) / 4) ? 64 : 32;
+}
+
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
 // back into the previous buffer (raw-sample carry); otherwise (TONES/NOISE) row o
 // starts at block o of the raw window.
@@ -621,6 +636,7 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         h->rot2 = rot2_chosen(h, h->mac3, nhi);
         h->fold = fold_chosen(h, h->rot2, nhi);
         h->fold_products = fold_products_chosen(h, h->fold);
+        h->wave_tones = wave_tones_chosen(h, h->mac3 ? h->fold_products : 0, max_rows, pl.ntg);
         if (h->mac3) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
@@ -851,7 +867,8 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     gsdr::MfmaKernel kind = h->mf_kind;
     if (h->mac3) {
         // whatever the entry, the stream pattern or the row count: one arithmetic per handle
-        kind = h->fold ? (h->fold_products == 4 ? gsdr::MfmaKernel::AsmRing16P4F : gsdr::MfmaKernel::AsmRing16P3F)
+        kind = h->fold ? (h->fold_products == 4 ? (h->wave_tones == 64 ? gsdr::MfmaKernel::AsmRing16P4FW : gsdr::MfmaKernel::AsmRing16P4F)
+                                                : gsdr::MfmaKernel::AsmRing16P3F)
                        : (h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3);
         a.img = h->d_img[hs];
         a.bfrag3 = h->d_bfrag3;
@@ -2048,6 +2065,7 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"fold\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? 1 : 0);
     s += ", \"fold_min_blocks\": " + std::to_string(kFoldMinBlocks);
     s += ", \"fold_products\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? h->fold_products : 0);
+    s += ", \"wave_tones\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? h->wave_tones : 32);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"frame_average\": " + std::to_string(h->avg_k);
     s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";

@@ -29,10 +29,6 @@ S_PSTRIDE = 58
 SGPR_CLOBBER = list(range(36, 80))
 
 
-def piece(unit, rh, sp):
-    return 1024 * (4 * unit + 2 * sp + rh)
-
-
 def dma_ops(par, slot_sreg, which):
     """LDS-DMA piece `which` of this wave of the image s[SB[par].x] into ring slot `slot_sreg`.
     M0 carries the wave-uniform LDS address; it is written right in front of its only reader and
@@ -46,6 +42,7 @@ def dma_ops(par, slot_sreg, which):
 
 
 def p_loads(dst, sp_):
+    """The float4 rows (Pr, Pi, -, -) of the two tone quarters of a 32-tone tile."""
     return [f"global_load_dwordx4 {vr(dst, 4)}, %[po], s[{sp_}:{sp_ + 1}]",
             f"global_load_dwordx4 {vr(dst + 4, 4)}, %[po], s[{sp_}:{sp_ + 1}] offset:256"]
 
@@ -62,23 +59,49 @@ class Loop:
       g_pload         gap of the load of the next span's P
       rotation        (p_cur, p_prev) -> [(gap, "rot" | "rotp", v_fma_f32)]: rotp reads this span's P
       vb, acc, kb, f0, p, addr, v_last, nagpr, bf    the register map
+      rows, tq        the wave tile: row halves (of 16 rows) and tone quarters (of 16 tones) per wave, 2 x 2 unless
+                      stated; 1 x 4 takes the pieces of one row half (chosen by the kernel through %[io..]) and the
+                      phasor images and P of two 32-tone tiles (the second through %[bo1], %[po1])
+    What follows from the wave tile: the pieces a wave copies per span (npiece), the ring slot (slot; an image in
+    memory stays units * 4 KiB, image_bytes), piece, frag, mfma_of, b_image, rotate_ops, p_loads.
     late, g_pload, rotation and p belong to the loops that keep P by parity; one that handles P differently
     (ring16p3r2) overrides the methods of the last section instead."""
 
     def __init__(self, **desc):
+        self.rows, self.tq = 2, 2
         self.__dict__.update(desc)
-        self.slot = self.units * 4 * 1024      # bytes of one ring slot
+        assert (self.rows, self.tq) in ((2, 2), (1, 4))
+        self.image_bytes = self.units * 4 * 1024           # a slot image in memory: both row halves
+        self.slot = self.units * 2 * self.rows * 1024      # bytes of one ring slot
+        self.npiece = self.units * self.rows // 2          # 1-KiB pieces of a slot that each of the four waves copies
         self.ng = 12 * self.units              # MFMAs per span
-        assert self.v_last + 1 + self.nagpr <= 256 and 16 * len(self.bf) == self.nagpr
+        assert self.v_last + 1 + self.nagpr <= 256 and 16 * len(self.bf) * (self.tq // 2) == self.nagpr
         assert not (set(self.bf) | {b + 1 for b in self.bf}) - set(SGPR_CLOBBER)
 
-    def frag(self, unit, rh, sp):
-        return self.f0 + 16 * unit + 8 * sp + 4 * rh
+    def piece(self, unit, rh, sp):
+        """byte offset of operand piece (unit, rh, sp) inside a ring slot"""
+        return 1024 * ((2 * unit + sp) * self.rows + rh)
 
-    # MFMA m of a unit: split m // 4, tile m % 4 = 2*rh + th
+    def frag(self, unit, rh, sp):
+        return self.f0 + 4 * ((2 * unit + sp) * self.rows + rh)
+
+    # MFMA m of a unit: split m // 4, tile m % 4 = tq*rh + th
     def mfma_of(self, m):
         s, t = divmod(m, 4)
-        return (t >> 1, t & 1) + self.split[s]    # rh, th, sp_a, sp_b
+        return divmod(t, self.tq) + self.split[s]    # rh, th, sp_a, sp_b
+
+    def b_image(self, image, th, sp):
+        """AGPR (relative to acc_base) of phasor image `image`, tone quarter th, split sp: per 32-tone tile the
+        images lie in the order of the table, (image, tone half, split)"""
+        return ((((th >> 1) * (self.nagpr // 16 // (self.tq // 2)) + image) * 2 + (th & 1)) * 2 + sp) * 4
+
+    def p_loads(self, dst, sp_):
+        """Loads of the P of one span into v[dst : dst + 8]"""
+        if self.tq == 2:
+            return p_loads(dst, sp_)
+        # (Pr, Pi) of four tone quarters: the first two floats of the float4 rows of two 32-tone tiles
+        return [f"global_load_dwordx2 {vr(dst + 2 * q, 2)}, %[{'po1' if q >> 1 else 'po'}], s[{sp_}:{sp_ + 1}]" +
+                (" offset:256" if q & 1 else "") for q in range(4)]
 
     def _uses(self, unit, rh, sp):
         return [12 * unit + m for m in range(12) if self.mfma_of(m)[0] == rh and self.mfma_of(m)[2] == sp]
@@ -94,7 +117,7 @@ class Loop:
         S_X = SB[par]["x"]
         return [
             f"s_min_u32 s{S_T0}, s{S_K}, s{S_NHI1}",
-            f"s_mul_i32 s{S_T1}, s{S_T0}, {self.slot}",
+            f"s_mul_i32 s{S_T1}, s{S_T0}, {self.image_bytes}",
             f"s_add_u32 s{S_X}, s{S_XB}, s{S_T1}",
             f"s_addc_u32 s{S_X + 1}, s{S_XB + 1}, 0",
             f"s_add_u32 s{S_K}, s{S_K}, 1",
@@ -106,9 +129,10 @@ class Loop:
         ops = []
         for part in range(2):                # 0: acc_r, 1: acc_i
             for i in range(16):
-                th = (i >> 2) & 1            # register i belongs to tile (rh, th) = (i >> 3, (i >> 2) & 1)
+                th = (i >> 2) % self.tq      # register i belongs to tile (rh, th) = divmod(i >> 2, tq)
                 c = self.coef[prod][part]
-                coef = c[:-1] + vr(p + 4 * th + "rimp".index(c[-1]))
+                assert "rimp".index(c[-1]) < 8 // self.tq
+                coef = c[:-1] + vr(p + 8 // self.tq * th + "rimp".index(c[-1]))
                 acc, k = vr(self.acc[part] + i), vr(self.kb[prod] + i)
                 ops.append(f"v_fma_f32 {acc}, {coef}, {k}, {acc}")
         return ops
@@ -129,13 +153,13 @@ class Loop:
         registers to clear: the first span rotates the late product "of the span before")"""
         A, B = SB["A"]["p"], SB["B"]["p"]
         return ([f"s_add_u32 s{A}, s{B}, s{S_PSTRIDE}", f"s_addc_u32 s{A + 1}, s{B + 1}, 0", "s_nop 4"] +
-                p_loads(self.p["A"], B), [], [self.kb[self.late]], self.p["B"])
+                self.p_loads(self.p["A"], B), [], [self.kb[self.late]], self.p["B"])
 
     def p_schedule(self, label):
         """[(gap, kind, text, tag)] of P and the rotation in a span of parity `label`"""
         other = "B" if label == "A" else "A"
         S_P, N_P = SB[label]["p"], SB[other]["p"]
-        return [(self.g_pload, "vm", tx, "p" + other) for tx in p_loads(self.p[other], S_P)] + \
+        return [(self.g_pload, "vm", tx, "p" + other) for tx in self.p_loads(self.p[other], S_P)] + \
                [(self.g_pload + 1, "salu", f"s_add_u32 s{N_P}, s{S_P}, s{S_PSTRIDE}", None),
                 (self.g_pload + 1, "salu", f"s_addc_u32 s{N_P + 1}, s{S_P + 1}, 0", None)] + \
                [(g, "rot", op, "p" + label if kind == "rotp" else None)      # loaded one span ago
@@ -170,12 +194,12 @@ def span(v, cnt, out, label):
                 assert NG + g - lu >= 23 and fu - g >= 8, (unit, rh, sp)
                 last_rd = f"f{unit}{rh}{sp}"
             gaps[g].append(("lds", f"ds_read_b128 {vr(v.frag(unit, rh, sp), 4)}, {vr(V_RD if unit else V_RDN)} "
-                            f"offset:{piece(unit, rh, sp)}", f"f{unit}{rh}{sp}"))
-    # image of span s+3 -> slot WR: pointer (this parity's set) in gaps 0..1, one piece per unit at
+                            f"offset:{v.piece(unit, rh, sp)}", f"f{unit}{rh}{sp}"))
+    # image of span s+3 -> slot WR: pointer (this parity's set) in gaps 0..1, this wave's pieces at
     # gaps 2, 10, 18, ..
     for i, sx in enumerate(v.image_pointer(label)):
         gaps[i // 3].append(("salu", sx, None))
-    for which in range(v.units):
+    for which in range(v.npiece):
         for tx in dma_ops(label, S_WR, which):
             gaps[2 + 8 * which].append(("dma" if tx.startswith("global") else "salu", tx, f"d{which}{label}"))
     for g, kind, text, tag in v.p_schedule(label):
@@ -196,11 +220,11 @@ def span(v, cnt, out, label):
         rh, th, sp_a, sp_b = v.mfma_of(m)
         if v.first_use(unit, rh, sp_a) == g:
             cnt.need_lgkm(f"f{unit}{rh}{sp_a}")
-        dst = v.kb[v.prod[unit]] + 4 * (2 * rh + th)
+        dst = v.kb[v.prod[unit]] + 4 * (v.tq * rh + th)
         first = v.prod.index(v.prod[unit]) == unit and m < 4 and v.from_zero(label)
         if "mfma" not in ABLATE:
             out.append(f"v_mfma_f32_16x16x32_f16 {vr(dst, 4)}, {vr(v.frag(unit, rh, sp_a), 4)}, "
-                       f"{ar(v.acc_base(label) + ((v.image[unit] * 2 + th) * 2 + sp_b) * 4)}, {'0' if first else vr(dst, 4)}")
+                       f"{ar(v.acc_base(label) + v.b_image(v.image[unit], th, sp_b))}, {'0' if first else vr(dst, 4)}")
         for kind, text, tag in gaps[g]:
             if kind == "lds":
                 if "lds" not in ABLATE:
@@ -223,7 +247,7 @@ def span(v, cnt, out, label):
                 out.append(text)
     # the image this wave started one span ago (span s+2's) must have landed before the barrier
     # publishes it: span s+1 prefetches from it
-    cnt.need_vm(f"d{v.units - 1}{other}")
+    cnt.need_vm(f"d{v.npiece - 1}{other}")
     # every read of THIS span's slot has returned (the barrier frees it for the copy of span s+4); the
     # prefetch of span s+1's first fragments (from the next slot) stays in flight across it
     cnt.need_lgkm(last_rd)
@@ -259,10 +283,11 @@ def generate(v):
         o(f"s_add_u32 s{v.bf[j]}, s{S_BF}, {4096 * j}")
         o(f"s_addc_u32 s{v.bf[j] + 1}, s{S_BF + 1}, 0")
     out.extend(p_load)
+    per_tile = 4 * len(v.bf)                # 1-KiB images of a 32-tone tile
     for f in range(v.nagpr // 4):
-        b = v.bf[f // 4]
+        b = v.bf[f % per_tile // 4]
         if "bimg" not in ABLATE:
-            o(f"global_load_dwordx4 {ar(4 * f)}, %[bo], s[{b}:{b + 1}] offset:{(f % 4) * 1024}")
+            o(f"global_load_dwordx4 {ar(4 * f)}, %[{'bo1' if f // per_tile else 'bo'}], s[{b}:{b + 1}] offset:{(f % 4) * 1024}")
     for base in zero_k + list(v.acc):
         for i in range(16):
             o(f"v_mov_b32 {vr(base + i)}, 0")
@@ -271,7 +296,7 @@ def generate(v):
     # images of spans 0, 1, 2 into slots 0, 1, 2 (pointer sets A, B, C: one per image)
     for par, slot in (("A", S_RD), ("B", S_RDN), ("C", S_RD2)):
         out.extend(v.image_pointer(par))
-        for which in range(v.units):
+        for which in range(v.npiece):
             o("s_nop 4")
             out.extend(dma_ops(par, slot, which))
         o("s_nop 4")
@@ -281,8 +306,8 @@ def generate(v):
     o("s_waitcnt vmcnt(0)")          # P of span 0, the phasor images and the three slot images
     out.extend(p_landed)
     o("s_barrier")
-    for rh, sp in ((0, 0), (1, 0), (0, 1), (1, 1)):
-        o(f"ds_read_b128 {vr(v.frag(0, rh, sp), 4)}, {vr(V_RD)} offset:{piece(0, rh, sp)}")
+    for rh, sp in ((rh, sp) for sp in range(2) for rh in range(v.rows)):
+        o(f"ds_read_b128 {vr(v.frag(0, rh, sp), 4)}, {vr(V_RD)} offset:{v.piece(0, rh, sp)}")
     o("s_waitcnt lgkmcnt(0)")
     cnt.lgkm = []
 
