@@ -233,6 +233,19 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
 enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F, AsmRing16P4FW };
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);
 const char *ddc_mfma_kernel_name(MfmaKernel kind);
+// What the host knows of one loop of the pre-converted family (AsmRing16P ... AsmRing16P4FW, all named
+// ddc_mfma_ring16p_kernel).  The rows stand in ddc_mfma.hip next to launch_ddc_mfma, which keeps each loop's conversion
+// kernel, loop kernel and grid rule beside them; demod.cpp picks a handle's row once (product_loop_chosen) and sizes,
+// fills, launches and describes by it.
+struct ProductLoop {
+    MfmaKernel kind;
+    int complex_mac, rotation_blocks, fold, fold_products, wave_tones;      // the handle's describe() values
+    int image_blocks;          // 32-sample blocks an image of MfmaLaunch::img holds: 1, or 2 (a folded span)
+    int image_uint4;           // uint4 per image: 512 (8 KiB), 768 (12 KiB) or 1024 (16 KiB)
+    // bfrag3 / ptab3 of the loop; null: AsmRing16P reads the tables of mfma_build_tables only
+    void (*build_tables)(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3, std::vector<float4> &ptab3);
+};
+const ProductLoop *product_loop(MfmaKernel kind);      // null: `kind` is not of the family
 
 // ---- batched FFT of arbitrary length + polyphase filter (NOISE mode, fft_kernels.hip) ----
 struct FftPlan {

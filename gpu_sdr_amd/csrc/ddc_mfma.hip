@@ -1665,6 +1665,44 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
     return hipGetLastError();
 }
 
+// The pre-converted family, one row per loop: what the host knows of it (ProductLoop, ddc_kernels.h: kind, the five
+// describe() values, blocks per image, uint4 per image -- 8 KiB per block, 12 KiB per block for the three-product
+// loops, 16 KiB per span of two blocks for the folded ones --, table builder) and what only the launch needs: the
+// conversion pass (conv: an image per block, convf: an image per span; one of the two) and its workgroup, the loop
+// that copies the images, and whether the grid is that of the wide tile (16-row tiles, eight 32-tone tiles per
+// workgroup).
+struct ProductLoopRow {
+    ProductLoop d;
+    void (*conv)(const MfmaLaunch, uint4 *, int);
+    void (*convf)(const MfmaLaunch, uint4 *, int, int);
+    unsigned conv_threads;
+    void (*loop)(const MfmaLaunch);
+    bool wide;
+};
+static void build_tables3_block(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3, std::vector<float4> &ptab3) {
+    mfma_build_tables3(pl, 1, fmod, bfrag3, ptab3);
+}
+static void build_tables3_pair(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3, std::vector<float4> &ptab3) {
+    mfma_build_tables3(pl, 2, fmod, bfrag3, ptab3);
+}
+static const ProductLoopRow kProductLoops[] = {
+    {{MfmaKernel::AsmRing16P, 4, 1, 0, 0, 32, 1, 512, nullptr}, ddc_convert_kernel, nullptr, 256, ddc_mfma_ring16p_kernel, false},
+    {{MfmaKernel::AsmRing16P3, 3, 1, 0, 0, 32, 1, 768, build_tables3_block}, ddc_convert3_kernel, nullptr, 128, ddc_mfma_ring16p3_kernel, false},
+    {{MfmaKernel::AsmRing16P3R2, 3, 2, 0, 0, 32, 1, 768, build_tables3_pair}, ddc_convert3_kernel, nullptr, 128, ddc_mfma_ring16p3r2_kernel, false},
+    {{MfmaKernel::AsmRing16P3F, 3, 2, 1, 3, 32, 2, 1024, mfma_build_tables3f}, nullptr, ddc_convert3f_kernel, 128, ddc_mfma_ring16p3f_kernel, false},
+    {{MfmaKernel::AsmRing16P4F, 3, 2, 1, 4, 32, 2, 1024, mfma_build_tables4f}, nullptr, ddc_convert4f_kernel, 128, ddc_mfma_ring16p4f_kernel, false},
+    {{MfmaKernel::AsmRing16P4FW, 3, 2, 1, 4, 64, 2, 1024, mfma_build_tables4f}, nullptr, ddc_convert4f_kernel, 128, ddc_mfma_ring16p4fw_kernel, true},
+};
+static const ProductLoopRow *product_loop_row(MfmaKernel kind) {
+    for (const ProductLoopRow &r : kProductLoops)
+        if (r.d.kind == kind) return &r;
+    return nullptr;
+}
+const ProductLoop *product_loop(MfmaKernel kind) {
+    const ProductLoopRow *r = product_loop_row(kind);
+    return r ? &r->d : nullptr;
+}
+
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st) {
     const MfmaShape &sh = a.sh;
     // shapes are checked on the host: a kernel reading past its tables faults the GPU
@@ -1691,46 +1729,26 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
         return hipErrorInvalidValue;
     }
     if (TT != 1 || PK != 32 || W != 4) return hipErrorInvalidValue;      // the assembly kernels
+    if (const ProductLoopRow *r = product_loop_row(kind)) {
+        // the conversion pass, then the loop that copies its images.  a.img: ngt * nimg images of the row's size;
+        // a.bfrag3 / a.ptab3: the tables of the row's builder
+        if (!a.img || (r->d.build_tables && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
+        const int nhi = (sh.nk8 + 3) / 4, nimg = (nhi + r->d.image_blocks - 1) / r->d.image_blocks;
+        const long long cgrid = (long long)sh.ngt * nimg;
+        const unsigned grid = r->wide ? ring_grid((sh.nout + 15) / 16, (sh.ntg + 7) / 8, 1) : ring_grid(sh.ngt, sh.ntq, 1);
+        if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
+        uint4 *img = const_cast<uint4 *>(a.img);
+        if (r->convf)
+            hipLaunchKernelGGL(r->convf, dim3((unsigned)cgrid), dim3(r->conv_threads), 0, st, a, img, nhi, nimg);
+        else
+            hipLaunchKernelGGL(r->conv, dim3((unsigned)cgrid), dim3(r->conv_threads), 0, st, a, img, nhi);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(r->loop, dim3(grid), dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
     unsigned grid = 0;
     switch (kind) {
-        case MfmaKernel::AsmRing16P:
-        case MfmaKernel::AsmRing16P3:
-        case MfmaKernel::AsmRing16P3R2:
-        case MfmaKernel::AsmRing16P3F:
-        case MfmaKernel::AsmRing16P4F:
-        case MfmaKernel::AsmRing16P4FW: {
-            // the conversion pass, then the loop that copies its images.  a.img: ngt * nimg images -- of 8 KiB per block,
-            // of 12 KiB per block for the three-product loops, of 16 KiB per span of two blocks for the folded ones;
-            // a.bfrag3 / a.ptab3: the tables of the product loop launched (mfma_build_tables3, 3f, 4f)
-            void (*conv)(const MfmaLaunch, uint4 *, int) = nullptr;             // an image per block
-            void (*convf)(const MfmaLaunch, uint4 *, int, int) = nullptr;       // an image per span
-            void (*loop)(const MfmaLaunch) = nullptr;
-            switch (kind) {
-                case MfmaKernel::AsmRing16P: conv = ddc_convert_kernel, loop = ddc_mfma_ring16p_kernel; break;
-                case MfmaKernel::AsmRing16P3: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3_kernel; break;
-                case MfmaKernel::AsmRing16P3R2: conv = ddc_convert3_kernel, loop = ddc_mfma_ring16p3r2_kernel; break;
-                case MfmaKernel::AsmRing16P3F: convf = ddc_convert3f_kernel, loop = ddc_mfma_ring16p3f_kernel; break;
-                case MfmaKernel::AsmRing16P4FW: convf = ddc_convert4f_kernel, loop = ddc_mfma_ring16p4fw_kernel; break;
-                default: convf = ddc_convert4f_kernel, loop = ddc_mfma_ring16p4f_kernel;
-            }
-            const bool products = kind != MfmaKernel::AsmRing16P;
-            if (!a.img || (products && (!a.bfrag3 || !a.ptab3))) return hipErrorInvalidValue;
-            const int nhi = (sh.nk8 + 3) / 4, nimg = convf ? (nhi + 1) / 2 : nhi;
-            const long long cgrid = (long long)sh.ngt * nimg;
-            // the wide loop: 16-row tiles, eight 32-tone tiles per workgroup
-            grid = kind == MfmaKernel::AsmRing16P4FW ? ring_grid((sh.nout + 15) / 16, (sh.ntg + 7) / 8, 1)
-                                                     : ring_grid(sh.ngt, sh.ntq, 1);
-            if (cgrid < 1 || cgrid > 0x7fffffffLL || !grid) return hipErrorInvalidValue;
-            uint4 *img = const_cast<uint4 *>(a.img);
-            if (convf)
-                hipLaunchKernelGGL(convf, dim3((unsigned)cgrid), dim3(128), 0, st, a, img, nhi, nimg);
-            else
-                hipLaunchKernelGGL(conv, dim3((unsigned)cgrid), dim3(products ? 128 : 256), 0, st, a, img, nhi);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(loop, dim3(grid), dim3(256), 0, st, a);
-            return hipGetLastError();
-        }
         case MfmaKernel::AsmRing16W8:
             if (!(grid = ring_grid(sh.ngt, (sh.ntg + 7) / 8, 1))) return hipErrorInvalidValue;
             hipLaunchKernelGGL(ddc_mfma_ring16w8_kernel, dim3(grid), dim3(512), 0, st, a);
@@ -1751,13 +1769,8 @@ hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLau
 }
 
 const char *ddc_mfma_kernel_name(MfmaKernel kind) {
+    if (product_loop_row(kind)) return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
     switch (kind) {
-        case MfmaKernel::AsmRing16P:
-        case MfmaKernel::AsmRing16P3:
-        case MfmaKernel::AsmRing16P3R2:
-        case MfmaKernel::AsmRing16P3F:
-        case MfmaKernel::AsmRing16P4F:
-        case MfmaKernel::AsmRing16P4FW: return "ddc_mfma_ring16p_kernel";     // one name for the pre-converted family
         case MfmaKernel::AsmRing16W8: return "ddc_mfma_ring16w8_kernel";
         case MfmaKernel::AsmRing16: return "ddc_mfma_ring16_kernel";
         case MfmaKernel::AsmRing: return "ddc_mfma_ring_kernel";

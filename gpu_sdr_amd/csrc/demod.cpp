@@ -182,14 +182,10 @@ struct gsdr_demod {
     // rounds: one image set per staging set (the main kernels of the calls in flight read theirs)
     bool prec = false;                 // image sets allocated: the path may be chosen
     gsdr::DevBuf<uint4> d_img[kStageSets];
-    // three real products per complex multiply (ddc_convert3_kernel + ddc_mfma_ring16p3_kernel, DESIGN.md section
-    // 4.1d): decided once, in setup_mfma; such a handle sends EVERY matrix-core launch through that pair
-    bool mac3 = false;
-    bool rot2 = false;                 // ... through ddc_mfma_ring16p3r2_kernel: one rotation per pair of blocks (section 4.1e)
-    bool fold = false;                 // ... through ddc_mfma_ring16p3f_kernel: each pair folded about its centre (section 4.1f)
-    int fold_products = 0;             // a folded handle's arithmetic: 3 = Gauss (ddc_mfma_ring16p3f_kernel), 4 = the plain four
-                                       // products (ddc_convert4f_kernel + ddc_mfma_ring16p4f_kernel, section 4.1g); 0: not folded
-    int wave_tones = 32;               // tones of a wave's tile: 64 = a handle of four products runs ddc_mfma_ring16p4fw_kernel (section 4.1h)
+    // the product loop of a handle with three real products per complex multiply (DESIGN.md sections 4.1d - 4.1h; a row
+    // of gsdr::product_loop): decided once, in setup_mfma (product_loop_chosen); such a handle sends EVERY matrix-core
+    // launch through that row's kernel pair.  Null: four products per block, the loop chosen per launch (enqueue_mfma)
+    const gsdr::ProductLoop *loop = nullptr;
     gsdr::DevBuf<uint4> d_bfrag3;
     gsdr::DevBuf<float4> d_ptab3;
     gsdr::DevBuf<uint4> d_bfrag;
@@ -477,9 +473,6 @@ bool prec_pays(const gsdr_demod *h, long long ngt, bool overlap) {
 // which test_gpu_mfma3.py::test_hdr_comb_sets_threshold measured the rule kept at every tested length.
 // GSDR_MFMA_3M: 1 = wherever there are images, 0 = never.
 constexpr long long kMac3MinBlocks = 94;
-bool mac3_chosen(const gsdr_demod *h, bool images, long long nhi) {
-    return images && (h->sw.mfma_3m == 1 || (h->sw.mfma_3m < 0 && nhi >= kMac3MinBlocks));
-}
 
 // A three-product handle rotates its partial sums into the accumulators once per pair of blocks
 // (ddc_mfma_ring16p3r2_kernel) instead of once per block: half the rotation FMAs, phasor images
@@ -489,9 +482,6 @@ bool mac3_chosen(const gsdr_demod *h, bool images, long long nhi) {
 // length (err / bound 0.84, 0.78, 0.56 at 94, 125, 250 blocks; shorter windows were not measured and keep the
 // 32-sample loop).  GSDR_MFMA_3M_ROT: 2 = every three-product handle, 1 (or anything else) = never.
 constexpr long long kRot2MinBlocks = 94;
-bool rot2_chosen(const gsdr_demod *h, bool mac3, long long nhi) {
-    return mac3 && nhi >= 1 && (h->sw.mfma_3m_rot == 2 || (h->sw.mfma_3m_rot < 0 && nhi >= kRot2MinBlocks));
-}
 
 // A handle that rotates once per pair folds each 64-sample span about its centre (ddc_convert3f_kernel +
 // ddc_mfma_ring16p3f_kernel): the phasor of sample j and of its partner 63 - j are conjugates, so
@@ -502,22 +492,14 @@ bool rot2_chosen(const gsdr_demod *h, bool mac3, long long nhi) {
 // it and every longer tested one (err / bound 0.84, 0.70, 0.51 at 94, 125, 250 blocks, against 0.84, 0.78, 0.56 not
 // folded; DESIGN.md section 4.1f, profiles/fold_parity_margins.json).  GSDR_MFMA_FOLD: 1 = every handle that rotates per pair, 0 (or anything else) = never.
 constexpr long long kFoldMinBlocks = 94;
-bool fold_chosen(const gsdr_demod *h, bool rot2, long long nhi) {
-    return rot2 && (h->sw.mfma_fold == 1 || (h->sw.mfma_fold < 0 && nhi >= kFoldMinBlocks));
-}
 
 // The arithmetic of a folded handle.  The plain four products fold completely -- the same
 // four units of K = 32 and 48 MFMAs per span as the Gauss fold, whose third sum has no symmetry -- and need two
 // product tile sets, the images of c and d only and 64 rotation FMAs per span instead of 96.  complex_mac,
-// rotation_blocks and fold in describe() name the rule that selected the handle (mac3_chosen, rot2_chosen,
-// fold_chosen: unchanged); fold_products names what it computes.  GSDR_MFMA_FOLD_PRODUCTS: 3 = the Gauss fold, 4 = the
+// rotation_blocks and fold in describe() name the rule that selected the handle (the three above: unchanged);
+// fold_products names what it computes.  GSDR_MFMA_FOLD_PRODUCTS: 3 = the Gauss fold, 4 = the
 // direct fold, unset = kFoldProductsDefault.
 constexpr int kFoldProductsDefault = 4;
-int fold_products_chosen(const gsdr_demod *h, bool fold) {
-    if (!fold) return 0;
-    const int p = h->sw.mfma_fold_products;
-    return p == 3 || p == 4 ? p : kFoldProductsDefault;
-}
 
 // The wave tile of a handle that sums the plain four products: 16 rows x 64 tones
 // (ddc_mfma_ring16p4fw_kernel) copies and reads half the operand bytes of 32 x 32 (ddc_mfma_ring16p4f_kernel) for the
@@ -525,11 +507,22 @@ int fold_products_chosen(const gsdr_demod *h, bool fold) {
 // It is taken where it launches no more waves for the handle's largest row count -- many tones; with 128 tones or
 // fewer it would run twice the workgroups, half of their waves idle.  GSDR_MFMA_WAVE_TONES: 64 = every such handle,
 // 32 = never, unset = by that rule.
-int wave_tones_chosen(const gsdr_demod *h, int fold_products, long long max_rows, long long ntg) {
-    if (fold_products != 4) return 32;
-    const int w = h->sw.mfma_wave_tones;
-    if (w == 32 || w == 64) return w;
-    return ((max_rows + 15) / 16) * ((ntg + 7) / 8) <= ((max_rows + 31) / 32) * ((ntg + 3) / 4) ? 64 : 32;
+//
+// The row of gsdr::product_loop for a handle by the five rules above, each asked only of a handle the one before it
+// took; null without images.  nhi: the window in 32-sample blocks; max_rows, ntg: the handle's largest row count and
+// its tone groups.
+const gsdr::ProductLoop *product_loop_chosen(const gsdr_demod *h, bool images, long long nhi, long long max_rows, long long ntg) {
+    using K = gsdr::MfmaKernel;
+    const gsdr::Switches &sw = h->sw;
+    const bool mac3 = images && (sw.mfma_3m == 1 || (sw.mfma_3m < 0 && nhi >= kMac3MinBlocks));
+    const bool rot2 = mac3 && nhi >= 1 && (sw.mfma_3m_rot == 2 || (sw.mfma_3m_rot < 0 && nhi >= kRot2MinBlocks));
+    const bool fold = rot2 && (sw.mfma_fold == 1 || (sw.mfma_fold < 0 && nhi >= kFoldMinBlocks));
+    const int p = sw.mfma_fold_products, w = sw.mfma_wave_tones;
+    const int products = p == 3 || p == 4 ? p : kFoldProductsDefault;
+    const bool wide = w == 32 || w == 64 ? w == 64 : ((max_rows + 15) / 16) * ((ntg + 7) / 8) <= ((max_rows + 31) / 32) * ((ntg + 3) / 4);
+    const K kind = !mac3 ? K::AsmRing16P : !rot2 ? K::AsmRing16P3 : !fold ? K::AsmRing16P3R2 : products != 4 ? K::AsmRing16P3F
+                   : wide ? K::AsmRing16P4FW : K::AsmRing16P4F;
+    return images ? gsdr::product_loop(kind) : nullptr;
 }
 
 // Tables and fixed shape of ddc_mfma_kernel.  `direct`: rows reach F-1 blocks
@@ -623,35 +616,23 @@ int setup_mfma(gsdr_demod *h, bool direct, const std::vector<long long> &tone) {
         const long long max_rows = direct ? h->L / M : (long long)h->batching;
         const long long ngt_max = (max_rows + 31) / 32;
         const long long nhi = (pl.nk8 + 3) / 4;
-        bool want = prec_pays(h, ngt_max, /*overlap=*/true);
-        const bool mac3 = mac3_chosen(h, want, nhi);
-        const bool fold = fold_chosen(h, rot2_chosen(h, mac3, nhi), nhi);
+        const gsdr::ProductLoop *row = product_loop_chosen(h, prec_pays(h, ngt_max, /*overlap=*/true), nhi, max_rows, pl.ntg);
         // uint4 per image set: 12 / 8 KiB per block, folded 16 KiB per pair of blocks
-        const size_t img_n = fold ? (size_t)ngt_max * (size_t)((nhi + 1) / 2) * 1024
-                                  : (size_t)ngt_max * (size_t)nhi * (mac3 ? 768 : 512);
-        if (want && img_n * sizeof(uint4) > (size_t)8 << 30) want = false;
-        for (int i = 0; i < kStageSets && want; ++i) HIPCHK(h, h->d_img[i].alloc(img_n));
-        h->prec = want;
-        h->mac3 = want && mac3;
-        h->rot2 = rot2_chosen(h, h->mac3, nhi);
-        h->fold = fold_chosen(h, h->rot2, nhi);
-        h->fold_products = fold_products_chosen(h, h->fold);
-        h->wave_tones = wave_tones_chosen(h, h->mac3 ? h->fold_products : 0, max_rows, pl.ntg);
-        if (h->mac3) {
+        const size_t img_n = row ? (size_t)ngt_max * (size_t)((nhi + row->image_blocks - 1) / row->image_blocks) * row->image_uint4 : 0;
+        if (img_n * sizeof(uint4) > (size_t)8 << 30) row = nullptr;
+        for (int i = 0; i < kStageSets && row; ++i) HIPCHK(h, h->d_img[i].alloc(img_n));
+        h->prec = row != nullptr;
+        h->loop = row && row->build_tables ? row : nullptr;      // AsmRing16P's row: chosen per launch
+        if (h->loop) {
             std::vector<uint4> bfrag3;
             std::vector<float4> ptab3;
-            if (h->fold_products == 4)
-                gsdr::mfma_build_tables4f(pl, fmod, bfrag3, ptab3);
-            else if (h->fold)
-                gsdr::mfma_build_tables3f(pl, fmod, bfrag3, ptab3);
-            else
-                gsdr::mfma_build_tables3(pl, h->rot2 ? 2 : 1, fmod, bfrag3, ptab3);
+            row->build_tables(pl, fmod, bfrag3, ptab3);
             HIPCHK(h, h->d_bfrag3.upload(bfrag3));
             HIPCHK(h, h->d_ptab3.upload(ptab3));
         }
     }
     h->mfma = true;
-    h->kernel_name = gsdr::ddc_mfma_kernel_name(h->mac3 ? gsdr::MfmaKernel::AsmRing16P3 : h->mf_kind);
+    h->kernel_name = gsdr::ddc_mfma_kernel_name(h->loop ? h->loop->kind : h->mf_kind);
     return 0;
 }
 
@@ -796,7 +777,7 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     sg.seg_clear = h->d_segmax + (size_t)next * h->nseg_alloc;
     sg.nseg_alloc = h->nseg_alloc;
     sg.seg_len = (long long)h->seg_k * a.sh.M;
-    if (h->mac3) a.sh.rt = 1;       // one kernel pair for every launch of the handle
+    if (h->loop) a.sh.rt = 1;       // one kernel pair for every launch of the handle
     if (a.sh.rt == 0) {
         // Two row tiles per workgroup (the second keeps the phasor images: 64 KiB less to load, one
         // preamble less, half as many workgroups).  Measured at decim 100 (13-block windows) for
@@ -865,11 +846,9 @@ int enqueue_mfma(gsdr_demod *h, const float2 *in, float2 *raw, long long raw_new
     // partners), that kernel ends 4-7 % earlier (C3: 145 against 152-158 us).  The overlapped entries
     // keep the 4-wave kernel: there the next buffer's workgroups fill the slots the older ones free.
     gsdr::MfmaKernel kind = h->mf_kind;
-    if (h->mac3) {
+    if (h->loop) {
         // whatever the entry, the stream pattern or the row count: one arithmetic per handle
-        kind = h->fold ? (h->fold_products == 4 ? (h->wave_tones == 64 ? gsdr::MfmaKernel::AsmRing16P4FW : gsdr::MfmaKernel::AsmRing16P4F)
-                                                : gsdr::MfmaKernel::AsmRing16P3F)
-                       : (h->rot2 ? gsdr::MfmaKernel::AsmRing16P3R2 : gsdr::MfmaKernel::AsmRing16P3);
+        kind = h->loop->kind;
         a.img = h->d_img[hs];
         a.bfrag3 = h->d_bfrag3;
         a.ptab3 = h->d_ptab3;
@@ -2058,14 +2037,16 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
          h->noise_fft ? "fp32 Stockham FFT behind the polyphase filter" : h->mfma ? "f16 MFMA, hi/lo split" : (h->mode == GSDR_CHIRP ? "fp32 VALU, integer phase" : (h->pipe ? "packed fp32 VALU" : "fp32 VALU"));
     s += "\", \"channels\": " + std::to_string(h->ddc_channels > 0 ? h->ddc_channels : h->N);
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
-    s += ", \"complex_mac\": " + std::to_string(h->mfma && h->mac3 ? 3 : 4);
+    // every other handle reports what the four-product loop's row says
+    const gsdr::ProductLoop &pr = h->mfma && h->loop ? *h->loop : *gsdr::product_loop(gsdr::MfmaKernel::AsmRing16P);
+    s += ", \"complex_mac\": " + std::to_string(pr.complex_mac);
     s += ", \"complex_mac_min_blocks\": " + std::to_string(kMac3MinBlocks);
-    s += ", \"rotation_blocks\": " + std::to_string(h->mfma && h->mac3 && h->rot2 ? 2 : 1);
+    s += ", \"rotation_blocks\": " + std::to_string(pr.rotation_blocks);
     s += ", \"rotation_min_blocks\": " + std::to_string(kRot2MinBlocks);
-    s += ", \"fold\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? 1 : 0);
+    s += ", \"fold\": " + std::to_string(pr.fold);
     s += ", \"fold_min_blocks\": " + std::to_string(kFoldMinBlocks);
-    s += ", \"fold_products\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? h->fold_products : 0);
-    s += ", \"wave_tones\": " + std::to_string(h->mfma && h->mac3 && h->rot2 && h->fold ? h->wave_tones : 32);
+    s += ", \"fold_products\": " + std::to_string(pr.fold_products);
+    s += ", \"wave_tones\": " + std::to_string(pr.wave_tones);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"frame_average\": " + std::to_string(h->avg_k);
     s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from _extents import PATTERNS, check_input_untouched, check_output, guarded_input, guarded_output
+from _product_loops import LOOPS
 from test_gpu_parity import (CHIRP_CASES, PFB_LDS_KERNELS, PFB_VARIANTS, TOL, crandn, make_chirp, make_direct, make_pfb,
                              rel_err_per_tone)
 
@@ -180,8 +181,8 @@ DIRECT_ENGINES = {
     "mfma16w8": (dict(_MF, GSDR_MFMA_ASM="5", GSDR_MFMA_PREC="0"), "ddc_mfma_ring16w8_kernel", None),
     "mfma16p":  (_PRE, P16, "by window"),
     "mfma_c":   (dict(_MF, GSDR_MFMA_ASM="0"), "ddc_mfma_kernel", None),
-    "mac3":     (dict(_PRE, GSDR_MFMA_3M="1", GSDR_MFMA_3M_ROT="1"), P16, (3, 1)),
-    "mac3r2":   (dict(_PRE, GSDR_MFMA_3M="1", GSDR_MFMA_3M_ROT="2", GSDR_TONES_FFT="0"), P16, (3, 2)),   # = forced_r2
+    "mac3":     (LOOPS["p3"][0], P16, (3, 1)),
+    "mac3r2":   (LOOPS["p3r2"][0], P16, (3, 2)),
 }
 MATRIX_ENGINES = ("mfma", "mfma16", "mfma16w8", "mfma16p", "mfma_c", "mac3", "mac3r2")
 

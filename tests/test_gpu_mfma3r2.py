@@ -2,155 +2,36 @@
 ddc_mfma_ring16p3r2_kernel; switch GSDR_MFMA_3M_ROT).
 
 Per-tone relative error against the fp64 oracle, bar 1e-5 as everywhere; every figure goes to the margin
-file.  The cases, the comb and the helpers are those of tests/test_gpu_parity.py and tests/test_gpu_mfma3.py."""
+file.  The cases every product loop runs are in tests/test_gpu_product_loops.py; the comb and the helpers are those of
+tests/test_gpu_parity.py and tests/_product_loops.py."""
 import numpy as np
 import pytest
 
 from _margins import record_info, record_margin
-from test_gpu_parity import (DIRECT_CASES, TOL, crandn, make_direct, make_pfb, rel_err_per_tone, run_device, run_host)
-from test_gpu_mfma3 import C3, VALU_CASES, _c3_handle, _hdr_errors, _HDR_REFS
+from _product_loops import (_c3_handle, COMMON, direct_parity, every_entry_is_bit_identical,
+                            extreme_and_nonfinite_samples, EXTREME_KINDS, EXTREME_SHAPES, force, _hdr_errors,
+                            _HDR_REFS, KERNEL, shape_id)
+from test_gpu_extents import clean_env
+from test_gpu_parity import DIRECT_CASES, make_direct, TOL
 
 pytestmark = pytest.mark.gpu
 
-KERNEL = "ddc_mfma_ring16p_kernel"          # the name every pre-converted loop reports
+
+@pytest.mark.parametrize("case", DIRECT_CASES, ids=shape_id)
+def test_direct_parity_pair_rotation(cuda_device, gsdr_lib, oracle_mod, monkeypatch, case):
+    """The parity sweep every product loop runs (direct_parity of tests/_product_loops.py), ddc_mfma_ring16p3r2_kernel
+    forced."""
+    force(monkeypatch, "p3r2")
+    direct_parity(cuda_device, oracle_mod, "p3r2", case)
 
 
-@pytest.fixture
-def forced_r2(monkeypatch):
-    monkeypatch.setenv("GSDR_DDC_MFMA", "1")
-    monkeypatch.setenv("GSDR_MFMA_ASM", "4")
-    monkeypatch.setenv("GSDR_MFMA_PREC", "1")
-    monkeypatch.setenv("GSDR_MFMA_3M", "1")
-    monkeypatch.setenv("GSDR_MFMA_3M_ROT", "2")
-    monkeypatch.setenv("GSDR_DDC_FEW", "0")
-    monkeypatch.setenv("GSDR_TONES_FFT", "0")
-
-
-def _is_r2(dem):
-    d = dem.describe()
-    return dem.kernel_name == KERNEL and d["complex_mac"] == 3 and d["rotation_blocks"] == 2
-
-
-@pytest.mark.parametrize("case", DIRECT_CASES, ids=lambda c: "N%d_M%d_F%d_L%d" % (c[0], c[2], c[3], c[4]))
-def test_direct_parity_pair_rotation(cuda_device, gsdr_lib, oracle_mod, forced_r2, case):
-    """One row tile, a partial last tile, N no multiple of 32, windows of one block, odd and even block counts,
-    M*F no multiple of 32, F from 1 to 8, consecutive buffers through both entries."""
-    N, rate, M, F, L, nbuf = case
-    rng = np.random.default_rng(1000 + N + M)
-    freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
-    if N >= 3:
-        freq[0], freq[1], freq[2] = 0, rate // 2 - 1, -(rate // 2) + 1
-    dem = make_direct(freq, rate, M, F, L)
-    if case in VALU_CASES:
-        assert not dem.kernel_name.startswith("ddc_mfma"), dem.kernel_name
-        assert dem.describe()["rotation_blocks"] == 1
-    else:
-        assert _is_r2(dem), (dem.kernel_name, dem.describe())
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    for c in range(nbuf):
-        x = crandn(rng, L)
-        y = (run_host if c % 2 else run_device)(dem, x, *(() if c % 2 else (cuda_device,)))
-        yr = ref.process(x)
-        assert y.size == yr.size == N * (L // M)
-        err = rel_err_per_tone(y.reshape(-1, N), yr)
-        print(f"case {case} ({(M * F + 31) // 32} blocks) buffer {c}: worst per-tone error {err.max():.3e}")
-        assert err.max() <= TOL, (c, err.max())
-    if case not in VALU_CASES:
-        assert _is_r2(dem)
-    dem.close()
-
-
-@pytest.mark.parametrize("blocks", [1, 2, 3, 4, 5])
-def test_shortest_windows(cuda_device, gsdr_lib, oracle_mod, forced_r2, blocks):
-    """Windows of one to five blocks: both exits of the trip with no, one and two whole trips in front."""
-    N, rate, F = 40, 1_000_000, 4
-    M = 8 * blocks                      # M * F = 32 * blocks
-    L = 64 * M
-    rng = np.random.default_rng(31 + blocks)
-    freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
-    dem = make_direct(freq, rate, M, F, L)
-    assert _is_r2(dem), (dem.kernel_name, dem.describe())
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    for c in range(3):
-        x = crandn(rng, L)
-        y = run_device(dem, x, cuda_device)
-        yr = ref.process(x)
-        err = rel_err_per_tone(y.reshape(-1, N), yr)
-        print(f"{blocks} blocks buffer {c}: worst per-tone error {err.max():.3e}")
-        assert err.max() <= TOL, (c, err.max())
-    dem.close()
-
-
-def test_tones_on_the_ddc_kernels_pair_rotation(cuda_device, gsdr_lib, oracle_mod, forced_r2):
-    """TONES through the DDC kernels, buffer length no multiple of nfft (short last batches)."""
-    N, rate, nfft, avg, L, nbuf = 5, 200_000_000, 1000, 4, 50_123, 4
-    rng = np.random.default_rng(2000 + nfft + avg)
-    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-    freq[0] = 0
-    dem = make_pfb(freq, rate, nfft, avg, L)
-    assert _is_r2(dem), (dem.kernel_name, dem.describe())
-    ref = oracle_mod.Pfb(freq, rate, nfft, avg, L)
-    emitted = 0
-    for c in range(nbuf):
-        x = crandn(rng, L)
-        y = (run_host if c % 2 else run_device)(dem, x, *(() if c % 2 else (cuda_device,)))
-        yr = ref.process(x)
-        assert y.size == yr.size, (c, y.size, yr.size)
-        emitted += len(yr)
-        if len(yr):
-            err = rel_err_per_tone(y.reshape(-1, N), yr)
-            print(f"tones buffer {c}: worst per-tone error {err.max():.3e}")
-            assert err.max() <= TOL, (c, err.max())
-    assert emitted > 0
-    assert _is_r2(dem)
-    dem.close()
-
-
-@pytest.mark.parametrize("kind", ["1e8", "1e10", "inf", "nan"])
-@pytest.mark.parametrize("shape", [(16, 10_000_000, 100, 4, 100_000), (32, 200_000_000, 1000, 4, 200_000),
-                                   (12, 9_000_000, 90, 4, 90_000)], ids=["M100", "M1000", "M90pad"])
-def test_extreme_and_nonfinite_samples_pair_rotation(cuda_device, gsdr_lib, oracle_mod, forced_r2, kind, shape):
-    """test_direct_extreme_and_nonfinite_samples of tests/test_gpu_parity.py, same three assertions."""
-    N, rate, M, F, L = shape
-    from gpu_sdr_amd.source import host_tones, tone_comb
-    freq, ampl, phase = tone_comb(N, rate, seed=77)
-    dem = make_direct(freq, rate, M, F, L)
-    assert _is_r2(dem), (dem.kernel_name, dem.describe())
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    at = (L // M // 2) * M + 3
-    rows = np.arange(L // M)
-    hit = (rows >= at // M) & (rows <= at // M + F - 1)
-    far = near = 0.0
-    for c in range(4):
-        x = host_tones(L, c * L, rate, freq, ampl, phase, sigma=1e-3, seed=700 + c)
-        if c == 1:
-            rms = float(np.sqrt(np.mean(np.abs(x) ** 2)))
-            x[at] = {"1e8": np.complex64(1e8 * rms * (0.6 + 0.8j)), "1e10": np.complex64(1e10 * rms * (0.6 - 0.8j)),
-                     "inf": np.complex64(complex(np.inf, 0.5)), "nan": np.complex64(complex(0.25, np.nan))}[kind]
-        y = run_device(dem, x, cuda_device).reshape(-1, N)
-        with np.errstate(invalid="ignore", over="ignore"):
-            yr = ref.process(x)
-        assert y.shape == yr.shape
-        fin_y = np.isfinite(y.real) & np.isfinite(y.imag)
-        fin_r = np.isfinite(yr.real) & np.isfinite(yr.imag)
-        if c == 1:
-            if kind in ("inf", "nan"):
-                assert not fin_r[hit].any(), "the oracle's rows that hold the sample are non-finite"
-                np.testing.assert_array_equal(fin_y, fin_r, err_msg=f"{kind}: non-finite outputs elsewhere than the oracle's")
-            else:
-                assert fin_y.all()
-                near = max(near, float(rel_err_per_tone(y[hit], yr[hit], "rows whose window holds the spike").max()))
-            keep = ~hit
-            keep[:F] = False
-            e = rel_err_per_tone(y[keep], yr[keep], "rows of the bad sample's buffer that do not hold it")
-        else:
-            assert fin_y.all(), (kind, c)
-            e = rel_err_per_tone(y[F:] if c == 0 else y, yr[F:] if c == 0 else yr, "the other buffers")
-        far = max(far, float(e.max()))
-    dem.close()
-    print(f"{kind} {shape}: far {far:.3e} near {near:.3e}")
-    assert far <= TOL, (kind, far)
-    assert near <= TOL, (kind, near)
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+@pytest.mark.parametrize("shape", list(EXTREME_SHAPES))
+def test_extreme_and_nonfinite_samples_pair_rotation(cuda_device, gsdr_lib, oracle_mod, monkeypatch, kind, shape):
+    """The extreme and non-finite samples every product loop runs (tests/_product_loops.py), ddc_mfma_ring16p3r2_kernel
+    forced."""
+    force(monkeypatch, "p3r2")
+    extreme_and_nonfinite_samples(cuda_device, oracle_mod, "p3r2", kind, shape)
 
 
 def _c3_default_rotation(monkeypatch):
@@ -167,74 +48,18 @@ def test_c3_is_bit_identical_through_every_entry(cuda_device, gsdr_lib, monkeypa
     """C3 by default (the loop its handle chose, reported and recorded) and with the pair rotation forced:
     process_device on two caller streams, submit_device in between, the synchronous host entry -- bit-equal to one
     in-order stream."""
-    import torch
-    from gpu_sdr_amd.source import device_tones
     rot, T = _c3_default_rotation(monkeypatch)
     assert rot == (2 if T <= 125 else 1), (rot, T)
     record_info(rot, "C3 by default: blocks per rotation")
     if rot_env:
-        monkeypatch.setenv("GSDR_MFMA_3M_ROT", rot_env)
+        force(monkeypatch, "p3r2")
         rot = int(rot_env)
-    N, rate, M, F, L = C3
-    a, (freq, ampl, phase) = _c3_handle()
-    b, _ = _c3_handle()
 
     def same(d):
         i = d.describe()
         return d.kernel_name == KERNEL and i["complex_mac"] == 3 and i["rotation_blocks"] == rot
 
-    assert same(a) and same(b)
-    pattern = ["s1", "sub", "s2", "host", "sub", "sub", "s1", "host", "sub"]
-    xs = []
-    for k in range(len(pattern)):
-        x = torch.empty(L, dtype=torch.complex64, device=cuda_device)
-        device_tones(x, k * L, rate, freq, ampl, phase, sigma=1e-3, seed=300 + k)
-        xs.append(x)
-    torch.cuda.synchronize()
-    want = []
-    for x in xs:
-        out = torch.empty(a.out_capacity, dtype=torch.complex64, device=cuda_device)
-        n = a.process_device(x, out)
-        torch.cuda.synchronize()
-        assert same(a)
-        want.append(out[:n].cpu().numpy())
-    s1, s2 = torch.cuda.Stream(cuda_device), torch.cuda.Stream(cuda_device)
-    outs = [torch.empty(b.out_capacity, dtype=torch.complex64, device=cuda_device) for _ in pattern]
-    got, pending = [None] * len(pattern), []
-
-    def drain():
-        while pending:
-            j = pending.pop(0)
-            n = b.wait()
-            torch.cuda.synchronize()
-            got[j] = outs[j][:n].cpu().numpy()
-
-    for k, how in enumerate(pattern):
-        if how == "sub":
-            if len(pending) == 3:
-                j = pending.pop(0)
-                n = b.wait()
-                got[j] = (j, n)
-            b.submit_device(xs[k], outs[k])
-            pending.append(k)
-        elif how == "host":
-            drain()
-            got[k] = run_host(b, xs[k].cpu().numpy())
-        else:
-            st = s1 if how == "s1" else s2
-            n = b.process_device(xs[k], outs[k], st)
-            got[k] = (k, n)
-        assert same(b), (k, how)
-    drain()
-    torch.cuda.synchronize()
-    for k, how in enumerate(pattern):
-        y = got[k]
-        if isinstance(y, tuple):
-            y = outs[y[0]][:y[1]].cpu().numpy()
-        assert y.size == want[k].size, (k, how)
-        np.testing.assert_array_equal(y, want[k], err_msg=f"buffer {k} via {how}")
-    a.close()
-    b.close()
+    every_entry_is_bit_identical(cuda_device, same)
 
 
 def test_switch_and_threshold(cuda_device, gsdr_lib, monkeypatch):
@@ -280,19 +105,14 @@ def test_hdr_comb_default_keeps_the_rule(cuda_device, gsdr_lib, oracle_mod, monk
     (oracle/recipe_b.py, complex64) against the fp64 oracle on the same buffers.  Asserted for GSDR_MFMA_3M_ROT unset
     at every length; the figures of both loops forced (ROT = 1, = 2) are recorded."""
     span_db = 60
-    monkeypatch.setenv("GSDR_DDC_MFMA", "1")
-    monkeypatch.setenv("GSDR_MFMA_ASM", "4")
-    monkeypatch.setenv("GSDR_MFMA_PREC", "1")
-    monkeypatch.setenv("GSDR_DDC_FEW", "0")
-    monkeypatch.delenv("GSDR_MFMA_3M", raising=False)
     failures = []
     for M in HDR_R2_DECIMS:
         res = {}
         for mode in ("1", "2", None):
             if mode is None:
-                monkeypatch.delenv("GSDR_MFMA_3M_ROT", raising=False)
+                clean_env(monkeypatch, COMMON)
             else:
-                monkeypatch.setenv("GSDR_MFMA_3M_ROT", mode)
+                force(monkeypatch, {"1": "p3", "2": "p3r2"}[mode])
             res[mode] = _hdr_errors(cuda_device, oracle_mod, span_db, M)
             assert res[mode][2] == 3, (M, mode)
         err32 = res[None][1]
@@ -318,7 +138,7 @@ def test_hdr_comb_default_keeps_the_rule(cuda_device, gsdr_lib, oracle_mod, monk
 def test_c3_full_size_margin(cuda_device, gsdr_lib, oracle_mod, monkeypatch):
     """C3 against the oracle through the default loop of its handle: the margin to record beside the 4.0e-7 of the
     32-sample loop."""
-    from test_gpu_parity import _full_size_direct
+    from test_gpu_parity import _full_size_direct, DIRECT_CASES
     for k in ("GSDR_MFMA_3M", "GSDR_MFMA_3M_ROT", "GSDR_MFMA_PREC"):
         monkeypatch.delenv(k, raising=False)
     _full_size_direct(cuda_device, oracle_mod, N=2048, M=1000, nbuf=3, subset=12)

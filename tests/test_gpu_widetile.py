@@ -3,34 +3,34 @@
 
 Every case builds two handles from the same parameters, GSDR_MFMA_WAVE_TONES = 64 and = 32, feeds both three
 consecutive buffers (the head and the tail are carried across calls) and asks for equal bytes; the 64 handle is also
-held to the bar of 1e-5 per tone against the fp64 oracle.  Helpers and the forced fold are those of
-test_gpu_parity.py, test_gpu_extents.py and test_gpu_fold4.py."""
+held to the bar of 1e-5 per tone against the fp64 oracle.  The cases every product loop runs are in
+tests/test_gpu_product_loops.py; the helpers and the forced loops are those of test_gpu_parity.py, test_gpu_extents.py
+and tests/_product_loops.py."""
 import numpy as np
 import pytest
 
-from test_gpu_parity import TOL, crandn, make_direct, make_pfb, rel_err_per_tone, run_device, run_host
-from test_gpu_extents import S_N65, S_ODD, clean_env, direct_inputs, expect_kernel, run_case
-from test_gpu_fold import KERNEL
-from test_gpu_fold4 import FOLD4_ENV, _is_fold4
+from _product_loops import LOOPS, force, is_loop
+from test_gpu_extents import clean_env
+from test_gpu_parity import TOL, crandn, make_direct, rel_err_per_tone, run_device, run_host
 
 pytestmark = pytest.mark.gpu
 
-WIDE_ENV = dict(FOLD4_ENV, GSDR_MFMA_WAVE_TONES="64")
-NARROW_ENV = dict(FOLD4_ENV, GSDR_MFMA_WAVE_TONES="32")
+WIDE_ENV, NARROW_ENV = LOOPS["p4fw"][0], LOOPS["p4f"][0]
+FOLD4_ENV = {k: v for k, v in WIDE_ENV.items() if k != "GSDR_MFMA_WAVE_TONES"}      # the tile left to the handle
 
 
 def _is_wide(dem, tones=64):
-    return _is_fold4(dem) and dem.describe()["wave_tones"] == tones
+    return is_loop(dem, {64: "p4fw", 32: "p4f"}[tones])
 
 
 def _pair(monkeypatch, cuda_device, oracle_mod, N, rate, M, F, L, seed):
     """Three buffers through a 64 handle and a 32 handle: equal bytes, and the 64 handle within TOL of the oracle."""
     rng = np.random.default_rng(seed)
     freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
-    clean_env(monkeypatch, WIDE_ENV)
+    force(monkeypatch, "p4fw")
     wide = make_direct(freq, rate, M, F, L)
     assert _is_wide(wide, 64), (wide.kernel_name, wide.describe())
-    clean_env(monkeypatch, NARROW_ENV)
+    force(monkeypatch, "p4f")
     narrow = make_direct(freq, rate, M, F, L)
     assert _is_wide(narrow, 32), (narrow.kernel_name, narrow.describe())
     ref = oracle_mod.Direct(freq, rate, M, F, L)
@@ -88,22 +88,6 @@ def test_window_no_multiple_of_32_or_64_bit_identical(cuda_device, gsdr_lib, ora
     print(f"M 90: worst per-tone error {worst:.3e}")
 
 
-@pytest.mark.parametrize("shape", [S_N65, S_ODD], ids=lambda c: "N%d_M%d_F%d_L%d" % (c[0], c[2], c[3], c[4]))
-def test_direct_extents_widetile(cuda_device, gsdr_lib, oracle_mod, monkeypatch, shape):
-    """The guard zones of tests/_extents.py around input and output (both patterns, both offsets of each), through
-    process_device and submit_device, the wide loop forced."""
-    N, rate, M, F, L = shape
-    clean_env(monkeypatch, WIDE_ENV)
-    freq, xs, yrs = direct_inputs(shape, oracle_mod)
-
-    def expect(dem, ran):
-        expect_kernel(KERNEL, 3, 2)(dem, ran)
-        d = dem.describe()
-        assert (d["fold"], d["fold_products"], d["wave_tones"]) == (1, 4, 64)
-
-    run_case(cuda_device, lambda: make_direct(freq, rate, M, F, L), expect, xs, yrs, N)
-
-
 def test_one_handle_every_entry_widetile(cuda_device, gsdr_lib, monkeypatch):
     """One handle, one loop: process_device, submit_device / wait and the host entry give the same bits for the same
     buffers (288 tones, M 1000, F 4, L 200 000: 125 blocks, 200 rows), and they are the bits of the 32-tone tile."""
@@ -115,7 +99,7 @@ def test_one_handle_every_entry_widetile(cuda_device, gsdr_lib, monkeypatch):
     xs = [crandn(rng, L) for _ in range(3)]
     got = {}
     for entry in ("process", "submit", "host", "narrow"):
-        clean_env(monkeypatch, NARROW_ENV if entry == "narrow" else WIDE_ENV)
+        force(monkeypatch, "p4f" if entry == "narrow" else "p4fw")
         dem = make_direct(freq, rate, M, F, L)
         assert _is_wide(dem, 32 if entry == "narrow" else 64), (dem.kernel_name, dem.describe())
         ys = []
@@ -139,32 +123,6 @@ def test_one_handle_every_entry_widetile(cuda_device, gsdr_lib, monkeypatch):
         for k, (y, w) in enumerate(zip(got[entry], got["process"])):
             assert y.size == w.size == N * (L // M), (entry, k)
             np.testing.assert_array_equal(y.view(np.int32), w.view(np.int32), err_msg=f"buffer {k} via {entry}")
-
-
-def test_tones_on_the_ddc_kernels_widetile(cuda_device, gsdr_lib, oracle_mod, monkeypatch):
-    """TONES through the DDC kernels (the FFT path off), buffer length no multiple of nfft (short last batches)."""
-    N, rate, nfft, avg, L, nbuf = 5, 200_000_000, 1000, 4, 50_123, 4
-    rng = np.random.default_rng(2000 + nfft + avg)
-    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-    freq[0] = 0
-    clean_env(monkeypatch, WIDE_ENV)
-    dem = make_pfb(freq, rate, nfft, avg, L)
-    assert _is_wide(dem), (dem.kernel_name, dem.describe())
-    ref = oracle_mod.Pfb(freq, rate, nfft, avg, L)
-    emitted = 0
-    for c in range(nbuf):
-        x = crandn(rng, L)
-        y = (run_host if c % 2 else run_device)(dem, x, *(() if c % 2 else (cuda_device,)))
-        yr = ref.process(x)
-        assert y.size == yr.size, (c, y.size, yr.size)
-        emitted += len(yr)
-        if len(yr):
-            err = rel_err_per_tone(y.reshape(-1, N), yr)
-            print(f"tones buffer {c}: worst per-tone error {err.max():.3e}")
-            assert err.max() <= TOL, (c, err.max())
-    assert emitted > 0
-    assert _is_wide(dem)
-    dem.close()
 
 
 def test_switch_wave_tones(cuda_device, gsdr_lib, monkeypatch):
