@@ -2,10 +2,13 @@
 environment that selects a loop -- EVERY selecting switch set, so that a switch added later cannot reroute the handle
 -- and the five describe() values a handle on that loop reports.  Shared by tests/test_gpu_product_loops.py (the cases
 every loop runs) and the loops' own files (test_gpu_mfma3.py, test_gpu_mfma3r2.py, test_gpu_fold.py, test_gpu_fold4.py,
-test_gpu_widetile.py), with the helpers those files have in common.  Not collected."""
+test_gpu_widetile.py), with the helpers those files have in common; the second half holds the seeded shape draw and the
+bodies of the engine-wide behavioural tests, which tests/test_gpu_parity.py runs on the engines up to the four-product
+build and tests/test_gpu_product_loops.py on each loop.  Not collected."""
 import numpy as np
 
-from test_gpu_parity import TOL, crandn, hdr_comb, make_direct, rel_err_per_tone, run_device, run_host
+from _margins import record_info, record_margin
+from test_gpu_parity import TOL, crandn, hdr_comb, make_direct, make_pfb, rel_err_per_tone, run_device, run_host
 
 KERNEL = "ddc_mfma_ring16p_kernel"          # the name every pre-converted loop reports
 DESCRIBE = ("complex_mac", "rotation_blocks", "fold", "fold_products", "wave_tones")
@@ -247,3 +250,332 @@ def _hdr_errors(cuda_device, oracle_mod, span_db, M):
         errs32.append(np.linalg.norm(y32[F:].astype(np.complex128) - yr[F:], axis=0) / den)
     dem.close()
     return np.array(errs), np.array(errs32), mac
+
+
+# ---------------------------------------------------------------------------
+# the engine-wide behavioural tests of tests/test_gpu_parity.py, their bodies stated once: called from there (every
+# engine up to the four-product build) and from tests/test_gpu_product_loops.py (each loop).  `check(dem, ran)`
+# asserts the engine of a handle, before its first call (ran false) and after its last.
+# ---------------------------------------------------------------------------
+FUZZ_SEED = 0
+FUZZ_F = (1, 8)
+FUZZ_M = (8, 13, 16, 20, 25, 33, 37, 40, 64, 72, 90, 100, 127, 250, 1000)
+FUZZ_ROWS = 70
+FUZZ_RATE = (1000, 65_536, 1_000_000, 200_000_000)
+FUZZ_N = (1, 2, 5, 31, 32, 33, 63, 64, 65, 130, 257)
+
+
+def matrix_cores_take(M, F, L):
+    """The setup rule of csrc/demod.cpp (setup_direct): a buffer holds the carry, and the zero padding behind a window
+    fits the next block."""
+    return L // M >= F - 1 and L >= 4 and (M * F + 31) // 32 * 32 - M * F <= M
+
+
+def loop_fuzz_shapes():
+    """36 DIRECT shapes (N, rate, M, F, L) nobody picked by hand, every one taken by the matrix cores (rejection
+    sampling against matrix_cores_take); tests/test_product_loops_host.py holds what the list must contain."""
+    rng = np.random.default_rng(FUZZ_SEED)
+    shapes = []
+    while len(shapes) < 36:
+        F = int(rng.integers(FUZZ_F[0], FUZZ_F[1] + 1))
+        M = int(rng.choice(FUZZ_M))
+        rows = int(rng.integers(max(F - 1, 1), FUZZ_ROWS + 1))
+        rate = int(rng.choice(FUZZ_RATE))
+        N = int(rng.choice(FUZZ_N))
+        if matrix_cores_take(M, F, M * rows):
+            shapes.append((N, rate, M, F, M * rows))
+    return shapes
+
+
+_REFS = {}
+
+
+def _once(key, build):
+    """What build() returns (a tuple of arrays and lists of arrays), computed once per session, shared by the engines
+    and never modified."""
+    if key not in _REFS:
+        got = build()
+        for part in got:
+            for a in (part if isinstance(part, list) else [part]):
+                a.flags.writeable = False
+        _REFS[key] = got
+    return _REFS[key]
+
+
+def _scaled(rng, L, scale):
+    return (crandn(rng, L) * np.float32(scale)).astype(np.complex64)
+
+
+def direct_stream(oracle_mod, shape, seed, scales, distinct=False, nref=None):
+    """-> (freq, xs, yrs): the tones, one white-noise buffer per entry of `scales` and the oracle's outputs for the
+    first `nref` of them (all by default), drawn in this order from default_rng(seed)."""
+    N, rate, M, F, L = shape
+    nref = len(scales) if nref is None else nref
+
+    def build():
+        rng = np.random.default_rng(seed)
+        if distinct:
+            freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
+        else:
+            freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
+        xs = [_scaled(rng, L, sc) for sc in scales]
+        ref = oracle_mod.Direct(freq, rate, M, F, L)
+        return freq, xs, [np.array(ref.process(x)) for x in xs[:nref]]
+    return _once(("direct", shape, seed, tuple(scales), distinct, nref), build)
+
+
+def fuzz_random_shapes(cuda_device, oracle_mod, check, name):
+    """The shapes of loop_fuzz_shapes(), three buffers each through the device entry: exact lengths, every tone within
+    TOL of the oracle."""
+    for it, shape in enumerate(loop_fuzz_shapes()):
+        N, rate, M, F, L = shape
+        freq, xs, yrs = direct_stream(oracle_mod, shape, 7770 + it, [1.0] * 3)
+        dem = make_direct(freq, rate, M, F, L)
+        check(dem, False)
+        worst = 0.0
+        for c, (x, yr) in enumerate(zip(xs, yrs)):
+            y = run_device(dem, x, cuda_device)
+            assert y.size == yr.size == N * (L // M), (it, shape, c, y.size, yr.size)
+            err = rel_err_per_tone(y.reshape(-1, N), yr)
+            worst = max(worst, float(err.max()))
+            assert err.max() <= TOL, (it, shape, c, float(err.max()))
+        check(dem, True)
+        dem.close()
+        print(f"{name} shape {it} {shape} ({(M * F + 31) // 32} blocks, {L // M} rows): worst per-tone error {worst:.3e}")
+
+
+def submit_equals_process(cuda_device, a, b, xs, what=""):
+    """The device buffers `xs` through process_device of `a`, one at a time, and through submit_device of `b` with up
+    to four outstanding: the same lengths and the same bits.  Returns b's outputs (host copies)."""
+    import torch
+    out_a = torch.empty(a.out_capacity, dtype=torch.complex64, device=cuda_device)
+    want = []
+    for x in xs:
+        n = a.process_device(x, out_a)
+        torch.cuda.synchronize()
+        want.append(out_a[:n].cpu().numpy())
+    outs = [torch.zeros(b.out_capacity, dtype=torch.complex64, device=cuda_device) for _ in xs]
+    torch.cuda.synchronize()
+    got, pending = [], []
+    for k, x in enumerate(xs):
+        if len(pending) == 4:
+            j = pending.pop(0)
+            got.append(outs[j][:b.wait()].cpu().numpy())
+        b.submit_device(x, outs[k])
+        pending.append(k)
+    while pending:
+        j = pending.pop(0)
+        got.append(outs[j][:b.wait()].cpu().numpy())
+    assert [len(y) for y in got] == [len(y) for y in want], what
+    for k, (y, yr) in enumerate(zip(got, want)):
+        np.testing.assert_array_equal(y, yr, err_msg=f"{what}buffer {k}")
+    return got
+
+
+def pipelined_fuzz(cuda_device, check, name):
+    """The first 12 shapes of loop_fuzz_shapes(), seven buffers each whose loudness changes by up to five orders from
+    one to the next: the overlapped entry with up to four outstanding against the in-order entry, bit for bit."""
+    import torch
+    for it, shape in enumerate(loop_fuzz_shapes()[:12]):
+        N, rate, M, F, L = shape
+        rng = np.random.default_rng(4200 + it)
+        freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
+        a, b = make_direct(freq, rate, M, F, L), make_direct(freq, rate, M, F, L)
+        check(a, False)
+        check(b, False)
+        xs = [torch.from_numpy(_scaled(rng, L, 10.0 ** rng.integers(-3, 3))).to(cuda_device) for _ in range(7)]
+        got = submit_equals_process(cuda_device, a, b, xs, f"{name} shape {it} {shape} ")
+        assert [len(y) for y in got] == [N * (L // M)] * 7, (it, shape)
+        check(a, True)
+        check(b, True)
+        a.close()
+        b.close()
+
+
+DYNAMIC_RANGE_SHAPE = (40, 10_000_000, 100, 4, 20_000)
+DYNAMIC_RANGE_SCALES = (1.0, 1e-6, 1e-6, 3e4, 1.0, 0.0, 1e-3, 0.0)
+
+
+def dynamic_range_and_scale_carry(cuda_device, oracle_mod, check):
+    """The matrix-core DDC scales every buffer into fp16 range from its own maximum (and
+    the previous buffer's, whose tail it still reads).  Same tolerance for inputs of
+    1e-6, 1 and 3e4, for a loud buffer followed by a quiet one and vice versa, and an
+    all-zero buffer gives exact zeros."""
+    N, rate, M, F, L = DYNAMIC_RANGE_SHAPE
+    freq, xs, yrs = direct_stream(oracle_mod, DYNAMIC_RANGE_SHAPE, 99, DYNAMIC_RANGE_SCALES)
+    dem = make_direct(freq, rate, M, F, L)
+    check(dem, False)
+    for c, (scale, x, yr) in enumerate(zip(DYNAMIC_RANGE_SCALES, xs, yrs)):
+        y = run_device(dem, x, cuda_device).reshape(-1, N)
+        assert y.shape == yr.shape, (c, scale)
+        assert np.isfinite(y.view(np.float32)).all(), (c, scale)
+        den = np.linalg.norm(yr, axis=0)
+        if den.max() == 0:
+            assert np.abs(y).max() == 0
+            continue
+        # rows fed by the previous (louder) buffer's tail dominate the norm of a quiet
+        # buffer: compare where the reference itself is not ~0
+        err = np.linalg.norm(y - yr, axis=0) / np.where(den == 0, 1, den)
+        record_margin(float(err.max()), f"buffer {c}, loudness {scale:g}")
+        assert err.max() <= TOL, (c, scale, err.max())
+    check(dem, True)
+    dem.close()
+
+
+def more_tap_phases(cuda_device, oracle_mod, check, F, M, alternate):
+    """pf_average 5..8: the packed-FP32 production kernel stops at 4, the matrix-core DDC
+    takes any window that is made of whole blocks behind its last sample.  Three buffers through the device entry, or
+    (`alternate`) through the device and the host entry in turn."""
+    N, rate, L = 70, 1_000_000, M * 300
+    freq, xs, yrs = direct_stream(oracle_mod, (N, rate, M, F, L), F, [1.0] * 3)
+    dem = make_direct(freq, rate, M, F, L)
+    check(dem, False)
+    for c, (x, yr) in enumerate(zip(xs, yrs)):
+        y = (run_host(dem, x) if alternate and c % 2 else run_device(dem, x, cuda_device)).reshape(-1, N)
+        assert y.shape == yr.shape, (F, c)
+        assert rel_err_per_tone(y, yr).max() <= TOL, (F, c)
+    check(dem, True)
+    dem.close()
+
+
+TWO_HANDLES = [(33, 10_000_000, 100, 4, 30_000), (70, 1_000_000, 40, 2, 16_000)]
+
+
+def two_handles_interleaved(cuda_device, oracle_mod, make, check):
+    """Two matrix-core demodulators fed alternately on one stream (the server's two RX front
+    ends): carry, scale slots and head/tail copies are per handle.  make(k, freq, rate, M, F, L) creates handle k (the
+    first before the second), check(k, dem, ran) asserts its engine."""
+    def build():
+        rng = np.random.default_rng(123)
+        freqs = [rng.integers(-rate // 2 + 1, rate // 2, size=N) for N, rate, M, F, L in TWO_HANDLES]
+        refs = [oracle_mod.Direct(freqs[k], rate, M, F, L) for k, (N, rate, M, F, L) in enumerate(TWO_HANDLES)]
+        xs, yrs = [], []
+        for c in range(4):
+            for k, (N, rate, M, F, L) in enumerate(TWO_HANDLES):
+                xs.append(_scaled(rng, L, 10.0 ** (c - 2 * k)))
+                yrs.append(np.array(refs[k].process(xs[-1])))
+        return freqs, xs, yrs
+    freqs, xs, yrs = _once("two handles", build)
+    dems = [make(k, freqs[k], *TWO_HANDLES[k][1:]) for k in range(2)]
+    for k, d in enumerate(dems):
+        check(k, d, False)
+    for c in range(4):
+        for k, (N, rate, M, F, L) in enumerate(TWO_HANDLES):
+            y = run_device(dems[k], xs[2 * c + k], cuda_device).reshape(-1, N)
+            assert y.shape == yrs[2 * c + k].shape, (c, k)
+            assert rel_err_per_tone(y, yrs[2 * c + k], f"handle {k}").max() <= TOL, (c, k)
+    for k, d in enumerate(dems):
+        check(k, d, True)
+        d.close()
+
+
+STREAMING_SHAPE = (9, 1_000_000, 100, 4, 60_000)
+
+
+def streaming_runs(cuda_device, check):
+    """One stream of 60 000 samples as one buffer and as three of 20 000 -> (freq, x, ya, yb), [rows][N] each."""
+    N, rate, M, F, L = STREAMING_SHAPE
+    rng = np.random.default_rng(5)
+    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
+    x = crandn(rng, L)
+    a = make_direct(freq, rate, M, F, L)
+    check(a, False)
+    ya = run_device(a, x, cuda_device).reshape(-1, N)
+    check(a, True)
+    a.close()
+    b = make_direct(freq, rate, M, F, L // 3)
+    check(b, False)
+    yb = np.concatenate([run_device(b, x[c * (L // 3):(c + 1) * (L // 3)], cuda_device) for c in range(3)]).reshape(-1, N)
+    check(b, True)
+    b.close()
+    return freq, x, ya, yb
+
+
+def pure_tones_demodulate_to_their_phasors(cuda_device, check):
+    """Closed form, no oracle: a comb demodulates to a_k e^{i phi_k} (DC gain of h is 1)."""
+    from gpu_sdr_amd.source import host_tones
+    rate, L, M, F, N = 10_000_000, 100_000, 100, 4, 12
+    freq = (np.arange(N) - N // 2) * 400_000 + 12_345  # >= 4 output bandwidths apart
+    ampl = np.linspace(0.02, 0.08, N).astype(np.float32)
+    phase = np.linspace(0, 6, N).astype(np.float32)
+    dem = make_direct(freq, rate, M, F, L)
+    check(dem, False)
+    ys = []
+    for c in range(2):
+        ys.append(run_device(dem, host_tones(L, c * L, rate, freq, ampl, phase), cuda_device).reshape(-1, N))
+    check(dem, True)
+    dem.close()
+    y = np.concatenate(ys)[F:]
+    want = ampl * np.exp(1j * phase.astype(np.float64))
+    worst = float(np.abs(y - want).max())
+    record_info(worst, "largest |y - a e^{i phi}| behind the first F rows (bar 5e-4)")
+    assert worst < 5e-4  # stop-band leakage of the other tones
+
+
+OVERLAP_SCALES = (1.0, 1e-4, 30.0, 1.0, 1e-3, 1e-3, 100.0, 1.0, 1.0, 1e-2, 5.0)
+
+
+def pipelined_overlapping_buffers(cuda_device, oracle_mod, check, N, L):
+    """gsdr_demod_submit_device: the main kernels of consecutive DIRECT buffers run on two
+    streams and overlap (the staging passes stay in order).  Buffers of very different
+    loudness follow each other, so a kernel that picked up its neighbour's scale slot, head
+    or tail copy would be far off.  Bit-equal to the in-order entry, and within tolerance
+    of the oracle."""
+    import torch
+    rate, M, F = 10_000_000, 100, 4
+    freq, xs_host, yrs = direct_stream(oracle_mod, (N, rate, M, F, L), 314, OVERLAP_SCALES, distinct=True, nref=4)
+    a, b = make_direct(freq, rate, M, F, L), make_direct(freq, rate, M, F, L)
+    check(a, False)
+    check(b, False)
+    xs = [torch.from_numpy(x.copy()).to(cuda_device) for x in xs_host]
+    got = submit_equals_process(cuda_device, a, b, xs)
+    for k, yo in enumerate(yrs):
+        assert got[k].size == yo.size, k
+        den = np.linalg.norm(yo, axis=0)
+        err = np.linalg.norm(got[k].reshape(-1, N) - yo, axis=0) / den
+        record_margin(float(err.max()), f"buffer {k}, loudness {OVERLAP_SCALES[k]:g}")
+        assert err.max() <= TOL, (k, err.max())
+    # the in-order entry keeps working on the same handle once the pipeline is drained
+    out = torch.empty(b.out_capacity, dtype=torch.complex64, device=cuda_device)
+    n = b.process_device(xs[0], out)
+    torch.cuda.synchronize()
+    assert n == N * (L // M)
+    check(a, True)
+    check(b, True)
+    a.close()
+    b.close()
+
+
+PIPELINED_TONES_SCALES = (1.0, 1e-3, 50.0, 1.0, 1e-2, 1.0, 7.0, 1.0, 1.0)
+
+
+def pipelined_tones(cuda_device, oracle_mod, check):
+    """TONES through gsdr_demod_submit_device, L no multiple of nfft: the carried length and the batch count change
+    from buffer to buffer.  Bit-equal to the in-order entry, within tolerance of the oracle."""
+    import torch
+    rate, nfft, F, L, N = 10_000_000, 250, 4, 100_003, 96
+
+    def build():
+        rng = np.random.default_rng(2718)
+        freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
+        xs = [_scaled(rng, L, sc) for sc in PIPELINED_TONES_SCALES]
+        ref = oracle_mod.Pfb(freq, rate, nfft, F, L)
+        return freq, xs, [np.array(ref.process(x)) for x in xs[:4]]
+    freq, xs_host, yrs = _once("pipelined tones", build)
+    a, b = make_pfb(freq, rate, nfft, F, L), make_pfb(freq, rate, nfft, F, L)
+    check(a, False)
+    check(b, False)
+    xs = [torch.from_numpy(x.copy()).to(cuda_device) for x in xs_host]
+    got = submit_equals_process(cuda_device, a, b, xs)
+    assert len({len(y) for y in got}) > 1          # the batch count does change
+    for k, yo in enumerate(yrs):
+        assert yo.size == got[k].size
+        yo = yo.reshape(-1, N)
+        den = np.linalg.norm(yo, axis=0)
+        err = np.linalg.norm(got[k].reshape(-1, N) - yo, axis=0) / den
+        record_margin(float(err.max()), f"buffer {k}, loudness {PIPELINED_TONES_SCALES[k]:g}")
+        assert err.max() <= TOL, (k, err.max())
+    check(a, True)
+    check(b, True)
+    a.close()
+    b.close()

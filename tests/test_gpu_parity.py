@@ -292,70 +292,37 @@ def test_pfb_and_chirp_fuzz_random_shapes(cuda_device, gsdr_lib, oracle_mod, eng
         dem.close()
 
 
+def _is_mfma(dem, ran):
+    assert ran or dem.kernel_name.startswith("ddc_mfma"), dem.kernel_name
+
+
+def _any_engine(dem, ran):
+    pass
+
+
 def test_mfma_dynamic_range_and_scale_carry(cuda_device, gsdr_lib, oracle_mod, mfma_engine):
     """The matrix-core DDC scales every buffer into fp16 range from its own maximum (and
     the previous buffer's, whose tail it still reads).  Same tolerance for inputs of
     1e-6, 1 and 3e4, for a loud buffer followed by a quiet one and vice versa, and an
-    all-zero buffer gives exact zeros."""
-    N, rate, M, F, L = 40, 10_000_000, 100, 4, 20_000
-    rng = np.random.default_rng(99)
-    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-    dem = make_direct(freq, rate, M, F, L)
-    assert dem.kernel_name.startswith("ddc_mfma")
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    for c, scale in enumerate([1.0, 1e-6, 1e-6, 3e4, 1.0, 0.0, 1e-3, 0.0]):
-        x = (crandn(rng, L) * np.float32(scale)).astype(np.complex64)
-        y = run_device(dem, x, cuda_device).reshape(-1, N)
-        yr = ref.process(x)
-        assert np.isfinite(y.view(np.float32)).all(), (c, scale)
-        if scale == 0.0 and c == 7:
-            pass
-        den = np.linalg.norm(yr, axis=0)
-        if den.max() == 0:
-            assert np.abs(y).max() == 0
-            continue
-        # rows fed by the previous (louder) buffer's tail dominate the norm of a quiet
-        # buffer: compare where the reference itself is not ~0
-        err = np.linalg.norm(y - yr, axis=0) / np.where(den == 0, 1, den)
-        assert err.max() <= TOL, (c, scale, err.max())
-    dem.close()
+    all-zero buffer gives exact zeros.  (The body, as those of the tests below that name _product_loops, is shared
+    with tests/test_gpu_product_loops.py, which runs it on every product loop.)"""
+    from _product_loops import dynamic_range_and_scale_carry
+    dynamic_range_and_scale_carry(cuda_device, oracle_mod, _is_mfma)
 
 
 @pytest.mark.parametrize("F", [5, 6, 7, 8])
 def test_mfma_more_tap_phases(cuda_device, gsdr_lib, oracle_mod, mfma_engine, F):
     """pf_average 5..8: the packed-FP32 production kernel stops at 4, the matrix-core DDC
     takes any window that is made of whole blocks behind its last sample."""
-    N, rate, M, L = 70, 1_000_000, 64, 64 * 300
-    rng = np.random.default_rng(F)
-    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-    dem = make_direct(freq, rate, M, F, L)
-    assert dem.kernel_name.startswith("ddc_mfma")
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    for c in range(3):
-        x = crandn(rng, L)
-        y = run_device(dem, x, cuda_device).reshape(-1, N)
-        yr = ref.process(x)
-        assert rel_err_per_tone(y, yr).max() <= TOL
-    dem.close()
+    from _product_loops import more_tap_phases
+    more_tap_phases(cuda_device, oracle_mod, _is_mfma, F, M=64, alternate=False)
 
 
 def test_mfma_two_handles_interleaved(cuda_device, gsdr_lib, oracle_mod, mfma_engine):
     """Two matrix-core demodulators fed alternately on one stream (the server's two RX front
     ends): carry, scale slots and head/tail copies are per handle."""
-    rng = np.random.default_rng(123)
-    cfgs = [(33, 10_000_000, 100, 4, 30_000), (70, 1_000_000, 40, 2, 16_000)]
-    dems, refs = [], []
-    for N, rate, M, F, L in cfgs:
-        freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-        dems.append(make_direct(freq, rate, M, F, L))
-        refs.append(oracle_mod.Direct(freq, rate, M, F, L))
-    for c in range(4):
-        for k, (N, rate, M, F, L) in enumerate(cfgs):
-            x = (crandn(rng, L) * np.float32(10.0 ** (c - 2 * k))).astype(np.complex64)
-            y = run_device(dems[k], x, cuda_device).reshape(-1, N)
-            assert rel_err_per_tone(y, refs[k].process(x)).max() <= TOL, (c, k)
-    for d in dems:
-        d.close()
+    from _product_loops import two_handles_interleaved
+    two_handles_interleaved(cuda_device, oracle_mod, lambda k, *shape: make_direct(*shape), lambda k, dem, ran: None)
 
 
 def hdr_comb(N, rate, L, span_db, rng, start):
@@ -607,16 +574,8 @@ def test_direct_extreme_and_nonfinite_samples(cuda_device, gsdr_lib, oracle_mod,
 
 def test_direct_streaming_equals_one_long_buffer(cuda_device, gsdr_lib, engine):
     """Concatenated per-buffer outputs == one call on the concatenated input."""
-    rate, M, F, N = 1_000_000, 100, 4, 9
-    rng = np.random.default_rng(5)
-    freq = rng.integers(-rate // 2 + 1, rate // 2, size=N)
-    x = crandn(rng, 60_000)
-    a = make_direct(freq, rate, M, F, 60_000)
-    ya = run_device(a, x, cuda_device).reshape(-1, N)
-    a.close()
-    b = make_direct(freq, rate, M, F, 20_000)
-    yb = np.concatenate([run_device(b, x[c * 20_000:(c + 1) * 20_000], cuda_device) for c in range(3)]).reshape(-1, N)
-    b.close()
+    from _product_loops import streaming_runs
+    _, _, ya, yb = streaming_runs(cuda_device, _any_engine)
     assert rel_err_per_tone(yb, ya).max() <= 2e-6
 
 
@@ -673,19 +632,8 @@ def test_direct_few_tones_long_decimation(cuda_device, gsdr_lib, oracle_mod, mon
 
 def test_direct_pure_tones_demodulate_to_their_phasors(cuda_device, gsdr_lib, engine):
     """Closed form, no oracle: a comb demodulates to a_k e^{i phi_k} (DC gain of h is 1)."""
-    from gpu_sdr_amd.source import host_tones
-    rate, L, M, F, N = 10_000_000, 100_000, 100, 4, 12
-    freq = (np.arange(N) - N // 2) * 400_000 + 12_345  # >= 4 output bandwidths apart
-    ampl = np.linspace(0.02, 0.08, N).astype(np.float32)
-    phase = np.linspace(0, 6, N).astype(np.float32)
-    dem = make_direct(freq, rate, M, F, L)
-    ys = []
-    for c in range(2):
-        ys.append(run_device(dem, host_tones(L, c * L, rate, freq, ampl, phase), cuda_device).reshape(-1, N))
-    dem.close()
-    y = np.concatenate(ys)[F:]
-    want = ampl * np.exp(1j * phase.astype(np.float64))
-    assert np.abs(y - want).max() < 5e-4  # stop-band leakage of the other tones
+    from _product_loops import pure_tones_demodulate_to_their_phasors
+    pure_tones_demodulate_to_their_phasors(cuda_device, _any_engine)
 
 
 # ---------------------------------------------------------------------------
@@ -1388,51 +1336,15 @@ def test_pipelined_submit_device_overlapping_buffers(cuda_device, gsdr_lib, orac
     loudness follow each other, so a kernel that picked up its neighbour's scale slot, head
     or tail copy would be far off.  Bit-equal to the in-order entry, and within tolerance
     of the oracle."""
-    import torch
+    from _product_loops import pipelined_overlapping_buffers
     monkeypatch.setenv("GSDR_DDC_MFMA", "1")
     monkeypatch.setenv("GSDR_MFMA_ASM", asm)
     monkeypatch.setenv("GSDR_PIPE_OVERLAP", overlap)
     monkeypatch.setenv("GSDR_PIPE_STREAMS", streams)
-    N, rate, M, F, L = 256, 10_000_000, 100, 4, 200_000
-    rng = np.random.default_rng(314)
-    freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
-    a, b = make_direct(freq, rate, M, F, L), make_direct(freq, rate, M, F, L)
-    assert b.kernel_name == ("ddc_mfma_ring_kernel" if asm == "2" else "ddc_mfma_ring16_kernel")
-    ref = oracle_mod.Direct(freq, rate, M, F, L)
-    scales = [1.0, 1e-4, 30.0, 1.0, 1e-3, 1e-3, 100.0, 1.0, 1.0, 1e-2, 5.0]
-    xs = [torch.from_numpy((crandn(rng, L) * np.float32(sc)).astype(np.complex64)).to(cuda_device) for sc in scales]
-    want = []
-    out_a = torch.empty(a.out_capacity, dtype=torch.complex64, device=cuda_device)
-    for x in xs:
-        n = a.process_device(x, out_a)
-        torch.cuda.synchronize()
-        want.append(out_a[:n].cpu().numpy())
-    outs = [torch.zeros(b.out_capacity, dtype=torch.complex64, device=cuda_device) for _ in xs]
-    torch.cuda.synchronize()
-    got, pending = [], []
-    for k, x in enumerate(xs):
-        if len(pending) == 4:
-            j = pending.pop(0)
-            got.append(outs[j][:b.wait()].cpu().numpy())
-        b.submit_device(x, outs[k])
-        pending.append(k)
-    while pending:
-        j = pending.pop(0)
-        got.append(outs[j][:b.wait()].cpu().numpy())
-    assert len(got) == len(want)
-    for k, (y, yr) in enumerate(zip(got, want)):
-        np.testing.assert_array_equal(y, yr, err_msg="buffer %d" % k)
-    for k, x in enumerate(xs[:4]):
-        yo = ref.process(x.cpu().numpy())
-        den = np.linalg.norm(yo, axis=0)
-        err = np.linalg.norm(got[k].reshape(-1, N) - yo, axis=0) / den
-        assert err.max() <= TOL, (k, err.max())
-    # the in-order entry keeps working on the same handle once the pipeline is drained
-    n = b.process_device(xs[0], outs[0])
-    torch.cuda.synchronize()
-    assert n == N * (L // M)
-    a.close()
-    b.close()
+
+    def check(dem, ran):
+        assert ran or dem.kernel_name == ("ddc_mfma_ring_kernel" if asm == "2" else "ddc_mfma_ring16_kernel"), dem.kernel_name
+    pipelined_overlapping_buffers(cuda_device, oracle_mod, check, N=256, L=200_000)
 
 
 @pytest.mark.parametrize("streams", ["2", "3", "fft"])
@@ -1443,50 +1355,15 @@ def test_pipelined_submit_device_tones(cuda_device, gsdr_lib, oracle_mod, monkey
     own choice, the frame-per-workgroup kernel with its two carry buffers.  L is no multiple of nfft:
     the carried length changes from buffer to buffer.  Bit-equal to the in-order entry, within
     tolerance of the oracle."""
-    import torch
+    from _product_loops import pipelined_tones
     monkeypatch.setenv("GSDR_DDC_MFMA", "1")
     if streams != "fft":
         monkeypatch.setenv("GSDR_TONES_FFT", "0")
         monkeypatch.setenv("GSDR_PIPE_STREAMS", streams)
-    rate, nfft, F, L, N = 10_000_000, 250, 4, 100_003, 96
-    rng = np.random.default_rng(2718)
-    freq = rng.choice(np.arange(-rate // 2 + 1, rate // 2), size=N, replace=False)
-    a, b = make_pfb(freq, rate, nfft, F, L), make_pfb(freq, rate, nfft, F, L)
-    assert b.kernel_name in PFB_LDS_KERNELS if streams == "fft" else b.kernel_name.startswith("ddc_mfma")
-    ref = oracle_mod.Pfb(freq, rate, nfft, F, L)
-    scales = [1.0, 1e-3, 50.0, 1.0, 1e-2, 1.0, 7.0, 1.0, 1.0]
-    xs = [torch.from_numpy((crandn(rng, L) * np.float32(sc)).astype(np.complex64)).to(cuda_device) for sc in scales]
-    out_a = torch.empty(a.out_capacity, dtype=torch.complex64, device=cuda_device)
-    want = []
-    for x in xs:
-        n = a.process_device(x, out_a)
-        torch.cuda.synchronize()
-        want.append(out_a[:n].cpu().numpy())
-    outs = [torch.zeros(b.out_capacity, dtype=torch.complex64, device=cuda_device) for _ in xs]
-    torch.cuda.synchronize()
-    got, pending = [], []
-    for k, x in enumerate(xs):
-        if len(pending) == 4:
-            j = pending.pop(0)
-            got.append(outs[j][:b.wait()].cpu().numpy())
-        b.submit_device(x, outs[k])
-        pending.append(k)
-    while pending:
-        j = pending.pop(0)
-        got.append(outs[j][:b.wait()].cpu().numpy())
-    assert [len(y) for y in got] == [len(y) for y in want]
-    assert len({len(y) for y in got}) > 1          # the batch count does change
-    for k, (y, yr) in enumerate(zip(got, want)):
-        np.testing.assert_array_equal(y, yr, err_msg="buffer %d" % k)
-    for k, x in enumerate(xs[:4]):
-        yo = ref.process(x.cpu().numpy())
-        assert yo.size == got[k].size
-        yo = yo.reshape(-1, N)
-        den = np.linalg.norm(yo, axis=0)
-        err = np.linalg.norm(got[k].reshape(-1, N) - yo, axis=0) / den
-        assert err.max() <= TOL, (k, err.max())
-    a.close()
-    b.close()
+
+    def check(dem, ran):
+        assert ran or (dem.kernel_name in PFB_LDS_KERNELS if streams == "fft" else dem.kernel_name.startswith("ddc_mfma")), dem.kernel_name
+    pipelined_tones(cuda_device, oracle_mod, check)
 
 
 def test_pipelined_soak_full_size(cuda_device, gsdr_lib, monkeypatch):
@@ -1561,6 +1438,7 @@ def test_pipelined_fuzz_random_shapes(cuda_device, gsdr_lib, monkeypatch, rt, to
     buffer), seven buffers each with up to four outstanding.  TONES on the DDC kernels
     (GSDR_TONES_FFT=0) or through the frame-per-workgroup kernel (the library's choice)."""
     import torch
+    from _product_loops import submit_equals_process
     monkeypatch.setenv("GSDR_DDC_MFMA", "1")
     monkeypatch.setenv("GSDR_MFMA_RT", rt)
     if tones == "ddc":
@@ -1586,26 +1464,7 @@ def test_pipelined_fuzz_random_shapes(cuda_device, gsdr_lib, monkeypatch, rt, to
             assert b.kernel_name in PFB_LDS_KERNELS
         xs = [torch.from_numpy((crandn(rng, L) * np.float32(10.0 ** rng.integers(-3, 3))).astype(np.complex64))
               .to(cuda_device) for _ in range(7)]
-        out_a = torch.empty(a.out_capacity, dtype=torch.complex64, device=cuda_device)
-        outs = [torch.zeros(b.out_capacity, dtype=torch.complex64, device=cuda_device) for _ in xs]
-        want = []
-        for x in xs:
-            n = a.process_device(x, out_a)
-            torch.cuda.synchronize()
-            want.append(out_a[:n].cpu().numpy())
-        got, pending = [], []
-        for k, x in enumerate(xs):
-            if len(pending) == 4:
-                j = pending.pop(0)
-                got.append(outs[j][:b.wait()].cpu().numpy())
-            b.submit_device(x, outs[k])
-            pending.append(k)
-        while pending:
-            j = pending.pop(0)
-            got.append(outs[j][:b.wait()].cpu().numpy())
-        for k, (y, yr) in enumerate(zip(got, want)):
-            np.testing.assert_array_equal(y, yr, err_msg="shape %d (%s N=%d F=%d L=%d) buffer %d"
-                                          % (it, b.kernel_name, N, F, L, k))
+        submit_equals_process(cuda_device, a, b, xs, "shape %d (%s N=%d F=%d L=%d) " % (it, b.kernel_name, N, F, L))
         a.close()
         b.close()
     assert ran_mfma >= 18

@@ -4,12 +4,20 @@ kernel name and the whole describe() tuple -- before the first call and after th
 
 Per-tone relative error against the fp64 oracle, bar 1e-5 as everywhere; every figure goes to the margin file.  What
 is particular to one loop (switches and thresholds, the HDR combs, C3, wide against narrow bits) is in that loop's own
-file."""
+file.
+
+The second half of the file brings the engine-wide behavioural tests of tests/test_gpu_parity.py (whose engine fixtures
+stop at the four-product build) to the loops: the bodies are those tests' own, shared through tests/_product_loops.py,
+at small shapes.  No test sets an engine switch by hand: force() is the only source, GSDR_PIPE_OVERLAP and
+GSDR_PIPE_STREAMS (which select no loop) excepted."""
 import numpy as np
 import pytest
 
-from _product_loops import (EXTREME_KINDS, EXTREME_SHAPES, LOOPS, VALU_CASES, direct_parity, extreme_and_nonfinite_samples, force,
-                            is_loop, shape_id)
+from _margins import record_info
+from _product_loops import (EXTREME_KINDS, EXTREME_SHAPES, LOOPS, STREAMING_SHAPE, VALU_CASES, direct_parity,
+                            dynamic_range_and_scale_carry, extreme_and_nonfinite_samples, force, fuzz_random_shapes, is_loop,
+                            more_tap_phases, pipelined_fuzz, pipelined_overlapping_buffers, pipelined_tones,
+                            pure_tones_demodulate_to_their_phasors, shape_id, streaming_runs, two_handles_interleaved)
 from test_gpu_parity import DIRECT_CASES, TOL, crandn, make_direct, make_pfb, rel_err_per_tone, run_device, run_host
 from test_gpu_extents import S_C3, S_N65, S_ODD, TONES_SHAPE, direct_inputs, run_case, run_tones
 
@@ -99,8 +107,6 @@ def test_tones_on_the_ddc_kernels(cuda_device, gsdr_lib, oracle_mod, loop):
 
 @pytest.mark.parametrize("kind", EXTREME_KINDS)
 @pytest.mark.parametrize("shape", list(EXTREME_SHAPES))
-
-
 def test_extreme_and_nonfinite_samples(cuda_device, gsdr_lib, oracle_mod, loop, kind, shape):
     extreme_and_nonfinite_samples(cuda_device, oracle_mod, loop, kind, shape)
 
@@ -156,3 +162,96 @@ def test_one_handle_every_entry(cuda_device, gsdr_lib, loop, N):
         for k, (y, w) in enumerate(zip(got[entry], got["process"])):
             assert y.size == w.size == N * (L // M), (entry, k)
             np.testing.assert_array_equal(y.view(np.int32), w.view(np.int32), err_msg=f"buffer {k} via {entry}")
+
+
+# ---------------------------------------------------------------------------
+# the engine-wide behavioural tests, on each loop
+# ---------------------------------------------------------------------------
+def _on(loop):
+    return lambda dem, ran: is_loop(dem, loop)
+
+
+def test_fuzz_random_shapes(cuda_device, gsdr_lib, oracle_mod, loop):
+    """36 seeded shapes nobody picked by hand (loop_fuzz_shapes; tests/test_product_loops_host.py states what they
+    cover: windows of one and two blocks, odd block counts, partial row tiles, rows == F - 1, F up to 8, 65 and 257
+    tones, M >= rate, the NCO sample index passing `rate` inside a buffer); every shape runs the loop."""
+    fuzz_random_shapes(cuda_device, oracle_mod, _on(loop), loop)
+
+
+def test_pipelined_fuzz(cuda_device, gsdr_lib, loop):
+    """The first 12 of those shapes through submit_device with up to four buffers in flight, the loudness changing by
+    up to five orders between consecutive buffers: each call's convert pass reads its own scale table and writes its
+    own image set, or the bits differ from the in-order entry's."""
+    pipelined_fuzz(cuda_device, _on(loop), loop)
+
+
+def test_dynamic_range_and_scale_carry(cuda_device, gsdr_lib, oracle_mod, loop):
+    """Loudness 1, 1e-6, 1e-6, 3e4, 1, 0, 1e-3, 0 in consecutive buffers: finite everywhere, exact zeros where the
+    oracle's are, every tone within TOL otherwise."""
+    dynamic_range_and_scale_carry(cuda_device, oracle_mod, _on(loop))
+
+
+@pytest.mark.parametrize("F", [5, 6, 7, 8])
+def test_more_tap_phases(cuda_device, gsdr_lib, oracle_mod, loop, F):
+    """pf_average 5 .. 8 at M = 40: windows of 200, 240, 280 and 320 samples -- 7, 8, 9 and 10 blocks (both parities of
+    the span count) with 24, 16, 8 and 0 samples of padding; the device and the host entry in turn."""
+    more_tap_phases(cuda_device, oracle_mod, _on(loop), F, M=40, alternate=True)
+
+
+def test_two_handles_interleaved(cuda_device, gsdr_lib, oracle_mod, loop):
+    """Two handles of one loop fed alternately, loudness 10 ** (c - 2k): image sets, d_bfrag3 / d_ptab3 and the scale
+    tables are per handle."""
+    two_handles_interleaved(cuda_device, oracle_mod, lambda k, *shape: make_direct(*shape),
+                            lambda k, dem, ran: is_loop(dem, loop))
+
+
+def test_two_handles_on_different_loops_interleaved(cuda_device, gsdr_lib, oracle_mod, monkeypatch, loop):
+    """The same with the second handle on the next loop of LOOPS (cyclically): the switches are read once per handle,
+    at creation, so the environment is forced anew between the two creations."""
+    names = list(LOOPS)
+    pair = (loop, names[(names.index(loop) + 1) % len(names)])
+
+    def make(k, *shape):
+        force(monkeypatch, pair[k])
+        return make_direct(*shape)
+    two_handles_interleaved(cuda_device, oracle_mod, make, lambda k, dem, ran: is_loop(dem, pair[k]))
+
+
+def test_streaming_equals_one_long_buffer(cuda_device, gsdr_lib, oracle_mod, loop):
+    """One stream as one buffer of 60 000 samples and as three of 20 000: both within TOL of the oracle of the whole
+    stream.  The difference between the two runs is recorded, not bounded (two runs inside TOL of a third need not be
+    within 2e-6 of each other, the figure test_direct_streaming_equals_one_long_buffer holds four-product engines to)."""
+    N, rate, M, F, L = STREAMING_SHAPE
+    freq, x, ya, yb = streaming_runs(cuda_device, _on(loop))
+    yr = oracle_mod.Direct(freq, rate, M, F, L).process(x)
+    assert ya.shape == yb.shape == yr.shape == (L // M, N)
+    ea = rel_err_per_tone(ya, yr, "one buffer")
+    eb = rel_err_per_tone(yb, yr, "three buffers")
+    den = np.linalg.norm(ya.astype(np.complex128), axis=0)
+    diff = float((np.linalg.norm(yb.astype(np.complex128) - ya, axis=0) / den).max())
+    record_info(diff, "three buffers against one buffer, worst per-tone difference")
+    print(f"{loop}: one buffer {ea.max():.3e}, three buffers {eb.max():.3e}, three against one {diff:.3e}")
+    assert ea.max() <= TOL and eb.max() <= TOL, (float(ea.max()), float(eb.max()))
+
+
+def test_pure_tones_demodulate_to_their_phasors(cuda_device, gsdr_lib, loop):
+    """Closed form, no oracle: |y - a e^{i phi}| < 5e-4 (the filter's stop band) behind the first F rows."""
+    pure_tones_demodulate_to_their_phasors(cuda_device, _on(loop))
+
+
+@pytest.mark.parametrize("overlap,streams", [("1", "2"), ("1", "3"), ("0", "2")])
+def test_pipelined_overlapping_buffers(cuda_device, gsdr_lib, oracle_mod, monkeypatch, loop, overlap, streams):
+    """Eleven buffers of loudness 1e-4 .. 100 with up to four in flight, 160 tones x 1000 rows (more than one workgroup
+    of tones on every loop): bit-equal to the in-order handle, the first four within TOL of the oracle, and
+    process_device works after the drain."""
+    monkeypatch.setenv("GSDR_PIPE_OVERLAP", overlap)
+    monkeypatch.setenv("GSDR_PIPE_STREAMS", streams)
+    pipelined_overlapping_buffers(cuda_device, oracle_mod, _on(loop), N=160, L=100_000)
+
+
+@pytest.mark.parametrize("streams", ["2", "3"])
+def test_pipelined_tones_on_the_ddc_kernels(cuda_device, gsdr_lib, oracle_mod, monkeypatch, loop, streams):
+    """TONES (nfft 250, 96 tones, L = 100 003) through submit_device, nine buffers of changing loudness and batch
+    count: bit-equal to the in-order handle, the first four within TOL of the oracle."""
+    monkeypatch.setenv("GSDR_PIPE_STREAMS", streams)
+    pipelined_tones(cuda_device, oracle_mod, _on(loop))
