@@ -157,7 +157,15 @@ SIGNATURES = [
     ("gsdr_tx_tone_bins", C.c_int, [C.c_int, _ip, _fp, C.c_int, _ip, _fp]),
     ("gsdr_source_chirp", C.c_int, [_vp, C.c_longlong, C.c_ulonglong,
                                     C.POINTER(ChirpParamC), C.c_float, _vp]),
+    ("gsdr_demod_create_ex", _vp, [C.POINTER(ParamC), C.c_uint]),
+    ("gsdr_txgen_create_ex", C.c_void_p, [C.POINTER(ParamC), C.POINTER(C.c_float), C.c_int, C.c_uint]),
+    ("gsdr_source_multichirp", C.c_int, [_vp, C.c_longlong, C.c_ulonglong, C.POINTER(ChirpParamC), _fp, C.c_int, _vp]),
+    ("gsdr_source_multichirp_sc16", C.c_int, [_vp, C.c_longlong, C.c_ulonglong, C.POINTER(ChirpParamC), _fp, C.c_int,
+                                              C.c_float, _vp, _vp]),
 ]
+
+CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
+MULTI_CHIRP_MAX = 16        # GSDR_MULTI_CHIRP_MAX
 
 _lib = None
 

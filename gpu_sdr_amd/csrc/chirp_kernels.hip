@@ -110,6 +110,13 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
     return __int_as_float(x);
 }
 
+// e0 + p mod period (e0 < period)
+__device__ __forceinline__ unsigned long long generic_advance(unsigned long long e0, int p, const ChirpShape &cs) {
+    unsigned long long e = e0 + (unsigned long long)p;
+    if (e >= cs.period) e = (e - cs.period < cs.period) ? e - cs.period : e % cs.period;
+    return e;
+}
+
 __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_demod_generic_kernel(const float2 *__restrict__ in,
                                                           float2 *__restrict__ out, long long n,
                                                           unsigned long long index0,
@@ -145,9 +152,7 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_lockin_generic_kernel(
         const float w = profile[p];
         const long long pos = base + p;
         const float2 s = pos < carry_len ? carry[pos] : in[pos - carry_len];
-        unsigned long long e = e0 + (unsigned long long)p;
-        if (e >= cs.period) e = (e - cs.period < cs.period) ? e - cs.period : e % cs.period;
-        const float2 d = demod_one(s, chirp_index(e, cs, small));
+        const float2 d = demod_one(s, chirp_index(generic_advance(e0, p, cs), cs, small));
         sx = fmaf(d.x, w, sx);
         sy = fmaf(d.y, w, sy);
     }
@@ -205,6 +210,32 @@ __device__ __forceinline__ void load_stretch(ChirpStretch &c, const float2 *__re
         const float2 *p = (int)pos < carry_len ? carry + pos : in + (pos - (unsigned)carry_len);
         c.smp[i] = *p;
         c.w[i] = w_seg[rc];          // zeroed at the use (a select here would wait for the load)
+    }
+}
+
+// The stretch `cur` (samples r0 + 64 i + lane of a step) demodulated by one chirp and added to its weighted sums: the
+// loop body of chirp_lockin_kernel and chirp_lockin_split_kernel below as a function, for the kernels that take several
+// chirps.  (The two single-chirp kernels keep the body written out: called from there the function compiles to the
+// same arithmetic in another register allocation and schedule, and their code objects stay what was measured.)
+// A, K: step_coeffs of the step; (sd, cd): the phasor of 64 A.
+// The lane's four samples are 64 apart: inside a step the index advances by 64*A (mod 2^32), the chirp phasor by one
+// fixed rotation -- one sincos per lane and stretch instead of four.
+__device__ __forceinline__ void lockin_stretch(const ChirpStretch &cur, unsigned r0, unsigned len, int lane, unsigned A,
+                                               unsigned K, float sd, float cd, float &sx, float &sy) {
+    float sn, cn;
+    sincos_index((int)(K + (r0 + (unsigned)lane) * A), sn, cn);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned r = r0 + (unsigned)(i * 64 + lane);
+        const float2 in = cur.smp[i];
+        const float chx = sn, chy = -cn;     // chirp = (sinpi, -cospi); in * conj(chirp): demod_one()
+        const float dx = chx * in.x + chy * in.y, dy = chx * in.y - chy * in.x;
+        const float w = r < len ? cur.w[i] : 0.f;
+        sx = fmaf(dx, w, sx);
+        sy = fmaf(dy, w, sy);
+        const float s2 = fmaf(sn, cd, cn * sd), c2 = fmaf(cn, cd, -(sn * sd));
+        sn = s2;
+        cn = c2;
     }
 }
 
@@ -355,6 +386,17 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_lockin_sum_kernel(const 
     if (lane == 63) out[v] = mk2c(sx, sy);
 }
 
+// Step fi and position rem inside it of the sample r (< len + 256) samples behind the start of step fi_w
+__device__ __forceinline__ void step_of_sample(unsigned r, unsigned fi_w, unsigned len, float inv_len, unsigned steps,
+                                               unsigned &fi, unsigned &rem) {
+    unsigned qd = (unsigned)((float)r * inv_len);         // r / len, off by at most one
+    rem = r - qd * len;
+    if ((int)rem < 0) { qd--; rem += len; }
+    if (rem >= len) { qd++; rem -= len; }
+    fi = fi_w + qd;
+    if (fi >= steps) fi %= steps;
+}
+
 // Undecimated demodulation: 4 consecutive runs of 64 samples per wave; the step
 // index of a sample is the wave's base step plus a small quotient.
 __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_demod_kernel(const float2 *__restrict__ in,
@@ -373,13 +415,8 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_demod_kernel(const float
         for (int i = 0; i < 4; ++i) {
             const long long o = o0 + i * 64 + lane;
             if (o < n) {
-                unsigned r = r_w + (unsigned)(i * 64 + lane);        // < len + 256
-                unsigned qd = (unsigned)((float)r * inv_len);         // r / len, off by at most one
-                unsigned rem = r - qd * len;
-                if ((int)rem < 0) { qd--; rem += len; }
-                if (rem >= len) { qd++; rem -= len; }
-                unsigned fi = fi_w + qd;
-                if (fi >= steps) fi %= steps;
+                unsigned fi, rem;
+                step_of_sample(r_w + (unsigned)(i * 64 + lane), fi_w, len, inv_len, steps, fi, rem);
                 unsigned A, K;
                 step_coeffs(fi, cs, A, K);
                 out[o] = demod_one(in[o], (int)(K + rem * A));
@@ -387,6 +424,265 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_demod_kernel(const float
         }
     }
 }
+
+// ---------------------------------------------------------------------------
+// Several chirps in one pass (GSDR_CREATE_MULTI_CHIRP): the chirps of a MultiChirp share num_steps, length and the
+// period, so the windows, the stretches, the carry and the running index are those of one chirp; only f0 and
+// chirpness -- A, K and the phasors that follow from them -- are per chirp.  Every kernel below reads a sample once
+// and demodulates it by every chirp; one chirp's arithmetic is that of the single-chirp kernels (the same inline
+// functions).  Outputs are [point or sample][chirp].
+//
+// Lock-in: one kernel for both single-chirp layouts.  A wave owns `per_part` consecutive stretches of a point
+// (parts == 1: the whole point, as in chirp_lockin_kernel, written straight to the output; parts > 1: the dealing of
+// chirp_lockin_split_kernel, partial sums [point][part][chirp], added by chirp_multi_lockin_sum_kernel in fixed
+// order).  The four samples of a stretch and their weights stay in registers while the chirps go by; the per-chirp
+// state -- the two sums, the step rotation (sd, cd), and A, K in scalar registers -- lives in arrays of NC entries
+// indexed at compile time (6 registers per chirp, ~100 at NC = 16), so the kernel is instantiated for whole groups
+// of kChirpGroup chirps and a handle takes the smallest that holds its chirps.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_lockin_kernel(
+    const float2 *__restrict__ carry, int carry_len, const float2 *__restrict__ in,
+    const float *__restrict__ profile, int ppt, int decim, int valid, int parts, int per_part,
+    float2 *__restrict__ dst, unsigned long long index0, MultiChirp mc) {
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wave = (int)blockIdx.x * 4 + wid;
+    if (wave >= valid * parts) return;
+    const int v = wave / parts, part = wave - v * parts;     // wave-uniform
+    const int n = mc.n;
+    const unsigned len = (unsigned)mc.length, steps = (unsigned)mc.num_steps;
+    const unsigned nst = (len + 255u) / 256u, total = (unsigned)decim * nst;
+    const unsigned q0 = (unsigned)part * (unsigned)per_part;
+    const unsigned q1 = q0 + (unsigned)per_part < total ? q0 + (unsigned)per_part : total;
+    float sx[NC], sy[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) sx[c] = sy[c] = 0.f;
+    if (q0 < q1) {
+        const unsigned base = (unsigned)v * (unsigned)ppt;  // position in the logical stage [carry | in]
+        unsigned d = q0 / nst, r0 = (q0 - d * nst) * 256u;
+        ChirpStretch cur, nxt;
+        load_stretch(cur, carry, carry_len, in, profile + (size_t)d * len, base + d * len, r0, len, lane);
+        asm volatile("" ::: "memory");                      // the loads stay in front of the divisions
+        const unsigned e0 = wrap_index(index0, base, chirp_shape_of(mc, 0));   // a multiple of len
+        unsigned fi = (e0 / len + d) % steps;
+        bool new_step = true;
+        unsigned A[NC], K[NC];
+        float sd[NC], cd[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            A[c] = K[c] = 0u;
+            sd[c] = 0.f;
+            cd[c] = 1.f;
+        }
+        for (unsigned q = q0; q < q1; ++q) {
+            if (new_step) {
+#pragma unroll
+                for (int c = 0; c < NC; ++c)
+                    if (c < n) {
+                        step_coeffs(fi, chirp_shape_of(mc, c), A[c], K[c]);
+                        sincos_index((int)(64u * A[c]), sd[c], cd[c]);
+                    }
+                new_step = false;
+            }
+            unsigned nd = d, nr0 = r0 + 256u;
+            if (nr0 >= len) {
+                nd = d + 1u;
+                nr0 = 0u;
+            }
+            if (q + 1u < q1)
+                load_stretch(nxt, carry, carry_len, in, profile + (size_t)nd * len, base + nd * len, nr0, len, lane);
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if (c < n) lockin_stretch(cur, r0, len, lane, A[c], K[c], sd[c], cd[c], sx[c], sy[c]);
+            cur = nxt;
+            if (nd != d) {
+                d = nd;
+                fi = fi + 1u == steps ? 0u : fi + 1u;
+                new_step = true;
+            }
+            r0 = nr0;
+        }
+    }
+    float2 *__restrict__ row = dst + (size_t)wave * (size_t)n;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < n) {
+            const float tx = wave_sum_to_lane63(sx[c]), ty = wave_sum_to_lane63(sy[c]);
+            if (lane == 63) row[c] = mk2c(tx, ty);
+        }
+}
+
+// a wave per (point, chirp): chirp_lockin_sum_kernel's order of additions over partial[point][part][chirp]
+__global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_lockin_sum_kernel(const float2 *__restrict__ partial, int rows,
+                                                                                int parts, int n, float2 *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int w = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // point * n + chirp
+    if (w >= rows) return;
+    const int v = w / n, c = w - v * n;
+    const float2 *__restrict__ pp = partial + (size_t)v * parts * n + c;
+    float sx = 0.f, sy = 0.f;
+    for (int p = lane; p < parts; p += 64) {
+        const float2 t = pp[(size_t)p * n];
+        sx += t.x;
+        sy += t.y;
+    }
+    sx = wave_sum_to_lane63(sx);
+    sy = wave_sum_to_lane63(sy);
+    if (lane == 63) out[w] = mk2c(sx, sy);
+}
+
+// chirp_lockin_generic_kernel for several chirps: one wave per point, any period
+template <int NC>
+__global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_lockin_generic_kernel(
+    const float2 *__restrict__ carry, int carry_len, const float2 *__restrict__ in,
+    const float *__restrict__ profile, int ppt, int valid, float2 *__restrict__ out,
+    unsigned long long index0, MultiChirp mc) {
+    const bool small = mc.period < 0xffffffffull && mc.num_steps < 0xfffffffeull;
+    const int lane = threadIdx.x & 63;
+    const int v = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (v >= valid) return;
+    const int n = mc.n;
+    const ChirpShape cs0 = chirp_shape_of(mc, 0);
+    const long long base = (long long)v * ppt;  // position in the logical stage
+    const unsigned long long e0 = (index0 + (unsigned long long)base) % mc.period;
+    float sx[NC], sy[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) sx[c] = sy[c] = 0.f;
+    for (int p = lane; p < ppt; p += 64) {
+        const float w = profile[p];
+        const long long pos = base + p;
+        const float2 s = pos < carry_len ? carry[pos] : in[pos - carry_len];
+        const unsigned long long e = generic_advance(e0, p, cs0);
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            if (c < n) {
+                const float2 d = demod_one(s, chirp_index(e, chirp_shape_of(mc, c), small));
+                sx[c] = fmaf(d.x, w, sx[c]);
+                sy[c] = fmaf(d.y, w, sy[c]);
+            }
+    }
+    float2 *__restrict__ row = out + (size_t)v * (size_t)n;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < n) {
+            const float tx = wave_sum_to_lane63(sx[c]), ty = wave_sum_to_lane63(sy[c]);
+            if (lane == 63) row[c] = mk2c(tx, ty);
+        }
+}
+
+// Undecimated: chirp_demod_kernel's walk over the samples; a lane writes the n outputs of its sample side by side
+__global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_demod_kernel(const float2 *__restrict__ in, float2 *__restrict__ out,
+                                                                           long long n_samples, unsigned long long index0,
+                                                                           MultiChirp mc) {
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = mc.n;
+    const unsigned len = (unsigned)mc.length, steps = (unsigned)mc.num_steps;
+    const float inv_len = 1.0f / (float)len;
+    const ChirpShape cs0 = chirp_shape_of(mc, 0);
+    const long long wave_stride = (long long)gridDim.x * 4 * 256;
+    for (long long o0 = ((long long)blockIdx.x * 4 + wid) * 256; o0 < n_samples; o0 += wave_stride) {
+        const unsigned e_w = wrap_index(index0, (unsigned)o0, cs0);
+        const unsigned fi_w = e_w / len, r_w = e_w - fi_w * len;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long o = o0 + i * 64 + lane;
+            if (o < n_samples) {
+                unsigned fi, rem;
+                step_of_sample(r_w + (unsigned)(i * 64 + lane), fi_w, len, inv_len, steps, fi, rem);
+                const float2 s = in[o];
+                float2 *__restrict__ row = out + (size_t)o * (size_t)n;
+                for (int c = 0; c < n; ++c) {
+                    unsigned A, K;
+                    step_coeffs(fi, chirp_shape_of(mc, c), A, K);
+                    row[c] = demod_one(s, (int)(K + rem * A));
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_demod_generic_kernel(const float2 *__restrict__ in,
+                                                                                   float2 *__restrict__ out, long long n_samples,
+                                                                                   unsigned long long index0, MultiChirp mc) {
+    const bool small = mc.period < 0xffffffffull && mc.num_steps < 0xfffffffeull;
+    const int n = mc.n;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < n_samples; o += stride) {
+        const unsigned long long e = (index0 + (unsigned long long)o) % mc.period;
+        const float2 s = in[o];
+        float2 *__restrict__ row = out + (size_t)o * (size_t)n;
+        for (int c = 0; c < n; ++c) row[c] = demod_one(s, chirp_index(e, chirp_shape_of(mc, c), small));
+    }
+}
+
+// the instantiation whose register arrays hold mc.n chirps
+#define GSDR_MULTI_DISPATCH(KERNEL, grid, ...)                                                                             \
+    switch ((mc.n + kChirpGroup - 1) / kChirpGroup) {                                                                      \
+        case 1: hipLaunchKernelGGL((KERNEL<1 * kChirpGroup>), grid, dim3(256), 0, st, __VA_ARGS__); break;                 \
+        case 2: hipLaunchKernelGGL((KERNEL<2 * kChirpGroup>), grid, dim3(256), 0, st, __VA_ARGS__); break;                 \
+        case 3: hipLaunchKernelGGL((KERNEL<3 * kChirpGroup>), grid, dim3(256), 0, st, __VA_ARGS__); break;                 \
+        default: hipLaunchKernelGGL((KERNEL<4 * kChirpGroup>), grid, dim3(256), 0, st, __VA_ARGS__); break;                \
+    }
+static_assert(4 * kChirpGroup == kMultiChirpMax, "the largest instantiation holds every chirp");
+
+hipError_t launch_chirp_multi_demod(const float2 *in, float2 *out, long long n_samples, unsigned long long index0,
+                                    const MultiChirp &mc, hipStream_t st) {
+    if (n_samples <= 0) return hipSuccess;
+    if (mc.n < 1 || mc.n > kMultiChirpMax) return hipErrorInvalidValue;
+    if (chirp_fits_32(chirp_shape_of(mc, 0))) {
+        long long blocks = (n_samples + 1023) / 1024;  // 256 samples per wave
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        hipLaunchKernelGGL(chirp_multi_demod_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, n_samples, index0, mc);
+    } else {
+        long long blocks = (n_samples + 255) / 256;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        hipLaunchKernelGGL(chirp_multi_demod_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, n_samples,
+                           index0, mc);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_chirp_multi_lockin(const float2 *carry, int carry_len, const float2 *in, const float *profile, int ppt,
+                                     int valid, float2 *out, unsigned long long index0, const MultiChirp &mc, hipStream_t st,
+                                     bool split, float2 *partial, int partial_cap) {
+    if (valid <= 0) return hipSuccess;
+    if (mc.n < 1 || mc.n > kMultiChirpMax) return hipErrorInvalidValue;
+    // (the conditions of launch_chirp_lockin)
+    const bool fast = chirp_fits_32(chirp_shape_of(mc, 0)) && ppt % (int)mc.length == 0 && index0 % mc.length == 0;
+    if (!fast) {
+        GSDR_MULTI_DISPATCH(chirp_multi_lockin_generic_kernel, dim3((unsigned)((valid + 3) / 4)), carry, carry_len, in, profile,
+                            ppt, valid, out, index0, mc);
+        return hipGetLastError();
+    }
+    const long long decim = ppt / (long long)mc.length, nst = ((long long)mc.length + 255) / 256, total = decim * nst;
+    long long parts = 1, per_part = total;
+    if (partial && split && valid <= 512) {
+        // few points with many samples each: launch_chirp_lockin's rule; a point's partial sums take parts * n slots
+        long long want = (4096 + valid - 1) / valid;
+        if (want > total / 4) want = total / 4;
+        if (want > partial_cap / ((long long)valid * mc.n)) want = partial_cap / ((long long)valid * mc.n);
+        if (want >= 2 && total >= 16 && total < 0x7fffffffLL) {
+            per_part = (total + want - 1) / want;
+            parts = (total + per_part - 1) / per_part;
+        }
+    }
+    const long long waves = (long long)valid * parts;
+    float2 *dst = parts > 1 ? partial : out;
+    GSDR_MULTI_DISPATCH(chirp_multi_lockin_kernel, dim3((unsigned)((waves + 3) / 4)), carry, carry_len, in, profile, ppt,
+                        (int)decim, valid, (int)parts, (int)per_part, dst, index0, mc);
+    if (parts > 1) {
+        const int rows = valid * mc.n;
+        hipLaunchKernelGGL(chirp_multi_lockin_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, partial, rows,
+                           (int)parts, mc.n, out);
+    }
+    return hipGetLastError();
+}
+#undef GSDR_MULTI_DISPATCH
+
+const char *chirp_multi_demod_kernel_name() { return "chirp_multi_demod_kernel"; }
+const char *chirp_multi_lockin_kernel_name() { return "chirp_multi_lockin_kernel"; }
 
 hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
                               unsigned long long index0, const ChirpShape &cs, hipStream_t st) {
@@ -538,6 +834,35 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void source_chirp_kernel(typename S
     st.finish((int)(threadIdx.x & 63));
 }
 
+// Several chirps added into one TX buffer: x[s] = term_0 + term_1 + ..., term_c the sample source_chirp_kernel writes
+// for chirp c (its two products, rounded), the additions in chirp order, real and imaginary part apart, each one IEEE
+// single-precision addition: contraction is off here, or a product would be fused into the sum that takes it.  The
+// sc16 store narrows the sum and counts what clips on the sum.
+template <typename Store, typename... Extra>
+__global__ __launch_bounds__(256) GSDR_NO_PK void source_multichirp_kernel(typename Store::Elem *__restrict__ out, long long n,
+                                                                           unsigned long long index0, MultiChirp mc,
+                                                                           MultiScale sc, Extra... extra) {
+#pragma clang fp contract(off)
+    Store st{out, extra...};
+    const bool small = mc.period < 0xffffffffull && mc.num_steps < 0xfffffffeull;
+    const int nc = mc.n;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += stride) {
+        const unsigned long long e = (index0 + (unsigned long long)o) % mc.period;
+        float re = 0.f, im = 0.f;
+        for (int k = 0; k < nc; ++k) {
+            float s, c;
+            sincos_index(chirp_index(e, chirp_shape_of(mc, k), small), s, c);
+            const float scale = sc.s[k];
+            const float tr = s * scale, ti = -c * scale;  // ref: kernels.cu:367-368
+            re = k == 0 ? tr : re + tr;                   // the sum starts from term_0, not from 0 + term_0
+            im = k == 0 ? ti : im + ti;
+        }
+        st.put(o, re, im);
+    }
+    st.finish((int)(threadIdx.x & 63));
+}
+
 // ---------------------------------------------------------------------------
 // TX tone comb at scale (row f3): x[s] = sum_k a_k e^(i phi_k) w_k^s, w_k = e^(+2 pi i f_k / rate).
 // ref: tone_gen, cpp/kernels.cu:589-684, builds one period (`rate` samples: 1.6 GB at 200 Msps) by an
@@ -670,6 +995,28 @@ hipError_t launch_source_chirp_sc16(void *out, long long n, unsigned long long i
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL((source_chirp_kernel<StoreSc16, float, unsigned long long *>), dim3((unsigned)blocks), dim3(256), 0, st,
                        reinterpret_cast<int *>(out), n, index0, cs, scale, gain, clipped);
+    return hipGetLastError();
+}
+
+hipError_t launch_source_multichirp(float2 *out, long long n, unsigned long long index0, const MultiChirp &mc,
+                                    const MultiScale &sc, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!out || mc.n < 1 || mc.n > kMultiChirpMax || mc.period < 1) return hipErrorInvalidValue;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL((source_multichirp_kernel<StoreC64>), dim3((unsigned)blocks), dim3(256), 0, st, out, n, index0, mc, sc);
+    return hipGetLastError();
+}
+
+hipError_t launch_source_multichirp_sc16(void *out, long long n, unsigned long long index0, const MultiChirp &mc,
+                                         const MultiScale &sc, float gain, unsigned long long *clipped, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!out || ((uintptr_t)out & 3) || ((uintptr_t)clipped & 7) || mc.n < 1 || mc.n > kMultiChirpMax || mc.period < 1)
+        return hipErrorInvalidValue;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL((source_multichirp_kernel<StoreSc16, float, unsigned long long *>), dim3((unsigned)blocks), dim3(256), 0,
+                       st, reinterpret_cast<int *>(out), n, index0, mc, sc, gain, clipped);
     return hipGetLastError();
 }
 

@@ -329,6 +329,45 @@ hipError_t launch_tones_synth_sc16(void *out, long long n, unsigned long long st
 const char *chirp_demod_kernel_name();
 const char *chirp_lockin_kernel_name();
 
+// ---- several chirps in one pass (GSDR_CREATE_MULTI_CHIRP) ------------------
+// The chirps share swipe_s and chirp_t, so num_steps, length and the period are common and the running index is one;
+// only f0 and chirpness differ.  Passed to the kernels by value: every field is wave-uniform.
+constexpr int kMultiChirpMax = 16;      // GSDR_MULTI_CHIRP_MAX
+constexpr int kChirpGroup = 4;          // the lock-in kernels keep their per-chirp state in register arrays of whole groups
+// (The per-chirp tables are vectors, not arrays: a kernel takes the structure as an argument and indexes it with a loop
+//  counter, and an array indexed that way makes the compiler copy the whole argument to scratch memory first; a vector
+//  is one value in scalar registers, whatever the index.)
+typedef int MultiChirpI __attribute__((ext_vector_type(kMultiChirpMax)));
+typedef unsigned MultiChirpU __attribute__((ext_vector_type(kMultiChirpMax)));
+typedef float MultiChirpF __attribute__((ext_vector_type(kMultiChirpMax)));
+struct MultiChirp {
+    unsigned long long num_steps, length, period;
+    int n;                              // 1 ... kMultiChirpMax
+    MultiChirpI f0;
+    MultiChirpU chirpness;
+};
+struct MultiScale {
+    MultiChirpF s;
+};
+__host__ __device__ __forceinline__ ChirpShape chirp_shape_of(const MultiChirp &mc, int c) {
+    ChirpShape cs;
+    cs.num_steps = mc.num_steps;
+    cs.length = mc.length;
+    cs.period = mc.period;
+    cs.chirpness = mc.chirpness[c];
+    cs.f0 = mc.f0[c];
+    return cs;
+}
+// out[o * n + c] = in[o] * conj(chirp_c(index0 + o)), o < n_samples: the samples are read once
+hipError_t launch_chirp_multi_demod(const float2 *in, float2 *out, long long n_samples, unsigned long long index0,
+                                    const MultiChirp &mc, hipStream_t st);
+// launch_chirp_lockin for every chirp of mc at once: out[v * n + c]; partial holds [point][part][chirp]
+hipError_t launch_chirp_multi_lockin(const float2 *carry, int carry_len, const float2 *in, const float *profile, int ppt,
+                                     int valid, float2 *out, unsigned long long index0, const MultiChirp &mc, hipStream_t st,
+                                     bool split, float2 *partial, int partial_cap);
+const char *chirp_multi_demod_kernel_name();
+const char *chirp_multi_lockin_kernel_name();
+
 // ---- synthetic sources ---------------------------------------------------
 hipError_t launch_source_tones(float2 *out, long long n, long long start, unsigned rate,
                                const unsigned *fmod_dev, const float *ampl_dev,
@@ -338,5 +377,11 @@ hipError_t launch_source_chirp(float2 *out, long long n, unsigned long long inde
                                const ChirpShape &cs, float scale, hipStream_t st);
 hipError_t launch_source_chirp_sc16(void *out, long long n, unsigned long long index0, const ChirpShape &cs, float scale,
                                     float gain, unsigned long long *clipped, hipStream_t st);
+// out[s] = term_0 + term_1 + ... in chirp order, term_c the sample launch_source_chirp writes for chirp c with sc.s[c];
+// every addition one IEEE single-precision operation.  _sc16: that sum narrowed, clipped components counted on the sum.
+hipError_t launch_source_multichirp(float2 *out, long long n, unsigned long long index0, const MultiChirp &mc,
+                                    const MultiScale &sc, hipStream_t st);
+hipError_t launch_source_multichirp_sc16(void *out, long long n, unsigned long long index0, const MultiChirp &mc,
+                                         const MultiScale &sc, float gain, unsigned long long *clipped, hipStream_t st);
 
 }  // namespace gsdr

@@ -234,6 +234,7 @@ struct gsdr_demod {
     gsdr::DevBuf<float> d_fft_win;                   // the PFB window on the device
     // ---- the parameters this handle was created with (gsdr_demod_prepare's rehearsal builds a twin) ----
     gsdr_param_c pc{};
+    unsigned flags = 0;                              // GSDR_CREATE_* of gsdr_demod_create_ex (the twin takes the same)
     std::vector<int> pc_wave_type, pc_freq, pc_chirp_f, pc_swipe_s;
     std::vector<float> pc_chirp_t;
     // ---- TONES / NOISE, a frame per workgroup: filter + in-LDS transform + bin selection (fft_kernels.hip) ----
@@ -249,7 +250,9 @@ struct gsdr_demod {
     gsdr::DevBuf<float2> d_avg_frames;               // [batching][ddc_channels]: where the PFB writes its frames instead of `out`
     gsdr::DevBuf<float2> d_avg_acc[2];               // [ddc_channels] each
     // ---- CHIRP ----
-    ChirpShape cs{};
+    ChirpShape cs{};                   // (several chirps: chirp 0; num_steps, length and the period are common to all)
+    int chirps = 1;                    // > 1: a GSDR_CREATE_MULTI_CHIRP handle; mc holds f0 and chirpness of every chirp
+    gsdr::MultiChirp mc{};
     int ppt = 0;
     gsdr_vna_helper vh{};
     gsdr::DevBuf<float> d_profile;
@@ -1071,9 +1074,10 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
     int ret;
     if (h->decim <= 0) {
         if (record_begin(h, st, &stop)) return -1;
-        HIPCHK(h, gsdr::launch_chirp_demod(in, out, h->L, h->last_index, h->cs, st));
+        if (h->chirps > 1) HIPCHK(h, gsdr::launch_chirp_multi_demod(in, out, h->L, h->last_index, h->mc, st));
+        else HIPCHK(h, gsdr::launch_chirp_demod(in, out, h->L, h->last_index, h->cs, st));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
-        ret = (int)h->L;                 // :390
+        ret = (int)(h->L * h->chirps);   // :390
     } else {
         const int valid = h->vh.valid_size;      // :361
         // chirp index of the first carried sample
@@ -1081,9 +1085,14 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
             (h->last_index + h->cs.period - (unsigned long long)h->carry_len % h->cs.period) %
             h->cs.period;
         if (record_begin(h, st, &stop)) return -1;
-        HIPCHK(h, gsdr::launch_chirp_lockin(h->d_ccarry[h->cparity], h->carry_len, in,
-                                            h->d_profile, h->ppt, valid, out, idx0, h->cs, st, h->sw.chirp_split,
-                                            h->d_chirp_part, h->d_chirp_part ? kChirpPartials : 0));
+        if (h->chirps > 1)
+            HIPCHK(h, gsdr::launch_chirp_multi_lockin(h->d_ccarry[h->cparity], h->carry_len, in, h->d_profile, h->ppt, valid,
+                                                      out, idx0, h->mc, st, h->sw.chirp_split, h->d_chirp_part,
+                                                      h->d_chirp_part ? kChirpPartials : 0));
+        else
+            HIPCHK(h, gsdr::launch_chirp_lockin(h->d_ccarry[h->cparity], h->carry_len, in,
+                                                h->d_profile, h->ppt, valid, out, idx0, h->cs, st, h->sw.chirp_split,
+                                                h->d_chirp_part, h->d_chirp_part ? kChirpPartials : 0));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
         // :369-380 the reference keeps the last new0 DEMODULATED samples; we
         // keep the same raw samples and re-demodulate them next call.
@@ -1104,7 +1113,7 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
         }
         h->carry_len = new0;
         gsdr_vna_helper_update(&h->vh);  // :382
-        ret = valid;
+        ret = valid * h->chirps;         // rows [point][chirp]
     }
     h->last_index = (h->last_index + (unsigned long long)h->L) % h->cs.period;  // :355
     return ret;
@@ -1296,9 +1305,17 @@ int setup_chirp(gsdr_demod *h, const gsdr_param_c *p) {
     if (!(cp.num_steps >= 1 && cp.length >= 1 && cp.num_steps <= 0x7fffffffffffffffULL / cp.length))
         return refuse(h, "chirp period overflows");
     h->cs = chirp_shape(cp);
+    // several chirps (demod_create has checked what they must share): chirp c differs in f0 and chirpness alone
+    const bool multi = h->chirps > 1;
+    if (multi) {
+        gsdr_chirp_param all[GSDR_MULTI_CHIRP_MAX];
+        for (int c = 0; c < h->chirps; ++c)
+            gsdr_chirp_derive(p->rate, p->freq[c], p->chirp_f[c], p->swipe_s[0], p->chirp_t[0], &all[c]);
+        if (const char *bad = gsdr::multi_chirp_shape(all, h->chirps, h->mc)) return refuse(h, bad);
+    }
     if (h->decim <= 0) {
-        h->kernel_name = gsdr::chirp_demod_kernel_name();
-        h->capacity = h->L;
+        h->kernel_name = multi ? gsdr::chirp_multi_demod_kernel_name() : gsdr::chirp_demod_kernel_name();
+        h->capacity = h->L * h->chirps;
         return 0;
     }
     const unsigned long long ppt = cp.length * (unsigned long long)h->decim;  // :231
@@ -1307,23 +1324,29 @@ int setup_chirp(gsdr_demod *h, const gsdr_param_c *p) {
     gsdr_vna_helper_init(&h->vh, h->ppt, (int)h->L);       // :235
     h->window.resize(h->ppt);
     gsdr_make_flat_window(h->ppt, h->ppt / 10, h->window.data());  // :246
-    h->kernel_name = gsdr::chirp_lockin_kernel_name();
-    h->capacity = h->L / h->ppt + 1;
+    h->kernel_name = multi ? gsdr::chirp_multi_lockin_kernel_name() : gsdr::chirp_lockin_kernel_name();
+    h->capacity = (h->L / h->ppt + 1) * h->chirps;
     if (h->d_profile.upload(h->window) != hipSuccess || h->d_ccarry[0].alloc((size_t)h->ppt) != hipSuccess ||
         h->d_ccarry[1].alloc((size_t)h->ppt) != hipSuccess || h->d_chirp_part.alloc((size_t)kChirpPartials) != hipSuccess)
         return refuse(h, "chirp allocation failed");
     return 0;
 }
 
-// gsdr_demod_create with the switches given (gsdr_demod_prepare's rehearsal twin takes its parent's)
-gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
+// gsdr_demod_create with the switches given (gsdr_demod_prepare's rehearsal twin takes its parent's) and the
+// GSDR_CREATE_* flags of gsdr_demod_create_ex
+gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw, unsigned flags) {
     create_error().clear();
+    if (flags & ~GSDR_CREATE_MULTI_CHIRP) {
+        create_error() = "unknown creation flag";
+        return nullptr;
+    }
     if (!p) {
         create_error() = "null parameters";
         return nullptr;
     }
     gsdr_demod *h = new gsdr_demod();
     h->sw = sw;
+    h->flags = flags;
     {
         h->pc = *p;
         auto keep = [](auto &dst, const auto *src, int n) {
@@ -1346,7 +1369,8 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
         if (p->wave_type[i] != last) mixed = true;
         if (p->wave_type[i] == GSDR_CHIRP) chirps++;
     }
-    if (chirps > 1) {
+    const bool multi = (flags & GSDR_CREATE_MULTI_CHIRP) != 0;
+    if (chirps > 1 && !multi) {
         fail_create(h, "Multiple chirp RX buffer demodulation has been requested. This feature is not implemented yet.");
         return nullptr;
     }
@@ -1361,6 +1385,13 @@ gsdr_demod *demod_create(const gsdr_param_c *p, const gsdr::Switches &sw) {
     if (h->L <= 0) {
         fail_create(h, "buffer_len must be positive");
         return nullptr;
+    }
+    if (last == GSDR_CHIRP && chirps > 1) {      // (one chirp with the flag is the plain single-chirp handle)
+        if (const char *bad = gsdr::multi_chirp_fault(p, chirps)) {
+            fail_create(h, bad);
+            return nullptr;
+        }
+        h->chirps = chirps;
     }
 
     {
@@ -1420,7 +1451,8 @@ const char *gsdr_last_error(const gsdr_demod *h) {
     return h ? h->err.c_str() : create_error().c_str();
 }
 
-gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gsdr::read_switches()); }
+gsdr_demod *gsdr_demod_create(const gsdr_param_c *p) { return demod_create(p, gsdr::read_switches(), 0u); }
+gsdr_demod *gsdr_demod_create_ex(const gsdr_param_c *p, unsigned flags) { return demod_create(p, gsdr::read_switches(), flags); }
 
 // The body of gsdr_demod_process_device and of its sc16 twin.  in16 != nullptr: the samples arrive as sc16 and are
 // widened into `wide` first (NODSP: straight into out) -- BEHIND the join below, because `wide` belongs to the handle:
@@ -1702,7 +1734,7 @@ int gsdr_demod_prepare(gsdr_demod *h, int what) {
     HIPCHK(h, hipDeviceSynchronize());
     if (what & GSDR_PREPARE_REHEARSE) {
         // a twin with the same parameters takes the process-wide first-use costs (see include/gsdr.h)
-        gsdr_demod *twin = demod_create(&h->pc, h->sw);
+        gsdr_demod *twin = demod_create(&h->pc, h->sw, h->flags);
         gsdr_c64 *pin_in = nullptr, *pin_out = nullptr;
         bool ok = twin != nullptr;
         ok = ok && (h->avg_k <= 1 || gsdr_demod_set_frame_average(twin, h->avg_k, h->avg_kind) == 0);
@@ -2036,6 +2068,7 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
                                    : "polyphase filter + fp32 Stockham FFT inside the LDS + bin selection, one launch") :
          h->noise_fft ? "fp32 Stockham FFT behind the polyphase filter" : h->mfma ? "f16 MFMA, hi/lo split" : (h->mode == GSDR_CHIRP ? "fp32 VALU, integer phase" : (h->pipe ? "packed fp32 VALU" : "fp32 VALU"));
     s += "\", \"channels\": " + std::to_string(h->ddc_channels > 0 ? h->ddc_channels : h->N);
+    if (h->mode == GSDR_CHIRP) s += ", \"chirps\": " + std::to_string(h->chirps);
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
     // every other handle reports what the four-product loop's row says
     const gsdr::ProductLoop &pr = h->mfma && h->loop ? *h->loop : *gsdr::product_loop(gsdr::MfmaKernel::AsmRing16P);

@@ -53,6 +53,46 @@ inline ChirpShape chirp_shape(const gsdr_chirp_param &cp) {
     return cs;
 }
 
+static_assert(kMultiChirpMax == GSDR_MULTI_CHIRP_MAX, "the kernels' tables hold GSDR_MULTI_CHIRP_MAX chirps");
+
+// What a GSDR_CREATE_MULTI_CHIRP request of C > 1 chirps must satisfy, RX and TX alike (include/gsdr.h, "several chirps
+// in one handle"): nullptr, or the refusal.  Looks at the parameters only.
+inline const char *multi_chirp_fault(const gsdr_param_c *p, int C) {
+    if (C > GSDR_MULTI_CHIRP_MAX) return "multi-chirp takes at most GSDR_MULTI_CHIRP_MAX (16) chirps";
+    if (!(p->n_freq >= C && p->n_chirp_f >= C && p->freq && p->chirp_f))
+        return "CHIRP needs freq[] and chirp_f[] for every wave_type entry";
+    // one sweep law for all: one entry, or C equal ones
+    auto shared = [C](const auto *v, int n) {
+        if (!v || (n != 1 && n != C)) return false;
+        for (int i = 1; i < n; ++i)
+            if (!(v[i] == v[0])) return false;
+        return true;
+    };
+    if (!shared(p->swipe_s, p->n_swipe_s) || !shared(p->chirp_t, p->n_chirp_t))
+        return "multi-chirp needs one swipe_s and one chirp_t for all chirps";
+    return nullptr;
+}
+
+// The chirps of a multi-chirp handle or call as the kernels take them: the common steps from cp[0], f0 and chirpness
+// of each.  nullptr, or why not.
+inline const char *multi_chirp_shape(const gsdr_chirp_param *cp, int C, MultiChirp &mc) {
+    if (C < 1 || C > GSDR_MULTI_CHIRP_MAX) return "the number of chirps must be in [1, GSDR_MULTI_CHIRP_MAX]";
+    if (cp[0].num_steps < 1 || cp[0].length < 1 || cp[0].num_steps > 0x7fffffffffffffffULL / cp[0].length)
+        return "chirp period overflows";
+    mc = MultiChirp{};
+    mc.num_steps = cp[0].num_steps;
+    mc.length = cp[0].length;
+    mc.period = cp[0].num_steps * cp[0].length;
+    mc.n = C;
+    for (int c = 0; c < C; ++c) {
+        if (cp[c].num_steps != cp[0].num_steps || cp[c].length != cp[0].length)
+            return "the chirps must share num_steps and length";
+        mc.f0[c] = cp[c].f0;
+        mc.chirpness[c] = cp[c].chirpness;
+    }
+    return nullptr;
+}
+
 }  // namespace gsdr
 
 #endif

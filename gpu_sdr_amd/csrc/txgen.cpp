@@ -47,6 +47,10 @@ struct gsdr_txgen {
     unsigned long long period = 1, last = 0;
     gsdr_chirp_param cp{};
     float scale = 1.f;
+    // several chirps added into one buffer (gsdr_txgen_create_ex, GSDR_CREATE_MULTI_CHIRP): n_chirps > 1, cp is chirp 0
+    int n_chirps = 1;
+    gsdr::MultiChirp mc{};
+    gsdr::MultiScale msc{};
     gsdr::TxBuffers<gsdr_c64> c64;
     // sc16 output (gsdr_txgen_*_sc16): the gain of the narrowing, the counter of clipped components (device memory,
     // zeroed at creation), and a staging buffer (4 bytes per sample) and a period buffer of its own
@@ -80,6 +84,10 @@ struct Complex64 {
                             unsigned long long *, hipStream_t st) {
         return gsdr::launch_source_chirp(reinterpret_cast<float2 *>(out), n, index0, cs, scale, st);
     }
+    static hipError_t multichirp(elem *out, long long n, unsigned long long index0, const gsdr::MultiChirp &mc,
+                                 const gsdr::MultiScale &sc, float, unsigned long long *, hipStream_t st) {
+        return gsdr::launch_source_multichirp(reinterpret_cast<float2 *>(out), n, index0, mc, sc, st);
+    }
 };
 
 struct Sc16 {
@@ -103,6 +111,10 @@ struct Sc16 {
     static hipError_t chirp(elem *out, long long n, unsigned long long index0, const ChirpShape &cs, float scale, float gain,
                             unsigned long long *clipped, hipStream_t st) {
         return gsdr::launch_source_chirp_sc16(out, n, index0, cs, scale, gain, clipped, st);
+    }
+    static hipError_t multichirp(elem *out, long long n, unsigned long long index0, const gsdr::MultiChirp &mc,
+                                 const gsdr::MultiScale &sc, float gain, unsigned long long *clipped, hipStream_t st) {
+        return gsdr::launch_source_multichirp_sc16(out, n, index0, mc, sc, gain, clipped, st);
     }
 };
 
@@ -175,6 +187,32 @@ int source_chirp(typename Fmt::elem *out_dev, long long n, unsigned long long la
     return 0;
 }
 
+// the sum of several chirps from the tables the kernel takes (mc, sc: checked by the caller)
+template <typename Fmt>
+int multichirp_launch(typename Fmt::elem *out_dev, long long n, unsigned long long last_index, const gsdr::MultiChirp &mc,
+                      const gsdr::MultiScale &sc, float gain, unsigned long long *clipped_dev, void *hip_stream) {
+    const hipError_t e = Fmt::multichirp(out_dev, n, last_index % mc.period, mc, sc, gain, clipped_dev, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return refuse<Fmt>("gsdr_source_multichirp", hipGetErrorString(e));
+    return 0;
+}
+
+// gsdr_source_multichirp and gsdr_source_multichirp_sc16: every refusal has a message; n == 0 touches nothing
+template <typename Fmt>
+int source_multichirp(typename Fmt::elem *out_dev, long long n, unsigned long long last_index, const gsdr_chirp_param *cp,
+                      const float *scale, int n_chirps, float gain, unsigned long long *clipped_dev, void *hip_stream) {
+    if (n == 0) return 0;
+    const char *bad = nullptr;
+    gsdr::MultiChirp mc;
+    gsdr::MultiScale sc{};
+    if (!out_dev || !cp || !scale || n < 0) bad = "bad arguments";
+    else if (n_chirps < 1 || n_chirps > GSDR_MULTI_CHIRP_MAX) bad = "n_chirps must be in [1, GSDR_MULTI_CHIRP_MAX]";
+    else bad = gsdr::multi_chirp_shape(cp, n_chirps, mc);
+    if (!bad) bad = Fmt::narrowing_fault(out_dev, gain, clipped_dev);
+    if (bad) return refuse<Fmt>("gsdr_source_multichirp", bad);
+    for (int c = 0; c < n_chirps; ++c) sc.s[c] = scale[c];
+    return multichirp_launch<Fmt>(out_dev, n, last_index, mc, sc, gain, clipped_dev, hip_stream);
+}
+
 // ref: get_from_tones :226-229, get_from_chirp :208-221.  get_device and get report under one name: gsdr_txgen_get
 template <typename Fmt>
 int get_device(gsdr_txgen *g, typename Fmt::elem *out_dev, void *hip_stream) {
@@ -184,7 +222,10 @@ int get_device(gsdr_txgen *g, typename Fmt::elem *out_dev, void *hip_stream) {
         rc = tones_fill<Fmt>(g, out_dev, g->buffer_len, (long long)(g->last % g->rate), hip_stream);
     } else {
         if (!set_device(g)) return refuse<Fmt>("gsdr_txgen_get", "hipSetDevice failed");
-        rc = source_chirp<Fmt>(out_dev, g->buffer_len, g->last, &g->cp, g->scale, g->sc16_gain, g->d_clipped, hip_stream);
+        if (g->n_chirps > 1)
+            rc = multichirp_launch<Fmt>(out_dev, g->buffer_len, g->last, g->mc, g->msc, g->sc16_gain, g->d_clipped, hip_stream);
+        else
+            rc = source_chirp<Fmt>(out_dev, g->buffer_len, g->last, &g->cp, g->scale, g->sc16_gain, g->d_clipped, hip_stream);
     }
     if (rc == 0) g->last = (g->last + (unsigned long long)g->buffer_len) % g->period;
     return rc;
@@ -367,11 +408,28 @@ void gsdr_txgen_close(gsdr_txgen *g) {
 
 // ref: TX_buffer_generator::TX_buffer_generator, cpp/USRP_buffer_generator.cpp:10-160
 gsdr_txgen *gsdr_txgen_create(const gsdr_param_c *p, const float *ampl, int n_ampl) {
+    return gsdr_txgen_create_ex(p, ampl, n_ampl, 0u);
+}
+
+int gsdr_source_multichirp(gsdr_c64 *out_dev, long long n, unsigned long long last_index, const gsdr_chirp_param *cp,
+                           const float *scale, int n_chirps, void *hip_stream) {
+    return source_multichirp<Complex64>(out_dev, n, last_index, cp, scale, n_chirps, 0.f, nullptr, hip_stream);
+}
+
+int gsdr_source_multichirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index, const gsdr_chirp_param *cp,
+                                const float *scale, int n_chirps, float gain, unsigned long long *clipped_dev,
+                                void *hip_stream) {
+    return source_multichirp<Sc16>(out_dev, n, last_index, cp, scale, n_chirps, gain, clipped_dev, hip_stream);
+}
+
+// flags: GSDR_CREATE_* (include/gsdr.h, "several chirps in one handle"); 0 is gsdr_txgen_create
+gsdr_txgen *gsdr_txgen_create_ex(const gsdr_param_c *p, const float *ampl, int n_ampl, unsigned flags) {
     create_error().clear();
     auto fail = [](const char *msg) {
         create_error() = msg;
         return (gsdr_txgen *)nullptr;
     };
+    if (flags & ~GSDR_CREATE_MULTI_CHIRP) return fail("unknown creation flag");
     if (!p) return fail("null parameters");
     if (p->buffer_len < 1) return fail("buffer_len must be positive");
     if (p->rate < 1) return fail("rate must be positive");
@@ -383,7 +441,7 @@ gsdr_txgen *gsdr_txgen_create(const gsdr_param_c *p, const float *ampl, int n_am
         chirps += p->wave_type[i] == GSDR_CHIRP;
         mixed |= p->wave_type[i] != last;
     }
-    if (chirps > 1)      // :26-29
+    if (chirps > 1 && !(flags & GSDR_CREATE_MULTI_CHIRP))      // :26-29
         return fail("Multiple chirp TX buffer generation has been requested. This feature is not implemented yet.");
     if (mixed)           // :31-34
         return fail("Mixed TX buffer generation has been requested. This feature is not implemented yet.");
@@ -406,9 +464,24 @@ gsdr_txgen *gsdr_txgen_create(const gsdr_param_c *p, const float *ampl, int n_am
         if (p->n_freq < 1 || p->n_chirp_f < 1 || p->n_swipe_s < 1 || p->n_chirp_t < 1 || !p->freq || !p->chirp_f ||
             !p->swipe_s || !p->chirp_t)
             return fail("CHIRP needs freq[0], chirp_f[0], swipe_s[0] and chirp_t[0]");
+        // several chirps: everything that can be refused is, before the device is touched
+        gsdr::MultiChirp mc{};
+        gsdr::MultiScale msc{};
+        if (chirps > 1) {
+            if (const char *bad = gsdr::multi_chirp_fault(p, chirps)) return fail(bad);
+            gsdr_chirp_param all[GSDR_MULTI_CHIRP_MAX];
+            for (int c = 0; c < chirps; ++c) {
+                gsdr_chirp_derive_tx(p->rate, p->freq[c], p->chirp_f[c], p->swipe_s[0], p->chirp_t[0], &all[c]);
+                msc.s[c] = c < n_ampl && ampl ? ampl[c] : 1.f;
+            }
+            if (const char *bad = gsdr::multi_chirp_shape(all, chirps, mc)) return fail(bad);
+        }
         if (p->device_index >= 0 && hipSetDevice(p->device_index) != hipSuccess)
             return fail("hipSetDevice failed (no such GPU?)");
         g = new gsdr_txgen();
+        g->n_chirps = chirps;
+        g->mc = mc;
+        g->msc = msc;
         g->device = p->device_index;
         g->rate = (unsigned)p->rate;
         // the TX side's own derivation: a step shorter than one sample also resets num_steps, and the slope

@@ -142,7 +142,7 @@ class RX_buffer_demodulator:
     """
 
     def __init__(self, init_parameters: param, init_diagnostic: bool = False,
-                 device_index: int = -1):
+                 device_index: int = -1, multi_chirp: bool = False):
         self.parameters = init_parameters
         self.diagnostic = bool(init_diagnostic)
         L = _lib.lib()
@@ -166,7 +166,12 @@ class RX_buffer_demodulator:
         pc.n_swipe_s = len(p.swipe_s)
         pc.device_index = int(device_index)
         self._L = L
-        self._h = L.gsdr_demod_create(C.byref(pc))
+        # multi_chirp: wave_type = CHIRP x C demodulates C chirps in one pass (GSDR_CREATE_MULTI_CHIRP), rows
+        # [point][chirp]; without it the request is refused as the reference refuses it
+        if multi_chirp:
+            self._h = L.gsdr_demod_create_ex(C.byref(pc), _lib.CREATE_MULTI_CHIRP)
+        else:
+            self._h = L.gsdr_demod_create(C.byref(pc))
         if not self._h:
             raise GsdrError(L.gsdr_last_error(None).decode())
         self.fcut = float(L.gsdr_demod_fcut(self._h))

@@ -56,7 +56,7 @@ class TX_buffer_generator:
     ``sc16_gain`` (32767 by default) is the factor of the narrowing, ``sc16_clipped()`` the number of components that
     did not fit since the generator was created (a diagnostic: it waits for the device)."""
 
-    def __init__(self, init_parameters: param, device_index: int = 0):
+    def __init__(self, init_parameters: param, device_index: int = 0, multi_chirp: bool = False):
         import ctypes as C
         from .demodulator import _carr
         p = self.parameters = init_parameters
@@ -81,7 +81,12 @@ class TX_buffer_generator:
         pc.n_swipe_s = len(p.swipe_s)
         pc.device_index = int(device_index)
         ampl = np.ascontiguousarray(list(p.ampl) if p.ampl else [], dtype=np.float32)
-        self._h = L.gsdr_txgen_create(C.byref(pc), ampl.ctypes.data_as(C.POINTER(C.c_float)), len(ampl))
+        # multi_chirp: wave_type = CHIRP x C adds C chirps (scaled by ampl[c]) into every buffer (GSDR_CREATE_MULTI_CHIRP)
+        ap = ampl.ctypes.data_as(C.POINTER(C.c_float))
+        if multi_chirp:
+            self._h = L.gsdr_txgen_create_ex(C.byref(pc), ap, len(ampl), _lib.CREATE_MULTI_CHIRP)
+        else:
+            self._h = L.gsdr_txgen_create(C.byref(pc), ap, len(ampl))
         if not self._h:
             raise GsdrError(L.gsdr_last_error(None).decode())
         self.mode = w_type(L.gsdr_txgen_mode(self._h))      # a NOISE request is TONES (the reference falls through)

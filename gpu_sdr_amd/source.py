@@ -82,3 +82,25 @@ def device_chirp(out_tensor, last_index: int, cp, scale: float = 1.0, stream=Non
                                  C.byref(cp), C.c_float(scale), C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise RuntimeError(L.gsdr_last_error(None).decode())
+
+
+def device_chirps(out, last_index: int, cps, scales, stream=None) -> None:
+    """Several TX chirps added into one buffer on the device (gsdr_source_multichirp): ``out[s]`` is the float32 sum, in
+    order, of the samples ``device_chirp`` writes for ``cps[c]`` with ``scales[c]``.  The chirps share num_steps and
+    length.  ``out``: a contiguous complex64 CUDA tensor."""
+    import torch
+    assert out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous()
+    if len(cps) != len(scales) or not cps:
+        raise ValueError("need one scale per chirp and at least one chirp")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    L = _lib.lib()
+    arr = (_lib.ChirpParamC * len(cps))()
+    for c, cp in enumerate(cps):
+        arr[c].num_steps, arr[c].length, arr[c].chirpness, arr[c].f0 = cp.num_steps, cp.length, cp.chirpness, cp.f0
+    sc = (C.c_float * len(cps))(*[float(v) for v in scales])
+    with torch.cuda.device(out.device):
+        rc = L.gsdr_source_multichirp(out.data_ptr(), out.numel(), C.c_ulonglong(last_index), arr, sc, len(cps),
+                                      C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(L.gsdr_last_error(None).decode())

@@ -26,7 +26,9 @@ class TX_buffer_generator {
     //! the parameters used to generate the signal (borrowed, like the reference)
     param* parameters;
 
-    TX_buffer_generator(param* init_parameters) : buffer_len((int)init_parameters->buffer_len), parameters(init_parameters), handle_(nullptr) {
+    //! gsdr_flags: GSDR_CREATE_* of gsdr_txgen_create_ex (an extension; GSDR_CREATE_MULTI_CHIRP: wave_type = CHIRP x C
+    //! adds C chirps, scaled by ampl[c], into every buffer).  0, the default, is the reference's behaviour.
+    TX_buffer_generator(param* init_parameters, unsigned gsdr_flags = 0) : buffer_len((int)init_parameters->buffer_len), parameters(init_parameters), handle_(nullptr) {
         std::vector<int> wt(parameters->wave_type.begin(), parameters->wave_type.end());
         gsdr_param_c pc;
         pc.rate = parameters->rate;
@@ -45,7 +47,7 @@ class TX_buffer_generator {
         pc.swipe_s = parameters->swipe_s.data();
         pc.n_swipe_s = (int)parameters->swipe_s.size();
         pc.device_index = RX_buffer_demodulator::device_index();
-        handle_ = gsdr_txgen_create(&pc, parameters->ampl.data(), (int)parameters->ampl.size());
+        handle_ = gsdr_txgen_create_ex(&pc, parameters->ampl.data(), (int)parameters->ampl.size(), gsdr_flags);
         if (!handle_) {
             std::fprintf(stderr, "ERROR: %s\n", gsdr_last_error(nullptr));
             std::exit(-1);

@@ -104,7 +104,10 @@ class RX_buffer_demodulator {
         return idx;
     }
 
-    RX_buffer_demodulator(param* init_parameters, bool init_diagnostic = false)
+    //! gsdr_flags: GSDR_CREATE_* of gsdr_demod_create_ex (an extension; GSDR_CREATE_MULTI_CHIRP: wave_type = CHIRP x C
+    //! is demodulated in one pass, rows [point][chirp]).  0, the default, is the reference's behaviour, its refusals
+    //! included.
+    RX_buffer_demodulator(param* init_parameters, bool init_diagnostic = false, unsigned gsdr_flags = 0)
         : parameters(init_parameters), fcut(0.f), handle_(nullptr), diagnostic_(init_diagnostic) {
         std::vector<int> wt(parameters->wave_type.begin(), parameters->wave_type.end());
         gsdr_param_c pc;
@@ -124,7 +127,7 @@ class RX_buffer_demodulator {
         pc.swipe_s = parameters->swipe_s.data();
         pc.n_swipe_s = (int)parameters->swipe_s.size();
         pc.device_index = device_index();
-        handle_ = gsdr_demod_create(&pc);
+        handle_ = gsdr_demod_create_ex(&pc, gsdr_flags);
         if (!handle_) {
             // the reference print_error()s and exit(-1)s on unsupported requests
             // (ref: cpp/USRP_demodulator.cpp:31-39,322-325)

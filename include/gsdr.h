@@ -69,6 +69,40 @@ typedef struct gsdr_demod gsdr_demod;
  * :31-34, unsupported type :322-325) this returns NULL with the same message. */
 gsdr_demod *gsdr_demod_create(const gsdr_param_c *p);
 
+/* ---- several chirps in one handle (an extension: the reference announces it and exits, ref:
+ * cpp/USRP_demodulator.cpp:31-34, cpp/USRP_buffer_generator.cpp:26-29) -------------------------------------------
+ * gsdr_demod_create_ex / gsdr_txgen_create_ex take creation flags.  flags == 0 is exactly gsdr_demod_create /
+ * gsdr_txgen_create, refusals included; a bit this header does not define is refused before anything else ("unknown
+ * creation flag").  GSDR_CREATE_MULTI_CHIRP lifts the "Multiple chirp ..." refusal: wave_type = CHIRP x C, 1 <= C <=
+ * GSDR_MULTI_CHIRP_MAX, demodulates (RX) or adds up (TX) C chirps in one pass over the buffer.  C == 1 is the
+ * single-chirp handle, launch for launch; mixed wave types stay refused as before.
+ *   - freq[c], chirp_f[c]: the span of chirp c; n_freq >= C and n_chirp_f >= C ("CHIRP needs freq[] and chirp_f[] for
+ *     every wave_type entry");
+ *   - swipe_s, chirp_t: shared, one entry each or C equal ones ("multi-chirp needs one swipe_s and one chirp_t for all
+ *     chirps"): num_steps, length, the samples per point, the period and the running index are common, f0 and the
+ *     chirpness per chirp (gsdr_chirp_derive for RX, gsdr_chirp_derive_tx for TX).
+ * All of this is refused before the device is touched.
+ * RX: gsdr_demod_channels() is C, rows are [point][chirp] ([sample][chirp] with decim == 0), a call returns valid * C
+ * (buffer_len * C), gsdr_demod_out_capacity() is (buffer_len / ppt + 1) * C (buffer_len * C).  Column c is what a
+ * single-CHIRP handle made from (rate, freq[c], chirp_f[c], swipe_s, chirp_t, decim, buffer_len) returns for the same
+ * stream of buffers -- same lengths, same carry, same index, call by call; the carry of raw samples and the window
+ * bookkeeping exist once per handle.  Every RX entry serves such a handle (process, process_device, submit,
+ * submit_device, wait, their sc16 forms, prepare -- the rehearsal twin is made with the same flags --, profile_*), under
+ * the extents contract below; gsdr_demod_set_frame_average stays TONES / NOISE only.  gsdr_demod_kernel_name reports
+ * chirp_multi_lockin_kernel / chirp_multi_demod_kernel when C > 1, gsdr_demod_describe adds "chirps": C.
+ * TX: x[s] = term_0[s] + term_1[s] + ... + term_(C-1)[s], term_c the sample gsdr_source_chirp writes for chirp c with
+ * scale ampl[c] (1 without ampl): (fl32(sin_c * scale_c), fl32(-cos_c * scale_c)).  The terms are added in chirp order
+ * starting FROM term_0, real and imaginary part apart, every addition one IEEE single-precision operation, nothing fused.
+ * The sc16 entries are that sum narrowed, bit for bit, clipped components counted on the sum.  get, get_device and their
+ * sc16 forms serve such a generator (the running index wraps at num_steps * length); gsdr_txgen_get_ptr* stays TONES only.
+ * gsdr_source_multichirp[_sc16] is the kernel on its own: n_chirps in [1, GSDR_MULTI_CHIRP_MAX], every cp[c] with the
+ * same num_steps and length (both >= 1), scale[c] per chirp (host arrays, read during the call), device out_dev as for
+ * gsdr_source_chirp[_sc16]; asynchronous on hip_stream; -1 with the reason in gsdr_last_error(NULL).  n == 0 touches
+ * nothing, not even the pointers. */
+#define GSDR_CREATE_MULTI_CHIRP 1u
+#define GSDR_MULTI_CHIRP_MAX 16
+gsdr_demod *gsdr_demod_create_ex(const gsdr_param_c *p, unsigned flags);
+
 /* ref: RX_buffer_demodulator::process, cpp/USRP_demodulator.cpp:330.
  * in_host : buffer_len complex64 (host, pinned or pageable), not modified.
  * out_host: room for gsdr_demod_out_capacity() complex64.
@@ -127,9 +161,11 @@ int gsdr_demod_submit_device(gsdr_demod *h, const gsdr_c64 *in_dev, gsdr_c64 *ou
  *    point anywhere into a larger allocation, and the output does not depend, bit for bit, on where they point or on
  *    what lies around the buffers.
  * (What tests/test_gpu_extents.py can and cannot see of this: DESIGN.md section 3.)
- * The writers further down (gsdr_txgen_get_device, gsdr_txgen_tones_fill, gsdr_source_tones, gsdr_source_chirp)
+ * The writers further down (gsdr_txgen_get_device, gsdr_txgen_tones_fill, gsdr_source_tones, gsdr_source_chirp,
+ * gsdr_source_multichirp)
  * write exactly the n (gsdr_txgen_get_device: buffer_len) samples they are asked for, to an 8-byte aligned out_dev.
- * Their sc16 forms (gsdr_txgen_get_device_sc16, gsdr_txgen_tones_fill_sc16, gsdr_source_chirp_sc16) and
+ * Their sc16 forms (gsdr_txgen_get_device_sc16, gsdr_txgen_tones_fill_sc16, gsdr_source_chirp_sc16,
+ * gsdr_source_multichirp_sc16) and
  * gsdr_narrow_sc16_device write exactly n (buffer_len) samples of gsdr_sc16 to an out_dev that needs 4-byte alignment
  * only and may point anywhere into a larger allocation: nothing in front of it or behind it is written, and the output
  * does not depend on where it points. */
@@ -286,8 +322,9 @@ void gsdr_demod_profile_enable(gsdr_demod *h, int enable);
  * their summed duration in milliseconds. */
 int gsdr_demod_profile_read(gsdr_demod *h, double *total_ms);
 /* Name of the kernel that carried the last call (as rocprofv3 reports it; the
- * CHIRP lock-in reports chirp_lockin_kernel for all its variants); before the
- * first call, the one a call of buffer_len samples runs. */
+ * CHIRP lock-in reports chirp_lockin_kernel for all its variants, a handle of
+ * several chirps chirp_multi_lockin_kernel or chirp_multi_demod_kernel); before
+ * the first call, the one a call of buffer_len samples runs. */
 const char *gsdr_demod_kernel_name(const gsdr_demod *h);
 
 /* ---- host-side pieces of the path (usable without a GPU) ---------------- */
@@ -481,6 +518,14 @@ long long gsdr_txgen_sc16_clipped(gsdr_txgen *g);
 int gsdr_source_chirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index,
                            const gsdr_chirp_param *cp, float scale, float gain,
                            unsigned long long *clipped_dev, void *hip_stream);
+
+/* ---- several chirps in one TX buffer ("several chirps in one handle" further up has the contract) ------------ */
+gsdr_txgen *gsdr_txgen_create_ex(const gsdr_param_c *p, const float *ampl, int n_ampl, unsigned flags);
+int gsdr_source_multichirp(gsdr_c64 *out_dev, long long n, unsigned long long last_index,
+                           const gsdr_chirp_param *cp, const float *scale, int n_chirps, void *hip_stream);
+int gsdr_source_multichirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long long last_index,
+                                const gsdr_chirp_param *cp, const float *scale, int n_chirps, float gain,
+                                unsigned long long *clipped_dev, void *hip_stream);
 
 #ifdef __cplusplus
 }
