@@ -162,10 +162,29 @@ SIGNATURES = [
     ("gsdr_source_multichirp", C.c_int, [_vp, C.c_longlong, C.c_ulonglong, C.POINTER(ChirpParamC), _fp, C.c_int, _vp]),
     ("gsdr_source_multichirp_sc16", C.c_int, [_vp, C.c_longlong, C.c_ulonglong, C.POINTER(ChirpParamC), _fp, C.c_int,
                                               C.c_float, _vp, _vp]),
+    ("gsdr_trigger_create", _vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    ("gsdr_trigger_set_levels", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_trigger_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    ("gsdr_trigger_feed", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _ip, _vp]),
+    ("gsdr_trigger_feed_host", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _ip]),
+    ("gsdr_trigger_reset", C.c_int, [_vp]),
+    ("gsdr_trigger_rows", C.c_longlong, [_vp]),
+    ("gsdr_trigger_close", None, [_vp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
 MULTI_CHIRP_MAX = 16        # GSDR_MULTI_CHIRP_MAX
+TRIGGER_HOST = -2           # GSDR_TRIGGER_HOST
+
+
+class TriggerLevelC(C.Structure):
+    """struct gsdr_trigger_level"""
+    _fields_ = [(n, C.c_float) for n in ("bx", "by", "dx", "dy", "lo", "hi")]
+
+
+class TriggerEventC(C.Structure):
+    """struct gsdr_trigger_event"""
+    _fields_ = [("row", C.c_longlong), ("channel", C.c_int), ("side", C.c_int), ("q", C.c_float), ("n_hit", C.c_int)]
 
 _lib = None
 

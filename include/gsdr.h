@@ -527,6 +527,74 @@ int gsdr_source_multichirp_sc16(gsdr_sc16 *out_dev, long long n, unsigned long l
                                 const gsdr_chirp_param *cp, const float *scale, int n_chirps, float gain,
                                 unsigned long long *clipped_dev, void *hip_stream);
 
+/* ---- trigger on the device: glitch events and snippets from demodulated rows (an extension: the reference's
+ * triggers run in its Python client, ref: pyUSRP/USRP_triggers.py, amplitude_trigger) -------------------------------
+ * A trigger object sees ONE stream of rows of n_ch complex64 each -- the [row][channel] layout every RX entry writes
+ * for DIRECT, TONES, averaged frames and multi-chirp handles.  Rows are numbered 0, 1, 2, ... from creation (or from
+ * gsdr_trigger_reset) and arrive in FEEDS of n_rows >= 0 rows.  Nothing below depends on where the stream is cut into
+ * feeds, with the two exceptions stated under "Capacity" and "Levels".
+ * Quantity.  Channel c has six floats {bx, by, dx, dy, lo, hi}.  For sample y of channel c:
+ *     t0 = y.x - bx;  t1 = y.y - by;  p0 = t0 * dx;  p1 = t1 * dy;  q = p0 + p1
+ *   every operation one IEEE single-precision operation rounded to nearest, nothing fused.  up = q > hi,
+ *   dn = !up && q < lo; the channel HITS in that row iff up || dn.  A NaN q never hits; lo = -Inf, hi = +Inf switches
+ *   a channel off.  No value of a level is refused.
+ * Row record.  A row hits iff any channel hits.  Its record: channel = the lowest-numbered hitting channel, side = +1
+ *   for up and -1 for dn, q = that channel's q, n_hit = the number of hitting channels.
+ * Trigger.  Row r is a trigger iff it hits and no row in [max(0, r - holdoff), r - 1] hits (hits closer than that are
+ *   the same glitch, chained hit to hit).  holdoff = 0 makes every hitting row a trigger.
+ * Emission.  A trigger at r owns the snippet rows [r - pre, r + post).  It is emitted by the feed that delivers row
+ *   r + post - 1: with that feed covering stream rows [R0, R1), iff R0 <= r + post - 1 < R1.  A trigger with r < pre is
+ *   never emitted (its hit still holds off later rows); one whose last row never arrives is never emitted.  Snippets of
+ *   different triggers may overlap; each is a full copy.
+ * Output of a feed, in ascending trigger row: events[e]; snippets[e][pre + post][n_ch], the input rows bit for bit (NaN
+ *   payloads and -0 included); the counts {n_events, n_dropped}.
+ * Capacity.  Of the triggers a feed would emit, the first max_events in row order are written and the rest are only
+ *   counted in n_dropped.  With n_dropped == 0 in every feed the concatenated output of a stream is the same for every
+ *   cutting.
+ * Levels.  gsdr_trigger_set_levels takes effect for the rows of later feeds.  A row's record is made with the levels in
+ *   force in the feed that delivered it and is never re-evaluated.
+ *
+ * gsdr_trigger_create: 1 <= n_ch <= 2^20, 1 <= max_rows <= 2^20, pre >= 0, post >= 1, pre + post <= 65536,
+ *   0 <= holdoff <= 2^30, 1 <= max_events <= 2^20, levels[n_ch] not NULL; anything else is refused before the device is
+ *   touched: NULL, and gsdr_last_error(NULL) starts with "gsdr_trigger_create: " and names the argument.  device_index
+ *   >= -1 as in gsdr_param_c; GSDR_TRIGGER_HOST makes a host-only object that touches no GPU: gsdr_trigger_feed_host,
+ *   _set_levels (the stream is ignored), _reset, _rows and _close are valid on it.  gsdr_trigger_feed_host is refused on
+ *   a device object and the device feeds on a host object (-1, gsdr_last_error(NULL)).  Everything the device feeds need
+ *   is allocated here, every byte count in 64 bits; gsdr_trigger_feed alone allocates its staging (max_events events
+ *   and snippets) the first time it is called.
+ * gsdr_trigger_feed_device: asynchronous on hip_stream (hipStream_t as void*), no synchronisation, no host read-back.
+ *   Reads exactly rows_dev[0, n_rows * n_ch); writes counts_dev[0..1] = {n_events, n_dropped} and at most max_events
+ *   events and snippets: nothing outside events_dev[0, max_events), snippets_dev[0, max_events * (pre + post) * n_ch)
+ *   and counts_dev[0, 2) is written, what lies behind n_events is unspecified.  The pointers need natural alignment
+ *   only (8 bytes for rows, events, snippets; 4 for counts) and may point anywhere into larger allocations.  n_rows >
+ *   max_rows or n_rows < 0: -1, state unchanged.  n_rows == 0 is a valid feed that emits nothing and touches no row
+ *   pointer.  Returns 0.
+ * gsdr_trigger_feed: the same launches, then waits for hip_stream and copies to the host only n_events events and
+ *   n_events snippets (events_host / snippets_host behind them stay untouched); returns n_events, *n_dropped when given.
+ * gsdr_trigger_feed_host: the same bits on the CPU.
+ * Stream order.  Like the handle's device entries, the feeds are ordered by the caller through hip_stream -- but a
+ *   trigger object does NOT remember streams or wait by itself: consecutive calls on one object (feeds, set_levels) must
+ *   be ordered by the caller, on the same stream or through the caller's own events, and rows_dev must stay unchanged
+ *   until the feed that reads it has finished.  gsdr_trigger_set_levels copies the levels before it returns.
+ * gsdr_trigger_reset: row numbering restarts at 0, carried rows and hit records are dropped (the levels stay).  The
+ *   caller must have ordered it behind the feeds in flight.  gsdr_trigger_rows: rows fed since creation / reset. */
+#define GSDR_TRIGGER_HOST (-2)
+typedef struct gsdr_trigger_level { float bx, by, dx, dy, lo, hi; } gsdr_trigger_level;
+typedef struct gsdr_trigger_event { long long row; int channel; int side; float q; int n_hit; } gsdr_trigger_event;
+typedef struct gsdr_trigger gsdr_trigger;
+gsdr_trigger *gsdr_trigger_create(int n_ch, int max_rows, int pre, int post, int holdoff, int max_events,
+                                  const gsdr_trigger_level *levels, int device_index);
+int gsdr_trigger_set_levels(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream);
+int gsdr_trigger_feed_device(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsdr_trigger_event *events_dev,
+                             gsdr_c64 *snippets_dev, int *counts_dev /* [2] */, void *hip_stream);
+int gsdr_trigger_feed(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsdr_trigger_event *events_host,
+                      gsdr_c64 *snippets_host, int *n_dropped, void *hip_stream);
+int gsdr_trigger_feed_host(gsdr_trigger *t, const gsdr_c64 *rows, int n_rows, gsdr_trigger_event *events,
+                           gsdr_c64 *snippets, int *n_dropped);
+int gsdr_trigger_reset(gsdr_trigger *t);
+long long gsdr_trigger_rows(const gsdr_trigger *t);
+void gsdr_trigger_close(gsdr_trigger *t);
+
 #ifdef __cplusplus
 }
 #endif
