@@ -170,11 +170,23 @@ SIGNATURES = [
     ("gsdr_trigger_reset", C.c_int, [_vp]),
     ("gsdr_trigger_rows", C.c_longlong, [_vp]),
     ("gsdr_trigger_close", None, [_vp]),
+    ("gsdr_welch_create", _vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    ("gsdr_welch_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_welch_read_device", C.c_int, [_vp, C.c_int, _vp, C.c_double, _vp, _vp]),
+    ("gsdr_welch_read", C.c_int, [_vp, C.c_int, _vp, C.c_double, _vp, _vp, _vp]),
+    ("gsdr_welch_mean_device", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_welch_feed_host", C.c_int, [_vp, _vp, C.c_int]),
+    ("gsdr_welch_read_host", C.c_int, [_vp, C.c_int, _vp, C.c_double, _vp, _vp]),
+    ("gsdr_welch_reset", C.c_int, [_vp]),
+    ("gsdr_welch_rows", C.c_longlong, [_vp]),
+    ("gsdr_welch_segments", C.c_longlong, [_vp]),
+    ("gsdr_welch_close", None, [_vp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
 MULTI_CHIRP_MAX = 16        # GSDR_MULTI_CHIRP_MAX
 TRIGGER_HOST = -2           # GSDR_TRIGGER_HOST
+WELCH_HOST = -2             # GSDR_WELCH_HOST
 
 
 class TriggerLevelC(C.Structure):

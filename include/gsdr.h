@@ -595,6 +595,84 @@ int gsdr_trigger_reset(gsdr_trigger *t);
 long long gsdr_trigger_rows(const gsdr_trigger *t);
 void gsdr_trigger_close(gsdr_trigger *t);
 
+/* ---- Welch spectra on the device: running noise spectra from demodulated rows (an extension: the reference's client
+ * does this on the host, ref: pyUSRP/USRP_noise.py:655-703, spec_from_samples, scipy.signal.welch per channel) ----------
+ * A welch object sees ONE stream of rows of n_ch complex64 each -- the [row][channel] layout every RX entry writes --
+ * numbered from 0 (since creation or gsdr_welch_reset), arriving in FEEDS of 0 <= n_rows <= max_rows rows.
+ * Segments.  Segment s is rows [s*step, s*step + nperseg); the feed that delivers its last row completes it.  After
+ *   `total` rows n_seg = total < nperseg ? 0 : (total - nperseg)/step + 1: the host knows it without a read-back.
+ * Per segment and channel, the real and imaginary part treated as the complex number they form, N = nperseg,
+ *   t_n = n - (N-1)/2:
+ *   1. detrend, in double: m = (1/N) sum x_n, b = sum x_n t_n / sum t_n^2, d_n = fl32(x_n - (m + b t_n)) -- the
+ *      subtraction in double, rounded once to float32.  GSDR_WELCH_DETREND_LINEAR as written, _CONSTANT: b = 0,
+ *      _NONE: d_n = x_n.  (A float32 subtraction loses 1e-4 .. 1e-2 of the density when the noise is 1e-3 .. 1e-5 of the
+ *      carrier: the double subtraction is part of the contract.)
+ *   2. window, in float32: e_n = d_n w_n; w is the caller's nperseg floats, or with window == NULL the periodic Hann
+ *      window 0.5 - 0.5 cos(2 pi n / N), evaluated in double and rounded to float (scipy's default).
+ *   3. transform: Z = FFT_N(e), forward, unnormalised, complex float32.
+ *   4. accumulate, for k = 0 .. N/2, Zm = conj Z[(N-k) mod N]: X = (Z[k] + Zm)/2 is the spectrum of the real part,
+ *      Y = (Z[k] - Zm)/(2i) that of the imaginary part; three DOUBLE accumulators per bin take A0 += |X|^2,
+ *      A1 += |Y|^2, A2 += Re(X conj Y), in segment order.
+ *   5. mean: a double S += the sum of the segment's first `step` rows, in a fixed order inside the segment and in
+ *      segment order across segments; S / (n_seg step) is the mean of rows [0, n_seg step).
+ * Reading.  psd[n_ch][2][N/2+1] floats: [c][0] is the one-sided density of the real part of g_c z, [c][1] of its
+ *   imaginary part.  With g = gr + i gi:  P_re = gr^2 A0 + gi^2 A1 - 2 gr gi A2,  P_im = gi^2 A0 + gr^2 A1 + 2 gr gi A2,
+ *   each times f_k / (fs sum w_n^2 n_seg), f_k = 2 for 0 < k < N/2 and 1 otherwise, sum w^2 in double from the float
+ *   values; all in double, rounded once to float.  mode chooses g: GSDR_WELCH_RAW g = 1; _ROTATE g = |m|/m with m the
+ *   object's own mean (the reference's rotate=True); _DBC g = 1/m (the reference's dbc; its later mean subtraction is
+ *   the detrend); _GAIN g = gain[c], n_ch complex64.  For ROTATE and DBC m == 0 or a non-finite m gives g = 1.  The
+ *   detrend is linear, so it commutes with g: the rotation is chosen when reading, from the mean of the whole run.
+ *   A read does not disturb the accumulation, returns n_seg (clamped to INT_MAX), and with n_seg == 0 writes nothing
+ *   and returns 0.
+ * Cutting.  The device output -- psd for every mode, and the mean -- does not depend, bit for bit, on where the stream
+ *   is cut into feeds.
+ * Poison.  An Inf or NaN reaches exactly the channel that holds it, from the segment that holds it onward; every other
+ *   channel keeps its bits.
+ * gsdr_welch_create: 1 <= n_ch <= 2^20, 1 <= max_rows <= 2^20, nperseg a power of two in [16, 8192] (the in-LDS plan
+ *   range), nperseg/8 <= step <= nperseg, detrend one of the three values, device_index >= -1 as in gsdr_param_c or
+ *   GSDR_WELCH_HOST for a host-only object that touches no GPU.  Anything else is refused before the device is
+ *   touched: NULL, and gsdr_last_error(NULL) starts with "gsdr_welch_create: " and names the argument.  Everything a
+ *   feed needs is allocated here, every byte count in 64 bits; a failed allocation is a refusal that states the MiB.
+ * gsdr_welch_feed_device: asynchronous on hip_stream (hipStream_t as void*), no synchronisation, no read-back; reads
+ *   exactly rows_dev[0, n_rows n_ch).  n_rows outside [0, max_rows]: -1, state unchanged.  n_rows == 0 is valid and
+ *   touches no pointer.  0, or -1 with gsdr_last_error(NULL).
+ * gsdr_welch_read_device: asynchronous; writes exactly psd_dev[0, n_ch 2 (N/2+1)); gain_dev is read for _GAIN only;
+ *   fs must be finite and > 0.  gsdr_welch_mean_device: mean_dev[0, n_ch) = S / (n_seg step) as complex64, returns
+ *   n_seg, nothing written with n_seg == 0.  gsdr_welch_read: read_device into the object's own buffer, waits for
+ *   hip_stream and copies psd (and the mean, if mean_host is given) to the host; gain_host is host memory.
+ *   Pointers need their natural alignment only (8 bytes complex, 4 float) and may point anywhere into larger allocations.
+ * gsdr_welch_feed_host / gsdr_welch_read_host: GSDR_WELCH_HOST objects only (and the device entries are refused on
+ *   them).  The host twin computes the same estimator in DOUBLE throughout (no rounding of d_n, a radix-2 double
+ *   transform) and returns doubles: psd[n_ch][2][N/2+1] and, if given, mean[n_ch][2].  It is the estimator's statement
+ *   in code, not a bit twin of the device.
+ * Stream order is the caller's, as for the trigger: the object remembers no stream and waits for none; rows_dev must
+ *   stay unchanged until the feed that reads it has finished.  gsdr_welch_reset: zeroes the accumulators and restarts
+ *   the row numbering; the caller must have ordered it behind the feeds in flight (on a device object it waits for the
+ *   device).  gsdr_welch_rows / _segments: rows fed and segments complete since creation / reset. */
+#define GSDR_WELCH_HOST (-2)
+#define GSDR_WELCH_DETREND_NONE 0
+#define GSDR_WELCH_DETREND_CONSTANT 1
+#define GSDR_WELCH_DETREND_LINEAR 2
+#define GSDR_WELCH_RAW 0
+#define GSDR_WELCH_ROTATE 1
+#define GSDR_WELCH_DBC 2
+#define GSDR_WELCH_GAIN 3
+typedef struct gsdr_welch gsdr_welch;
+gsdr_welch *gsdr_welch_create(int n_ch, int max_rows, int nperseg, int step, int detrend,
+                              const float *window /* nperseg, or NULL */, int device_index);
+int gsdr_welch_feed_device(gsdr_welch *w, const gsdr_c64 *rows_dev, int n_rows, void *hip_stream);
+int gsdr_welch_read_device(gsdr_welch *w, int mode, const gsdr_c64 *gain_dev, double fs, float *psd_dev, void *hip_stream);
+int gsdr_welch_read(gsdr_welch *w, int mode, const gsdr_c64 *gain_host, double fs, float *psd_host,
+                    gsdr_c64 *mean_host /* n_ch, may be NULL */, void *hip_stream);
+int gsdr_welch_mean_device(gsdr_welch *w, gsdr_c64 *mean_dev, void *hip_stream);
+int gsdr_welch_feed_host(gsdr_welch *w, const gsdr_c64 *rows, int n_rows);
+int gsdr_welch_read_host(gsdr_welch *w, int mode, const gsdr_c64 *gain, double fs, double *psd,
+                         double *mean /* n_ch x 2, may be NULL */);
+int gsdr_welch_reset(gsdr_welch *w);
+long long gsdr_welch_rows(const gsdr_welch *w);
+long long gsdr_welch_segments(const gsdr_welch *w);
+void gsdr_welch_close(gsdr_welch *w);
+
 #ifdef __cplusplus
 }
 #endif
