@@ -1,6 +1,7 @@
 """The Welch accumulator on the device (include/gsdr.h, "Welch spectra on the device"): parity
-with the float64 oracle of tests/_welch.py on the same float32 rows, bit-identical output whatever the cutting,
-extents, poison, real handles in front and the gsdr_welch_read entry.
+with the float64 oracle of tests/_welch.py on the same float32 rows -- a handful of shapes up to 1030 channels, and the
+grid of every segment kernel x every detrend x the default and a caller's window --, bit-identical output whatever the
+cutting, extents, poison, a mean of exactly zero, real handles in front and the gsdr_welch_read entry.
 
 Measured worst per-bin relative errors (bar 1e-5) are written to the file that GSDR_WELCH_MARGINS names, when it
 is set; the committed copy is profiles/welch_margins.json.  They also go into the suite's parity margins (_margins.py)."""
@@ -13,7 +14,8 @@ import pytest
 
 from _extents import OUT_SENTINEL_BITS, check_input_untouched, guarded_input
 from _margins import record_margin
-from _welch import MODES, PARITY_BAR, Oracle, cuttings, floor_ratio, n_segments, noise_rows, rel_err, some_gain
+from _welch import (GRID, GRID_SHAPES, MODES, PARITY_BAR, Oracle, cuttings, floor_ratio, grid_case, grid_precondition, grid_total,
+                    grid_window, n_segments, noise_rows, rel_err, some_gain)
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +70,18 @@ def stream_of(name):
     return _memo[name]
 
 
+def case_of(name):
+    """(n_ch, nperseg, step, rows, x, detrend, window) of a PARITY case (linear, the default window) or of the grid case
+    "grid<nperseg>" (linear, Hann) / "grid<nperseg>_<detrend>_<window>" of tests/_welch.py."""
+    if name in PARITY:
+        n_ch, nperseg, step, rows, _, _ = PARITY[name]
+        return n_ch, nperseg, step, rows, stream_of(name)[0], "linear", None
+    nperseg, detrend, window = (name[4:].split("_") + ["linear", "hann"])[:3]
+    nperseg = int(nperseg)
+    n_ch, step = GRID_SHAPES[nperseg]
+    return n_ch, nperseg, step, grid_total(nperseg), grid_case(nperseg, detrend, window)[0], detrend, grid_window(nperseg, window)
+
+
 def feed_all(w, x, cut, dev, stream=None):
     import torch
     at = 0
@@ -116,20 +130,66 @@ def test_parity_with_the_float64_oracle(spectrum, cuda_device, name):
     assert worst <= PARITY_BAR, worst
 
 
-@pytest.mark.parametrize("name", ["3x16_step16", "3x16_step2", "5x64", "65x256_step100", "1030x64", "2x8192"])
+@pytest.mark.parametrize("window", ["hann", "own"])
+@pytest.mark.parametrize("detrend", ["linear", "constant", "none"])
+@pytest.mark.parametrize("nperseg", list(GRID_SHAPES))
+def test_parity_over_the_grid(spectrum, cuda_device, nperseg, detrend, window):
+    """Every instantiation of welch_segment_kernel (16 .. 8192 points: every radix plan, either result buffer, one- and
+    two-level detrend sums, 1 .. 64 segments per workgroup, the LDS request above 64 KiB) x every detrend x the default
+    and a caller's window (asymmetric, signed, one zero tap), against the float64 oracle at the project's bar.  What the
+    case must fulfil itself -- noise in every bin, the float32 model of the contract within a third of the bar, spectra
+    that differ between the variants -- is asserted without a GPU in tests/test_welch_host.py::test_grid_preconditions."""
+    assert (nperseg, detrend, window) in GRID
+    n_ch, step = GRID_SHAPES[nperseg]
+    rows = grid_total(nperseg)
+    fs = 2.0e5
+    pre = grid_precondition(nperseg, detrend, window, fs=fs)
+    if not pre["ok"]:
+        pytest.skip(f"not a fair case (tests/test_welch_host.py::test_grid_preconditions fails on it): {pre}")
+    x, o = grid_case(nperseg, detrend, window)
+    assert o.n_seg == n_segments(rows, nperseg, step) >= 9
+    gain = some_gain(n_ch)
+    cut = cuttings(rows, nperseg, step)["sevens" if nperseg <= 1024 else "several"]
+    w = spectrum.device_welch(n_ch, max(cut), nperseg, step, detrend=detrend, window=grid_window(nperseg, window), device_index=0)
+    feed_all(w, x, cut, cuda_device)
+    worst = 0.0
+    for m in MODES:
+        want = o.psd(m, fs=fs, gain=gain)
+        f, got, n = w.read(m, fs=fs, gain=gain if m == "gain" else None)
+        assert n == o.n_seg == w.segments and w.rows_seen == rows and got.dtype == np.float32
+        err = rel_err(got, want)
+        print(f"welch grid {nperseg} {detrend} {window} {m}: {err:.3e} (model {pre['model']:.3e}, floor ratio {pre['floor']:.3f})")
+        margin(f"grid {nperseg} {detrend} {window} {m}", err)
+        worst = max(worst, err)
+    mean = w.mean()
+    w.close()
+    assert np.allclose(f, np.fft.rfftfreq(nperseg, 1 / fs))
+    there = o.mean != 0
+    assert there.all() or detrend == "none"
+    assert np.max(np.abs(mean - o.mean)[there] / np.abs(o.mean)[there], initial=0.0) <= 2.0 ** -23
+    assert worst <= PARITY_BAR, worst
+
+
+CUTTING = ["3x16_step16", "3x16_step2", "5x64", "65x256_step100", "1030x64", "2x8192"]
+# the other six kernels at the grid's channel counts and steps (linear, Hann), and 512 points -- the one size where a
+# segment's slot in its workgroup changes with the cutting AND the detrend sums go through the LDS -- once more with the
+# constant detrend and a caller's window
+CUTTING += ["grid32", "grid128", "grid512", "grid1024", "grid2048", "grid4096", "grid512_constant_own"]
+
+
+@pytest.mark.parametrize("name", CUTTING)
 def test_output_does_not_depend_on_the_cutting(spectrum, cuda_device, name):
     """Device against device, bit for bit: psd of every mode and the mean."""
     import torch
-    n_ch, nperseg, step, rows, _, _ = PARITY[name]
-    x, _ = stream_of(name)
+    n_ch, nperseg, step, rows, x, detrend, window = case_of(name)
     gain = some_gain(n_ch)
     cuts = cuttings(rows, nperseg, step)
-    if rows > 5000:
+    if rows > 5000 if name in PARITY else nperseg >= 2048:
         cuts.pop("short"), cuts.pop("sevens")            # thousands of feeds: the other cuttings cover the long segments
         cuts["thirds"] = [rows // 3, rows // 3 + 1, rows - 2 * (rows // 3) - 1]
     ref = None
     for cname, cut in cuts.items():
-        w = spectrum.device_welch(n_ch, max(max(cut), 1), nperseg, step, device_index=0)
+        w = spectrum.device_welch(n_ch, max(max(cut), 1), nperseg, step, detrend=detrend, window=window, device_index=0)
         stream = torch.cuda.Stream() if cname in ("empties", "several") else None
         torch.cuda.synchronize()
         feed_all(w, x, cut, cuda_device, stream=stream)
@@ -184,21 +244,21 @@ def _guards_intact(whole, view, n):
 
 
 @pytest.mark.parametrize("pattern,off", [("nan", 1), ("huge", 0), ("huge", 1)])
-@pytest.mark.parametrize("name", ["3x16_step2", "65x256_step100"])
+@pytest.mark.parametrize("name", ["3x16_step2", "65x256_step100", "grid512_none_own"])
 def test_extents_and_alignment(spectrum, gsdr_lib, cuda_device, name, pattern, off):
     """Rows, psd, mean and gain as views into larger allocations between guard zones, natural alignment only: the rows
-    are read and not written, the zones around every output stay intact, the output is that of plain tensors."""
+    are read and not written, the zones around every output stay intact, the output is that of plain tensors.  (The
+    third case: a caller's window, no detrend, the 512-point kernel.)"""
     import torch
-    n_ch, nperseg, step, rows, _, _ = PARITY[name]
-    x, _ = stream_of(name)
+    n_ch, nperseg, step, rows, x, detrend, window = case_of(name)
     K1 = nperseg // 2 + 1
     gain = some_gain(n_ch)
     cut = cuttings(rows, nperseg, step)["empties"]
-    plain = spectrum.device_welch(n_ch, max(cut), nperseg, step, device_index=0)
+    plain = spectrum.device_welch(n_ch, max(cut), nperseg, step, detrend=detrend, window=window, device_index=0)
     feed_all(plain, x, cut, cuda_device)
     want = read_all(plain, gain)
     plain.close()
-    w = spectrum.device_welch(n_ch, max(cut), nperseg, step, device_index=0)
+    w = spectrum.device_welch(n_ch, max(cut), nperseg, step, detrend=detrend, window=window, device_index=0)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     at = 0
     for n in cut:
@@ -258,6 +318,71 @@ def test_poison_stays_in_its_channel(spectrum, cuda_device):
         assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32)), k
         assert not np.isfinite(got[k][2]).any(), k
         assert np.isfinite(early[k]).all(), k
+
+
+@pytest.mark.parametrize("nperseg", [512, 2048])
+def test_poison_stays_in_its_channel_through_the_lds_sums(spectrum, cuda_device, nperseg):
+    """The scheme of test_poison_stays_in_its_channel where the detrend sums of a segment go through the LDS (more than
+    one wave per segment).  512 points, three channels: two segments share a workgroup, and a feed that completes an odd
+    number of segments puts the last segment of one channel beside the first of the next -- the poisoned channel 1 sits
+    beside channel 0 and beside channel 2.  2048 points, two channels: sixteen waves, two samples per thread."""
+    import torch
+    n_ch, step = GRID_SHAPES[nperseg]
+    rows = grid_total(nperseg)
+    x, _ = grid_case(nperseg, "linear", "hann")
+    bad = x.copy()
+    at = nperseg + 5                                      # not in segment 0, in every later segment that reaches it
+    bad[at, 1] = np.inf
+    bad[nperseg + 5 * step + 1, 1] = np.nan
+    early_rows = at + 1                                   # the poisoned row is in, segment 1 is not complete
+    assert n_segments(early_rows, nperseg, step) == 1 and n_segments(early_rows + 27, nperseg, step) == 1
+    assert (n_segments(rows, nperseg, step) - 1) % 2 == 1 and at // step < n_segments(rows, nperseg, step)      # 9 segments in the last feed; the mean reaches the row
+    gain = some_gain(n_ch)
+    runs = []
+    for data, cut in ((x, [rows]), (bad, [early_rows, 27, rows - early_rows - 27])):
+        w = spectrum.device_welch(n_ch, rows, nperseg, step, device_index=0)
+        t = torch.from_numpy(data).to(cuda_device)
+        early, fed = None, 0
+        for n in cut:
+            w.feed(t[fed:fed + n])
+            fed += n
+            if fed == early_rows and len(cut) > 1:
+                early = read_all(w, gain)
+        runs.append((read_all(w, gain), early))
+        w.close()
+    (clean, _), (got, early) = runs
+    others = [c for c in range(n_ch) if c != 1]
+    for k in list(MODES) + ["mean"]:
+        assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32)), k
+        assert not np.isfinite(got[k][1]).any(), k
+        assert np.isfinite(early[k]).all(), k
+
+
+def test_a_mean_of_exactly_zero_reads_with_unit_gain(spectrum, cuda_device):
+    """The contract: for ROTATE and DBC a mean of exactly 0 gives g = 1.  Channel 0 of three holds multiples of 1/1024
+    with rows 2i and 2i + 1 the negatives of each other, so the first `step` (even) rows of every segment sum to zero
+    exactly, in double, in any order; channels 1 and 2 are noise on a carrier.  Channel 0 then reads the bits of RAW in
+    both modes, and channels 1 and 2 do not: the fallback is per channel."""
+    n_ch, nperseg, step = 3, 64, 32
+    rows = nperseg + 9 * step + 3
+    x = noise_rows(rows, n_ch, seed=4)
+    rng = np.random.default_rng(8)
+    k = rng.integers(-512, 513, size=(rows // 2 + 1, 2))
+    pairs = (k[:, 0] + 1j * k[:, 1]) / 1024.0
+    x[:, 0] = np.stack([pairs, -pairs], axis=1).reshape(-1)[:rows].astype(np.complex64)
+    assert (x[0:2 * (rows // 2):2, 0] == -x[1:rows:2, 0]).all() and np.abs(x[:, 0]).max() > 0.25 and step % 2 == 0
+    w = spectrum.device_welch(n_ch, rows, nperseg, step, detrend="constant", device_index=0)
+    feed_all(w, x, [100, rows - 100], cuda_device)
+    got = read_all(w, some_gain(n_ch))
+    assert w.segments == n_segments(rows, nperseg, step) == 10
+    w.close()
+    assert got["mean"][0].real == 0 and got["mean"][0].imag == 0
+    assert (got["mean"][1:] != 0).all()
+    assert np.isfinite(got["raw"]).all() and (got["raw"] > 0).all()
+    for m in ("rotate", "dbc"):
+        assert np.array_equal(got[m][0].view(np.uint32), got["raw"][0].view(np.uint32)), m
+    for c in (1, 2):
+        assert not np.array_equal(got["rotate"][c].view(np.uint32), got["raw"][c].view(np.uint32)), c
 
 
 def _behind_a_handle(spectrum, dev, dem, rate, freq, n_buffers, nperseg):

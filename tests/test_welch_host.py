@@ -1,12 +1,14 @@
 """The Welch estimator on the host (include/gsdr.h, "Welch spectra on the device"): the numpy oracle of tests/_welch.py
 against scipy.signal.welch, the library's host twin (GSDR_WELCH_HOST) against the oracle, the refusals of every entry
-and the poison rule.  No GPU."""
+and the poison rule; and the preconditions of the grid of cases the GPU tests run (tests/_welch.py, GRID), which look at
+the oracle and at the float32 model only.  No GPU."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from _welch import HOST_BAR, MODES, Oracle, cuttings, hann32, n_segments, noise_rows, rel_err, some_gain
+from _welch import (DETRENDS, DISTINCT, GRID, GRID_SHAPES, HOST_BAR, MODEL_BAR, MODES, WINDOWS, Oracle, cuttings, grid_case,
+                    grid_precondition, grid_total, hann32, n_segments, noise_rows, own_window, rel_err, some_gain)
 
 SHAPES = [(16, 16), (16, 2), (64, 32), (256, 100), (256, 256), (1024, 512), (8192, 4096)]
 
@@ -241,3 +243,42 @@ def test_poison_stays_in_its_channel(spectrum, poison):
     # the poisoned row has been fed, but the first segment that holds it (rows 64 .. 127) is not complete yet
     early, _, segs, _, _ = run_host(spectrum, bad[:127], nperseg, step, [127])
     assert segs == 2 and np.isfinite(early["raw"]).all()
+
+
+def test_the_grid_covers_every_kernel_detrend_and_window():
+    assert sorted(GRID_SHAPES) == [16 << k for k in range(10)] and len(GRID) == len(set(GRID)) == 60
+    assert {d for _, d, _ in GRID} == {"linear", "constant", "none"} and {w for _, _, w in GRID} == {"hann", "own"}
+    steps = {N: GRID_SHAPES[N][1] for N in GRID_SHAPES}
+    assert any(s == N for N, s in steps.items()) and any(8 * s == N for N, s in steps.items()) and any(s & (s - 1) for s in steps.values())
+    for N, (n_ch, step) in GRID_SHAPES.items():
+        assert n_segments(grid_total(N), N, step) >= 9 and 1 <= step <= N
+    assert sum(n_ch % 2 for n_ch, _ in GRID_SHAPES.values()) >= 6
+
+
+@pytest.mark.parametrize("nperseg", list(GRID_SHAPES))
+def test_own_window_is_asymmetric_signed_and_has_a_zero_tap(nperseg):
+    w = own_window(nperseg)
+    assert w.dtype == np.float32 and w.shape == (nperseg,)
+    assert w[3] == 0 and (w < 0).sum() >= nperseg // 5 - 1 and (w > 0).sum() > nperseg // 2
+    # neither reversed, nor mirrored about N/2 as the Hann window is, nor shifted by one tap, nor without its signs
+    for other in (w[::-1], np.roll(w[::-1], 1), np.roll(w, 1), np.roll(w, -1), np.abs(w)):
+        assert np.max(np.abs(other - w)) > 0.1
+
+
+@pytest.mark.parametrize("nperseg", list(GRID_SHAPES))
+def test_grid_preconditions(nperseg):
+    """For the six cases of one nperseg, at the fs the GPU test reads with: every bin carries noise in every mode; the
+    float32 model of the contract meets a third of the bar against the oracle (measured: 1.2e-7 .. 1.5e-6, the worst at
+    8192 points, constant, Hann) -- so the input is one a float32 pipeline can resolve, and the device has two thirds of
+    the bar for its own transform; and the case tells its variants apart (measured: the raw spectra of two detrends or
+    two windows on the same rows differ by 0.4 .. 270 of the smaller on some bin)."""
+    for detrend in DETRENDS:
+        for window in WINDOWS:
+            x, o = grid_case(nperseg, detrend, window)
+            assert x.shape == (grid_total(nperseg), GRID_SHAPES[nperseg][0]) and x.dtype == np.complex64 and o.n_seg >= 9
+            pre = grid_precondition(nperseg, detrend, window, fs=2.0e5)
+            print(f"welch grid {nperseg} {detrend} {window}: floor {pre['floor']:.3f} model {pre['model']:.3e} distinct {pre['distinct']:.3g}")
+            assert pre["floor"] > 0.01, (detrend, window, pre)
+            assert pre["model"] <= MODEL_BAR, (detrend, window, pre)
+            assert pre["distinct"] > DISTINCT, (detrend, window, pre)
+            assert pre["ok"]
