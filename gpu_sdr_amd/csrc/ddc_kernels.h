@@ -48,6 +48,9 @@ struct Switches {
                                 // (ddc_mfma_ring16p4f_kernel); 3: Gauss's three (ddc_mfma_ring16p3f_kernel); 4: the four
     int mfma_wave_tones = -1;   // GSDR_MFMA_WAVE_TONES, -1 unset: a handle that sums the plain four products takes the loop with wave tiles of
                                 // 16 rows x 64 tones (ddc_mfma_ring16p4fw_kernel) when that launches no more waves; 64: every such handle; 32: never
+    int mfma_span = -1;         // GSDR_MFMA_SPAN, -1 unset: a handle that took the wide tile by its own rule (GSDR_MFMA_WAVE_TONES unset) and has a
+                                // window of kSpan128MinBlocks blocks or more rotates once per 128 samples (ddc_mfma_ring16p4fw2_kernel); 128: every
+                                // handle on the wide tile; 64 (or anything else): never
     int mfma_timing = 0;        // GSDR_MFMA_TIMING, 0: timing-only modes 1 - 3 (builds with -DGSDR_TIMING_BUILD only)
     bool noise_fft = true;      // GSDR_NOISE_FFT, 1: NOISE through the polyphase filter + FFT; 0: every bin a DDC tone
     bool tones_fft = true;      // GSDR_TONES_FFT, 1: TONES through filter + FFT + bin selection; 0: every bin a DDC tone
@@ -169,7 +172,8 @@ struct MfmaLaunch {
     float2 *out;
     const uint4 *img;          // AsmRing16P: [ngt][nhi] pre-converted ring-slot images of 8 KiB (ddc_convert_kernel);
                                // AsmRing16P3: of 12 KiB (ddc_convert3_kernel); AsmRing16P3F: [ngt][ceil(nhi/2)] of 16 KiB
-                               // (ddc_convert3f_kernel); AsmRing16P4F: the same of ddc_convert4f_kernel
+                               // (ddc_convert3f_kernel); AsmRing16P4F: the same of ddc_convert4f_kernel; AsmRing16P4FW2:
+                               // [ngt][ceil(nhi/4)] of 32 KiB (ddc_convert4f2_kernel)
     const uint4 *bfrag3;       // AsmRing16P3 / AsmRing16P3R2: phasor images c, d-c, c+d of mfma_build_tables3, span 1 / 2
                                // AsmRing16P3F: c, d, c+d, c-d of mfma_build_tables3f; AsmRing16P4F: c, d of mfma_build_tables4f
     const float4 *ptab3;       // AsmRing16P3: [ceil(nk8/4) + 1][NT32*32]  (Pr, Pi, Pr-Pi, Pr+Pi) of w_n^(hi*32);
@@ -197,6 +201,10 @@ void mfma_build_tables3f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, 
 // the direct folded loop (AsmRing16P4F): images c, d of w^(j - 31.5), j < 32, and the span phasors of mfma_build_tables3f
 void mfma_build_tables4f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
                          std::vector<float4> &ptab3);
+// the direct folded loop over 128-sample spans (AsmRing16P4FW2): images c, d of w^(j - 63.5), j < 64 (K-half 0: j < 32, then K-half 1),
+// and (Pr, Pi, Pi-Pr, Pr+Pi) of w_n^(128*span + 63.5)
+void mfma_build_tables4f2(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                          std::vector<float4> &ptab3);
 // The staging pass in front of the matrix-core kernels.  The logical stream of a call is T = [B | A]: A the new
 // buffer x[0 .. n), B what the previous call left in front of it (DIRECT: the raw-sample carry, read from the head
 // copy the previous pass wrote; TONES: the unconsumed end of the previous raw window, copied to b_dst).  One pass
@@ -227,10 +235,11 @@ hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
 // multiply (chosen per handle, demod.cpp), AsmRing16P3R2: that loop rotating its partial sums once per pair of
 // blocks (tables of mfma_build_tables3 with span 2 in bfrag3 / ptab3), AsmRing16P3F: three products over 64-sample spans
 // folded about their centre (images of ddc_convert3f_kernel, tables of mfma_build_tables3f in bfrag3 / ptab3), AsmRing16P4F: that fold with the plain four products (images of
-// ddc_convert4f_kernel, tables of mfma_build_tables4f), AsmRing16P4FW: that loop, images and tables on wave tiles of 16 rows x 64 tones; AsmRing:
+// ddc_convert4f_kernel, tables of mfma_build_tables4f), AsmRing16P4FW: that loop, images and tables on wave tiles of 16 rows x 64 tones; AsmRing16P4FW2: the wide-tile loop
+// over spans of 128 samples folded about their centre (images of ddc_convert4f2_kernel, tables of mfma_build_tables4f2); AsmRing:
 // round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled (TT, PK, W apply to it only; the assembly kernels are
 // TT = 1, PK = 32, W = 4).
-enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F, AsmRing16P4FW };
+enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F, AsmRing16P4FW, AsmRing16P4FW2 };
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);
 const char *ddc_mfma_kernel_name(MfmaKernel kind);
 // What the host knows of one loop of the pre-converted family (AsmRing16P ... AsmRing16P4FW, all named
@@ -240,8 +249,8 @@ const char *ddc_mfma_kernel_name(MfmaKernel kind);
 struct ProductLoop {
     MfmaKernel kind;
     int complex_mac, rotation_blocks, fold, fold_products, wave_tones;      // the handle's describe() values
-    int image_blocks;          // 32-sample blocks an image of MfmaLaunch::img holds: 1, or 2 (a folded span)
-    int image_uint4;           // uint4 per image: 512 (8 KiB), 768 (12 KiB) or 1024 (16 KiB)
+    int image_blocks;          // 32-sample blocks an image of MfmaLaunch::img holds: 1, 2 (a folded span) or 4 (a folded span of 128 samples)
+    int image_uint4;           // uint4 per image: 512 (8 KiB), 768 (12 KiB), 1024 (16 KiB) or 2048 (32 KiB)
     // bfrag3 / ptab3 of the loop; null: AsmRing16P reads the tables of mfma_build_tables only
     void (*build_tables)(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3, std::vector<float4> &ptab3);
 };

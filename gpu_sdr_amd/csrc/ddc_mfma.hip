@@ -65,6 +65,7 @@
 #include "ddc_mfma_ring16p3f_gen.h"
 #include "ddc_mfma_ring16p4f_gen.h"
 #include "ddc_mfma_ring16p4fw_gen.h"
+#include "ddc_mfma_ring16p4fw2_gen.h"
 
 namespace gsdr {
 
@@ -1057,9 +1058,16 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
 //     Re = sum a*c - sum b*d = sum_{j<32} (a_j + a_j')*c_j + (b_j' - b_j)*d_j
 //     Im = sum a*d + sum b*c = sum_{j<32} (a_j - a_j')*d_j + (b_j + b_j')*c_j
 // Same a, b, a', b', same piece layout; units V1 = a_j + a_j', V2 = b_j' - b_j, V3 = a_j - a_j', V4 = b_j + b_j'.
+//
+// Spans of 128 samples (kHalves = 2, ddc_convert4f2_kernel; tools/gen_ddc_mfma_ring16p4fw2.py):
+// the direct fold about the centre of four blocks, t = j - 63.5, partner 127 - j, 64 partner pairs per V.  The 32-KiB slot
+// image holds piece 4*u + 2*sp + rh, u = 2*V + K-half, K-half 0: j = 0..31, 1: j = 32..63 -- a thread converts its eight
+// j of either.  The last span of a window of nhi blocks holds nhi mod 4 of them (0: four): a sample or a partner in a
+// block past the window is an exact zero and nothing of that block is loaded.
 // ---------------------------------------------------------------------------------------------
-template <bool kDirect>
+template <bool kDirect, int kHalves = 1>
 __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void convert_fold(const MfmaLaunch &a, uint4 *__restrict__ img, int nhi, int nspan) {
+    static_assert(kHalves == 1 || (kHalves == 2 && kDirect), "128-sample spans: the direct fold only");
     const MfmaShape &sh = a.sh;
     const int l = threadIdx.x & 63, rh = threadIdx.x >> 6;
     const int r = 16 * rh + (l & 15), g = l >> 4;
@@ -1069,48 +1077,56 @@ __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops"))) void co
     const int oc = o < sh.nout ? o : sh.nout - 1;
     const float2 *xbase = gt == 0 ? a.head + sh.carry_len : (gt == sh.ngt - 1 ? a.tail - sh.tail0 : a.x);
     const float2 *xrow = xbase + (long long)(oc + sh.woff) * sh.M;
-    const int k0 = sp * 64 + 8 * g;          // sample of j = 8*g; j + jj at k0 + jj
-    const int k1 = sp * 64 + 56 - 8 * g;     // the partner of j + jj at k1 + 7 - jj
-    const bool whole = 2 * sp + 1 < nhi;     // the span's second block lies inside the window's extent
-    const float4u *px = reinterpret_cast<const float4u *>(xrow + k0);
-    const float4v x0 = px[0], x1 = px[1], x2 = px[2], x3 = px[3];
-    const float4v h0 = *reinterpret_cast<const float4v *>(a.taps + k0) * S;
-    const float4v h1 = *reinterpret_cast<const float4v *>(a.taps + k0 + 4) * S;
-    const float4v zero = {0.f, 0.f, 0.f, 0.f};
-    float4v y0 = zero, y1 = zero, y2 = zero, y3 = zero, g0 = zero, g1 = zero;
-    if (whole) {
-        const float4u *py = reinterpret_cast<const float4u *>(xrow + k1);
-        y0 = py[0], y1 = py[1], y2 = py[2], y3 = py[3];
-        g0 = *reinterpret_cast<const float4v *>(a.taps + k1) * S;
-        g1 = *reinterpret_cast<const float4v *>(a.taps + k1 + 4) * S;
-    }
-    const float xr[8] = {x0.x, x0.z, x1.x, x1.z, x2.x, x2.z, x3.x, x3.z};
-    const float xi[8] = {x0.y, x0.w, x1.y, x1.w, x2.y, x2.w, x3.y, x3.w};
-    const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-    const float yr[8] = {y0.x, y0.z, y1.x, y1.z, y2.x, y2.z, y3.x, y3.z};
-    const float yi[8] = {y0.y, y0.w, y1.y, y1.w, y2.y, y2.w, y3.y, y3.w};
-    const float gs[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-    half8 hi[4], lo[4];
+    uint4 *dst = img + (size_t)blockIdx.x * (kHalves * GSDR_MFMA_RING16P3F_SLOT / 16) + rh * 64 + l;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int kh = 0; kh < kHalves; ++kh) {
+        const int k0 = sp * (64 * kHalves) + 32 * kh + 8 * g;                        // sample of j = 32*kh + 8*g; j + jj at k0 + jj
+        const int k1 = sp * (64 * kHalves) + 64 * kHalves - 8 - 32 * kh - 8 * g;     // the partner of j + jj at k1 + 7 - jj
+        const bool have = kHalves == 1 || 2 * kHalves * sp + kh < nhi;               // the block of j lies inside the window's extent
+        const bool whole = 2 * kHalves * sp + 2 * kHalves - 1 - kh < nhi;            // so does the block of the partners
+        const float4v zero = {0.f, 0.f, 0.f, 0.f};
+        float4v x0 = zero, x1 = zero, x2 = zero, x3 = zero, h0 = zero, h1 = zero;
+        if (have) {
+            const float4u *px = reinterpret_cast<const float4u *>(xrow + k0);
+            x0 = px[0], x1 = px[1], x2 = px[2], x3 = px[3];
+            h0 = *reinterpret_cast<const float4v *>(a.taps + k0) * S;
+            h1 = *reinterpret_cast<const float4v *>(a.taps + k0 + 4) * S;
+        }
+        float4v y0 = zero, y1 = zero, y2 = zero, y3 = zero, g0 = zero, g1 = zero;
+        if (whole) {
+            const float4u *py = reinterpret_cast<const float4u *>(xrow + k1);
+            y0 = py[0], y1 = py[1], y2 = py[2], y3 = py[3];
+            g0 = *reinterpret_cast<const float4v *>(a.taps + k1) * S;
+            g1 = *reinterpret_cast<const float4v *>(a.taps + k1 + 4) * S;
+        }
+        const float xr[8] = {x0.x, x0.z, x1.x, x1.z, x2.x, x2.z, x3.x, x3.z};
+        const float xi[8] = {x0.y, x0.w, x1.y, x1.w, x2.y, x2.w, x3.y, x3.w};
+        const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+        const float yr[8] = {y0.x, y0.z, y1.x, y1.z, y2.x, y2.z, y3.x, y3.z};
+        const float yi[8] = {y0.y, y0.w, y1.y, y1.w, y2.y, y2.w, y3.y, y3.w};
+        const float gs[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+        half8 hi[4], lo[4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
 #pragma clang fp contract(off)
-        const float pa = mul_legacy(xr[j], hs[j]), pb = mul_legacy(xi[j], hs[j]);
-        // a half span: exact zeros, whatever the registers would multiply to
-        const float qa = whole ? mul_legacy(yr[7 - j], gs[7 - j]) : 0.f, qb = whole ? mul_legacy(yi[7 - j], gs[7 - j]) : 0.f;
-        const float u[4] = {pa + qa, kDirect ? qb - pb : pb - qb, kDirect ? pa - qa : pa + pb, kDirect ? pb + qb : qa + qb};
+            // a missing block: exact zeros, whatever the registers would multiply to
+            const float pa = have ? mul_legacy(xr[j], hs[j]) : 0.f, pb = have ? mul_legacy(xi[j], hs[j]) : 0.f;
+            const float qa = whole ? mul_legacy(yr[7 - j], gs[7 - j]) : 0.f, qb = whole ? mul_legacy(yi[7 - j], gs[7 - j]) : 0.f;
+            const float u[4] = {pa + qa, kDirect ? qb - pb : pb - qb, kDirect ? pa - qa : pa + pb, kDirect ? pb + qb : qa + qb};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                _Float16 h, w;
+                split_one(u[c], h, w);
+                hi[c][j] = h;
+                lo[c][j] = w;
+            }
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            _Float16 h, w;
-            split_one(u[c], h, w);
-            hi[c][j] = h;
-            lo[c][j] = w;
+            const int u = kHalves * c + kh;
+            dst[(4 * u) * 64] = __builtin_bit_cast(uint4, hi[c]);
+            dst[(4 * u + 2) * 64] = __builtin_bit_cast(uint4, lo[c]);
         }
-    }
-    uint4 *dst = img + (size_t)blockIdx.x * (GSDR_MFMA_RING16P3F_SLOT / 16) + rh * 64 + l;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        dst[(4 * c) * 64] = __builtin_bit_cast(uint4, hi[c]);
-        dst[(4 * c + 2) * 64] = __builtin_bit_cast(uint4, lo[c]);
     }
 }
 
@@ -1120,6 +1136,10 @@ __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) 
 
 __global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert4f_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
     convert_fold<true>(a, img, nhi, nspan);
+}
+
+__global__ __launch_bounds__(128) __attribute__((target("no-packed-fp32-ops"))) void ddc_convert4f2_kernel(const MfmaLaunch a, uint4 *__restrict__ img, int nhi, int nspan) {
+    convert_fold<true, 2>(a, img, nhi, nspan);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p3f_kernel(
@@ -1249,6 +1269,70 @@ __global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops")
                    GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),
                    [nhi] GSDR_SGPR(nhi)
                  : GSDR_MFMA_RING16P4FW_CLOBBERS);
+    if (!st0) return;
+    // the accumulators come back from this wave's 8 KiB: real parts of tone quarters 0..3, then the imaginary parts
+    const int lane2 = (int)(fresh_tid() & 63u);
+    float16v accr, acci;
+    const float4v *acc = reinterpret_cast<const float4v *>(lds) + wave * 512 + lane2;
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const float4v vr = acc[qd * 64], vi = acc[(qd + 4) * 64];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            accr[qd * 4 + j] = vr[j];
+            acci[qd * 4 + j] = vi[j];
+        }
+    }
+    store_tile16w(a, gt, rh, tg0, tg1, st0, st1, lane2, accr, acci);
+}
+
+// ---------------------------------------------------------------------------------------------
+// That loop over spans of 128 samples (tools/gen_ddc_mfma_ring16p4fw2.py): images of
+// ddc_convert4f2_kernel (32 KiB per span, of which the ring takes the sixteen pieces of row half rh), tables of
+// mfma_build_tables4f2 (sixteen phasor images per 32-tone tile, P per 128 samples).  Per sample the same MFMAs; the products
+// of 128 samples are rotated into the accumulators at once: half the rotation FMAs, P loads, barriers and ring rotations.
+// Grid, tile decode, idle waves and epilogue are those of ddc_mfma_ring16p4fw_kernel.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 2) __attribute__((target("no-packed-fp32-ops"))) void ddc_mfma_ring16p4fw2_kernel(
+    const MfmaLaunch a) {
+    // ring (4 slots of 16 KiB) while the loop runs, then the accumulators (4 waves x 8 KiB)
+    __shared__ uint4 lds[GSDR_MFMA_RING16P4FW2_BYTES / 16];
+    static_assert(GSDR_MFMA_RING16P4FW2_BYTES >= 4 * 8192, "the accumulators fit");
+    static_assert(2 * GSDR_MFMA_RING16P4FW2_BYTES <= 160 * 1024, "two workgroups per compute unit");
+    static_assert(GSDR_MFMA_RING16P4FW2_SLOT == GSDR_MFMA_RING16P4F_SLOT, "a ring slot is one row half of a 32-KiB slot image");
+    const MfmaShape &sh = a.sh;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int ntq = (sh.ntg + 7) >> 3;
+    const int g16 = (q / ntq) * 8 + xcd;
+    if (g16 * 16 >= sh.nout) return;          // no row in this tile
+    const int gt = g16 >> 1, rh = g16 & 1;
+    const int tg_raw = ((q % ntq) * 4 + wave) * 2;
+    const bool st0 = tg_raw < sh.ntg, st1 = tg_raw + 1 < sh.ntg;
+    const int tg0 = st0 ? tg_raw : sh.ntg - 1, tg1 = st1 ? tg_raw + 1 : sh.ntg - 1;
+
+    const int Np = sh.NT32 * 32;
+    const int nhi = ((sh.nk8 + 3) / 4 + 3) / 4;      // spans: slot images of a row tile
+    const int lane = (int)(fresh_tid() & 63u);
+    const unsigned po = (unsigned)(tg0 * 32 + (lane & 15)) * 16u, po1 = (unsigned)(tg1 * 32 + (lane & 15)) * 16u;
+    const unsigned bo = (unsigned)tg0 * 16384u + (unsigned)lane * 16u, bo1 = (unsigned)tg1 * 16384u + (unsigned)lane * 16u;
+    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)lds;
+    const unsigned rd16 = lds_base + (unsigned)lane * 16u;
+    // this wave copies units 2*wave and 2*wave + 1 of row half rh of every image: pieces 4*u + rh (hi) and 4*u + 2 + rh
+    // (lo) of the image become pieces 2*u and 2*u + 1 of the ring slot
+    const unsigned io0 = (unsigned)(8 * wave + rh) * 1024u + (unsigned)lane * 16u, io1 = io0 + 2048u, io2 = io0 + 4096u,
+                   io3 = io0 + 6144u;
+    const unsigned wrs = lds_base + (unsigned)wave * 4096u;
+    const unsigned accaddr = lds_base + (unsigned)wave * 8192u + (unsigned)lane * 16u;
+    const unsigned long long ibb = (unsigned long long)(a.img + (size_t)gt * nhi * (2 * GSDR_MFMA_RING16P4F_SLOT / 16)),
+                             ppb = (unsigned long long)a.ptab3, bfb = (unsigned long long)a.bfrag3;
+    asm volatile(GSDR_MFMA_RING16P4FW2_TEXT
+                 :
+                 : [io0] "v"(io0), [io1] "v"(io1), [io2] "v"(io2), [io3] "v"(io3), [po] "v"(po), [po1] "v"(po1), [bo] "v"(bo),
+                   [bo1] "v"(bo1), [lane16] "v"(rd16), [accaddr] "v"(accaddr), GSDR_SGPR_PAIR(ib, ibb), [wrs] GSDR_SGPR(wrs),
+                   GSDR_SGPR_PAIR(pp, ppb), GSDR_SGPR_PAIR(bf, bfb), [pstride] GSDR_SGPR((unsigned)Np * 16u),
+                   [nhi] GSDR_SGPR(nhi)
+                 : GSDR_MFMA_RING16P4FW2_CLOBBERS);
     if (!st0) return;
     // the accumulators come back from this wave's 8 KiB: real parts of tone quarters 0..3, then the imaginary parts
     const int lane2 = (int)(fresh_tid() & 63u);
@@ -1596,15 +1680,15 @@ void mfma_build_tables3(const MfmaPlan &pl, int span, const std::vector<unsigned
 }
 
 // Span phasors of the folded loops: per (span, tone) the phasor of the span's centre w_n^(64*span + 31.5) as
-// (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.
-static void fold_span_phasors(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<float4> &ptab3) {
+// (Pr, Pi, Pi-Pr, Pr+Pi), one row more than there are spans.  blocks = 4: spans of 128 samples, w_n^(128*span + 63.5).
+static void fold_span_phasors(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<float4> &ptab3, int blocks = 2) {
     const int Np = pl.ntg * pl.TT * 32;
     const unsigned long long rate2 = 2ULL * pl.rate;
-    const int nrow = ((pl.nk8 + 3) / 4 + 1) / 2;
+    const int nrow = ((pl.nk8 + 3) / 4 + blocks - 1) / blocks;
     ptab3.assign((size_t)(nrow + 1) * Np, make_float4(0.f, 0.f, 0.f, 0.f));
     for (int row = 0; row < nrow; ++row)
         for (int n = 0; n < Np; ++n) {
-            const unsigned long long t2 = (128ULL * (unsigned long long)row + 63ULL) % rate2;
+            const unsigned long long t2 = (64ULL * blocks * (unsigned long long)row + 32ULL * blocks - 1ULL) % rate2;
             double re, im;
             half_phasor(pl.rate, (unsigned long long)(((unsigned __int128)fmod[n] * t2) % rate2), re, im);
             ptab3[(size_t)row * Np + n] = make_float4((float)re, (float)im, (float)(im - re), (float)(re + im));
@@ -1612,10 +1696,10 @@ static void fold_span_phasors(const MfmaPlan &pl, const std::vector<unsigned> &f
 }
 
 // c_j + i*d_j = w^(j - 31.5), j < 32, of the folded loops: from the exact integer phase in half samples (mod 2*rate);
-// t = j - 31.5 < 0: the conjugate of w^(31.5 - j)
-static void fold_phasor(unsigned rate, unsigned long long fm, int j, double &c, double &d) {
+// t = j - 31.5 < 0: the conjugate of w^(31.5 - j).  pairs = 64: w^(j - 63.5), j < 64, of the 128-sample spans.
+static void fold_phasor(unsigned rate, unsigned long long fm, int j, double &c, double &d, int pairs = 32) {
     double wr, wi;
-    half_phasor(rate, (fm * (unsigned long long)(63 - 2 * j)) % (2ULL * rate), wr, wi);
+    half_phasor(rate, (fm * (unsigned long long)(2 * pairs - 1 - 2 * j)) % (2ULL * rate), wr, wi);
     c = wr, d = -wi;
 }
 
@@ -1644,6 +1728,21 @@ void mfma_build_tables4f(const MfmaPlan &pl, const std::vector<unsigned> &fmod, 
         v[0] = (float)c, v[1] = (float)d;
     });
     fold_span_phasors(pl, fmod, ptab3);
+}
+
+// Tables of the direct folded loop over 128-sample spans (ddc_mfma_ring16p4fw2_kernel).  Per
+// 32-tone tile 16 B images (16 KiB): c_j and d_j of w^(j - 63.5) for the 64 partner pairs, K-half 0 (j < 32) then K-half
+// 1, each formed in double from the exact half-sample phase, rounded once and split as in mfma_build_tables4f; P per
+// 128-sample span.
+void mfma_build_tables4f2(const MfmaPlan &pl, const std::vector<unsigned> &fmod, std::vector<uint4> &bfrag3,
+                          std::vector<float4> &ptab3) {
+    const unsigned rate = pl.rate;
+    build_images3<2>(pl, fmod, 2, bfrag3, [rate](unsigned long long fm, int j, float *v) {
+        double c, d;
+        fold_phasor(rate, fm, j, c, d, 64);
+        v[0] = (float)c, v[1] = (float)d;
+    });
+    fold_span_phasors(pl, fmod, ptab3, 4);
 }
 
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st) {
@@ -1692,6 +1791,7 @@ static const ProductLoopRow kProductLoops[] = {
     {{MfmaKernel::AsmRing16P3F, 3, 2, 1, 3, 32, 2, 1024, mfma_build_tables3f}, nullptr, ddc_convert3f_kernel, 128, ddc_mfma_ring16p3f_kernel, false},
     {{MfmaKernel::AsmRing16P4F, 3, 2, 1, 4, 32, 2, 1024, mfma_build_tables4f}, nullptr, ddc_convert4f_kernel, 128, ddc_mfma_ring16p4f_kernel, false},
     {{MfmaKernel::AsmRing16P4FW, 3, 2, 1, 4, 64, 2, 1024, mfma_build_tables4f}, nullptr, ddc_convert4f_kernel, 128, ddc_mfma_ring16p4fw_kernel, true},
+    {{MfmaKernel::AsmRing16P4FW2, 3, 2, 1, 4, 64, 4, 2048, mfma_build_tables4f2}, nullptr, ddc_convert4f2_kernel, 128, ddc_mfma_ring16p4fw2_kernel, true},
 };
 static const ProductLoopRow *product_loop_row(MfmaKernel kind) {
     for (const ProductLoopRow &r : kProductLoops)
@@ -1779,3 +1879,19 @@ const char *ddc_mfma_kernel_name(MfmaKernel kind) {
 }
 
 }  // namespace gsdr
+
+// For the host tests (no device): the tables of mfma_build_tables4f2 for n_tiles 32-tone tiles of frequency words fmod
+// (mod rate) and a window of nblk 32-sample blocks.  images: [n_tiles][16][64] uint4 (8 fp16 each), p: [spans + 1][32 *
+// n_tiles] float4.  Returns the number of span rows of p (spans + 1), or -1.
+extern "C" int gsdr_mfma_tables4f2_host_(unsigned rate, const unsigned *fmod, int n_tiles, int nblk, void *images, float *p) {
+    if (!rate || !fmod || n_tiles < 1 || nblk < 1 || !images || !p) return -1;
+    gsdr::MfmaPlan pl{};
+    pl.TT = 1, pl.PK = 32, pl.ntg = n_tiles, pl.nk8 = 4 * nblk, pl.MF = 32 * nblk, pl.M = 32 * nblk, pl.rate = rate;
+    const std::vector<unsigned> fm(fmod, fmod + (size_t)32 * n_tiles);
+    std::vector<uint4> b;
+    std::vector<float4> pt;
+    gsdr::mfma_build_tables4f2(pl, fm, b, pt);
+    __builtin_memcpy(images, b.data(), b.size() * sizeof(uint4));
+    __builtin_memcpy(p, pt.data(), pt.size() * sizeof(float4));
+    return (int)(pt.size() / ((size_t)32 * n_tiles));
+}

@@ -86,6 +86,7 @@ gsdr::Switches gsdr::read_switches() {
     s.mfma_fold = env("GSDR_MFMA_FOLD", -1);
     s.mfma_fold_products = env("GSDR_MFMA_FOLD_PRODUCTS", -1);
     s.mfma_wave_tones = env("GSDR_MFMA_WAVE_TONES", -1);
+    s.mfma_span = env("GSDR_MFMA_SPAN", -1);
     s.mfma_timing = env("GSDR_MFMA_TIMING", 0);
     s.noise_fft = env("GSDR_NOISE_FFT", 1) != 0;
     s.tones_fft = env("GSDR_TONES_FFT", 1) != 0;
@@ -511,7 +512,14 @@ constexpr int kFoldProductsDefault = 4;
 // fewer it would run twice the workgroups, half of their waves idle.  GSDR_MFMA_WAVE_TONES: 64 = every such handle,
 // 32 = never, unset = by that rule.
 //
-// The row of gsdr::product_loop for a handle by the five rules above, each asked only of a handle the one before it
+// The span of a handle on the wide tile: 128 samples folded about their centre
+// (ddc_convert4f2_kernel + ddc_mfma_ring16p4fw2_kernel) take the MFMAs of two 64-sample spans and one rotation, one P
+// load, one barrier and one ring rotation instead of two.  GSDR_MFMA_SPAN: 128 = every handle on the wide tile, 64 = never,
+// unset = a handle that took the wide tile by its own rule (GSDR_MFMA_WAVE_TONES unset: a forced wave tile keeps the
+// 64-sample spans and their bits) with a window of kSpan128MinBlocks blocks or more; 0: the unset rule never takes it.
+constexpr long long kSpan128MinBlocks = 125;
+
+// The row of gsdr::product_loop for a handle by the six rules above, each asked only of a handle the one before it
 // took; null without images.  nhi: the window in 32-sample blocks; max_rows, ntg: the handle's largest row count and
 // its tone groups.
 const gsdr::ProductLoop *product_loop_chosen(const gsdr_demod *h, bool images, long long nhi, long long max_rows, long long ntg) {
@@ -523,8 +531,9 @@ const gsdr::ProductLoop *product_loop_chosen(const gsdr_demod *h, bool images, l
     const int p = sw.mfma_fold_products, w = sw.mfma_wave_tones;
     const int products = p == 3 || p == 4 ? p : kFoldProductsDefault;
     const bool wide = w == 32 || w == 64 ? w == 64 : ((max_rows + 15) / 16) * ((ntg + 7) / 8) <= ((max_rows + 31) / 32) * ((ntg + 3) / 4);
+    const bool span128 = sw.mfma_span == 128 || (sw.mfma_span < 0 && w < 0 && kSpan128MinBlocks > 0 && nhi >= kSpan128MinBlocks);
     const K kind = !mac3 ? K::AsmRing16P : !rot2 ? K::AsmRing16P3 : !fold ? K::AsmRing16P3R2 : products != 4 ? K::AsmRing16P3F
-                   : wide ? K::AsmRing16P4FW : K::AsmRing16P4F;
+                   : !wide ? K::AsmRing16P4F : span128 ? K::AsmRing16P4FW2 : K::AsmRing16P4FW;
     return images ? gsdr::product_loop(kind) : nullptr;
 }
 
@@ -2080,6 +2089,8 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
     s += ", \"fold_min_blocks\": " + std::to_string(kFoldMinBlocks);
     s += ", \"fold_products\": " + std::to_string(pr.fold_products);
     s += ", \"wave_tones\": " + std::to_string(pr.wave_tones);
+    s += ", \"span_samples\": " + std::to_string(pr.image_blocks == 4 ? 128 : 64);
+    s += ", \"span128_min_blocks\": " + std::to_string(kSpan128MinBlocks);
     s += ", \"pipeline_streams\": " + std::to_string(h->sw.pipe_streams);
     s += ", \"frame_average\": " + std::to_string(h->avg_k);
     s += std::string(", \"frame_average_kind\": \"") + (h->avg_kind == GSDR_AVERAGE_POWER ? "power" : "complex") + "\"";

@@ -59,6 +59,8 @@ class Loop:
       g_pload         gap of the load of the next span's P
       rotation        (p_cur, p_prev) -> [(gap, "rot" | "rotp", v_fma_f32)]: rotp reads this span's P
       vb, acc, kb, f0, p, addr, v_last, nagpr, bf    the register map
+      frag_units      the units whose fragments have registers of their own (all of them unless stated): unit u takes
+                      those of unit u % frag_units, free 23 MFMAs after unit u - frag_units read them last
       rows, tq        the wave tile: row halves (of 16 rows) and tone quarters (of 16 tones) per wave, 2 x 2 unless
                       stated; 1 x 4 takes the pieces of one row half (chosen by the kernel through %[io..]) and the
                       phasor images and P of two 32-tone tiles (the second through %[bo1], %[po1])
@@ -68,8 +70,10 @@ class Loop:
     (ring16p3r2) overrides the methods of the last section instead."""
 
     def __init__(self, **desc):
-        self.rows, self.tq = 2, 2
+        self.rows, self.tq, self.frag_units = 2, 2, None
         self.__dict__.update(desc)
+        self.frag_units = self.frag_units or self.units
+        assert self.units % self.frag_units == 0
         assert (self.rows, self.tq) in ((2, 2), (1, 4))
         self.image_bytes = self.units * 4 * 1024           # a slot image in memory: both row halves
         self.slot = self.units * 2 * self.rows * 1024      # bytes of one ring slot
@@ -83,7 +87,7 @@ class Loop:
         return 1024 * ((2 * unit + sp) * self.rows + rh)
 
     def frag(self, unit, rh, sp):
-        return self.f0 + 4 * ((2 * unit + sp) * self.rows + rh)
+        return self.f0 + 4 * ((2 * (unit % self.frag_units) + sp) * self.rows + rh)
 
     # MFMA m of a unit: split m // 4, tile m % 4 = tq*rh + th
     def mfma_of(self, m):
@@ -187,11 +191,13 @@ def span(v, cnt, out, label):
     for unit in list(range(1, v.units)) + [0]:
         for (rh, sp), rel in v.read_at.items():
             g = (12 * unit if unit else NG) + rel
-            lu, fu = v.last_use(unit, rh, sp), v.first_use(unit, rh, sp)
+            # the registers were last read by unit - frag_units, of this span or of the one before
+            lu, fu = v.last_use((unit - v.frag_units) % v.units, rh, sp), v.first_use(unit, rh, sp)
+            lu -= NG if lu >= g else 0
             if unit == 0:
                 assert g - lu >= 23 and NG + fu - g >= 8, (unit, rh, sp)
             else:
-                assert NG + g - lu >= 23 and fu - g >= 8, (unit, rh, sp)
+                assert g - lu >= 23 and fu - g >= 8, (unit, rh, sp)
                 last_rd = f"f{unit}{rh}{sp}"
             gaps[g].append(("lds", f"ds_read_b128 {vr(v.frag(unit, rh, sp), 4)}, {vr(V_RD if unit else V_RDN)} "
                             f"offset:{v.piece(unit, rh, sp)}", f"f{unit}{rh}{sp}"))

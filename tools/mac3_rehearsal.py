@@ -22,12 +22,16 @@ comb at M 1000.
 Re = sum (a_j + a_j')*c_j + (b_j' - b_j)*d_j, Im = sum (a_j - a_j')*d_j + (b_j + b_j')*c_j over j < 32, two units summed
 into one fp32 result, acc += P*(Re + i*Im)), 60 dB comb at 250, 125, 94, 63 and 32 blocks and the 40 dB comb at M 1000.
 
+--fold4 --span 128: the direct fold over 64-sample spans beside the same fold over 128-sample spans (DESIGN.md section
+4.1i: t = j - 63.5, partner 127 - j, 64 partner pairs per unit, one rotation per 128 samples), same combs.
+
 Reads nothing but oracle/ and gpu_sdr_amd/source.py.
 
     python3 tools/mac3_rehearsal.py > profiles/mac3_rehearsal.log
     python3 tools/mac3_rehearsal.py --rot-span 64 > profiles/mac3r2_rehearsal.log
     python3 tools/mac3_rehearsal.py --fold > profiles/fold_rehearsal.log
     python3 tools/mac3_rehearsal.py --fold4 > profiles/fold4_rehearsal.log
+    python3 tools/mac3_rehearsal.py --fold4 --span 128 > profiles/span128_rehearsal.log
 """
 import os
 import sys
@@ -79,9 +83,10 @@ def phasor(ph, rate):
 def emulate(x, taps, freq, rate, M, F, products, span=32, fold=False):
     """rows F-1 .. nout-1 of the first buffer (windows that lie inside it); returns [rows][tones] complex128.
     span: samples per block sum and rotation (64: the pair rotation of section 4.1e, three products only);
-    fold: the 64-sample span folded about its centre (section 4.1f; products 4: the direct fold of section 4.1g)"""
+    fold: the 64-sample span folded about its centre (section 4.1f; products 4: the direct fold of section 4.1g,
+    which also folds a 128-sample span about its centre: 64 partner pairs, section 4.1i)"""
     assert span == 32 or products == 3 or fold
-    assert not fold or span == 64
+    assert not fold or span == 64 or (span == 128 and products == 4)
     N, MF = len(freq), M * F
     nout = len(x) // M
     rows = np.arange(F - 1, nout)
@@ -107,17 +112,18 @@ def emulate(x, taps, freq, rate, M, F, products, span=32, fold=False):
     wr, wi = phasor((fm[None, :] * lo[:, None]) % rate, rate)            # [span][N]
     c, d = wr.astype(f32), wi.astype(f32)
     if fold:
-        j = np.arange(32, dtype=np.int64)
-        ph2 = (fm[None, :] * (63 - 2 * j)[:, None]) % (2 * rate)          # w^(j - 31.5) = conj(w^(31.5 - j)), half samples
+        H = span // 2                                                     # partner pairs of a span
+        j = np.arange(H, dtype=np.int64)
+        ph2 = (fm[None, :] * (span - 1 - 2 * j)[:, None]) % (2 * rate)    # w^(j - (span-1)/2) = conj(w^((span-1)/2 - j)), half samples
         cc, dd = np.cos(np.pi * ph2 / rate), np.sin(np.pi * ph2 / rate)
     for blk in range(nhi):
         ab, bb = a[:, span * blk: span * blk + span], b[:, span * blk: span * blk + span]
         pr, pi = phasor((fm * ((blk * span) % rate)) % rate, rate)
         if fold and products == 4:
-            aj, bj, ap, bp = ab[:, :32], bb[:, :32], ab[:, :31:-1], bb[:, :31:-1]
+            aj, bj, ap, bp = ab[:, :H], bb[:, :H], ab[:, :H - 1:-1], bb[:, :H - 1:-1]
             re = (split_sum((aj + ap).astype(f32), cc.astype(f32)) + split_sum((bp - bj).astype(f32), dd.astype(f32))).astype(f32)
             im = (split_sum((aj - ap).astype(f32), dd.astype(f32)) + split_sum((bj + bp).astype(f32), cc.astype(f32))).astype(f32)
-            ps2 = (fm * ((128 * blk + 63) % (2 * rate))) % (2 * rate)
+            ps2 = (fm * ((2 * span * blk + span - 1) % (2 * rate))) % (2 * rate)
             pr, pi = np.cos(np.pi * ps2 / rate), -np.sin(np.pi * ps2 / rate)
             prf, pif = pr.astype(f32)[None, :], pi.astype(f32)[None, :]
             accr = fma(fma(accr, prf, re), -pif, im)
@@ -241,7 +247,34 @@ def main_fold4():
                   f"{errs[4].max():.3e} {(errs[4] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
 
 
+def main_span128():
+    N, rate, F = 64, 200_000_000, 4
+    print("span_dB  M  blocks | err32 (reference fp32 order) | direct fold, 64-sample spans: worst err, worst err/bound | "
+          "128-sample spans: worst err, worst err/bound | median, max per-tone ratio 128/64")
+    for span_db, decims in ((60, (2000, 1000, 750, 500, 375, 256)), (40, (1000,))):
+        for M in decims:
+            L = 200 * M
+            freq, x = comb(N, rate, L, span_db, np.random.default_rng(4242 + span_db))
+            ref = oracle.Direct(freq, rate, M, F, L)
+            taps = ref.taps()
+            yr = ref.process(x).astype(np.complex128)[F:]
+            y32 = recipe_b.Direct(freq, rate, M, F, L, acc=np.complex64).process(x).astype(np.complex128)[F:]
+            den = np.linalg.norm(yr, axis=0)
+            err32 = np.linalg.norm(y32 - yr, axis=0) / den
+            bound = np.maximum(1e-5, 3.0 * err32)
+            errs = {}
+            for sp in (64, 128):
+                y = emulate(x, taps, freq, rate, M, F, 4, span=sp, fold=True)[1:]
+                errs[sp] = np.linalg.norm(y - yr, axis=0) / den
+            ratio = errs[128] / errs[64]
+            print(f"{span_db:3d} {M:5d} {(M * F + 31) // 32:4d} | {err32.max():.3e} | {errs[64].max():.3e} {(errs[64] / bound).max():.3f} | "
+                  f"{errs[128].max():.3e} {(errs[128] / bound).max():.3f} | {np.median(ratio):.2f} {ratio.max():.2f}", flush=True)
+
+
 def main():
+    if "--fold4" in sys.argv and "--span" in sys.argv:
+        assert sys.argv[sys.argv.index("--span") + 1] == "128"
+        return main_span128()
     if "--fold4" in sys.argv:
         return main_fold4()
     if "--fold" in sys.argv:
