@@ -1,13 +1,15 @@
 """The trigger on the device (gsdr_trigger_feed_device / gsdr_trigger_feed; trigger_kernels.hip) against the library's
 host twin fed the same rows: events, snippets and counts bit for bit, on every case and cutting of tests/_trigger.py;
-extents, streams, set_levels / reset in stream order, and behind real DIRECT and TONES handles."""
+long feeds (several steps per selection chunk, capped grids) and stream rows beyond 2^31; extents, streams, set_levels /
+reset in stream order, and behind real DIRECT and TONES handles."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from _extents import OUT_SENTINEL_BITS, check_input_untouched, guarded_input, guarded_output
-from _trigger import CASE_IDS, CASES, EVENT_DTYPE, LEVEL_DTYPE, default_levels, same_bits
+from _trigger import (CASE_IDS, CASES, EVENT_DTYPE, LARGE_CASES, LARGE_IDS, LEVEL_DTYPE, PAST_FEEDS, PAST_N, PAST_PARAMS, PAST_TAIL,
+                      default_levels, past_2g_stream, same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +85,61 @@ def test_feed_device_equals_the_host_twin(trig, cuda_device, case):
         d.close()
         assert_feeds_equal(got, want, (case.name, cut))
         assert sum(len(e) for e, _, _ in want) > 0
+
+
+@pytest.mark.parametrize("large", LARGE_CASES, ids=LARGE_IDS)
+def test_long_feeds_equal_the_host_twin(trig, cuda_device, large):
+    """Chunks of several 64-byte steps in trigger_select_kernel (L = 128 ... 1088), its block scans with every slot in use,
+    and the row passes beyond their grid caps: what each case reaches is stated beside it in tests/_trigger.py."""
+    import torch
+    case = large.case()
+    whole = torch.from_numpy(case.rows).to(cuda_device)            # one upload; the feeds are views of it
+    for cut in case.cuts:
+        want = host_feeds(trig, params(case), case.levels, case.feeds(cut))
+        d = DeviceRun(trig, params(case), case.levels, cuda_device)
+        got, at = [], 0
+        for n in cut:
+            got.append(d.feed(whole[at:at + n]))
+            at += n
+        assert d.t.rows_seen == case.rows.shape[0]
+        d.close()
+        assert_feeds_equal(got, want, (case.name, cut))
+        assert sum(len(e) for e, _, _ in want) > 0
+
+
+def test_rows_past_2_to_the_31(trig, cuda_device):
+    """2 049 quiet feeds of 2^20 rows from one tensor, enqueued back to back with nothing read, then a tail with pulses: the
+    events are those of a host twin that saw ONE quiet feed, with 2048 * 2^20 added to the rows, and the same snippets.
+    (Nothing hits in the quiet rows, so only the row numbers and the carried rows depend on the prefix, and the carried
+    rows are the same quiet rows; tests/test_trigger_host.py checks that shift on the host twin over all 2 049 feeds.)"""
+    import torch
+    quiet, tail, lv = past_2g_stream()
+    h = trig.host_trigger(*PAST_PARAMS, lv)
+    ev, _, _ = h.feed(quiet)
+    assert len(ev) == 0
+    we, ws, wd = h.feed(tail)
+    we["row"] += (PAST_FEEDS - 1) * PAST_N
+    assert list(we["row"]) == [(1 << 31) + (1 << 20) + r for r in (0, 700, 4990)] and wd == 0
+
+    d = DeviceRun(trig, PAST_PARAMS, lv, cuda_device)
+    xq, xt = torch.from_numpy(quiet).to(cuda_device), torch.from_numpy(tail).to(cuda_device)
+    seen = torch.zeros(2, dtype=torch.int64, device=cuda_device)
+    for _ in range(PAST_FEEDS):
+        d.enqueue(xq)
+        seen += d.cnt                                              # on the stream of the feeds: no read-back
+    assert seen.cpu().tolist() == [0, 0]
+    assert d.t.rows_seen == PAST_FEEDS * PAST_N
+    ge, gs, gd = d.feed(xt)
+    assert d.t.rows_seen == PAST_FEEDS * PAST_N + PAST_TAIL == (1 << 31) + (1 << 20) + 5000
+    assert_feeds_equal([(ge, gs, gd)], [(we, ws, wd)], "past 2^31")
+    # reset: the numbering restarts at 0, where the pulse in row 0 has r < pre and is not emitted
+    d.t.reset()
+    assert d.t.rows_seen == 0
+    h.reset()
+    want = h.feed(tail)
+    assert list(want[0]["row"]) == [700, 4990]
+    assert_feeds_equal([d.feed(xt)], [want], "behind reset")
+    d.close(), h.close()
 
 
 @pytest.mark.parametrize("name,cut", [("planted", [32, 32]), ("planted_overflow", [64]), ("special", [7] * 9 + [1]),

@@ -1,11 +1,13 @@
 """The trigger's host twin (gsdr_trigger_* over GSDR_TRIGGER_HOST, host_logic.cpp) against the literal model of
-tests/_trigger.py, bit for bit; the refusals, the struct layouts and the Python mirror.  No GPU."""
+tests/_trigger.py, bit for bit; the refusals, the struct layouts and the Python mirror.  The vectorised model is pinned to
+the literal one on every small case, and the host twin to the vectorised one on the long feeds and past row 2^31.  No GPU."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from _trigger import CASE_IDS, CASES, EVENT_DTYPE, LEVEL_DTYPE, Model, default_levels, same_bits
+from _trigger import (CASE_IDS, CASES, EVENT_DTYPE, LARGE_CASES, LARGE_IDS, LEVEL_DTYPE, PAST_FEEDS, PAST_N, PAST_PARAMS, PAST_TAIL,
+                      Model, default_levels, lane_width, past_2g_stream, same_bits, select_chunk)
 
 
 @pytest.fixture(scope="module")
@@ -38,6 +40,95 @@ def test_host_twin_matches_the_model(trig, case):
         assert_feeds_equal(run_host(trig, case, cut), want, (case.name, cut))
         emitted += sum(len(e) for e, _, _ in want)
     assert emitted > 0, "a case that emits nothing checks nothing"
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_vectorised_model_equals_the_literal_model(case):
+    """stream_expected, the only model the long cases have, against Model on every case and cut, bit for bit."""
+    for cut in case.cuts:
+        assert_feeds_equal(case.expected_vec(cut), case.expected(cut), (case.name, cut))
+
+
+def test_select_chunk_is_what_the_kernel_computes():
+    assert [select_chunk(E) for E in (1, 65_536, 65_537, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, (1 << 20) + 4)] == \
+        [64, 64, 128, 1024, 1024, 1088, 1088]
+    for E in (150, 65_536, 65_537, 200_001, 913_044, (1 << 20) + 4):
+        L = select_chunk(E)
+        assert L % 64 == 0 and 1024 * L >= E and (L == 64 or 1024 * (L - 64) < E)
+
+
+LARGE_EVENTS = {"edge_65536": None, "edge_65537": None, "million_4ch": None, "chain_40ch": 1, "chain_40ch_broken": 4,
+                "wide_65ch_long": None, "every7_200k_holdoff6": None, "every7_200k_holdoff7": 1}
+
+
+@pytest.mark.parametrize("large", LARGE_CASES, ids=LARGE_IDS)
+def test_host_twin_matches_the_vectorised_model_on_long_feeds(trig, large):
+    case = large.case()
+    for cut in case.cuts:
+        want = case.expected_vec(cut)
+        assert_feeds_equal(run_host(trig, case, cut), want, (case.name, cut))
+        n = sum(len(e) for e, _, _ in want)
+        assert n > 0, "a cut that emits nothing checks nothing"
+        if LARGE_EVENTS[case.name] is not None:
+            assert n == LARGE_EVENTS[case.name], (case.name, cut, n)
+    dropped = sum(d for _, _, d in case.expected_vec(case.cuts[0]))
+    if case.name.startswith("edge_"):
+        assert dropped > 0 and case.max_events == 1024          # the cut at max_events, behind all 1024 (513) chunks
+    else:
+        assert dropped == 0
+    if case.name == "every7_200k_holdoff6":
+        assert n > 28_000
+
+
+def test_long_cases_reach_what_they_are_for():
+    """The chunk lengths and grid caps each long case names, restated from launch_trigger_feed."""
+    seen = {}
+    for large in LARGE_CASES:
+        case = large.case()
+        for cut in case.cuts:
+            for n in cut:
+                E = case.post - 1 + n
+                seen.setdefault(case.name, set()).add(select_chunk(E))
+                if case.n_ch <= 64:
+                    rpw = 64 >> lane_width(case.n_ch)
+                    if -(-n // rpw) > 65_536:
+                        seen[case.name].add("hits cap")
+                elif n > 65_536:
+                    seen[case.name].add("wide cap")
+    assert seen["edge_65536"] == {64} and seen["edge_65537"] == {128, 64}      # 64: the eight rows behind the long feed
+    assert {1088, 1024, 896} <= seen["million_4ch"]
+    assert seen["chain_40ch"] == seen["chain_40ch_broken"] == {128, "hits cap"}
+    assert {128, "wide cap"} <= seen["wide_65ch_long"]
+    assert 256 in seen["every7_200k_holdoff6"] and 256 in seen["every7_200k_holdoff7"]
+    caps = next(c for c in CASES if c.name == "caps_2048_overflow")
+    S = caps.pre + caps.post
+    assert (S - 1) * caps.n_ch > 1 << 19 and caps.max_events * S * caps.n_ch > 1 << 21
+    assert any(0 < n < S - 1 for cut in caps.cuts for n in cut)
+    drops = [sum(d for _, _, d in caps.expected(cut)) for cut in caps.cuts]
+    assert any(d > 0 for d in drops) and any(d == 0 for d in drops)
+
+
+def test_rows_past_2_to_the_31_on_the_host_twin(trig):
+    """2 049 quiet feeds of 2^20 rows, then a tail with pulses: the events are those of a twin that saw ONE quiet feed, 2048 *
+    2^20 rows later, with the same snippets -- every row number along the way is 64 bits wide."""
+    quiet, tail, lv = past_2g_stream()
+    full, short = trig.host_trigger(*PAST_PARAMS, lv), trig.host_trigger(*PAST_PARAMS, lv)
+    for _ in range(PAST_FEEDS):
+        ev, _, dropped = full.feed(quiet)
+        assert len(ev) == 0 and dropped == 0
+    ev, _, _ = short.feed(quiet)
+    assert len(ev) == 0
+    (ge, gs, gd), (we, ws, wd) = full.feed(tail), short.feed(tail)
+    assert full.rows_seen == PAST_FEEDS * PAST_N + PAST_TAIL == (1 << 31) + (1 << 20) + 5000
+    assert list(ge["row"]) == [(1 << 31) + (1 << 20) + r for r in (0, 700, 4990)]
+    we = we.copy()
+    we["row"] += (PAST_FEEDS - 1) * PAST_N
+    assert same_bits(ge, we) and same_bits(gs, ws) and gd == wd == 0
+    assert same_bits(gs[0], np.concatenate([quiet[-3:], tail[:5]]))
+    full.reset()
+    ev, sn, _ = full.feed(tail)
+    assert list(ev["row"]) == [700, 4990] and same_bits(sn[0], tail[697:705])      # row 0 < pre: a trigger, not emitted
+    full.close(), short.close()
 
 
 def test_planted_case_is_what_the_issue_states(trig):
@@ -233,3 +324,16 @@ def test_case_list_holds_every_class_the_suite_relies_on():
                     seen.add("hit chained across a feed boundary")
     assert seen == {"deferred event", "trigger before pre", "hit chained across a feed boundary", "switched-off channel",
                     "row with n_hit > 1", "overflowing feed", "feed shorter than the carry"}, seen
+    # every lane width of trigger_hits_kernel, and both sides of each power of two up to the wide kernel's first channel
+    n_chs = {case.n_ch for case in CASES}
+    assert {lane_width(n) for n in n_chs if n <= 64} == set(range(7))
+    assert all((1 << k) in n_chs and (1 << k) + 1 in n_chs for k in range(7)), sorted(n_chs)
+    # the wide kernel: one step exactly, one channel into the second and the third, and more than two steps
+    assert {256, 257, 513} <= n_chs
+    # a row with two hits whose lowest channel is 0 and whose other one is the last channel, as an event of its own
+    for case in CASES:
+        if case.name.startswith("lanes_") and case.name.endswith("_h0"):
+            ev = np.concatenate([e for e, _, _ in case.expected(case.cuts[0])])
+            both = ev[ev["n_hit"] == 2]
+            assert len(both) == 1 and both["channel"][0] == 0 and both["side"][0] == -1, case.name
+            assert case.n_ch - 1 in ev["channel"] and {1, -1} <= set(ev["side"]), case.name
