@@ -77,10 +77,8 @@ __device__ __forceinline__ int chirp_index(unsigned long long e, const ChirpShap
     return (int)idx;
 }
 
-// the 32-bit fast kernels cover num_steps, length and period below 2^31 / 2^32
-__host__ __device__ inline bool chirp_fits_32(const ChirpShape &cs) {
-    return cs.period < 0xffffffffull && cs.num_steps < 0x7fffffffull && cs.length < 0x800000ull;
-}
+// the 32-bit fast kernels cover num_steps, length and period below 2^31 / 2^32 (the launchers ask; chirp_plan.h)
+inline bool chirp_fits_32(const ChirpShape &cs) { return chirp_plan_fits_32(cs.num_steps, cs.length, cs.period); }
 
 __device__ __forceinline__ float2 demod_one(float2 in, int index) {
     float s, c;
@@ -628,10 +626,12 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void chirp_multi_demod_generic_kern
 static_assert(4 * kChirpGroup == kMultiChirpMax, "the largest instantiation holds every chirp");
 
 hipError_t launch_chirp_multi_demod(const float2 *in, float2 *out, long long n_samples, unsigned long long index0,
-                                    const MultiChirp &mc, hipStream_t st) {
+                                    const MultiChirp &mc, hipStream_t st, ChirpPlan *used) {
     if (n_samples <= 0) return hipSuccess;
     if (mc.n < 1 || mc.n > kMultiChirpMax) return hipErrorInvalidValue;
-    if (chirp_fits_32(chirp_shape_of(mc, 0))) {
+    const bool fast = chirp_fits_32(chirp_shape_of(mc, 0));
+    if (used) used->form = fast ? kChirpPlain : kChirpGeneric;
+    if (fast) {
         long long blocks = (n_samples + 1023) / 1024;  // 256 samples per wave
         if (blocks > 256 * 16) blocks = 256 * 16;
         hipLaunchKernelGGL(chirp_multi_demod_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, n_samples, index0, mc);
@@ -646,28 +646,19 @@ hipError_t launch_chirp_multi_demod(const float2 *in, float2 *out, long long n_s
 
 hipError_t launch_chirp_multi_lockin(const float2 *carry, int carry_len, const float2 *in, const float *profile, int ppt,
                                      int valid, float2 *out, unsigned long long index0, const MultiChirp &mc, hipStream_t st,
-                                     bool split, float2 *partial, int partial_cap) {
+                                     bool split, float2 *partial, int partial_cap, ChirpPlan *used) {
     if (valid <= 0) return hipSuccess;
     if (mc.n < 1 || mc.n > kMultiChirpMax) return hipErrorInvalidValue;
-    // (the conditions of launch_chirp_lockin)
-    const bool fast = chirp_fits_32(chirp_shape_of(mc, 0)) && ppt % (int)mc.length == 0 && index0 % mc.length == 0;
-    if (!fast) {
+    // a point's partial sums take parts * n slots
+    const ChirpPlan plan = chirp_lockin_plan(chirp_fits_32(chirp_shape_of(mc, 0)), mc.length, ppt, index0, valid, mc.n, split,
+                                             partial ? partial_cap : 0);
+    if (used) *used = plan;
+    if (plan.form == kChirpGeneric) {
         GSDR_MULTI_DISPATCH(chirp_multi_lockin_generic_kernel, dim3((unsigned)((valid + 3) / 4)), carry, carry_len, in, profile,
                             ppt, valid, out, index0, mc);
         return hipGetLastError();
     }
-    const long long decim = ppt / (long long)mc.length, nst = ((long long)mc.length + 255) / 256, total = decim * nst;
-    long long parts = 1, per_part = total;
-    if (partial && split && valid <= 512) {
-        // few points with many samples each: launch_chirp_lockin's rule; a point's partial sums take parts * n slots
-        long long want = (4096 + valid - 1) / valid;
-        if (want > total / 4) want = total / 4;
-        if (want > partial_cap / ((long long)valid * mc.n)) want = partial_cap / ((long long)valid * mc.n);
-        if (want >= 2 && total >= 16 && total < 0x7fffffffLL) {
-            per_part = (total + want - 1) / want;
-            parts = (total + per_part - 1) / per_part;
-        }
-    }
+    const long long decim = ppt / (long long)mc.length, parts = plan.parts, per_part = plan.per_part;
     const long long waves = (long long)valid * parts;
     float2 *dst = parts > 1 ? partial : out;
     GSDR_MULTI_DISPATCH(chirp_multi_lockin_kernel, dim3((unsigned)((waves + 3) / 4)), carry, carry_len, in, profile, ppt,
@@ -685,9 +676,11 @@ const char *chirp_multi_demod_kernel_name() { return "chirp_multi_demod_kernel";
 const char *chirp_multi_lockin_kernel_name() { return "chirp_multi_lockin_kernel"; }
 
 hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
-                              unsigned long long index0, const ChirpShape &cs, hipStream_t st) {
+                              unsigned long long index0, const ChirpShape &cs, hipStream_t st, ChirpPlan *used) {
     if (n <= 0) return hipSuccess;
-    if (chirp_fits_32(cs)) {
+    const bool fast = chirp_fits_32(cs);
+    if (used) used->form = fast ? kChirpPlain : kChirpGeneric;
+    if (fast) {
         long long blocks = (n + 1023) / 1024;  // 256 samples per wave
         if (blocks > 256 * 16) blocks = 256 * 16;
         hipLaunchKernelGGL(chirp_demod_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, n,
@@ -704,34 +697,25 @@ hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
 hipError_t launch_chirp_lockin(const float2 *carry, int carry_len, const float2 *in,
                                const float *profile, int ppt, int valid, float2 *out,
                                unsigned long long index0, const ChirpShape &cs, hipStream_t st,
-                               bool split, float2 *partial, int partial_cap) {
+                               bool split, float2 *partial, int partial_cap, ChirpPlan *used) {
     if (valid <= 0) return hipSuccess;
-    // the fast kernel needs windows made of whole steps that start on a step boundary:
-    // true for every window the demodulator forms (ppt = length*decim, see enqueue_chirp)
-    const bool fast = chirp_fits_32(cs) && ppt % (int)cs.length == 0 && index0 % cs.length == 0;
-    if (fast && partial && valid <= 512) {
-        // few points with many samples each: deal a point's stretches to several waves (GSDR_CHIRP_SPLIT=0: never)
-        const long long decim = ppt / (long long)cs.length, nst = ((long long)cs.length + 255) / 256, total = decim * nst;
-        long long parts = (4096 + valid - 1) / valid;            // ~4096 waves in the launch
-        if (parts > total / 4) parts = total / 4;                // at least four stretches per wave
-        if (parts > partial_cap / valid) parts = partial_cap / valid;
-        if (split && parts >= 2 && total >= 16 && total < 0x7fffffffLL) {
-            const long long per_part = (total + parts - 1) / parts;
-            parts = (total + per_part - 1) / per_part;
-            const long long waves = (long long)valid * parts;
-            hipLaunchKernelGGL(chirp_lockin_split_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, carry, carry_len, in,
-                               profile, ppt, (int)decim, valid, (int)parts, (int)per_part, partial, index0, cs);
-            hipLaunchKernelGGL(chirp_lockin_sum_kernel, dim3((unsigned)((valid + 3) / 4)), dim3(256), 0, st, partial, valid,
-                               (int)parts, out);
-            return hipGetLastError();
-        }
-    }
-    if (fast)
+    const ChirpPlan plan = chirp_lockin_plan(chirp_fits_32(cs), cs.length, ppt, index0, valid, 1, split, partial ? partial_cap : 0);
+    if (used) *used = plan;
+    if (plan.form == kChirpSplit) {
+        // few points with many samples each: a point's stretches dealt to several waves
+        const long long decim = ppt / (long long)cs.length, parts = plan.parts, per_part = plan.per_part;
+        const long long waves = (long long)valid * parts;
+        hipLaunchKernelGGL(chirp_lockin_split_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, carry, carry_len, in,
+                           profile, ppt, (int)decim, valid, (int)parts, (int)per_part, partial, index0, cs);
+        hipLaunchKernelGGL(chirp_lockin_sum_kernel, dim3((unsigned)((valid + 3) / 4)), dim3(256), 0, st, partial, valid,
+                           (int)parts, out);
+    } else if (plan.form == kChirpPlain) {
         hipLaunchKernelGGL(chirp_lockin_kernel, dim3((unsigned)((valid + 3) / 4)), dim3(256), 0, st,
                            carry, carry_len, in, profile, ppt, ppt / (int)cs.length, valid, out, index0, cs);
-    else
+    } else {
         hipLaunchKernelGGL(chirp_lockin_generic_kernel, dim3((unsigned)((valid + 3) / 4)), dim3(256),
                            0, st, carry, carry_len, in, profile, ppt, valid, out, index0, cs);
+    }
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 
 #include <vector>
 
+#include "chirp_plan.h"
 #include "dev_owner.h"
 
 // No packed FP32 (v_pk_*_f32) in a kernel that may share a SIMD with the matrix-core DDC loop of another
@@ -311,6 +312,7 @@ PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n
 const char *pfb_kernel_name(const PfbChoice &c);
 
 // ---- chirp ---------------------------------------------------------------
+// (every chirp launcher below leaves the form it launched in *used when that is given: chirp_plan.h)
 struct ChirpShape {
     unsigned long long num_steps, length, period;  // period = num_steps*length
     unsigned chirpness;
@@ -319,13 +321,14 @@ struct ChirpShape {
 
 // out[o] = in[o] * conj(chirp(index0 + o)), o < n
 hipError_t launch_chirp_demod(const float2 *in, float2 *out, long long n,
-                              unsigned long long index0, const ChirpShape &cs, hipStream_t st);
+                              unsigned long long index0, const ChirpShape &cs, hipStream_t st, ChirpPlan *used = nullptr);
 // y[v] = sum_p demod(stage[v*ppt+p]) * profile[p], v < valid, where the logical
 // stage is [carry (carry_len samples) | in]; index0 is the chirp index of stage[0].
 hipError_t launch_chirp_lockin(const float2 *carry, int carry_len, const float2 *in,
                                const float *profile, int ppt, int valid, float2 *out,
                                unsigned long long index0, const ChirpShape &cs, hipStream_t st,
-                               bool split, float2 *partial, int partial_cap);   // partial sums of split points (may be null)
+                               bool split, float2 *partial, int partial_cap,    // partial sums of split points (may be null)
+                               ChirpPlan *used = nullptr);
 hipError_t launch_warm(hipStream_t st);
 // TX tone comb: out[s] = sum_k q0[k] w_k^(start + s), s < n; fmod = f mod rate, btab[k][64] = w_k^lo,
 // ctab[k][16] = w_k^(64 j), w_k = e^(+2 pi i f_k / rate) (ref: tone_gen, cpp/kernels.cu:589-684)
@@ -369,11 +372,11 @@ __host__ __device__ __forceinline__ ChirpShape chirp_shape_of(const MultiChirp &
 }
 // out[o * n + c] = in[o] * conj(chirp_c(index0 + o)), o < n_samples: the samples are read once
 hipError_t launch_chirp_multi_demod(const float2 *in, float2 *out, long long n_samples, unsigned long long index0,
-                                    const MultiChirp &mc, hipStream_t st);
+                                    const MultiChirp &mc, hipStream_t st, ChirpPlan *used = nullptr);
 // launch_chirp_lockin for every chirp of mc at once: out[v * n + c]; partial holds [point][part][chirp]
 hipError_t launch_chirp_multi_lockin(const float2 *carry, int carry_len, const float2 *in, const float *profile, int ppt,
                                      int valid, float2 *out, unsigned long long index0, const MultiChirp &mc, hipStream_t st,
-                                     bool split, float2 *partial, int partial_cap);
+                                     bool split, float2 *partial, int partial_cap, ChirpPlan *used = nullptr);
 const char *chirp_multi_demod_kernel_name();
 const char *chirp_multi_lockin_kernel_name();
 

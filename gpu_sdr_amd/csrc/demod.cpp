@@ -262,6 +262,8 @@ struct gsdr_demod {
     int cparity = 0;
     int carry_len = 0;                 // spare_size (ref :54,:369)
     unsigned long long last_index = 0; // ref :217,:355
+    unsigned long long chirp_calls[3] = {0, 0, 0};   // calls of this handle by the form that ran (gsdr::ChirpForm)
+    long long chirp_parts = 1;         // waves per point of the last call (> 1: it was split)
 
     // ---- profiling ----
     bool prof = false;
@@ -1081,10 +1083,11 @@ int enqueue_pfb_average(gsdr_demod *h, const float2 *in, float2 *out, hipStream_
 int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) {
     hipEvent_t stop = nullptr;
     int ret;
+    gsdr::ChirpPlan plan;                // the form the launcher took (gsdr_demod_describe: chirp_calls, chirp_parts)
     if (h->decim <= 0) {
         if (record_begin(h, st, &stop)) return -1;
-        if (h->chirps > 1) HIPCHK(h, gsdr::launch_chirp_multi_demod(in, out, h->L, h->last_index, h->mc, st));
-        else HIPCHK(h, gsdr::launch_chirp_demod(in, out, h->L, h->last_index, h->cs, st));
+        if (h->chirps > 1) HIPCHK(h, gsdr::launch_chirp_multi_demod(in, out, h->L, h->last_index, h->mc, st, &plan));
+        else HIPCHK(h, gsdr::launch_chirp_demod(in, out, h->L, h->last_index, h->cs, st, &plan));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
         ret = (int)(h->L * h->chirps);   // :390
     } else {
@@ -1097,11 +1100,11 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
         if (h->chirps > 1)
             HIPCHK(h, gsdr::launch_chirp_multi_lockin(h->d_ccarry[h->cparity], h->carry_len, in, h->d_profile, h->ppt, valid,
                                                       out, idx0, h->mc, st, h->sw.chirp_split, h->d_chirp_part,
-                                                      h->d_chirp_part ? kChirpPartials : 0));
+                                                      h->d_chirp_part ? kChirpPartials : 0, &plan));
         else
             HIPCHK(h, gsdr::launch_chirp_lockin(h->d_ccarry[h->cparity], h->carry_len, in,
                                                 h->d_profile, h->ppt, valid, out, idx0, h->cs, st, h->sw.chirp_split,
-                                                h->d_chirp_part, h->d_chirp_part ? kChirpPartials : 0));
+                                                h->d_chirp_part, h->d_chirp_part ? kChirpPartials : 0, &plan));
         if (stop) HIPCHK(h, hipEventRecord(stop, st));
         // :369-380 the reference keeps the last new0 DEMODULATED samples; we
         // keep the same raw samples and re-demodulate them next call.
@@ -1125,6 +1128,10 @@ int enqueue_chirp(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st) 
         ret = valid * h->chirps;         // rows [point][chirp]
     }
     h->last_index = (h->last_index + (unsigned long long)h->L) % h->cs.period;  // :355
+    if (plan.form >= 0 && plan.form < 3) {
+        h->chirp_calls[plan.form]++;
+        h->chirp_parts = plan.parts;
+    }
     return ret;
 }
 
@@ -2077,7 +2084,14 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
                                    : "polyphase filter + fp32 Stockham FFT inside the LDS + bin selection, one launch") :
          h->noise_fft ? "fp32 Stockham FFT behind the polyphase filter" : h->mfma ? "f16 MFMA, hi/lo split" : (h->mode == GSDR_CHIRP ? "fp32 VALU, integer phase" : (h->pipe ? "packed fp32 VALU" : "fp32 VALU"));
     s += "\", \"channels\": " + std::to_string(h->ddc_channels > 0 ? h->ddc_channels : h->N);
-    if (h->mode == GSDR_CHIRP) s += ", \"chirps\": " + std::to_string(h->chirps);
+    if (h->mode == GSDR_CHIRP) {
+        s += ", \"chirps\": " + std::to_string(h->chirps);
+        // calls so far by the lock-in (or undecimated) form that ran, and the waves per point of the last one
+        s += ", \"chirp_calls\": {\"plain\": " + std::to_string(h->chirp_calls[gsdr::kChirpPlain]) + ", \"split\": " +
+             std::to_string(h->chirp_calls[gsdr::kChirpSplit]) + ", \"generic\": " +
+             std::to_string(h->chirp_calls[gsdr::kChirpGeneric]) + "}";
+        s += ", \"chirp_parts\": " + std::to_string(h->chirp_parts);
+    }
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
     // every other handle reports what the four-product loop's row says
     const gsdr::ProductLoop &pr = h->mfma && h->loop ? *h->loop : *gsdr::product_loop(gsdr::MfmaKernel::AsmRing16P);

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "chirp_plan.h"
 #include "trigger_state.h"
 #include "welch_state.h"
 
@@ -215,6 +216,21 @@ void gsdr_chirp_derive_tx(int rate, int freq0, int chirp_f, int swipe_s,
     cp->length = len;
     cp->chirpness = (slope > -9.2e18 && slope < 9.2e18) ? (unsigned int)(long long)slope : 0u;
     cp->f0 = (start > -2147483649.0 && start < 2147483648.0) ? (int)start : INT_MIN;
+}
+
+// The lock-in form a CHIRP call takes (chirp_plan.h: the function the launchers themselves ask).
+int gsdr_chirp_lockin_plan(unsigned long long num_steps, unsigned long long length, long long ppt,
+                           unsigned long long index0, int valid, int chirps, int split, int partial_cap, int *parts,
+                           int *per_part) {
+    if (num_steps < 1 || length < 1 || num_steps > 0x7fffffffffffffffULL / length || ppt < 1 || ppt > INT_MAX || valid < 1 || chirps < 1 ||
+        chirps > GSDR_MULTI_CHIRP_MAX || partial_cap < 0)
+        return -1;
+    const gsdr::ChirpPlan p =
+        gsdr::chirp_lockin_plan(gsdr::chirp_plan_fits_32(num_steps, length, num_steps * length), length, ppt, index0, valid,
+                                chirps, split != 0, partial_cap);
+    if (parts) *parts = (int)p.parts;
+    if (per_part) *per_part = (int)p.per_part;
+    return p.form;
 }
 
 // sc16 input widened on the host: an exact int16 -> float conversion and one IEEE multiply per component, what

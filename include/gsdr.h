@@ -295,7 +295,9 @@ void gsdr_reload_env(void);
  * kernel (that of the last launch, see gsdr_demod_kernel_name), kernel family,
  * row tiles per workgroup, pipeline streams, and every GSDR_* environment
  * variable that is set in the process (the handle itself read the switches
- * when it was created).  Returns the text length (truncated to cap-1
+ * when it was created).  CHIRP handles add "chirp_calls": {"plain": a, "split": b, "generic": c}, this handle's calls
+ * so far by the form that ran (gsdr_chirp_lockin_plan; undecimated calls are plain or generic), and "chirp_parts",
+ * the waves per point of the last call.  Returns the text length (truncated to cap-1
  * characters + NUL). */
 int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap);
 /* gsdr_w_type actually dispatched (ref: USRP_demodulator.cpp:19-25,56). */
@@ -378,6 +380,26 @@ void gsdr_chirp_derive(int rate, int freq0, int chirp_f, int swipe_s,
  * one sample also resets num_steps to chirp_t * rate before the slope is taken from it (:118-125). */
 void gsdr_chirp_derive_tx(int rate, int freq0, int chirp_f, int swipe_s,
                           float chirp_t, gsdr_chirp_param *cp);
+
+/* Which form of the lock-in a CHIRP call takes -- the rule the library's own launchers ask, host only.  The call
+ * integrates `valid` points of ppt samples each, the first at chirp index index0, for `chirps` chirps at once:
+ *   PLAIN    a wave per point (the 32-bit fast kernel);
+ *   SPLIT    the 256-sample stretches of a point dealt to *parts waves of *per_part stretches (the last may hold
+ *            fewer), their partial sums -- valid * parts * chirps of partial_cap slots -- added in fixed order:
+ *            few points (valid <= 512) of at least 16 stretches, at least four stretches per wave; split == 0
+ *            (GSDR_CHIRP_SPLIT=0) never;
+ *   GENERIC  the 64-bit kernel: length >= 2^23, num_steps >= 2^31 - 1, a period of num_steps * length >= 2^32 - 1,
+ *            or points that are not whole steps starting on a step boundary (ppt % length, index0 % length).
+ * PLAIN: *parts = 1, *per_part = every stretch of a point; GENERIC: 1 and 0.  parts and per_part may be NULL.
+ * Returns the form, or -1 for arguments no handle has (a zero or overflowing sweep, ppt, valid or chirps < 1,
+ * chirps > GSDR_MULTI_CHIRP_MAX, partial_cap < 0).  A handle uses partial_cap 16384 and reports the forms its
+ * calls took in gsdr_demod_describe: "chirp_calls" and "chirp_parts". */
+#define GSDR_CHIRP_FORM_PLAIN 0
+#define GSDR_CHIRP_FORM_SPLIT 1
+#define GSDR_CHIRP_FORM_GENERIC 2
+int gsdr_chirp_lockin_plan(unsigned long long num_steps, unsigned long long length, long long ppt,
+                           unsigned long long index0, int valid, int chirps, int split, int partial_cap, int *parts,
+                           int *per_part);
 
 /* ---- the pyUSRP command surface (host only) ------------------------------
  * One JSON command per measurement arrives on the async socket, framed by an

@@ -363,15 +363,15 @@ def test_noise_extents(cuda_device, gsdr_lib, oracle_mod, monkeypatch, nfft, avg
 # ---------------------------------------------------------------------------
 # CHIRP, NODSP
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("row,kernel", [(0, "chirp_demod_kernel"), (1, "chirp_lockin_kernel"), (12, "chirp_lockin_kernel")],
+@pytest.mark.parametrize("row,kernel,form,parts", [(0, "chirp_demod_kernel", "plain", 1), (1, "chirp_lockin_kernel", "plain", 1),
+                                                   (12, "chirp_lockin_kernel", "split", 20)],
                          ids=["undecimated_L5000", "ppt7_remainder2", "ppt20000_split"])
-def test_chirp_extents(cuda_device, gsdr_lib, oracle_mod, monkeypatch, row, kernel):
+def test_chirp_extents(cuda_device, gsdr_lib, oracle_mod, monkeypatch, row, kernel, form, parts):
     """CHIRP_CASES of tests/test_gpu_parity.py: undecimated; 7 samples per point with 2 left over per buffer; 20 000
     samples per point, 1.5 points per buffer (chirp_lockin_split_kernel deals a point to several waves and
-    chirp_lockin_sum_kernel adds their sums).  A handle reports all three lock-in kernels as chirp_lockin_kernel and
-    describe() says no more, so the name cannot tell the split pair from the plain kernel: that the third row runs it
-    rests on the library's rule (points longer than a wave's share, GSDR_CHIRP_SPLIT unset = on), which is not
-    asserted here."""
+    chirp_lockin_sum_kernel adds their sums).  A handle reports all three lock-in kernels as chirp_lockin_kernel; which
+    of them ran is in describe()["chirp_calls"]: every call of a handle took `form`, the third row's the split pair
+    with 20 waves per point (80 stretches, four per wave)."""
     rate, f0, f1, steps, t, decim, L, _ = CHIRP_CASES[row]
     clean_env(monkeypatch, {})
 
@@ -381,7 +381,16 @@ def test_chirp_extents(cuda_device, gsdr_lib, oracle_mod, monkeypatch, row, kern
         xs = [crandn(rng, L) for _ in range(NBUF)]
         return xs, [np.array(ref.process(x)) for x in xs]
     xs, yrs = cached(("chirp", row), build)
-    run_case(cuda_device, lambda: make_chirp(rate, f0, f1, steps, t, decim, L), expect_kernel(kernel), xs, yrs, 1)
+    name = expect_kernel(kernel)
+
+    def expect(dem, ran):
+        name(dem, ran)
+        d = dem.describe()
+        want = dict({"plain": 0, "split": 0, "generic": 0}, **({form: len(xs)} if ran else {}))
+        assert d["chirp_calls"] == want, (d["chirp_calls"], want)
+        if ran:
+            assert d["chirp_parts"] == parts and d["chirp_calls"][form] > 0, d
+    run_case(cuda_device, lambda: make_chirp(rate, f0, f1, steps, t, decim, L), expect, xs, yrs, 1)
 
 
 def test_nodsp_extents(cuda_device, gsdr_lib, monkeypatch):

@@ -33,6 +33,22 @@ SHAPES = {
     "split_one_point": (20_000_000, 100, 1.0, 1, 200_000),
 }
 NBUF = 3
+# describe()["chirp_calls"] / ["chirp_parts"]: the lock-in form every call of a shape takes (csrc/chirp_plan.h), and the
+# waves per point of the split shapes -- 80 stretches in parts of four; 782 stretches, 195 waves wanted, in parts of five
+# -- for every number of chirps up to 16 (the partial sums of one or two points fit the buffer 512 times over)
+SPLIT_PARTS = {"split_1p5_points": 20, "split_one_point": 157}
+
+
+def form_of(shape):
+    return "split" if shape.startswith("split_") else "generic" if shape.startswith("generic_") else "plain"
+
+
+def assert_forms(dem, shape, calls):
+    d = dem.describe()
+    want = dict({"plain": 0, "split": 0, "generic": 0}, **{form_of(shape): calls})
+    assert d["chirp_calls"] == want, (shape, d["chirp_calls"], want)
+    assert d["chirp_calls"][form_of(shape)] > 0
+    assert d["chirp_parts"] == SPLIT_PARTS.get(shape, 1), (shape, d["chirp_parts"])
 
 
 def spans(rate, n=16):
@@ -94,6 +110,7 @@ def test_multichirp_parity(cuda_device, gsdr_lib, oracle_mod, shape, C):
         if C >= 4:          # chirp 3 is chirp 0 again
             assert np.array_equal(y[:, 0].copy().view(np.int32), y[:, 3].copy().view(np.int32))
     assert dem.out_capacity == ((L // (dem.window().size) + 1) * C if decim else L * C)
+    assert_forms(dem, shape, len(xs))
     dem.close()
 
 
@@ -136,6 +153,8 @@ def test_multichirp_equals_single_chirp_handles(cuda_device, gsdr_lib, shape):
             yr = np.stack(ys, axis=1)
             worst = max(worst, float(rel_err_per_tone(y, yr).max()))
             same_bits = same_bits and np.array_equal(y.view(np.int32), yr.view(np.int32))
+    for h in [multi] + singles:
+        assert_forms(h, shape, 4)
     multi.close()
     for s in singles:
         s.close()
@@ -259,6 +278,8 @@ def test_one_chirp_with_the_flag_is_the_single_chirp_handle(cuda_device, gsdr_li
         x = crandn(rng, L)
         ya, yb = run_device(flagged, x, cuda_device), run_device(plain, x, cuda_device)
         assert np.array_equal(ya.view(np.int32), yb.view(np.int32))
+    assert_forms(flagged, shape, 3)
+    assert_forms(plain, shape, 3)
     flagged.close()
     plain.close()
 
