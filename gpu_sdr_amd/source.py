@@ -32,8 +32,9 @@ def tone_comb(n_tones: int, rate: int, seed: int):
 
 
 def host_tones(n: int, start: int, rate: int, freq, ampl, phase, sigma: float = 0.0,
-               seed: int = 0, tone_block: int = 64) -> np.ndarray:
-    """Host (numpy, float64 phase) version of the source formula; for tests."""
+               seed: int = 0, tone_block: int = 64, dtype=np.complex64) -> np.ndarray:
+    """Host (numpy, float64 phase) version of the source formula; for tests.  ``dtype=np.complex128`` returns the
+    float64 sum as it is, without the rounding to the device's sample type."""
     idx = (start + np.arange(n, dtype=np.int64)) % rate
     acc = np.zeros(n, dtype=np.complex128)
     freq = np.asarray(freq, dtype=np.int64)
@@ -45,7 +46,7 @@ def host_tones(n: int, start: int, rate: int, freq, ampl, phase, sigma: float = 
     if sigma > 0:
         rng = np.random.default_rng(seed)
         acc += sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
-    return acc.astype(np.complex64)
+    return acc.astype(dtype)
 
 
 def device_tones(out_tensor, start: int, rate: int, freq, ampl, phase, sigma: float = 0.0,

@@ -1549,11 +1549,12 @@ def test_tx_tone_generator_at_scale(cuda_device, gsdr_lib):
     phase once per tone and 1024 samples, two table factors for the rest) against the per-sample synthesis of
     the input source (one float sincos of an exact integer phase per tone and sample), buffer by buffer --
     the second case across the wrap of the sample index at `rate`, with a buffer length that is no multiple
-    of 1024, and into host memory on alternate buffers (gsdr_txgen_get)."""
+    of 1024, and into host memory on alternate buffers (gsdr_txgen_get).  That reference is a float32 device kernel
+    itself: the first 4099 samples of every buffer are held to the float64 model (host_tones, complex128) too."""
     import torch
     import gpu_sdr_amd as g
     from gpu_sdr_amd.generator import tone_bins
-    from gpu_sdr_amd.source import device_tones, tone_comb
+    from gpu_sdr_amd.source import device_tones, host_tones, tone_comb
     for N, rate, L, nbuf in [(2048, 200_000_000, 150_000, 3), (300, 1_000_000, 99_999, 13)]:
         freq, ampl, phase = tone_comb(N, rate, 17)
         tx = g.TX_buffer_generator(g.param(mode="TX", rate=rate, buffer_len=L, freq=[int(f) for f in freq],
@@ -1576,6 +1577,11 @@ def test_tx_tone_generator_at_scale(cuda_device, gsdr_lib):
             err = float((got - want).abs().max())
             record_margin(err / float(np.sum(a2)), "max abs error / sum of amplitudes")
             assert err <= 2e-6 * float(np.sum(a2)), (N, c, err)
+            # the per-sample synthesis is float32 too: the beginning of every buffer against the float64 model as well
+            model = host_tones(4099, start % rate, rate, f2, a2, np.zeros(len(f2), dtype=np.float32), dtype=np.complex128)
+            err = float(np.max(np.abs(got[:4099].cpu().numpy() - model)))
+            record_margin(err / float(np.sum(a2)), "max abs error / sum of amplitudes")
+            assert err <= 2e-6 * float(np.sum(a2)), (N, c, err, "model")
             start = (start + L) % period
         tx.close()
 
