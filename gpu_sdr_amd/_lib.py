@@ -72,6 +72,20 @@ class ChirpParamC(C.Structure):
                 ("chirpness", C.c_uint), ("f0", C.c_int)]
 
 
+class PfbPlanInC(C.Structure):
+    """struct gsdr_pfb_plan_in"""
+    _fields_ = [(n, C.c_int) for n in (
+        "nfft", "avg", "blue_m", "frames", "n_out", "cus",
+        "pfb_cu", "pfb_direct", "pfb_col", "pfb_cu_nt", "pfb_teams", "pfb_radix8", "pfb_fr", "pfb_wide")]
+
+
+class PfbPlanOutC(C.Structure):
+    """struct gsdr_pfb_plan_out"""
+    _fields_ = [(n, C.c_int) for n in (
+        "cu", "threads", "G", "twl", "lds", "b_off", "b_len", "col", "direct", "dir_s", "dir_gs", "teams",
+        "len", "n_radices")] + [("radices", C.c_int * 16)]
+
+
 # every symbol include/gsdr.h declares: (name, restype, argtypes)
 _vp, _ip, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
 SIGNATURES = [
@@ -122,6 +136,9 @@ SIGNATURES = [
     ("gsdr_pfb_lds_stages", C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     ("gsdr_chirp_lockin_plan", C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_ulonglong, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("gsdr_pfb_plan", C.c_int, [C.POINTER(PfbPlanInC), C.POINTER(PfbPlanOutC)]),
+    ("gsdr_pfb_plan_many", C.c_int, [_vp, C.c_int, _vp]),
+    ("gsdr_pfb_blue_length", C.c_int, [C.c_int] * 5),
     ("gsdr_txgen_tones_create", C.c_void_p, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int]),
     ("gsdr_txgen_tones_fill", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
     ("gsdr_txgen_close", None, [C.c_void_p]),

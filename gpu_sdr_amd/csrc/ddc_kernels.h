@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "chirp_plan.h"
+#include "pfb_plan.h"
 #include "dev_owner.h"
 
 // No packed FP32 (v_pk_*_f32) in a kernel that may share a SIMD with the matrix-core DDC loop of another
@@ -282,34 +283,31 @@ hipError_t launch_pfb_average(const float2 *frames, long long n_frames, int n_ch
                               float2 *acc_out, float2 *out, hipStream_t st);
 const char *fft_kernel_name();
 // The whole PFB of a frame in one workgroup (filter, in-LDS transform, bin selection): frames of up to
-// kPfbLdsMaxN points whose prime factors do not exceed kPfbLdsMaxPrime.
-constexpr int kPfbLdsMaxN = 8192;
-constexpr int kPfbLdsMaxPrime = 127;
-constexpr int kPfbLdsTwMaxN = 4096;                       // up to here the twiddle table sits in the LDS as well
-constexpr int kPfbLdsMaxBytes = (2 * kPfbLdsMaxN + kPfbLdsMaxPrime + 1) * 8;   // two frame buffers + roots: 129 KiB of the 160 KiB
-int pfb_lds_plan(int n, int *radices16, bool radix8);    // number of stages, -1 when the length does not fit
+// kPfbLdsMaxN points whose prime factors do not exceed kPfbLdsMaxPrime.  Which kernel takes a call, and in what
+// shape, is pfb_plan.h's to say (pfb_lds_plan, pfb_cu_fits, pfb_choose, PfbChoice, the kPfb* limits).
 // logical window [carry (new_0 samples) | in (window_len - new_0)]; frames_n complete frames -> out[frame][n_out]
 // (sel: bin per output column, nullptr = all nfft bins); W[spare_begin .. +spare_n) -> carry_out
 // (round 3) a run of consecutive frames per compute unit when it fits the LDS, else a frame per workgroup; `blue`:
 // transform through Bluestein's identity at length blue->m (frame lengths with a prime factor above kPfbLdsMaxPrime;
 // tw is then the table of length m, blue->d_tw)
-// `*kernel`: the name of the kernel launched (left alone when nothing was)
+// `*kernel`: the name of the kernel launched (left alone when nothing was); `*used`, when given: the choice the call
+// was launched by (also when it had nothing to launch)
 hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, const float *window, const float2 *tw,
                           int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
                           float2 *carry_out, int spare_begin, int spare_n, long long window_len, hipStream_t st,
-                          const FftPlan *blue, const Switches &sw, const char **kernel);
-bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw);  // does one frame fit the run kernel's LDS layout
-// Which of the two kernels launch_pfb_lds() runs for a call of frames_n frames, and its shape
-struct PfbChoice {
-    bool cu;                   // pfb_cu_kernel (a run of frames per compute unit); false: pfb_lds_kernel
-    int threads;               // per workgroup
-    int G;                     // frames per workgroup (pfb_lds_kernel: FR)
-    int twl;                   // the twiddle table sits in the LDS too
-    size_t lds;                // dynamic LDS bytes
-    int b_off, b_len, col, direct, dir_s, dir_gs, teams;   // pfb_cu_kernel only, see PfbCuArgs
-};
-PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n_out, int cus, const Switches &sw);
-const char *pfb_kernel_name(const PfbChoice &c);
+                          const FftPlan *blue, const Switches &sw, const char **kernel, PfbChoice *used = nullptr);
+// the rule of pfb_plan.h asked with a handle's switches and its Bluestein plan (null: none)
+inline PfbSwitches pfb_switches(const Switches &sw) {
+    PfbSwitches p;
+    p.pfb_cu = sw.pfb_cu; p.pfb_direct = sw.pfb_direct; p.pfb_col = sw.pfb_col; p.pfb_cu_nt = sw.pfb_cu_nt;
+    p.pfb_teams = sw.pfb_teams; p.pfb_radix8 = sw.pfb_radix8; p.pfb_fr = sw.pfb_fr; p.pfb_wide = sw.pfb_wide;
+    return p;
+}
+inline bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw) { return pfb_cu_fits(nfft, avg, len, pfb_switches(sw)); }
+inline PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n_out, int cus, const Switches &sw) {
+    return pfb_choose(nfft, avg, blue ? blue->m : 0, blue ? blue->n_radices : 0, blue ? blue->radices : nullptr, frames_n, n_out,
+                      cus, pfb_switches(sw));
+}
 
 // ---- chirp ---------------------------------------------------------------
 // (every chirp launcher below leaves the form it launched in *used when that is given: chirp_plan.h)

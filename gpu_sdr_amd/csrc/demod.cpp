@@ -244,6 +244,11 @@ struct gsdr_demod {
     gsdr::DevBuf<float2> d_pfb_tw;                   // w_nfft^k
     gsdr::DevBuf<int> d_pfb_sel;                     // TONES: bin of every output column
     gsdr::DevBuf<float2> d_pfb_carry[kStageSets];    // the samples a call leaves over (at most F*nfft)
+    // what launch_pfb_lds chose call by call (gsdr_demod_describe: pfb_last, pfb_calls)
+    gsdr::PfbChoice pfb_last{};
+    int pfb_last_frames = -1;                        // frames of the last call; -1: no call yet
+    unsigned long long pfb_calls_cu = 0, pfb_calls_lds = 0, pfb_calls_direct[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long pfb_calls_teams = 0, pfb_calls_runs = 0, pfb_calls_short = 0;   // with teams, G >= 2, a short last run
     // ---- TONES / NOISE, mean of avg_k consecutive frames (gsdr_demod_set_frame_average; 1: off, nothing below is used) ----
     int avg_k = 1, avg_kind = GSDR_AVERAGE_COMPLEX;
     int avg_count = 0;                               // frames of the open group, summed in d_avg_acc[avg_seq % 2]
@@ -994,7 +999,16 @@ int enqueue_pfb_lds(gsdr_demod *h, const float2 *in, float2 *out, hipStream_t st
     hipEvent_t stop = nullptr;
     if (record_begin(h, st, &stop)) return -1;
     HIPCHK(h, gsdr::launch_pfb_lds(carry, h->bh.new_0, in, h->d_fft_win, tw, h->nfft, h->F, cb, sel, h->ddc_channels, out,
-                                   carry_out, h->bh.spare_begin, spare_n, wlen, st, blue, h->sw, &h->kernel_name));
+                                   carry_out, h->bh.spare_begin, spare_n, wlen, st, blue, h->sw, &h->kernel_name, &h->pfb_last));
+    {
+        const gsdr::PfbChoice &c = h->pfb_last;
+        h->pfb_last_frames = cb;
+        (c.cu ? h->pfb_calls_cu : h->pfb_calls_lds)++;
+        if (c.cu && c.direct >= 0 && c.direct <= 5) h->pfb_calls_direct[c.direct]++;
+        if (c.cu && c.teams) h->pfb_calls_teams++;
+        if (c.G >= 2) h->pfb_calls_runs++;
+        if (cb > 0 && c.G >= 1 && cb % c.G != 0) h->pfb_calls_short++;
+    }
     if (stop) HIPCHK(h, hipEventRecord(stop, st));
     h->win_seq++;
     const int ret = h->ddc_channels * cb;  // :546 (TONES), copy_size :638 (NOISE)
@@ -1299,10 +1313,8 @@ int setup_pfb(gsdr_demod *h, const gsdr_param_c *p) {
     const bool direct_ok = gsdr::pfb_lds_plan(h->nfft, radices16, sw.pfb_radix8) >= 0;
     // a prime factor above 127 (or GSDR_PFB_BLUESTEIN=1: any length, for tests): Bluestein's identity inside
     // the workgroup, when a frame at the padded length m = 2^ceil(log2(2 nfft - 1)) fits the LDS
-    long long blue_m = 1;
-    while (blue_m < 2LL * h->nfft - 1) blue_m <<= 1;
-    const bool blue_ok = (sw.pfb_bluestein < 0 ? !direct_ok : sw.pfb_bluestein != 0) &&
-                         blue_m <= gsdr::kPfbLdsMaxN && gsdr::pfb_cu_fits(h->nfft, F, (int)blue_m, sw);
+    const long long blue_m = gsdr::pfb_blue_length(h->nfft, F, sw.pfb_bluestein, gsdr::pfb_switches(sw));
+    const bool blue_ok = blue_m > 0;
     if (sw.pfb_lds && (direct_ok || blue_ok) && (noise ? noise_fft : sw.tones_fft))
         return setup_pfb_lds(h, noise, F, tone, blue_ok ? blue_m : 0);
     const bool tones_global = !noise && sw.tones_fft;
@@ -2091,6 +2103,22 @@ int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap) {
              std::to_string(h->chirp_calls[gsdr::kChirpSplit]) + ", \"generic\": " +
              std::to_string(h->chirp_calls[gsdr::kChirpGeneric]) + "}";
         s += ", \"chirp_parts\": " + std::to_string(h->chirp_parts);
+    }
+    if (h->pfb_lds) {
+        // the shape launch_pfb_lds chose for the last call (pfb_plan.h; frames -1: no call yet), and this handle's calls
+        // so far by kernel, by the run kernel's filter (direct variant 0 - 5, 0: staged), with teams, with runs of
+        // G >= 2 frames and with a last run short of G frames
+        const gsdr::PfbChoice &c = h->pfb_last;
+        auto n = [](unsigned long long v) { return std::to_string(v); };
+        s += std::string(", \"pfb_last\": {\"kernel\": \"") + (h->pfb_last_frames < 0 ? "none" : gsdr::pfb_kernel_name(c)) + "\"";
+        s += ", \"threads\": " + std::to_string(c.threads) + ", \"G\": " + std::to_string(c.G);
+        s += ", \"direct\": " + std::to_string(c.direct) + ", \"dir_s\": " + std::to_string(c.dir_s);
+        s += ", \"dir_gs\": " + std::to_string(c.dir_gs) + ", \"col\": " + std::to_string(c.col);
+        s += ", \"teams\": " + std::to_string(c.teams) + ", \"twl\": " + std::to_string(c.twl);
+        s += ", \"lds\": " + n(c.lds) + ", \"frames\": " + std::to_string(h->pfb_last_frames) + "}";
+        s += ", \"pfb_calls\": {\"pfb_cu_kernel\": " + n(h->pfb_calls_cu) + ", \"pfb_lds_kernel\": " + n(h->pfb_calls_lds) + ", \"direct\": [";
+        for (int v = 0; v < 6; ++v) s += (v ? ", " : "") + n(h->pfb_calls_direct[v]);
+        s += "], \"teams\": " + n(h->pfb_calls_teams) + ", \"runs\": " + n(h->pfb_calls_runs) + ", \"short_last_run\": " + n(h->pfb_calls_short) + "}";
     }
     s += ", \"row_tiles_per_workgroup\": " + std::to_string(h->mfma ? h->last_rt : 0);
     // every other handle reports what the four-product loop's row says

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "chirp_plan.h"
+#include "pfb_plan.h"
 #include "trigger_state.h"
 #include "welch_state.h"
 
@@ -231,6 +232,51 @@ int gsdr_chirp_lockin_plan(unsigned long long num_steps, unsigned long long leng
     if (parts) *parts = (int)p.parts;
     if (per_part) *per_part = (int)p.per_part;
     return p.form;
+}
+
+// The kernel and shape a TONES / NOISE call takes inside the LDS (pfb_plan.h: the function launch_pfb_lds itself asks).
+int gsdr_pfb_plan(const gsdr_pfb_plan_in *in, gsdr_pfb_plan_out *out) {
+    if (!in || !out) return -1;
+    if (in->nfft < 1 || in->nfft > gsdr::kPfbLdsMaxN || in->avg < 1 || in->frames < 0 || in->n_out < 1 || in->cus < 1 || in->blue_m < 0)
+        return -1;
+    gsdr::PfbSwitches sw;
+    sw.pfb_cu = in->pfb_cu; sw.pfb_direct = in->pfb_direct != 0; sw.pfb_col = in->pfb_col; sw.pfb_cu_nt = in->pfb_cu_nt;
+    sw.pfb_teams = in->pfb_teams != 0; sw.pfb_radix8 = in->pfb_radix8 != 0; sw.pfb_fr = in->pfb_fr; sw.pfb_wide = in->pfb_wide;
+    int r[32], nr;
+    if (in->blue_m > 0) {
+        long long m = 1;
+        while (m < 2LL * in->nfft - 1) m <<= 1;
+        if (m != in->blue_m || m > gsdr::kPfbLdsMaxN || !gsdr::pfb_cu_fits(in->nfft, in->avg, in->blue_m, sw)) return -1;
+        nr = gsdr::fft_radices(in->blue_m, r, 32);
+    } else {
+        nr = gsdr::pfb_lds_plan(in->nfft, r, sw.pfb_radix8);
+        if (nr < 0) return -1;
+    }
+    const gsdr::PfbChoice c = gsdr::pfb_choose(in->nfft, in->avg, in->blue_m, nr, r, in->frames, in->n_out, in->cus, sw);
+    if (in->blue_m > 0 && !c.cu) return -1;                // only the run kernel knows Bluestein's identity
+    *out = gsdr_pfb_plan_out{};
+    out->cu = c.cu; out->threads = c.threads; out->G = c.G; out->twl = c.twl; out->lds = (int)c.lds;
+    out->b_off = c.b_off; out->b_len = c.b_len; out->col = c.col; out->direct = c.direct; out->dir_s = c.dir_s;
+    out->dir_gs = c.dir_gs; out->teams = c.teams;
+    out->len = in->blue_m > 0 ? in->blue_m : in->nfft;
+    out->n_radices = nr;
+    for (int i = 0; i < nr && i < 16; ++i) out->radices[i] = r[i];
+    return 0;
+}
+
+int gsdr_pfb_plan_many(const gsdr_pfb_plan_in *in, int count, gsdr_pfb_plan_out *out) {
+    if (count < 0 || (count > 0 && (!in || !out))) return -1;
+    for (int i = 0; i < count; ++i)
+        if (gsdr_pfb_plan(in + i, out + i) != 0) return -1;
+    return 0;
+}
+
+int gsdr_pfb_blue_length(int nfft, int avg, int pfb_bluestein, int pfb_direct, int pfb_radix8) {
+    if (nfft < 1 || avg < 1) return 0;
+    gsdr::PfbSwitches sw;
+    sw.pfb_direct = pfb_direct != 0;
+    sw.pfb_radix8 = pfb_radix8 != 0;
+    return gsdr::pfb_blue_length(nfft, avg, pfb_bluestein, sw);
 }
 
 // sc16 input widened on the host: an exact int16 -> float conversion and one IEEE multiply per component, what

@@ -243,7 +243,9 @@ class RX_buffer_demodulator:
 
     def describe(self) -> dict:
         """The engine this handle resolved to (gsdr_demod_describe): dominant kernel, family,
-        row tiles per workgroup, pipeline streams, every GSDR_* variable set in the process."""
+        row tiles per workgroup, pipeline streams, every GSDR_* variable set in the process.  TONES / NOISE
+        handles inside the LDS add "pfb_last" (the shape of the last call, as gsdr_pfb_plan gives it) and
+        "pfb_calls" (the calls so far by kernel, filter variant, teams, runs and short last runs)."""
         import json
         buf = C.create_string_buffer(4096)
         self._L.gsdr_demod_describe(self._h, buf, len(buf))

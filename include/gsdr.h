@@ -297,7 +297,11 @@ void gsdr_reload_env(void);
  * variable that is set in the process (the handle itself read the switches
  * when it was created).  CHIRP handles add "chirp_calls": {"plain": a, "split": b, "generic": c}, this handle's calls
  * so far by the form that ran (gsdr_chirp_lockin_plan; undecimated calls are plain or generic), and "chirp_parts",
- * the waves per point of the last call.  Returns the text length (truncated to cap-1
+ * the waves per point of the last call.  TONES / NOISE handles that run inside the LDS add "pfb_last", the shape of the last
+ * call as gsdr_pfb_plan gives it -- {"kernel", "threads", "G", "direct", "dir_s", "dir_gs", "col", "teams", "twl", "lds",
+ * "frames"}, kernel "none" and frames -1 before the first call -- and "pfb_calls", the calls so far: {"pfb_cu_kernel": a,
+ * "pfb_lds_kernel": b, "direct": [six counts, the run kernel's calls by filter variant 0 - 5], "teams": with teams,
+ * "runs": with G >= 2, "short_last_run": with a frame count that is no multiple of G}.  Returns the text length (truncated to cap-1
  * characters + NUL). */
 int gsdr_demod_describe(const gsdr_demod *h, char *buf, int cap);
 /* gsdr_w_type actually dispatched (ref: USRP_demodulator.cpp:19-25,56). */
@@ -400,6 +404,33 @@ void gsdr_chirp_derive_tx(int rate, int freq0, int chirp_f, int swipe_s,
 int gsdr_chirp_lockin_plan(unsigned long long num_steps, unsigned long long length, long long ppt,
                            unsigned long long index0, int valid, int chirps, int split, int partial_cap, int *parts,
                            int *per_part);
+
+/* The kernel and shape a TONES / NOISE call inside the LDS takes (csrc/pfb_plan.h: the function launch_pfb_lds itself
+ * asks, call by call; host only, no GPU needed).  in: frames of nfft points, avg taps, blue_m the padded Bluestein length
+ * of the handle or 0 (gsdr_pfb_blue_length), the complete frames of the call, its output columns per frame (NOISE: nfft),
+ * the device's compute units, and the GSDR_PFB_* switches by value (unset: pfb_cu -1, pfb_direct 1, pfb_col -1,
+ * pfb_cu_nt 0, pfb_teams 1, pfb_radix8 1, pfb_fr 0, pfb_wide -1).  out: cu 1 pfb_cu_kernel (a run of G consecutive
+ * frames per workgroup), 0 pfb_lds_kernel (a set of G frames per workgroup; the fields from b_off on are 0 then);
+ * direct: the run kernel's filter, 0 staged through the LDS (col 1: column-wise, 0: point-wise), else straight out of
+ * global memory with <columns per thread, blocks> registers: 1 <1, 11>, 2 <2, 7>, 5 <3, 5>, 3 <4, 4>, 4 <1, 11> in
+ * dir_s groups of threads that own dir_gs consecutive frames each; teams: the frames of a run go through the stages
+ * on teams of threads / G threads; len: the transform length (nfft or blue_m) and radices[n_radices] its stages.
+ * Returns 0, or -1 for arguments no handle has (a length the LDS kernels do not take, blue_m that is not that length).
+ * gsdr_pfb_plan_many: `count` plans in one call (the first refusal ends it with -1). */
+typedef struct gsdr_pfb_plan_in {
+    int nfft, avg, blue_m, frames, n_out, cus;
+    int pfb_cu, pfb_direct, pfb_col, pfb_cu_nt, pfb_teams, pfb_radix8, pfb_fr, pfb_wide;
+} gsdr_pfb_plan_in;
+typedef struct gsdr_pfb_plan_out {
+    int cu, threads, G, twl, lds, b_off, b_len, col, direct, dir_s, dir_gs, teams;
+    int len, n_radices, radices[16];
+} gsdr_pfb_plan_out;
+int gsdr_pfb_plan(const gsdr_pfb_plan_in *in, gsdr_pfb_plan_out *out);
+int gsdr_pfb_plan_many(const gsdr_pfb_plan_in *in, int count, gsdr_pfb_plan_out *out);
+/* The padded length a handle of nfft points and avg taps runs Bluestein's identity at inside the LDS, 0 when it
+ * transforms the frames directly or not in the LDS at all; pfb_bluestein: GSDR_PFB_BLUESTEIN (-1 unset), pfb_direct
+ * and pfb_radix8 as above. */
+int gsdr_pfb_blue_length(int nfft, int avg, int pfb_bluestein, int pfb_direct, int pfb_radix8);
 
 /* ---- the pyUSRP command surface (host only) ------------------------------
  * One JSON command per measurement arrives on the async socket, framed by an

@@ -34,10 +34,15 @@ def write_margins(exitstatus=0):
            "worst_per_test_function": dict(sorted(summary.items(), key=lambda t: -t[1])),
            "per_test": dict(sorted(MARGINS.items(), key=lambda t: -t[1])),
            "other_figures": dict(sorted(INFO.items()))}
+    write_record("parity_margins.json", doc)
+
+
+def write_record(name, doc, **dump_args):
+    """One JSON record of a run, in the directory the parity margins go to"""
     out_dir = os.path.join(ROOT, "gpurun_out")
     try:
         os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "parity_margins.json"), "w") as fh:
-            json.dump(doc, fh, indent=1)
+        with open(os.path.join(out_dir, name), "w") as fh:
+            json.dump(doc, fh, indent=1, **dump_args)
     except OSError:
         pass

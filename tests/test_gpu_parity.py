@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import _pfb
 from _margins import record_info, record_margin
 
 pytestmark = pytest.mark.gpu
@@ -748,24 +749,57 @@ NOISE_FFT_CASES = [
     (17 * 19 * 4, 3, 30_000, 3),               # 1292: two primes above 13 (19 first, 17 through the generic stage)
     (48, 8, 300, 6),                           # frames longer than a buffer: calls without a frame; 22 frames per workgroup
     (131 * 4, 2, 20_000, 2),                   # 524: prime factor 131 > 127 -> not for the in-LDS kernel
-    (101, 2, 5_000, 3),                        # a prime frame: one stage, one column per frame, 11 frames per workgroup
-    (2 * 17, 3, 3_000, 3),                     # 34: 31 frames per workgroup, prime-first stage with two columns
+    (101, 2, 5_000, 3),                        # a prime frame: one stage; the run kernel, ten thread groups of 101 threads
+    (2 * 17, 3, 3_000, 3),                     # 34: the run kernel, 30 thread groups, prime-first stage with two columns
     (2 * 509, 4, 60_000, 3),                   # 1018: prime factor 509 -> Bluestein through 2048 inside the LDS (round 3)
     (4 * 251, 3, 50_000, 3),                   # 1004: the same through 2048
     (1021, 2, 30_000, 3),                      # a prime frame through 2048
     (3 * 1009, 2, 40_000, 3),                  # 3027 -> 8192: the longest Bluestein length the LDS takes
-    (2048, 4, 100_000, 2),                     # two frames per compute unit at most: the run kernel's LDS limit
+    (2048, 4, 100_000, 2),                     # 49 frames per call: too few to fill the run kernel's units, a frame per workgroup
     (4096, 4, 100_000, 2),                     # no room for a run's raw samples in the LDS: four taps filter straight out of memory
-    (4096, 3, 100_000, 2),                     # ... three taps do not: the frame-per-workgroup kernel
+    (4096, 3, 100_000, 2),                     # ... and so do three: the direct filter with a zero tap
     (3001, 4, 40_000, 3),                      # a prime frame through 8192 with the direct filter (two buffers of 8192 fill the LDS)
     (3072, 4, 200_000, 2),                     # 16 16 4 3, 65 frames per call: too few to fill the run kernel's units
     (250, 4, 20_000, 3),                       # 10 5 5: the radix-10 butterfly (a 2 joined with a 5)
     (70, 3, 5_000, 3),                         # 7 10
-    (600, 4, 30_000, 3),                       # 8 5 5 3; column-wise filter (four taps, >= 512 columns)
+    (600, 4, 30_000, 3),                       # 8 3 5 5; 512 threads, two columns per thread in the direct filter
     (1536, 4, 60_000, 2),                      # 8 8 8 3
-    (1230, 3, 60_000, 3),                      # 41 6 5 with three taps: the run kernel's point-wise filter
-    (1000, 5, 50_000, 3),                      # five taps: the fifth is read inside the filter loop
+    (1230, 3, 60_000, 3),                      # 41 6 5 with three taps: the direct filter, two columns per thread
+    (1000, 5, 50_000, 3),                      # five taps, 50 frames per call: two frames per workgroup of pfb_lds_kernel
 ]
+# what the comments above say of the shape a case's last call runs in, asserted from describe()["pfb_last"] (path "lds",
+# 256 compute units; tests/test_gpu_pfb_runs.py has the shapes that only many frames per call reach)
+NOISE_FFT_BRANCH = {
+    (48, 8): {"kernel": "pfb_lds_kernel", "G": 22},
+    (101, 2): {"kernel": "pfb_cu_kernel", "direct": 4, "dir_s": 10},
+    (34, 3): {"kernel": "pfb_cu_kernel", "direct": 4, "dir_s": 30},
+    (2048, 4): {"kernel": "pfb_lds_kernel", "G": 1},
+    (4096, 4): {"kernel": "pfb_cu_kernel", "direct": 3, "G": 1},
+    (4096, 3): {"kernel": "pfb_cu_kernel", "direct": 3, "G": 1},
+    (3001, 4): {"kernel": "pfb_cu_kernel", "direct": 5},
+    (3072, 4): {"kernel": "pfb_lds_kernel", "frames": 65},
+    (600, 4): {"kernel": "pfb_cu_kernel", "threads": 512, "direct": 2},
+    (1230, 3): {"kernel": "pfb_cu_kernel", "direct": 2},
+    (1000, 5): {"kernel": "pfb_lds_kernel", "G": 2},
+}
+
+
+def cuda_device_cus():
+    import torch
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+def pfb_last_is_the_plan(dem, lib, nfft, avg, frames, env=None):
+    """describe()["pfb_last"] of the call that just ran is what gsdr_pfb_plan says of its frame count on this device"""
+    d = dem.describe()
+    if "pfb_last" not in d:
+        return None
+    cus = cuda_device_cus()
+    sw = _pfb.switches_of_env(env or {})
+    plan = _pfb.plan(lib, nfft, avg, frames, cus, sw=sw)
+    assert plan is not None
+    _pfb.describe_matches_plan(d["pfb_last"], plan, frames)
+    return d["pfb_last"]
 
 
 @pytest.mark.parametrize("path", ["fft", "ddc"])
@@ -862,6 +896,10 @@ def test_noise_fft_stage_parity(cuda_device, gsdr_lib, oracle_mod, monkeypatch, 
             assert e_all <= TOL
             if yr.shape[0] >= 8:
                 assert rel_err_per_tone(y.reshape(-1, nfft), yr).max() <= TOL
+    if path == "lds":
+        last = pfb_last_is_the_plan(dem, gsdr_lib, nfft, avg, yr.shape[0])
+        for k, v in NOISE_FFT_BRANCH.get((nfft, avg), {}).items():
+            assert last is not None and last[k] == v, (k, last, v)
     dem.close()
 
 
@@ -882,7 +920,7 @@ PFB_VARIANT_SHAPES = [
     (64, 4, 9_000, 3),        # short frames: thread groups in the direct filter
     (200, 4, 30_011, 3),      # 8 5 5, groups that do not divide the workgroup, L not a multiple of the frame
     (512, 4, 700, 8),         # calls without a frame (the carry alone moves), then one
-    (1024, 4, 60_000, 3),     # one column per thread
+    (1024, 4, 60_000, 3),     # one column per thread where the run kernel is forced; 58 frames per call fill too few units: by default a frame per workgroup
     (1230, 4, 60_000, 3),     # two columns per thread, matrix-core first stage (41)
     (1536, 4, 60_000, 2),     # two columns, 8 8 8 3
     (2600, 4, 80_000, 2),     # three columns per thread
@@ -892,7 +930,28 @@ PFB_VARIANT_SHAPES = [
     (1230, 2, 60_000, 3),     # two taps
     (200, 3, 30_011, 3),      # three taps, thread groups
     (1000, 6, 60_000, 3),     # six taps: staged through the LDS, point-wise
+    (128, 4, 75_264, 3),      # 588 frames per call: runs of two frames in four thread groups, teams
+    (1024, 4, 524_288, 2),    # 512 frames per call: runs of two frames, teams of eight waves
 ]
+# The comments above name the shape of the run kernel: that of GSDR_PFB_CU=1 (with no switch set, calls of a few dozen
+# long frames fill too few units and go to pfb_lds_kernel).  Asserted from describe()["pfb_last"] in that row.
+PFB_VARIANT_FORCED_SHAPE = {
+    (64, 4, 9_000): {"direct": 4, "dir_s": 8},
+    (200, 4, 30_011): {"direct": 4, "dir_s": 2},
+    (512, 4, 700): {"direct": 1},
+    (1024, 4, 60_000): {"direct": 1, "threads": 1024},
+    (1230, 4, 60_000): {"direct": 2, "threads": 1024},
+    (1536, 4, 60_000): {"direct": 2},
+    (2600, 4, 80_000): {"direct": 5},
+    (4096, 4, 100_000): {"direct": 3, "G": 1},
+    (1018, 4, 40_000): {"direct": 1},
+    (1024, 1, 30_000): {"direct": 1},
+    (1230, 2, 60_000): {"direct": 2},
+    (200, 3, 30_011): {"direct": 4, "dir_s": 2},
+    (1000, 6, 60_000): {"direct": 0, "col": 0},
+    (128, 4, 75_264): {"direct": 4, "dir_s": 4, "G": 2, "teams": 1},
+    (1024, 4, 524_288): {"direct": 1, "G": 2, "teams": 1},
+}
 
 
 @pytest.mark.parametrize("env,kernel,what", PFB_VARIANTS,
@@ -932,6 +991,16 @@ def test_noise_every_kernel_variant(cuda_device, gsdr_lib, oracle_mod, monkeypat
                 record_margin(e_all, "all bins together")
                 assert e_all <= TOL, what
         assert emitted >= 1
+        last = pfb_last_is_the_plan(dem, gsdr_lib, nfft, avg, yr.shape[0], env)
+        if env == {"GSDR_PFB_CU": "1"}:
+            assert last["kernel"] == "pfb_cu_kernel"
+            for k, v in PFB_VARIANT_FORCED_SHAPE[(nfft, avg, L)].items():
+                assert last[k] == v, (k, last, v)
+        if L in (75_264, 524_288):
+            # the two shapes with runs: the switch rows compare something
+            assert last["G"] >= 2 or last["kernel"] == "pfb_lds_kernel" or env.get("GSDR_PFB_CU_NT") == "512"
+            if env == {"GSDR_PFB_TEAMS": "0"}:
+                assert last["teams"] == 0 and _pfb.plan(gsdr_lib, nfft, avg, yr.shape[0], cuda_device_cus())["teams"] == 1
         dem.close()
     finally:
         for k in env:
