@@ -200,12 +200,25 @@ SIGNATURES = [
     ("gsdr_welch_rows", C.c_longlong, [_vp]),
     ("gsdr_welch_segments", C.c_longlong, [_vp]),
     ("gsdr_welch_close", None, [_vp]),
+    ("gsdr_decim_create", _vp, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int]),
+    ("gsdr_decim_next_rows", C.c_int, [_vp, C.c_int]),
+    ("gsdr_decim_out_capacity", C.c_longlong, [_vp]),
+    ("gsdr_decim_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    ("gsdr_decim_feed", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    ("gsdr_decim_feed_host", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_decim_get_taps", C.c_int, [_vp, _fp, C.c_int]),
+    ("gsdr_decim_reset", C.c_int, [_vp]),
+    ("gsdr_decim_rows", C.c_longlong, [_vp]),
+    ("gsdr_decim_rows_out", C.c_longlong, [_vp]),
+    ("gsdr_decim_close", None, [_vp]),
+    ("gsdr_decim_default_taps", C.c_int, [C.c_int, _fp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
 MULTI_CHIRP_MAX = 16        # GSDR_MULTI_CHIRP_MAX
 TRIGGER_HOST = -2           # GSDR_TRIGGER_HOST
 WELCH_HOST = -2             # GSDR_WELCH_HOST
+DECIM_HOST = -2             # GSDR_DECIM_HOST
 
 
 class TriggerLevelC(C.Structure):

@@ -726,6 +726,67 @@ long long gsdr_welch_rows(const gsdr_welch *w);
 long long gsdr_welch_segments(const gsdr_welch *w);
 void gsdr_welch_close(gsdr_welch *w);
 
+/* ---- FIR decimation on the device: a second decimation stage behind demodulated rows (an extension: the reference's
+ * client decimates on the host, ref: pyUSRP/USRP_noise.py:1401-1402, scipy.signal.decimate(ftype='fir') per channel) ---
+ * A decim object sees ONE stream of rows of n_ch complex64 each -- the [row][channel] layout every RX entry writes --
+ * numbered from 0 (since creation or gsdr_decim_reset), arriving in FEEDS of 0 <= n_rows <= max_rows rows.  Its
+ * parameters: the factor q, T real float32 taps h[0..T), and an offset p >= 0, the stream row on which the window of
+ * output 0 ends.
+ * Output law.  y[o] = sum_{t<T} h[t] x[o q + p - (T-1) + t], per channel, real and imaginary part apart; rows before
+ *   the stream (index < 0) are zero.  After `total` rows the object has emitted
+ *   n_out(total) = total <= p ? 0 : (total - 1 - p)/q + 1 output rows: the host knows it without a read-back.  A feed
+ *   emits n_out(total + n_rows) - n_out(total) rows [out_row][channel], possibly 0.  p = q - 1 is the DDC's own frame
+ *   law; p = (T-1)/2 with odd symmetric taps is scipy.signal.decimate(zero_phase=True).
+ * Arithmetic.  The order is fixed, so that device, host twin and any cutting give the same bits.  F = ceil(T/q).
+ *   Chunk j (0 <= j < F) is the taps t with max(0, T - (j+1)q) <= t < T - jq: chunks are cut from the END of the taps,
+ *   so chunk j of output o always covers the absolute row block [(o-j)q + p + 1 - q, (o-j)q + p + 1).  A chunk sum
+ *   starts at +0 and takes its taps in ascending t, acc = fma(h[t], x, acc), each step one IEEE single-precision fused
+ *   multiply-add; rows before the stream are skipped (a chunk whose whole block lies before the stream is +0).  The
+ *   output is the chunk sums added oldest first, (((P_{F-1} + P_{F-2}) + ...) + P_0), each addition one float32
+ *   addition, nothing else fused.  A block's contribution to its F outputs depends on that block alone.
+ * Cutting.  The concatenated output does not depend, bit for bit, on where the stream is cut into feeds.
+ * Poison.  An Inf or NaN reaches exactly the outputs whose T-row window holds it, zero taps included, in its own
+ *   channel; everything else keeps its bits.
+ * gsdr_decim_create: 1 <= n_ch <= 2^20, 1 <= max_rows <= 2^20, 1 <= q <= 4096, 1 <= n_taps <= 64 q, every tap finite,
+ *   0 <= offset <= 2^30, device_index >= -1 as in gsdr_param_c or GSDR_DECIM_HOST for a host-only object that touches
+ *   no GPU; taps == NULL requires n_taps == 0 and q >= 2 and selects the default taps.  Anything else is refused before
+ *   the device is touched: NULL, and gsdr_last_error(NULL) starts with "gsdr_decim_create: " and names the argument.
+ *   Everything a feed needs is allocated here, every byte count in 64 bits; a failed allocation is a refusal that
+ *   states the MiB.
+ * Default taps: scipy's FIR decimation design, T = 20 q + 1, firwin(T, 1/q, window='hamming') -- the ideal low-pass with
+ *   cutoff 1/q of Nyquist times the symmetric Hamming window, scaled to sum 1 -- evaluated in double and rounded once
+ *   to float32.  gsdr_decim_default_taps(q, w): host only; writes 20 q + 1 floats and returns that count, or -1
+ *   (q outside [2, 4096], w NULL).
+ * gsdr_decim_next_rows: the rows a feed of n_rows would emit now (-1: n_rows outside [0, max_rows]);
+ *   gsdr_decim_out_capacity: the most rows one feed can emit, (max_rows - 1)/q + 1.
+ * gsdr_decim_feed_device: asynchronous on hip_stream (hipStream_t as void*), no synchronisation, no read-back, at most
+ *   three launches; reads exactly rows_dev[0, n_rows n_ch), writes exactly out_dev[0, emitted n_ch); returns the rows
+ *   emitted, or -1 with gsdr_last_error(NULL).  Pointers need 8-byte alignment only and may point anywhere into larger
+ *   allocations.  n_rows == 0 is valid and touches no pointer; n_rows outside [0, max_rows]: -1, state unchanged.
+ * gsdr_decim_feed: the same launches, then waits for hip_stream and copies the emitted rows to out_host.
+ * gsdr_decim_feed_host: GSDR_DECIM_HOST objects only (and the device feeds are refused on them): a BIT TWIN of the
+ *   device (std::fmaf, plain float additions).
+ * Stream order is the caller's, as for the trigger and Welch objects: the object remembers no stream and waits for
+ *   none; rows_dev must stay unchanged until the feed that reads it has finished.  gsdr_decim_reset restarts the row
+ *   numbering; the caller must have ordered it behind the feeds in flight.  gsdr_decim_get_taps: copies min(cap, T)
+ *   taps and returns T.  gsdr_decim_rows / _rows_out: rows fed and rows emitted since creation / reset.  On a NULL
+ *   object close is a no-op, the getters return 0, the feeds and reset return -1 with the reason. */
+#define GSDR_DECIM_HOST (-2)
+typedef struct gsdr_decim gsdr_decim;
+gsdr_decim *gsdr_decim_create(int n_ch, int max_rows, int q, int n_taps, const float *taps /* n_taps, or NULL */,
+                              long long offset, int device_index);
+int gsdr_decim_next_rows(const gsdr_decim *d, int n_rows);
+long long gsdr_decim_out_capacity(const gsdr_decim *d);
+int gsdr_decim_feed_device(gsdr_decim *d, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, void *hip_stream);
+int gsdr_decim_feed(gsdr_decim *d, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_host, void *hip_stream);
+int gsdr_decim_feed_host(gsdr_decim *d, const gsdr_c64 *rows, int n_rows, gsdr_c64 *out);
+int gsdr_decim_get_taps(const gsdr_decim *d, float *w, int cap);
+int gsdr_decim_reset(gsdr_decim *d);
+long long gsdr_decim_rows(const gsdr_decim *d);
+long long gsdr_decim_rows_out(const gsdr_decim *d);
+void gsdr_decim_close(gsdr_decim *d);
+int gsdr_decim_default_taps(int q, float *w);
+
 #ifdef __cplusplus
 }
 #endif
