@@ -1,17 +1,21 @@
 """The FIR decimator without a GPU (include/gsdr.h, "FIR decimation on the device"): the default taps against
 scipy.signal.firwin, the host twin (GSDR_DECIM_HOST) against scipy.signal.decimate and against the float64 oracle of
 tests/_decim.py over a grid of factors, tap counts and offsets, the count law, the cuttings, poison, every refusal and
-the entries on a NULL object.
+the entries on a NULL object.  fma32 and contract_bits of tests/_decim.py -- the paragraph "Arithmetic" written out
+from the header, with no ring -- against a rational reference and against the twin, bit for bit, over the run shapes
+of the kernels; two deliberately wrong models that the twin must differ from; the counts across stream row 2^31.
 
 Measured here (bar 1e-5): host twin against scipy.signal.decimate 0.8e-7 .. 2.0e-7; against the oracle over the grid
 2.7e-8 .. 7.2e-6, the largest at q = 4096 (signed random taps, chains of 4096 fused multiply-adds: 7.2e-6 with 2 q + 3
 taps, 6.8e-6 with 64 q); the device gives the same bits (tests/test_gpu_decim.py)."""
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from _decim import (INPUTS, PARITY_BAR, caller_taps, carrier, cuttings, n_out, noise, oracle, rel_err, run_host, same_bits)
+from _decim import (INPUTS, PARITY_BAR, RUN_F, RUN_Q, VALUE_KINDS, caller_taps, carrier, check_values_model, contract_bits, cuttings, fma32,
+                    n_out, noise, oracle, rel_err, run_host, run_modelled, run_tap_counts, same_bits, same_values, values_case)
 
 
 @pytest.fixture(scope="module")
@@ -204,6 +208,192 @@ def test_reset_restarts_the_stream(decimate):
     got = np.concatenate([d.feed(x[:64]), d.feed(x[64:])])
     d.close()
     assert same_bits(got, want)
+
+
+# ---- the bit model of the contract (tests/_decim.py: fma32, contract_bits) ----------------------------------------
+
+def _f32(v):
+    return np.float32(v)
+
+
+def _round_once(a, b, c):
+    """float32(a b + c) from the exact rational value, rounded once, ties to even: the reference of fma32."""
+    a, b, c = _f32(a), _f32(b), _f32(c)
+    exact = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    if exact == 0:
+        p_neg = bool(np.signbit(a)) != bool(np.signbit(b))
+        if a != 0 and b != 0:                      # the product is not zero: it cancels c exactly, +0
+            return _f32(0.0)
+        return _f32(-0.0) if p_neg and np.signbit(c) else _f32(0.0)          # (+-0) + (+-0)
+    mag = abs(exact)
+    e = mag.numerator.bit_length() - mag.denominator.bit_length()           # 2^(e-1) < mag < 2^(e+1)
+    if Fraction(2) ** e > mag:
+        e -= 1
+    ulp = Fraction(2) ** (max(e, -126) - 23)
+    n, rest = divmod(mag, ulp)
+    if rest * 2 > ulp or (rest * 2 == ulp and n % 2 == 1):
+        n += 1
+    val = n * ulp
+    out = np.inf if val >= Fraction(2) ** 128 else float(val)
+    return _f32(-out if exact < 0 else out)
+
+
+def _fma_triples():
+    """(a, b, c) float32 triples: the issue's counter-example and its family (a b just above or just below half an ulp
+    of c, c of both signs and both last-bit parities), subnormal results, results that round up into the next binade,
+    exact cancellations, signed zeros, and a few thousand random ones over many exponents."""
+    rng = np.random.default_rng(77)
+    u = 2.0 ** -23
+    t = [(2.0 ** -24 * (1 + u), 1 - u, 1 + u)]
+    for k in range(1, 400):
+        for sign in (1.0, -1.0):
+            c = sign * (1 + k * u)                                   # ulp(c) = 2^-23: half an ulp is 2^-24
+            for above in (1 + k * u, 1 - (k % 7 + 1) * u / 2):       # a b = 2^-24 (1 +- few 2^-23): beside the tie
+                t.append((2.0 ** -24 * (1 + u), above, c))
+                t.append((-(2.0 ** -24) * (1 + u), above, c))
+    for k in range(300):                                             # subnormal results, ties among them
+        t.append(((1 + k * u) * 2.0 ** -70, (1.5 + k * u) * 2.0 ** -70, (k % 5) * 2.0 ** -149))
+        t.append(((3 + 2 * k) * 2.0 ** -100, 2.0 ** -50, -(k % 3) * 2.0 ** -148))     # odd multiples of 2^-150: ties
+    for k in range(300):                                             # round up into the next binade
+        t.append((2.0 ** -24, 1 + k * u, 2 - u))
+        t.append((-(1 + u * k), 2.0 ** -25, -(1 - u / 2)))
+    for k in range(200):                                             # exact cancellation: +0
+        a, b = 1 + k * u, 2.0 ** (k % 20 - 10)
+        t.append((a, b, -(a * b)))
+        t.append((-a, b, a * b))
+    t += [(0.0, 1.0, 0.0), (-0.0, 1.0, 0.0), (-0.0, 1.0, -0.0), (0.0, -1.0, -0.0), (0.0, 0.0, -0.0), (3e38, 3.0, -3e38), (3e38, 2.0, 3e38)]
+    m = rng.standard_normal((3000, 3)) * 2.0 ** rng.integers(-40, 40, size=(3000, 3))
+    m[:1000, 2] = -(m[:1000, 0].astype(np.float32).astype(np.float64) * m[:1000, 1].astype(np.float32)) * (1 + rng.integers(-3, 4, 1000) * u)
+    arr = np.concatenate([np.array(t, dtype=np.float64), m]).astype(np.float32)
+    assert np.all(np.isfinite(arr))
+    return arr
+
+
+def test_fma32_rounds_once():
+    tr = _fma_triples()
+    a, b, c = tr[:, 0], tr[:, 1], tr[:, 2]
+    assert tr.shape[0] >= 5000
+    got = fma32(a, b, c)
+    want = np.array([_round_once(*row) for row in tr], dtype=np.float32)
+    assert got.dtype == np.float32
+    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, [(tr[i].tolist(), float(got[i]), float(want[i])) for i in bad[:5]]
+    # what the triples hold: the issue's counter-example gives 1 + 2^-23, subnormal results, a binade crossed, +0
+    u = np.float32(2.0 ** -23)
+    assert got[0] == np.float32(1) + u
+    tiny = np.float32(np.finfo(np.float32).tiny)
+    assert np.count_nonzero((got != 0) & (np.abs(got) < tiny)) >= 100
+    assert np.count_nonzero((np.abs(c) < 2) & (np.abs(got) == 2)) >= 1 and np.count_nonzero((np.abs(c) < 1) & (np.abs(got) == 1)) >= 1
+    cancelled = (a != 0) & (c != 0) & (a.astype(np.float64) * b.astype(np.float64) == -c.astype(np.float64))
+    assert np.count_nonzero(cancelled) >= 100 and not np.any(np.signbit(got[cancelled]))
+    # ... and they discriminate: the expression that rounds to float64 first and to float32 second is wrong on some
+    with np.errstate(over="ignore"):
+        twice = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+    differ = np.flatnonzero(twice.view(np.uint32) != got.view(np.uint32))
+    assert 0 in differ and twice[0] == np.float32(1) + 2 * u
+    up, down = twice[differ].astype(np.float64) > got[differ], twice[differ].astype(np.float64) < got[differ]
+    assert up.any() and down.any() and differ.size >= 20, differ.size
+
+
+MODEL_GRID = [(q, F) for q in RUN_Q for F in RUN_F if run_modelled(F, q)]      # q in {1, 3}: every F; q in {8, 9, 17}: F <= 22
+
+
+@pytest.mark.parametrize("q,F", MODEL_GRID)
+def test_host_twin_has_the_bits_of_the_contract(decimate, q, F):
+    """The twin against contract_bits, bit for bit: every T of the run shapes, the offsets {0, q-1, q, (T-1)//2, T+5},
+    3 channels, F + 5 outputs or more (those whose windows begin before the stream and the steady state), as one feed
+    and as feeds of 7 rows.  The model takes about 15 us per output and tap, so F in {63, 64} is modelled for q in
+    {1, 3} only."""
+    for T in run_tap_counts(F, q):
+        h = caller_taps(T)
+        for k, offset in enumerate(sorted({0, q - 1, q, (T - 1) // 2, T + 5})):
+            rows = offset + (F + 4) * q + 3
+            x = noise(rows, 3, seed=90 + k)
+            want = contract_bits(x, q, h, offset)
+            assert want.shape[0] == n_out(rows, offset, q) >= F + 4
+            for cname in ("one", "sevens"):
+                got = run_host(decimate, x, q, h, offset, cuttings(rows, q)[cname])
+                assert same_bits(got, want), (q, F, T, offset, cname, int(np.flatnonzero((got != want).any(axis=1))[0]))
+
+
+def _wrong_variant(x, q, taps, offset, newest_first=False, cut_from_start=False):
+    """contract_bits with one law broken on purpose: the chunk sums added newest first, or the chunks cut from the
+    START of the taps (chunk F-1 is t < q, chunk 0 the short one at the end)."""
+    xf = np.ascontiguousarray(x, dtype=np.complex64).view(np.float32)
+    h = np.asarray(taps, dtype=np.float32)
+    T, n2 = h.shape[0], xf.shape[1]
+    F = (T + q - 1) // q
+    m = n_out(x.shape[0], offset, q)
+    y = np.zeros((m, n2), dtype=np.float32)
+    for o in range(m):
+        first = o * q + offset - (T - 1)
+        P = []
+        for j in range(F):
+            span = range((F - 1 - j) * q, min(T, (F - j) * q)) if cut_from_start else range(max(0, T - (j + 1) * q), T - j * q)
+            acc = np.zeros(n2, dtype=np.float32)
+            for t in span:
+                if first + t >= 0:
+                    acc = fma32(h[t], xf[first + t], acc)
+            P.append(acc)
+        order = P if newest_first else P[::-1]
+        s = order[0]
+        for p in order[1:]:
+            s = (s + p).astype(np.float32)
+        y[o] = s
+    return y.view(np.complex64)
+
+
+def test_the_model_has_teeth(decimate):
+    """F = 21, q = 2, noise.  The unbroken variant is contract_bits (so the helper is the same law); each broken one
+    differs from the twin, and so does an ordinary float32 dot product in tap order."""
+    q, T, offset, rows = 2, 41, 20, 120
+    x, h = noise(rows, 3, seed=95), caller_taps(T)
+    twin = run_host(decimate, x, q, h, offset)
+    assert twin.shape[0] == 50
+    assert same_bits(_wrong_variant(x, q, h, offset), contract_bits(x, q, h, offset)) and same_bits(twin, contract_bits(x, q, h, offset))
+    for broken in (dict(newest_first=True), dict(cut_from_start=True)):
+        bad = _wrong_variant(x, q, h, offset, **broken)
+        differ = (bad.view(np.uint32) != twin.view(np.uint32))
+        assert differ.any(), broken
+        assert rel_err(bad, oracle(x, q, h, offset)) <= PARITY_BAR        # and the float64 bar does not see it
+        print(f"{broken}: {differ.any(axis=1).sum()} of {twin.shape[0]} output rows differ")
+    xp = np.concatenate([np.zeros((T - 1, 3), dtype=np.complex64), x]).view(np.float32)
+    plain = np.zeros((50, 6), dtype=np.float32)
+    for o in range(50):
+        for t in range(T):
+            plain[o] = fma32(h[t], xp[o * q + offset + t], plain[o])
+    assert (plain.view(np.uint32) != twin.view(np.float32).view(np.uint32)).any(axis=1).all()
+
+
+@pytest.mark.parametrize("kind", VALUE_KINDS)
+def test_values_twin_against_the_model(decimate, kind):
+    """Subnormal products and sums, rows of -0, and chunk sums that overflow: the twin against the model, and the model
+    against what the case is there for (tests/test_gpu_decim.py runs the same cases on the device)."""
+    x, h, q, offset = values_case(kind)
+    want = contract_bits(x, q, h, offset)
+    check_values_model(kind, want)
+    for cname in ("one", "sevens"):
+        got = run_host(decimate, x, q, h, offset, cuttings(x.shape[0], q)[cname])
+        assert same_values(got, want), (kind, cname)
+
+
+def test_host_twin_counts_past_2_to_the_31_rows(decimate):
+    """2 049 feeds of 2^20 zero rows through the cheapest shape (q = 4096, one tap, one channel): the counts of every
+    feed against n_out in Python integers, across stream row 2^31.  (About 12 s: measured before it was added; the
+    device crosses 2^31 and 2^32 with data in tests/test_gpu_decim.py.)"""
+    q, offset, n = 4096, 4101, 1 << 20
+    d = decimate.host_decimator(1, n, q, taps=np.ones(1, dtype=np.float32), offset=offset)
+    x = np.zeros((n, 1), dtype=np.complex64)
+    total = 0
+    for k in range(2049):
+        want = n_out(total + n, offset, q) - n_out(total, offset, q)
+        assert d.next_rows(n) == want
+        y = d.feed(x)
+        total += n
+        assert y.shape == (want, 1) and not y.view(np.uint32).any(), k
+        assert d.rows_seen == total and d.rows_out == n_out(total, offset, q), k
+    d.close()
+    assert total == (1 << 31) + n and want == 256
 
 
 def test_entries_on_a_null_object(gsdr_lib):

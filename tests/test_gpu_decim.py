@@ -1,7 +1,10 @@
 """The FIR decimator on the GPU (include/gsdr.h, "FIR decimation on the device"): the device output against the host
 twin (the same bits) and against the float64 oracle of tests/_decim.py, the cuttings, the extents of what a feed reads
 and writes, poison, empty feeds, the refusals of a feed, a stream of the caller's, gsdr_decim_feed, and a chain of a
-DIRECT handle, a decimator and a Welch object.
+DIRECT handle, a decimator and a Welch object.  Every run shape of the two kernels (tests/_decim.py, RUN_F x RUN_Q)
+against the twin and against the bit model of the contract's arithmetic (contract_bits); reset on a device object;
+subnormals, signed zeros and overflowing chunk sums; streams of more than 2^31 and 2^32 rows and the offset at its
+bound of 2^30 (measured on an MI355X: 0.09 s, 0.18 s and 0.02 s for the 2 049, 4 097 and 1 026 feeds).
 
 Measured worst per-channel relative errors (bar 1e-5) are written to the file that GSDR_DECIM_MARGINS names, when it is
 set; profiles/decim_margins.json is the committed copy."""
@@ -11,9 +14,10 @@ import os
 import numpy as np
 import pytest
 
-from _decim import PARITY_BAR, caller_taps, carrier, cuttings, n_out, noise, oracle, rel_err, run_device, run_host, same_bits
+from _decim import (PARITY_BAR, RUN_F, RUN_Q, VALUE_KINDS, caller_taps, carrier, check_values_model, contract_bits, cuttings, n_out, noise,
+                    oracle, rel_err, run_device, run_host, run_modelled, run_shapes, same_bits, same_values, values_case)
 from _extents import check_input_untouched, check_output, guarded_input, guarded_output
-from _margins import record_margin
+from _margins import record_info, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -199,6 +203,189 @@ def test_feed_to_the_host(decimate, cuda_device):
     parts = [d.feed(xd[at:at + 200], stream=stream).copy() for at in range(0, rows, 200)] + [d.feed(xd[:0], stream=stream)]
     d.close()
     assert same_bits(np.concatenate(parts), run_host(decimate, x, q, taps, offset))
+
+
+@pytest.mark.parametrize("q", RUN_Q)
+def test_every_run_shape(decimate, cuda_device, q):
+    """The grid of tests/_decim.py (RUN_F x RUN_Q x pad 0, q - 1 and in between): every chunks-per-thread of
+    decim_partial_kernel with full and clamped last groups, every count of turns and tail of decim_combine_kernel, and
+    factors on both sides of the 8 rows a thread has in flight.  Each case as one feed and cut unevenly with max_rows the
+    largest feed, so that the ring wraps inside the case; the same bits as the host twin, and as the model of the
+    contract where it is affordable (run_modelled)."""
+    shapes = run_shapes(q)
+    assert len(shapes) >= (3 if q > 1 else 1) * len(RUN_F)
+    for name, n_ch, _, T, offset, rows in shapes:
+        F = (T + q - 1) // q
+        x, h = noise(rows, n_ch, seed=13), caller_taps(T)
+        twin = run_host(decimate, x, q, h, offset)
+        assert twin.shape == (n_out(rows, offset, q), n_ch) and twin.shape[0] >= F + 13
+        one = run_device(decimate, x, q, h, offset, cuda_device)
+        assert same_bits(one, twin), (name, "one feed")
+        cut = cuttings(rows, q)["uneven"]
+        assert (max(cut) - 1) // q + 2 + F < F + 13               # fewer ring blocks than the case has blocks: it wraps
+        assert same_bits(run_device(decimate, x, q, h, offset, cuda_device, cut, max_rows=max(cut)), twin), (name, "uneven")
+        if run_modelled(F, q):
+            assert same_bits(one, contract_bits(x, q, h, offset)), (name, "contract")
+        err = rel_err(one, oracle(x, q, h, offset))
+        margin(name, err)
+        assert err <= PARITY_BAR, (name, err)
+
+
+@pytest.mark.parametrize("T", [3, 141])
+@pytest.mark.parametrize("offset", [2, 6, 70])
+def test_reset_on_the_device(decimate, cuda_device, T, offset):
+    """q = 7, F = 1 and F = 21.  Stream A ends in the middle of a block and leaves open chunk sums in the ring; after
+    reset() stream B, in two feeds, gives what a fresh object and the twin give: the first block of B starts from +0
+    where it begins before row 0 (offsets 2 and 70: r0 < 0) and where it begins on row 0 (offset q - 1 = 6)."""
+    import torch
+    n_ch, q = 3, 7
+    h = caller_taps(T)
+    a, b = carrier(45 + offset % 5, n_ch, seed=52), noise(offset + 30 * q + 4, n_ch, seed=53)
+    r0 = offset % q + 1 - q
+    assert (r0 < 0) == (offset % q != q - 1) and (a.shape[0] - r0) % q != 0          # A ends inside a block
+    want = run_host(decimate, b, q, h, offset)
+    fresh = run_device(decimate, b, q, h, offset, cuda_device, [64, b.shape[0] - 64], max_rows=64 + 30 * q)
+    d = decimate.device_decimator(n_ch, 64 + 30 * q, q, taps=h, offset=offset, device_index=0)
+    ad, bd = torch.from_numpy(a).to(cuda_device), torch.from_numpy(b).to(cuda_device)
+    out = torch.zeros((want.shape[0] + 8, n_ch), dtype=torch.complex64, device=cuda_device)
+    m = d.feed_device(ad, out)
+    assert d.rows_seen == a.shape[0] and d.rows_out == m == n_out(a.shape[0], offset, q)
+    torch.cuda.synchronize()                                      # the contract leaves the ordering to the caller
+    d.reset()
+    assert d.rows_seen == 0 and d.rows_out == 0 and d.next_rows(offset + 1) == 1
+    m = d.feed_device(bd[:64], out)
+    m += d.feed_device(bd[64:], out[m:])
+    torch.cuda.synchronize()
+    assert d.rows_seen == b.shape[0] and d.rows_out == m == want.shape[0] == n_out(b.shape[0], offset, q) >= 30
+    got = out[:m].cpu().numpy()
+    d.close()
+    assert same_bits(got, want) and same_bits(fresh, want)
+
+
+@pytest.mark.parametrize("kind", VALUE_KINDS)
+def test_values_device_twin_and_model(decimate, cuda_device, kind):
+    """Subnormal products and sums (the device keeps them, as std::fmaf does), rows of -0 (every output +0: a chunk sum
+    starts at +0), and chunk sums that overflow to +Inf and -Inf, which the combine adds to NaN.  Device, twin and model
+    agree bit for bit, except that a NaN matches any NaN: x86 and the GPU give the NaN of an Inf - Inf different signs and
+    the contract fixes neither (same_values)."""
+    x, h, q, offset = values_case(kind)
+    model = contract_bits(x, q, h, offset)
+    check_values_model(kind, model)
+    twin = run_host(decimate, x, q, h, offset)
+    for cname in ("one", "sevens"):
+        got = run_device(decimate, x, q, h, offset, cuda_device, cuttings(x.shape[0], q)[cname])
+        assert same_values(got, twin) and same_values(got, model), (kind, cname)
+        check_values_model(kind, got)
+
+
+# ---- streams of more than 2^31 and 2^32 rows: one device buffer of 2^20 rows of period LONG_R, fed again and again ----
+LONG_N, LONG_R = 1 << 20, 1024
+
+
+def long_pattern():
+    return noise(LONG_R, 1, seed=19)
+
+
+def short_reference(decimate, q, h, offset):
+    """(rows, offset') of the host twin on a short stream of the same period: offset' = offset mod R q, enough rows for
+    R + F outputs whose windows lie inside the stream.
+    Why it may stand for the long stream: an output is a function of the T rows of its window alone (the chunks are cut
+    relative to the window's end and each chunk sum depends on its block's rows alone), provided the window does not
+    begin before the stream.  The stream has period R, so two windows that end a multiple of R rows apart hold the same
+    rows.  Output o ends on row o q + offset; with offset' = offset (mod R q) and o' = o (mod R) the ends differ by a
+    multiple of R (and for odd q, which is a unit mod R, by nothing else: all R phases are distinct)."""
+    T = h.shape[0]
+    F = (T + q - 1) // q
+    p = offset % (LONG_R * q)
+    rows = p + T + (LONG_R + F) * q
+    x = np.tile(long_pattern(), (rows // LONG_R + 1, 1))[:rows]
+    y = run_host(decimate, x, q, h, p)
+    lo = max(0, -(-(T - 1 - p) // q))                            # first output whose window lies inside the stream
+    assert y.shape[0] >= LONG_R + F + 1 and lo <= F and same_bits(y[lo:F + 1], y[lo + LONG_R:F + 1 + LONG_R])
+    return y, p
+
+
+def expected_rows(short, p, q, T, offset, o_first, count):
+    """Outputs o_first .. o_first + count - 1 of the long stream, out of the short reference."""
+    assert o_first * q + offset - (T - 1) >= 0                   # no window begins before the stream
+    o = np.arange(o_first, o_first + count, dtype=np.int64) % LONG_R
+    o = np.where(o * q + p < T - 1, o + LONG_R, o)
+    return short[o]
+
+
+def run_long(decimate, dev, q, h, offset, feeds, keep):
+    """`feeds` feeds of the one device buffer, nothing uploaded or read in the loop; the count of every feed against
+    n_out in Python integers.  feed index -> (first output, rows) for the feeds in `keep`; the seconds it took."""
+    import time
+    import torch
+    d = decimate.device_decimator(1, LONG_N, q, taps=h, offset=offset, device_index=0)
+    xd = torch.from_numpy(np.tile(long_pattern(), (LONG_N // LONG_R, 1))).to(dev)
+    scratch = torch.zeros((d.out_capacity, 1), dtype=torch.complex64, device=dev)
+    kept = {k: torch.zeros((d.out_capacity, 1), dtype=torch.complex64, device=dev) for k in keep}
+    torch.cuda.synchronize()
+    t0, total, first = time.perf_counter(), 0, {}
+    for k in range(feeds):
+        want = n_out(total + LONG_N, offset, q) - n_out(total, offset, q)
+        assert d.next_rows(LONG_N) == want, k
+        first[k] = (n_out(total, offset, q), want)
+        assert d.feed_device(xd, kept.get(k, scratch)) == want, k
+        total += LONG_N
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    assert d.rows_seen == total == feeds * LONG_N and d.rows_out == n_out(total, offset, q)
+    got = {k: (first[k][0], kept[k][:first[k][1]].cpu().numpy()) for k in keep}
+    d.close()
+    return got, seconds
+
+
+def test_rows_past_2_to_the_31(decimate, cuda_device):
+    """q = 7, T = 141 (F = 21), offset 70, 2 049 feeds: the first feed against the twin fed the same rows, the feed that
+    begins at stream row 2^31 (the last) against the short reference."""
+    q, offset, h = 7, 70, caller_taps(141)
+    got, seconds = run_long(decimate, cuda_device, q, h, offset, 2049, (0, 2048))
+    record_info(seconds, "seconds")
+    print(f"decim past 2^31: {seconds:.2f} s")
+    x = np.tile(long_pattern(), (LONG_N // LONG_R, 1))
+    o0, y0 = got[0]
+    assert o0 == 0 and same_bits(y0, run_host(decimate, x, q, h, offset))
+    short, p = short_reference(decimate, q, h, offset)
+    o1, y1 = got[2048]
+    assert o1 == n_out(1 << 31, offset, q) and y1.shape[0] >= LONG_N // q
+    assert same_bits(y1, expected_rows(short, p, q, 141, offset, o1, y1.shape[0]))
+
+
+def test_rows_and_outputs_past_2_to_the_32(decimate, cuda_device):
+    """q = 1, T = 5, offset 0, 4 097 feeds: blocks, outputs and rows are the same numbers and all pass 2^32 with the
+    last feed, which begins at stream row 2^32."""
+    q, offset, h = 1, 0, caller_taps(5)
+    got, seconds = run_long(decimate, cuda_device, q, h, offset, 4097, (0, 4096))
+    record_info(seconds, "seconds")
+    print(f"decim past 2^32: {seconds:.2f} s")
+    x = np.tile(long_pattern(), (LONG_N // LONG_R, 1))
+    assert got[0][0] == 0 and same_bits(got[0][1], run_host(decimate, x, q, h, offset))
+    short, p = short_reference(decimate, q, h, offset)
+    o1, y1 = got[4096]
+    assert o1 == 1 << 32 and y1.shape[0] == LONG_N
+    assert same_bits(y1, expected_rows(short, p, q, 5, offset, o1, LONG_N))
+
+
+def test_offset_at_its_bound(decimate, cuda_device):
+    """offset = 2^30, the accepted bound (2^30 + 1 is refused): 1 024 feeds emit nothing, the next reaches row
+    offset + 1 and emits the first outputs; it and the feed after it against the short reference."""
+    from gpu_sdr_amd import GsdrError
+    q, offset, h = 7, 1 << 30, caller_taps(141)
+    with pytest.raises(GsdrError, match=r"gsdr_decim_create: .*offset"):
+        decimate.device_decimator(1, LONG_N, q, taps=h, offset=offset + 1, device_index=0)
+    assert all(n_out(k * LONG_N, offset, q) == 0 for k in range(1025)) and n_out(1025 * LONG_N, offset, q) == (LONG_N - 1) // q + 1
+    got, seconds = run_long(decimate, cuda_device, q, h, offset, 1026, (1023, 1024, 1025))
+    record_info(seconds, "seconds")
+    print(f"decim offset 2^30: {seconds:.2f} s")
+    short, p = short_reference(decimate, q, h, offset)
+    assert p == offset % (LONG_R * q) == 4096 and got[1023][1].shape[0] == 0
+    (oa, ya), (ob, yb) = got[1024], got[1025]
+    assert oa == 0 and ob == ya.shape[0] == (LONG_N - 1) // q + 1 and yb.shape[0] >= LONG_N // q
+    assert same_bits(ya, expected_rows(short, p, q, 141, offset, oa, ya.shape[0]))
+    assert same_bits(yb, expected_rows(short, p, q, 141, offset, ob, yb.shape[0]))
 
 
 def test_handle_decimator_welch_chain(decimate, cuda_device):
