@@ -212,6 +212,20 @@ SIGNATURES = [
     ("gsdr_decim_rows_out", C.c_longlong, [_vp]),
     ("gsdr_decim_close", None, [_vp]),
     ("gsdr_decim_default_taps", C.c_int, [C.c_int, _fp]),
+    ("gsdr_sweep_create", _vp, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
+    ("gsdr_sweep_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_sweep_feed_host", C.c_int, [_vp, _vp, C.c_int]),
+    ("gsdr_sweep_read_device", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("gsdr_sweep_read", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("gsdr_sweep_read_host", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_sweep_slope", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_sweep_reset", C.c_int, [_vp, C.c_longlong]),
+    ("gsdr_sweep_rows", C.c_longlong, [_vp]),
+    ("gsdr_sweep_sweeps", C.c_longlong, [_vp]),
+    ("gsdr_sweep_point_rows", C.c_longlong, [_vp, C.c_longlong]),
+    ("gsdr_sweep_close", None, [_vp]),
+    ("gsdr_sweep_shape_for_chirp", C.c_int, [C.POINTER(ChirpParamC), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    ("gsdr_vna_axis", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong, C.c_double, C.POINTER(C.c_double)]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
@@ -219,6 +233,8 @@ MULTI_CHIRP_MAX = 16        # GSDR_MULTI_CHIRP_MAX
 TRIGGER_HOST = -2           # GSDR_TRIGGER_HOST
 WELCH_HOST = -2             # GSDR_WELCH_HOST
 DECIM_HOST = -2             # GSDR_DECIM_HOST
+SWEEP_HOST = -2             # GSDR_SWEEP_HOST
+SWEEP_MAX_FEED = 1 << 24    # GSDR_SWEEP_MAX_FEED
 
 
 class TriggerLevelC(C.Structure):
