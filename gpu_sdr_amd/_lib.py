@@ -226,6 +226,18 @@ SIGNATURES = [
     ("gsdr_sweep_close", None, [_vp]),
     ("gsdr_sweep_shape_for_chirp", C.c_int, [C.POINTER(ChirpParamC), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("gsdr_vna_axis", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong, C.c_double, C.POINTER(C.c_double)]),
+    ("gsdr_resmap_constants", C.c_int, [C.c_double] * 7 + [C.POINTER(C.c_double)]),
+    ("gsdr_resmap_create", _vp, [C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int]),
+    ("gsdr_resmap_set_offsets", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_resmap_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    ("gsdr_resmap_feed", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    ("gsdr_resmap_feed_host", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_resmap_n_out", C.c_int, [_vp]),
+    ("gsdr_resmap_kind", C.c_int, [_vp]),
+    ("gsdr_resmap_get_constants", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int]),
+    ("gsdr_resmap_get_offsets", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int]),
+    ("gsdr_resmap_get_channels", C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
+    ("gsdr_resmap_close", None, [_vp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
@@ -235,6 +247,8 @@ WELCH_HOST = -2             # GSDR_WELCH_HOST
 DECIM_HOST = -2             # GSDR_DECIM_HOST
 SWEEP_HOST = -2             # GSDR_SWEEP_HOST
 SWEEP_MAX_FEED = 1 << 24    # GSDR_SWEEP_MAX_FEED
+RESMAP_HOST = -2            # GSDR_RESMAP_HOST
+RESMAP_NCONST = 7           # GSDR_RESMAP_NCONST
 
 
 class TriggerLevelC(C.Structure):

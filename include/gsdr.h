@@ -878,6 +878,82 @@ void gsdr_sweep_close(gsdr_sweep *s);
 int gsdr_sweep_shape_for_chirp(const gsdr_chirp_param *cp, long long decim, long long *n_points, long long *group);
 int gsdr_vna_axis(double rate, double freq0, double chirp_f, double swipe_s, long long n_points, double rf, double *f);
 
+/* ---- resonator map on the device: demodulated I/Q to resonance-frequency shift and quality factor, behind demodulated
+ * rows (an extension: the reference's client does it on the host, per channel, after every timestream has crossed PCIe
+ * and TCP, ref: pyUSRP/USRP_noise.py:1070-1108, calculate_frequency_timestream; its frequency-noise entries,
+ * :1660-1667, are empty stubs) -----------------------------------------------------------------------------------------
+ * A resmap object sees FEEDS of 0 <= n_rows <= max_rows rows of n_ch complex64 each -- the [row][channel] layout every RX
+ * entry writes -- and emits the same number of rows of n_out complex64.  Output column k is computed from input column
+ * channels[k]: the list may select a subset, reorder and repeat; channels == NULL is the identity and requires
+ * n_out == n_ch.  Each sample is mapped on its own: the object carries no stream state except its offsets.
+ * Constants.  Each output column has, in double, n = (nr, ni) the cable term, g = (gr, gi) = 1/n, K = (kr, ki) = n/Qe,
+ *   hf0 = f0/2 in Hz and two offsets x0, y0 (0 until gsdr_resmap_set_offsets).  gsdr_resmap_constants derives
+ *   GSDR_RESMAP_NCONST = 7 doubles {nr, ni, gr, gi, kr, ki, hf0} on the host from the reference's fit tuple and the tone:
+ *   f_tone in Hz, f0 in MHz, A, phi, D, Qe = Qe_re + i Qe_im.  theta = 1e-6 D (f_tone - f0 1e6) + phi,
+ *   n = A (cos 2 pi theta, sin 2 pi theta), g = (nr, -ni) / (nr nr + ni ni),
+ *   K = (nr Qe_re + ni Qe_im, ni Qe_re - nr Qe_im) / (Qe_re Qe_re + Qe_im Qe_im), hf0 = f0 1e6 / 2, all in double as
+ *   written.  It is the only place they are computed: the device and the twin receive the same numbers.  -1, with
+ *   gsdr_last_error(NULL) = "gsdr_resmap_constants: " and the argument's name: a non-finite input, A <= 0, f0 <= 0,
+ *   Qe == 0 (named as Qe_re and Qe_im), constants NULL.
+ * Arithmetic.  One law, in double; sx, sy are the input sample promoted to double.  Every multiply that feeds an add is
+ *   an explicit fused multiply-add (so that no compiler's contraction can change the law); +, - and / are IEEE double
+ *   operations; every output is rounded once to float32.
+ *   GSDR_RESMAP_CAL, the calibrated S21 s/n (what diagnostic_VNA_noise plots):
+ *     zr = fma(sx, gr, -(sy gi)), zi = fma(sx, gi, sy gr); out = (fl32(zr - x0), fl32(zi - y0)).
+ *   GSDR_RESMAP_X_DQR and GSDR_RESMAP_X_QR, q = (1/Qe) / (1 - s/n) = K / (n - s):
+ *     wr = nr - sx, wi = ni - sy, m = fma(wr, wr, wi wi), a = fma(kr, wr, ki wi), b = fma(ki, wr, -(kr wi)),
+ *     qr = a / m, qi = b / m.  out.x = fl32(fma(hf0, qi, -x0)), the shift of the resonance frequency in Hz, in both;
+ *     out.y = fl32(qr - y0) in X_DQR, the inverse Qr (linear in dissipation: what a spectrum wants), and
+ *     out.y = fl32(m / a - y0) in X_QR, the reference's 1 / Re(q).
+ *   A sample equal to n gives what IEEE gives (0/0, m/0) and traps nothing.  An Inf or NaN in a sample reaches that
+ *   sample's output and no other.  The offsets stand in for the reference's "- np.mean(...)": a caller reads a mean
+ *   from the first feed or from the Welch object behind the map and sets it once; the subtraction then happens in
+ *   double, before the only rounding.
+ * gsdr_resmap_create: 1 <= n_ch <= 2^20, 1 <= max_rows <= 2^20, 1 <= n_out <= 2^20, channels NULL (n_out == n_ch) or
+ *   n_out entries in [0, n_ch), constants n_out x GSDR_RESMAP_NCONST finite doubles, kind one of the three,
+ *   device_index >= -1 as in gsdr_param_c or GSDR_RESMAP_HOST for a host-only object that touches no GPU.  Anything else
+ *   is refused before the device is touched: NULL, and gsdr_last_error(NULL) starts with "gsdr_resmap_create: " and
+ *   names the argument.  Everything gsdr_resmap_feed_device and gsdr_resmap_set_offsets need is allocated here; a failed
+ *   allocation is a refusal that states the MiB.
+ * gsdr_resmap_set_offsets: xy holds n_out x (x0, y0) doubles, all finite, and is copied before the call returns; NULL
+ *   sets zeros.  On a device object the new offsets are ordered on hip_stream: feeds enqueued on it before the call see
+ *   the old ones, feeds enqueued after it the new ones.  On a host object it is immediate.
+ * gsdr_resmap_feed_device: ONE launch on hip_stream (hipStream_t as void*): no allocation, no synchronisation, no
+ *   read-back; reads exactly rows_dev[0, n_rows n_ch), writes exactly out_dev[0, n_rows n_out); returns n_rows, or -1
+ *   with gsdr_last_error(NULL).  Pointers need 8-byte alignment only and may point anywhere into larger allocations.
+ *   n_rows == 0 is valid and touches no pointer; n_rows outside [0, max_rows]: -1.  out_dev == rows_dev is allowed
+ *   exactly when the channel list is the identity (NULL, or n_out == n_ch and channels[k] == k); any other overlap of
+ *   the two extents is refused.
+ * gsdr_resmap_feed: the same launch into a staging buffer of the object (max_rows n_out samples, allocated by the first
+ *   such call), then waits for hip_stream and copies to out_host.
+ * gsdr_resmap_feed_host: GSDR_RESMAP_HOST objects only (and the device feeds are refused on them): a BIT TWIN of the
+ *   device; rows and out may be the same buffer under the rule above.
+ * Getters: gsdr_resmap_n_out, gsdr_resmap_kind; gsdr_resmap_get_constants / _get_offsets / _get_channels copy
+ *   min(cap, n_out) columns (7 doubles, 2 doubles, 1 int each; the identity is written out) and return n_out.
+ * Stream order is the caller's, as for the trigger, Welch, decim and sweep objects: the object remembers no stream and
+ *   waits for none; rows_dev must stay unchanged until the feed that reads it has finished.  On a NULL object close is
+ *   a no-op, the getters return 0, the feeds and set_offsets return -1 with the reason. */
+#define GSDR_RESMAP_HOST (-2)
+#define GSDR_RESMAP_CAL 0
+#define GSDR_RESMAP_X_DQR 1
+#define GSDR_RESMAP_X_QR 2
+#define GSDR_RESMAP_NCONST 7
+typedef struct gsdr_resmap gsdr_resmap;
+int gsdr_resmap_constants(double f_tone, double f0, double A, double phi, double D, double Qe_re, double Qe_im,
+                          double *constants /* GSDR_RESMAP_NCONST */);
+gsdr_resmap *gsdr_resmap_create(int n_ch, int max_rows, int n_out, const int *channels /* n_out, or NULL */,
+                                const double *constants /* n_out x GSDR_RESMAP_NCONST */, int kind, int device_index);
+int gsdr_resmap_set_offsets(gsdr_resmap *r, const double *xy /* n_out x 2, or NULL */, void *hip_stream);
+int gsdr_resmap_feed_device(gsdr_resmap *r, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, void *hip_stream);
+int gsdr_resmap_feed(gsdr_resmap *r, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_host, void *hip_stream);
+int gsdr_resmap_feed_host(gsdr_resmap *r, const gsdr_c64 *rows, int n_rows, gsdr_c64 *out);
+int gsdr_resmap_n_out(const gsdr_resmap *r);
+int gsdr_resmap_kind(const gsdr_resmap *r);
+int gsdr_resmap_get_constants(const gsdr_resmap *r, double *constants, int cap);
+int gsdr_resmap_get_offsets(const gsdr_resmap *r, double *xy, int cap);
+int gsdr_resmap_get_channels(const gsdr_resmap *r, int *channels, int cap);
+void gsdr_resmap_close(gsdr_resmap *r);
+
 #ifdef __cplusplus
 }
 #endif
