@@ -1,6 +1,6 @@
 // decim.cpp -- the device part of a decim object (the contract: include/gsdr.h, "FIR decimation on the device"): what
 // it owns on the GPU and the sequencing of a feed.  Creation, the refusals of the arguments, the default taps and the
-// host twin are in host_logic.cpp, the kernels in decim_kernels.hip.
+// host twin are in host_logic.cpp, the kernels in decim_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is two launches on the caller's stream (one when it completes no output row) and no host synchronisation.
 // What the HOST has to know of the stream is only the number of rows fed: from it follow the blocks the feed touches,
@@ -13,11 +13,11 @@
 #include <vector>
 
 #include "decim_kernels.h"
-#include "host_util.h"
+#include "stage_dev.h"
 
 namespace gsdr {
 
-struct DecimDev {
+struct DecimDev : StageDev {
     DevBuf<float2> ring;                     // [ring_blocks][F][n_ch]
     DevBuf<float> taps;                      // [F q + kDecimTapsPad]: zeros, the taps, zeros (decim_kernels.h)
     DevBuf<float2> out;                      // [out_capacity][n_ch]: what gsdr_decim_feed copies from
@@ -25,24 +25,15 @@ struct DecimDev {
 
 }  // namespace gsdr
 
-using gsdr::create_error;
 using gsdr::DecimDev;
+using gsdr::refuse;
+using gsdr::result;
+using gsdr::set_device;
 
 namespace {
 
-int refuse(const char *entry, const std::string &what) {
-    create_error() = std::string(entry) + ": " + what;
-    return -1;
-}
-
-bool set_device(const gsdr_decim *d) { return d->device < 0 || hipSetDevice(d->device) == hipSuccess; }
-
 // nullptr or why a device entry cannot take this object
-const char *object_fault(const gsdr_decim *d) {
-    if (!d) return "null object";
-    if (d->device == GSDR_DECIM_HOST || !d->dev) return "a host object (GSDR_DECIM_HOST) takes gsdr_decim_feed_host";
-    return nullptr;
-}
+const char *object_fault(const gsdr_decim *d) { return gsdr::object_fault(d, "a host object (GSDR_DECIM_HOST) takes gsdr_decim_feed_host"); }
 
 // the launches of one feed on st; the rows emitted, or -1 with the reason noted.  n_rows >= 1, the arguments checked.
 int enqueue_feed(gsdr_decim *d, const char *me, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, hipStream_t st) {
@@ -59,7 +50,7 @@ int enqueue_feed(gsdr_decim *d, const char *me, const gsdr_c64 *rows_dev, int n_
     f.n_emit = (int)(o1 - o0);
     f.k_out = o0 + d->offset / d->q;
     const hipError_t e = gsdr::launch_decim_feed(f, st);
-    if (e != hipSuccess) return refuse(me, hipGetErrorString(e));
+    if (e != hipSuccess) return result(me, e);
     d->total += n_rows;
     return f.n_emit;
 }
@@ -69,32 +60,16 @@ int enqueue_feed(gsdr_decim *d, const char *me, const gsdr_c64 *rows_dev, int n_
 extern "C" {
 
 int gsdr_decim_dev_create_(gsdr_decim *d) {
-    const char *const me = "gsdr_decim_create";
-    if (d->device >= 0 && hipSetDevice(d->device) != hipSuccess) return refuse(me, "device_index: hipSetDevice failed (no such GPU?)");
     const size_t n_ch = (size_t)d->n_ch, F = (size_t)d->F, q = (size_t)d->q, T = (size_t)d->n_taps;
     const size_t ring = (size_t)d->ring_blocks * F * n_ch, out = (size_t)gsdr_decim_out_capacity(d) * n_ch;
     const size_t bytes = (ring + out) * sizeof(float2) + (F * q + (size_t)gsdr::kDecimTapsPad) * sizeof(float);
     const std::string asked = "(n_ch, max_rows, q, n_taps: " + std::to_string(bytes >> 20) + " MiB)";
     std::vector<float> padded(F * q + (size_t)gsdr::kDecimTapsPad, 0.f);
     std::copy(d->taps.begin(), d->taps.end(), padded.begin() + (std::ptrdiff_t)(F * q - T));
-    DecimDev *v = new DecimDev();
-    d->dev = v;
     // (the ring needs no clearing: a block's sums start at +0 with its first row)
-    const bool ok = v->ring.alloc(ring) == hipSuccess && v->out.alloc(out) == hipSuccess && v->taps.upload(padded) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete v;
-        d->dev = nullptr;
-        return refuse(me, "device allocation failed " + asked);
-    }
-    return 0;
-}
-
-void gsdr_decim_dev_close_(gsdr_decim *d) {
-    if (d->device >= 0) (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();                    // the owners order nothing (dev_owner.h)
-    delete static_cast<DecimDev *>(d->dev);
-    d->dev = nullptr;
+    return gsdr::create_dev<DecimDev>(d, "gsdr_decim_create", asked, [&](DecimDev &v) {
+        return v.ring.alloc(ring) == hipSuccess && v.out.alloc(out) == hipSuccess && v.taps.upload(padded) == hipSuccess;
+    });
 }
 
 int gsdr_decim_feed_device(gsdr_decim *d, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, void *hip_stream) {
@@ -120,10 +95,7 @@ int gsdr_decim_feed(gsdr_decim *d, const gsdr_c64 *rows_dev, int n_rows, gsdr_c6
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int emitted = enqueue_feed(d, me, rows_dev, n_rows, reinterpret_cast<gsdr_c64 *>((float2 *)v->out), st);
     if (emitted < 0) return -1;
-    hipError_t e = hipSuccess;
-    if (emitted > 0) e = hipMemcpyAsync(out_host, v->out, (size_t)emitted * (size_t)d->n_ch * sizeof(gsdr_c64), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? emitted : refuse(me, hipGetErrorString(e));
+    return result(me, gsdr::fetch(hipSuccess, st, {{out_host, v->out, (size_t)emitted * (size_t)d->n_ch * sizeof(gsdr_c64)}}), emitted);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // decim_state.h -- the FIR decimator (include/gsdr.h, "FIR decimation on the device") as host_logic.cpp and decim.cpp
 // share it.  host_logic.cpp owns creation, the refusals, the default taps, the count law and the host twin; decim.cpp
-// hangs the device part on `dev` through the hooks below.  No HIP here: host_logic.cpp is built alone by a host
+// hangs the device part on `dev` through the hook below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host
 // compiler (tests/test_decim_sanitizers.py), where the hooks are absent and only host objects exist.
 //
 // Blocks.  The contract's block B is the q rows that end on row B q + p.  Both sides count blocks from the one that
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/gsdr.h"
+#include "stage_state.h"
 
 struct gsdr_decim {
     int n_ch = 0, max_rows = 0, q = 0, n_taps = 0;
@@ -24,7 +25,7 @@ struct gsdr_decim {
     long long ring_blocks = 0;                // (max_rows - 1)/q + 2 + F
     std::vector<float> taps;
     std::vector<gsdr_c64> ring;               // host twin: [ring_blocks][F][n_ch]
-    void *dev = nullptr;                      // gsdr::DecimDev (decim.cpp)
+    gsdr::StageDev *dev = nullptr;            // gsdr::DecimDev (decim.cpp)
 };
 
 // output rows complete after `total` rows
@@ -38,7 +39,6 @@ extern "C" {
 // decim.cpp; weak in host_logic.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
 // after every bound has been checked.
 int gsdr_decim_dev_create_(gsdr_decim *d);
-void gsdr_decim_dev_close_(gsdr_decim *d);
 }
 
 #endif

@@ -1,7 +1,9 @@
-// host_logic.cpp -- the host-only pieces of the RX demodulation path:
-// window/tap generation, the integer carry state machines, the tone->bin map
-// and the chirp parameter derivation.  No HIP here; everything is callable on
-// a machine without a GPU (tests -m "not gpu").
+// host_logic.cpp -- everything of the library that needs no GPU.  First the host-only pieces of the RX and TX paths:
+// window/tap generation, the integer carry state machines, the tone->bin map, the chirp parameter derivation, the
+// plans the launchers ask, and the host forms of the sc16 conversions and the frame average.  Then, the larger part,
+// the five objects behind demodulated rows (trigger, welch, decim, sweep, resmap: the stages), one section each:
+// creation and its refusals, the bookkeeping and the host twin; what the sections share is in stage_state.h and just
+// above the first of them.  No HIP here; everything is callable on a machine without a GPU (tests -m "not gpu").
 //
 // "ref:" citations are relative to /root/reference.
 #include "../../include/gsdr.h"
@@ -20,13 +22,27 @@
 #include "decim_state.h"
 #include "pfb_plan.h"
 #include "resmap_state.h"
+#include "stage_state.h"
 #include "sweep_state.h"
 #include "trigger_state.h"
 #include "welch_state.h"
 
+extern "C" void gsdr_stage_dev_close_(int device, gsdr::StageDev *dev) __attribute__((weak));   // stage_dev.cpp
+
 namespace {
 // ref: headers/kernels.cuh:34 -- the reference's float pi literal.
 constexpr float kPiF = 3.14159265358979f;
+
+using gsdr::stage_device_fault;
+using gsdr::stage_refuse;
+
+// gsdr_X_close of every stage: the device part first (the hook waits for the device), then the object
+template <class Stage>
+void stage_close(Stage *s) {
+    if (!s) return;
+    if (s->dev && gsdr_stage_dev_close_) gsdr_stage_dev_close_(s->device, s->dev);
+    delete s;
+}
 }  // namespace
 
 extern "C" {
@@ -295,9 +311,7 @@ void gsdr_widen_sc16_host(const gsdr_sc16 *in, gsdr_c64 *out, long long n, float
 // Mean of k consecutive frames per channel on the host, the arithmetic of include/gsdr.h operation for operation: what
 // pfb_average_kernel (fft_kernels.hip) computes on the device, bit for bit.  Every sum and product is stored to a float
 // before it is used again, and the function is compiled without contraction, so no compiler fuses a product into a sum.
-// demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (this file without demod.cpp) has nobody to tell
-void gsdr_note_error_(const char *msg) __attribute__((weak));
-
+// (Its refusal goes where the stages' go: gsdr_note_error_, stage_state.h.)
 #if defined(__clang__)
 #define GSDR_NO_CONTRACT
 #elif defined(__GNUC__)
@@ -406,15 +420,8 @@ long long gsdr_narrow_sc16_host(const gsdr_c64 *in, gsdr_sc16 *out, long long n,
 // same bits.
 int gsdr_trigger_dev_create_(gsdr_trigger *t, const gsdr_trigger_level *levels) __attribute__((weak));
 int gsdr_trigger_dev_set_levels_(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream) __attribute__((weak));
-void gsdr_trigger_dev_close_(gsdr_trigger *t) __attribute__((weak));
 
 namespace {
-int trigger_refuse(const char *entry, const std::string &what) {
-    const std::string msg = std::string(entry) + ": " + what;
-    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
-    return -1;
-}
-
 GSDR_NO_CONTRACT
 inline gsdr_trigger_rec trigger_row_host(const gsdr_c64 *row, const gsdr_trigger_level *lv, int n_ch) {
 #if defined(__clang__)
@@ -444,7 +451,7 @@ inline gsdr_trigger_rec trigger_row_host(const gsdr_c64 *row, const gsdr_trigger
 gsdr_trigger *gsdr_trigger_create(int n_ch, int max_rows, int pre, int post, int holdoff, int max_events,
                                   const gsdr_trigger_level *levels, int device_index) {
     const char *const me = "gsdr_trigger_create";
-    const char *bad = nullptr;
+    std::string bad;
     if (n_ch < 1 || n_ch > (1 << 20)) bad = "n_ch must be in [1, 1048576]";
     else if (max_rows < 1 || max_rows > (1 << 20)) bad = "max_rows must be in [1, 1048576]";
     else if (pre < 0) bad = "pre must be >= 0";
@@ -453,15 +460,14 @@ gsdr_trigger *gsdr_trigger_create(int n_ch, int max_rows, int pre, int post, int
     else if (holdoff < 0 || holdoff > (1 << 30)) bad = "holdoff must be in [0, 1073741824]";
     else if (max_events < 1 || max_events > (1 << 20)) bad = "max_events must be in [1, 1048576]";
     else if (!levels) bad = "levels must not be NULL";
-    else if (device_index < GSDR_TRIGGER_HOST) bad = "device_index must be >= -1 or GSDR_TRIGGER_HOST";
-    else if (device_index != GSDR_TRIGGER_HOST && !gsdr_trigger_dev_create_) bad = "device_index: this build has host objects only (GSDR_TRIGGER_HOST)";
-    if (bad) {
-        trigger_refuse(me, bad);
+    else bad = stage_device_fault(device_index, "GSDR_TRIGGER_HOST", gsdr_trigger_dev_create_ != nullptr);
+    if (!bad.empty()) {
+        stage_refuse(me, bad);
         return nullptr;
     }
     gsdr_trigger *t = new (std::nothrow) gsdr_trigger();
     if (!t) {
-        trigger_refuse(me, "out of memory");
+        stage_refuse(me, "out of memory");
         return nullptr;
     }
     t->n_ch = n_ch, t->max_rows = max_rows, t->pre = pre, t->post = post, t->holdoff = holdoff, t->max_events = max_events;
@@ -480,21 +486,21 @@ gsdr_trigger *gsdr_trigger_create(int n_ch, int max_rows, int pre, int post, int
         t->trig.assign((size_t)(post - 1), 0);
     } catch (const std::bad_alloc &) {
         delete t;
-        trigger_refuse(me, "pre + post and n_ch: no host memory for the carried rows");
+        stage_refuse(me, "pre + post and n_ch: no host memory for the carried rows");
         return nullptr;
     }
     return t;
 }
 
 int gsdr_trigger_set_levels(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream) {
-    if (!t || !levels) return trigger_refuse("gsdr_trigger_set_levels", "null argument");
+    if (!t || !levels) return stage_refuse("gsdr_trigger_set_levels", "null argument");
     if (t->device != GSDR_TRIGGER_HOST) return gsdr_trigger_dev_set_levels_(t, levels, hip_stream);
     t->levels.assign(levels, levels + t->n_ch);
     return 0;
 }
 
 int gsdr_trigger_reset(gsdr_trigger *t) {
-    if (!t) return trigger_refuse("gsdr_trigger_reset", "null object");
+    if (!t) return stage_refuse("gsdr_trigger_reset", "null object");
     // the device path reads `total` on the host and takes nothing from the carry of a stream that has just begun
     t->total = 0;
     t->last_hit = -1;
@@ -505,22 +511,18 @@ int gsdr_trigger_reset(gsdr_trigger *t) {
 
 long long gsdr_trigger_rows(const gsdr_trigger *t) { return t ? t->total : 0; }
 
-void gsdr_trigger_close(gsdr_trigger *t) {
-    if (!t) return;
-    if (t->dev && gsdr_trigger_dev_close_) gsdr_trigger_dev_close_(t);
-    delete t;
-}
+void gsdr_trigger_close(gsdr_trigger *t) { stage_close(t); }
 
 int gsdr_trigger_feed_host(gsdr_trigger *t, const gsdr_c64 *rows, int n_rows, gsdr_trigger_event *events,
                            gsdr_c64 *snippets, int *n_dropped) {
     const char *const me = "gsdr_trigger_feed_host";
-    if (!t) return trigger_refuse(me, "null object");
+    if (!t) return stage_refuse(me, "null object");
     if (t->device != GSDR_TRIGGER_HOST)
-        return trigger_refuse(me, "a device object takes gsdr_trigger_feed or gsdr_trigger_feed_device");
-    if (n_rows < 0 || n_rows > t->max_rows) return trigger_refuse(me, "n_rows must be in [0, max_rows]");
+        return stage_refuse(me, "a device object takes gsdr_trigger_feed or gsdr_trigger_feed_device");
+    if (n_rows < 0 || n_rows > t->max_rows) return stage_refuse(me, "n_rows must be in [0, max_rows]");
     if (n_dropped) *n_dropped = 0;
     if (n_rows == 0) return 0;
-    if (!rows || !events || !snippets) return trigger_refuse(me, "null buffer");
+    if (!rows || !events || !snippets) return stage_refuse(me, "null buffer");
     const size_t n_ch = (size_t)t->n_ch, n = (size_t)n_rows;
     const size_t P = (size_t)(t->post - 1), K = (size_t)(t->pre + t->post - 1), S = (size_t)(t->pre + t->post);
     const long long R0 = t->total, base = R0 - (long long)P;     // window entry j is stream row base + j
@@ -530,7 +532,7 @@ int gsdr_trigger_feed_host(gsdr_trigger *t, const gsdr_c64 *rows, int n_rows, gs
         wrec.resize(P + n);
         wtrig.assign(P + n, 0);
     } catch (const std::bad_alloc &) {
-        return trigger_refuse(me, "out of memory");
+        return stage_refuse(me, "out of memory");
     }
     for (size_t j = 0; j < P; ++j) wrec[j] = t->recs[j], wtrig[j] = t->trig[j];
     for (size_t i = 0; i < n; ++i) {
@@ -579,15 +581,8 @@ int gsdr_trigger_feed_host(gsdr_trigger *t, const gsdr_c64 *rows, int n_rows, gs
 // the float32 pipeline of the contract; they agree with this to the float32 transform's error, not bit for bit.
 int gsdr_welch_dev_create_(gsdr_welch *w) __attribute__((weak));
 int gsdr_welch_dev_reset_(gsdr_welch *w) __attribute__((weak));
-void gsdr_welch_dev_close_(gsdr_welch *w) __attribute__((weak));
 
 namespace {
-int welch_refuse(const char *entry, const std::string &what) {
-    const std::string msg = std::string(entry) + ": " + what;
-    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
-    return -1;
-}
-
 int welch_count(long long n_seg) { return n_seg > INT_MAX ? INT_MAX : (int)n_seg; }
 
 // in-place radix-2 forward transform of N = 2 * tw.size() / 2 points; tw: (cos, -sin)(2 pi k / N), k < N / 2
@@ -658,22 +653,21 @@ void welch_segment_host(gsdr_welch *w, long long s, int c, std::vector<double> &
 
 gsdr_welch *gsdr_welch_create(int n_ch, int max_rows, int nperseg, int step, int detrend, const float *window, int device_index) {
     const char *const me = "gsdr_welch_create";
-    const char *bad = nullptr;
+    std::string bad;
     if (n_ch < 1 || n_ch > (1 << 20)) bad = "n_ch must be in [1, 1048576]";
     else if (max_rows < 1 || max_rows > (1 << 20)) bad = "max_rows must be in [1, 1048576]";
     else if (nperseg < 16 || nperseg > 8192 || (nperseg & (nperseg - 1))) bad = "nperseg must be a power of two in [16, 8192]";
     else if (step < nperseg / 8 || step > nperseg) bad = "step must be in [nperseg / 8, nperseg]";
     else if (detrend != GSDR_WELCH_DETREND_NONE && detrend != GSDR_WELCH_DETREND_CONSTANT && detrend != GSDR_WELCH_DETREND_LINEAR)
         bad = "detrend must be GSDR_WELCH_DETREND_NONE, _CONSTANT or _LINEAR";
-    else if (device_index < GSDR_WELCH_HOST) bad = "device_index must be >= -1 or GSDR_WELCH_HOST";
-    else if (device_index != GSDR_WELCH_HOST && !gsdr_welch_dev_create_) bad = "device_index: this build has host objects only (GSDR_WELCH_HOST)";
-    if (bad) {
-        welch_refuse(me, bad);
+    else bad = stage_device_fault(device_index, "GSDR_WELCH_HOST", gsdr_welch_dev_create_ != nullptr);
+    if (!bad.empty()) {
+        stage_refuse(me, bad);
         return nullptr;
     }
     gsdr_welch *w = new (std::nothrow) gsdr_welch();
     if (!w) {
-        welch_refuse(me, "out of memory");
+        stage_refuse(me, "out of memory");
         return nullptr;
     }
     w->n_ch = n_ch, w->max_rows = max_rows, w->nperseg = nperseg, w->step = step, w->detrend = detrend;
@@ -694,7 +688,7 @@ gsdr_welch *gsdr_welch_create(int n_ch, int max_rows, int nperseg, int step, int
         }
     } catch (const std::bad_alloc &) {
         delete w;
-        welch_refuse(me, "n_ch and nperseg: no host memory for the accumulators");
+        stage_refuse(me, "n_ch and nperseg: no host memory for the accumulators");
         return nullptr;
     }
     if (device_index != GSDR_WELCH_HOST && gsdr_welch_dev_create_(w) != 0) {       // has noted why
@@ -705,7 +699,7 @@ gsdr_welch *gsdr_welch_create(int n_ch, int max_rows, int nperseg, int step, int
 }
 
 int gsdr_welch_reset(gsdr_welch *w) {
-    if (!w) return welch_refuse("gsdr_welch_reset", "null object");
+    if (!w) return stage_refuse("gsdr_welch_reset", "null object");
     if (w->dev && gsdr_welch_dev_reset_ && gsdr_welch_dev_reset_(w) != 0) return -1;
     w->total = 0;
     w->pending.clear();
@@ -719,19 +713,15 @@ long long gsdr_welch_rows(const gsdr_welch *w) { return w ? w->total : 0; }
 
 long long gsdr_welch_segments(const gsdr_welch *w) { return w ? gsdr_welch_segments_of(w->total, w->nperseg, w->step) : 0; }
 
-void gsdr_welch_close(gsdr_welch *w) {
-    if (!w) return;
-    if (w->dev && gsdr_welch_dev_close_) gsdr_welch_dev_close_(w);
-    delete w;
-}
+void gsdr_welch_close(gsdr_welch *w) { stage_close(w); }
 
 int gsdr_welch_feed_host(gsdr_welch *w, const gsdr_c64 *rows, int n_rows) {
     const char *const me = "gsdr_welch_feed_host";
-    if (!w) return welch_refuse(me, "null object");
-    if (w->device != GSDR_WELCH_HOST) return welch_refuse(me, "a device object takes gsdr_welch_feed_device");
-    if (n_rows < 0 || n_rows > w->max_rows) return welch_refuse(me, "n_rows must be in [0, max_rows]");
+    if (!w) return stage_refuse(me, "null object");
+    if (w->device != GSDR_WELCH_HOST) return stage_refuse(me, "a device object takes gsdr_welch_feed_device");
+    if (n_rows < 0 || n_rows > w->max_rows) return stage_refuse(me, "n_rows must be in [0, max_rows]");
     if (n_rows == 0) return 0;
-    if (!rows) return welch_refuse(me, "null buffer: rows");
+    if (!rows) return stage_refuse(me, "null buffer: rows");
     const size_t n_ch = (size_t)w->n_ch, n = (size_t)n_rows;
     std::vector<double> re, im;
     try {
@@ -740,7 +730,7 @@ int gsdr_welch_feed_host(gsdr_welch *w, const gsdr_c64 *rows, int n_rows) {
         for (size_t i = 0; i < n * n_ch; ++i) w->pending[at + 2 * i] = (double)rows[i].x, w->pending[at + 2 * i + 1] = (double)rows[i].y;
         re.resize((size_t)w->nperseg), im.resize((size_t)w->nperseg);
     } catch (const std::bad_alloc &) {
-        return welch_refuse(me, "out of memory");
+        return stage_refuse(me, "out of memory");
     }
     const long long s0 = gsdr_welch_segments_of(w->total, w->nperseg, w->step);
     w->total += n_rows;
@@ -758,12 +748,12 @@ int gsdr_welch_feed_host(gsdr_welch *w, const gsdr_c64 *rows, int n_rows) {
 
 int gsdr_welch_read_host(gsdr_welch *w, int mode, const gsdr_c64 *gain, double fs, double *psd, double *mean) {
     const char *const me = "gsdr_welch_read_host";
-    if (!w) return welch_refuse(me, "null object");
-    if (w->device != GSDR_WELCH_HOST) return welch_refuse(me, "a device object takes gsdr_welch_read or gsdr_welch_read_device");
-    if (mode < GSDR_WELCH_RAW || mode > GSDR_WELCH_GAIN) return welch_refuse(me, "mode must be GSDR_WELCH_RAW, _ROTATE, _DBC or _GAIN");
-    if (!(fs > 0.0) || !std::isfinite(fs)) return welch_refuse(me, "fs must be finite and > 0");
-    if (mode == GSDR_WELCH_GAIN && !gain) return welch_refuse(me, "gain must not be NULL with GSDR_WELCH_GAIN");
-    if (!psd) return welch_refuse(me, "null buffer: psd");
+    if (!w) return stage_refuse(me, "null object");
+    if (w->device != GSDR_WELCH_HOST) return stage_refuse(me, "a device object takes gsdr_welch_read or gsdr_welch_read_device");
+    if (mode < GSDR_WELCH_RAW || mode > GSDR_WELCH_GAIN) return stage_refuse(me, "mode must be GSDR_WELCH_RAW, _ROTATE, _DBC or _GAIN");
+    if (!(fs > 0.0) || !std::isfinite(fs)) return stage_refuse(me, "fs must be finite and > 0");
+    if (mode == GSDR_WELCH_GAIN && !gain) return stage_refuse(me, "gain must not be NULL with GSDR_WELCH_GAIN");
+    if (!psd) return stage_refuse(me, "null buffer: psd");
     const long long n_seg = gsdr_welch_segments_of(w->total, w->nperseg, w->step);
     if (n_seg == 0) return 0;
     const int N = w->nperseg, K1 = N / 2 + 1;
@@ -796,15 +786,8 @@ int gsdr_welch_read_host(gsdr_welch *w, int mode, const gsdr_c64 *gain, double f
 // fused multiply-adds and every addition is the one decim_partial_kernel / decim_combine_kernel (decim_kernels.hip)
 // make, so the bits are the same.
 int gsdr_decim_dev_create_(gsdr_decim *d) __attribute__((weak));
-void gsdr_decim_dev_close_(gsdr_decim *d) __attribute__((weak));
 
 namespace {
-int decim_refuse(const char *entry, const std::string &what) {
-    const std::string msg = std::string(entry) + ": " + what;
-    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
-    return -1;
-}
-
 // output row of block k (complete) out of the ring: the chunk sums oldest first
 GSDR_NO_CONTRACT
 void decim_emit_host(const gsdr_decim *d, long long k, gsdr_c64 *out) {
@@ -849,7 +832,7 @@ int gsdr_decim_default_taps(int q, float *w) {
 
 gsdr_decim *gsdr_decim_create(int n_ch, int max_rows, int q, int n_taps, const float *taps, long long offset, int device_index) {
     const char *const me = "gsdr_decim_create";
-    const char *bad = nullptr;
+    std::string bad;
     if (n_ch < 1 || n_ch > (1 << 20)) bad = "n_ch must be in [1, 1048576]";
     else if (max_rows < 1 || max_rows > (1 << 20)) bad = "max_rows must be in [1, 1048576]";
     else if (q < 1 || q > 4096) bad = "q must be in [1, 4096]";
@@ -857,21 +840,20 @@ gsdr_decim *gsdr_decim_create(int n_ch, int max_rows, int q, int n_taps, const f
     else if (!taps && q < 2) bad = "q must be >= 2 for the default taps (taps == NULL)";
     else if (taps && (n_taps < 1 || n_taps > 64 * q)) bad = "n_taps must be in [1, 64 q]";
     else if (offset < 0 || offset > (1LL << 30)) bad = "offset must be in [0, 1073741824]";
-    else if (device_index < GSDR_DECIM_HOST) bad = "device_index must be >= -1 or GSDR_DECIM_HOST";
-    else if (device_index != GSDR_DECIM_HOST && !gsdr_decim_dev_create_) bad = "device_index: this build has host objects only (GSDR_DECIM_HOST)";
-    if (!bad && taps)
+    else bad = stage_device_fault(device_index, "GSDR_DECIM_HOST", gsdr_decim_dev_create_ != nullptr);
+    if (bad.empty() && taps)
         for (int t = 0; t < n_taps; ++t)
             if (!std::isfinite(taps[t])) {
                 bad = "taps must all be finite";
                 break;
             }
-    if (bad) {
-        decim_refuse(me, bad);
+    if (!bad.empty()) {
+        stage_refuse(me, bad);
         return nullptr;
     }
     gsdr_decim *d = new (std::nothrow) gsdr_decim();
     if (!d) {
-        decim_refuse(me, "out of memory");
+        stage_refuse(me, "out of memory");
         return nullptr;
     }
     const int T = taps ? n_taps : 20 * q + 1;
@@ -889,7 +871,7 @@ gsdr_decim *gsdr_decim_create(int n_ch, int max_rows, int q, int n_taps, const f
         }
     } catch (const std::bad_alloc &) {
         delete d;
-        decim_refuse(me, "n_ch, max_rows, q and n_taps: no host memory for the carried chunk sums (" + std::to_string(ring_bytes >> 20) + " MiB)");
+        stage_refuse(me, "n_ch, max_rows, q and n_taps: no host memory for the carried chunk sums (" + std::to_string(ring_bytes >> 20) + " MiB)");
         return nullptr;
     }
     if (device_index != GSDR_DECIM_HOST && gsdr_decim_dev_create_(d) != 0) {       // has noted why
@@ -901,7 +883,7 @@ gsdr_decim *gsdr_decim_create(int n_ch, int max_rows, int q, int n_taps, const f
 
 int gsdr_decim_next_rows(const gsdr_decim *d, int n_rows) {
     if (!d) return 0;
-    if (n_rows < 0 || n_rows > d->max_rows) return decim_refuse("gsdr_decim_next_rows", "n_rows must be in [0, max_rows]");
+    if (n_rows < 0 || n_rows > d->max_rows) return stage_refuse("gsdr_decim_next_rows", "n_rows must be in [0, max_rows]");
     return (int)(gsdr_decim_out_of(d->total + n_rows, d->offset, d->q) - gsdr_decim_out_of(d->total, d->offset, d->q));
 }
 
@@ -914,7 +896,7 @@ int gsdr_decim_get_taps(const gsdr_decim *d, float *w, int cap) {
 }
 
 int gsdr_decim_reset(gsdr_decim *d) {
-    if (!d) return decim_refuse("gsdr_decim_reset", "null object");
+    if (!d) return stage_refuse("gsdr_decim_reset", "null object");
     // the ring needs no clearing: a block's sums start at +0 with its first row, and no output reads a block before row 0
     d->total = 0;
     return 0;
@@ -924,21 +906,17 @@ long long gsdr_decim_rows(const gsdr_decim *d) { return d ? d->total : 0; }
 
 long long gsdr_decim_rows_out(const gsdr_decim *d) { return d ? gsdr_decim_out_of(d->total, d->offset, d->q) : 0; }
 
-void gsdr_decim_close(gsdr_decim *d) {
-    if (!d) return;
-    if (d->dev && gsdr_decim_dev_close_) gsdr_decim_dev_close_(d);
-    delete d;
-}
+void gsdr_decim_close(gsdr_decim *d) { stage_close(d); }
 
 int gsdr_decim_feed_host(gsdr_decim *d, const gsdr_c64 *rows, int n_rows, gsdr_c64 *out) {
     const char *const me = "gsdr_decim_feed_host";
-    if (!d) return decim_refuse(me, "null object");
-    if (d->device != GSDR_DECIM_HOST) return decim_refuse(me, "a device object takes gsdr_decim_feed or gsdr_decim_feed_device");
-    if (n_rows < 0 || n_rows > d->max_rows) return decim_refuse(me, "n_rows must be in [0, max_rows]");
+    if (!d) return stage_refuse(me, "null object");
+    if (d->device != GSDR_DECIM_HOST) return stage_refuse(me, "a device object takes gsdr_decim_feed or gsdr_decim_feed_device");
+    if (n_rows < 0 || n_rows > d->max_rows) return stage_refuse(me, "n_rows must be in [0, max_rows]");
     if (n_rows == 0) return 0;
-    if (!rows) return decim_refuse(me, "null buffer: rows");
+    if (!rows) return stage_refuse(me, "null buffer: rows");
     const int emitted = (int)(gsdr_decim_out_of(d->total + n_rows, d->offset, d->q) - gsdr_decim_out_of(d->total, d->offset, d->q));
-    if (emitted > 0 && !out) return decim_refuse(me, "null buffer: out");
+    if (emitted > 0 && !out) return stage_refuse(me, "null buffer: out");
     const size_t n_ch = (size_t)d->n_ch, F = (size_t)d->F;
     const long long q = d->q, r0 = gsdr_decim_r0(d->offset, d->q), shift = d->offset / q;
     const int T = d->n_taps;
@@ -971,17 +949,10 @@ int gsdr_decim_feed_host(gsdr_decim *d, const gsdr_c64 *rows, int n_rows, gsdr_c
 // The host twin walks the rows in stream order; every addition, the division, the fma of the variance and the block
 // order of the slope are the ones sweep_kernels.hip makes, so the bits are the same.
 int gsdr_sweep_dev_create_(gsdr_sweep *s) __attribute__((weak));
-void gsdr_sweep_dev_close_(gsdr_sweep *s) __attribute__((weak));
 int gsdr_sweep_dev_reset_(gsdr_sweep *s) __attribute__((weak));
 int gsdr_sweep_dev_slope_(gsdr_sweep *s, double *d_host, void *hip_stream) __attribute__((weak));
 
 namespace {
-int sweep_refuse(const char *entry, const std::string &what) {
-    const std::string msg = std::string(entry) + ": " + what;
-    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
-    return -1;
-}
-
 long long sweep_rows_of(const gsdr_sweep *s, long long p) {
     return gsdr_sweep_rows_of(gsdr_sweep_edge_of(s->first_row, s->n_points, s->group),
                               gsdr_sweep_edge_of(s->first_row + s->total, s->n_points, s->group), p, s->group);
@@ -1005,21 +976,20 @@ float sweep_var_host(double sum, double q, double n) {
 
 gsdr_sweep *gsdr_sweep_create(int n_ch, long long n_points, long long group, long long first_row, int device_index) {
     const char *const me = "gsdr_sweep_create";
-    const char *bad = nullptr;
+    std::string bad;
     if (n_ch < 1 || n_ch > (1 << 20)) bad = "n_ch must be in [1, 1048576]";
     else if (n_points < 1 || n_points > (1LL << 24)) bad = "n_points must be in [1, 16777216]";
     else if (n_points * (long long)n_ch > (1LL << 25)) bad = "n_points * n_ch must be <= 33554432 (32 bytes each)";
     else if (group < 1 || group > (1LL << 30)) bad = "group must be in [1, 1073741824]";
     else if (first_row < 0 || first_row > (1LL << 62)) bad = "first_row must be in [0, 2^62]";
-    else if (device_index < GSDR_SWEEP_HOST) bad = "device_index must be >= -1 or GSDR_SWEEP_HOST";
-    else if (device_index != GSDR_SWEEP_HOST && !gsdr_sweep_dev_create_) bad = "device_index: this build has host objects only (GSDR_SWEEP_HOST)";
-    if (bad) {
-        sweep_refuse(me, bad);
+    else bad = stage_device_fault(device_index, "GSDR_SWEEP_HOST", gsdr_sweep_dev_create_ != nullptr);
+    if (!bad.empty()) {
+        stage_refuse(me, bad);
         return nullptr;
     }
     gsdr_sweep *s = new (std::nothrow) gsdr_sweep();
     if (!s) {
-        sweep_refuse(me, "out of memory");
+        stage_refuse(me, "out of memory");
         return nullptr;
     }
     s->n_ch = n_ch, s->n_points = n_points, s->group = group, s->first_row = first_row, s->device = device_index;
@@ -1029,7 +999,7 @@ gsdr_sweep *gsdr_sweep_create(int n_ch, long long n_points, long long group, lon
             s->acc.assign(cells * 4, 0.0);
         } catch (const std::bad_alloc &) {
             delete s;
-            sweep_refuse(me, "n_ch and n_points: no host memory for the accumulators (" + std::to_string((cells * 32) >> 20) + " MiB)");
+            stage_refuse(me, "n_ch and n_points: no host memory for the accumulators (" + std::to_string((cells * 32) >> 20) + " MiB)");
             return nullptr;
         }
     } else if (gsdr_sweep_dev_create_(s) != 0) {                   // has noted why
@@ -1039,16 +1009,12 @@ gsdr_sweep *gsdr_sweep_create(int n_ch, long long n_points, long long group, lon
     return s;
 }
 
-void gsdr_sweep_close(gsdr_sweep *s) {
-    if (!s) return;
-    if (s->dev && gsdr_sweep_dev_close_) gsdr_sweep_dev_close_(s);
-    delete s;
-}
+void gsdr_sweep_close(gsdr_sweep *s) { stage_close(s); }
 
 int gsdr_sweep_reset(gsdr_sweep *s, long long first_row) {
     const char *const me = "gsdr_sweep_reset";
-    if (!s) return sweep_refuse(me, "null object");
-    if (first_row < 0 || first_row > (1LL << 62)) return sweep_refuse(me, "first_row must be in [0, 2^62]");
+    if (!s) return stage_refuse(me, "null object");
+    if (first_row < 0 || first_row > (1LL << 62)) return stage_refuse(me, "first_row must be in [0, 2^62]");
     if (s->dev) {
         if (!gsdr_sweep_dev_reset_ || gsdr_sweep_dev_reset_(s) != 0) return -1;      // has noted why
     } else {
@@ -1072,12 +1038,12 @@ int gsdr_sweep_feed_host(gsdr_sweep *s, const gsdr_c64 *rows, int n_rows) {
 #pragma clang fp contract(off)
 #endif
     const char *const me = "gsdr_sweep_feed_host";
-    if (!s) return sweep_refuse(me, "null object");
-    if (s->device != GSDR_SWEEP_HOST) return sweep_refuse(me, "a device object takes gsdr_sweep_feed_device");
-    if (n_rows < 0 || n_rows > GSDR_SWEEP_MAX_FEED) return sweep_refuse(me, "n_rows must be in [0, 16777216]");
+    if (!s) return stage_refuse(me, "null object");
+    if (s->device != GSDR_SWEEP_HOST) return stage_refuse(me, "a device object takes gsdr_sweep_feed_device");
+    if (n_rows < 0 || n_rows > GSDR_SWEEP_MAX_FEED) return stage_refuse(me, "n_rows must be in [0, 16777216]");
     if (n_rows == 0) return 0;
-    if (s->total > GSDR_SWEEP_MAX_ROWS - n_rows) return sweep_refuse(me, "n_rows: the stream would pass 2^61 rows");
-    if (!rows) return sweep_refuse(me, "null buffer: rows");
+    if (s->total > GSDR_SWEEP_MAX_ROWS - n_rows) return stage_refuse(me, "n_rows: the stream would pass 2^61 rows");
+    if (!rows) return stage_refuse(me, "null buffer: rows");
     const size_t n_ch = (size_t)s->n_ch;
     const long long R = s->first_row + s->total;
     long long p = (R / s->group) % s->n_points, in = R % s->group;          // the point of the row and its place in the group
@@ -1107,9 +1073,9 @@ int gsdr_sweep_read_host(gsdr_sweep *s, gsdr_c64 *mean, gsdr_c64 *var) {
 #pragma clang fp contract(off)
 #endif
     const char *const me = "gsdr_sweep_read_host";
-    if (!s) return sweep_refuse(me, "null object");
-    if (s->device != GSDR_SWEEP_HOST) return sweep_refuse(me, "a device object takes gsdr_sweep_read or gsdr_sweep_read_device");
-    if (!mean) return sweep_refuse(me, "null buffer: mean");
+    if (!s) return stage_refuse(me, "null object");
+    if (s->device != GSDR_SWEEP_HOST) return stage_refuse(me, "a device object takes gsdr_sweep_read or gsdr_sweep_read_device");
+    if (!mean) return stage_refuse(me, "null buffer: mean");
     const gsdr_sweep_edge ea = gsdr_sweep_edge_of(s->first_row, s->n_points, s->group),
                           eb = gsdr_sweep_edge_of(s->first_row + s->total, s->n_points, s->group);
     const size_t n_ch = (size_t)s->n_ch;
@@ -1137,9 +1103,9 @@ int gsdr_sweep_slope(gsdr_sweep *s, double *d_host, void *hip_stream) {
 #pragma clang fp contract(off)
 #endif
     const char *const me = "gsdr_sweep_slope";
-    if (!s) return sweep_refuse(me, "null object");
-    if (!d_host) return sweep_refuse(me, "null buffer: d_host");
-    if (s->dev) return gsdr_sweep_dev_slope_ ? gsdr_sweep_dev_slope_(s, d_host, hip_stream) : sweep_refuse(me, "no device part in this build");
+    if (!s) return stage_refuse(me, "null object");
+    if (!d_host) return stage_refuse(me, "null buffer: d_host");
+    if (s->dev) return gsdr_sweep_dev_slope_ ? gsdr_sweep_dev_slope_(s, d_host, hip_stream) : stage_refuse(me, "no device part in this build");
     const long long terms = s->n_points - 1, blocks = gsdr_sweep_slope_blocks(s->n_points);
     for (int c = 0; c < s->n_ch; ++c) {
         double sx = 0.0, sy = 0.0;
@@ -1167,19 +1133,19 @@ int gsdr_sweep_slope(gsdr_sweep *s, double *d_host, void *hip_stream) {
 
 int gsdr_sweep_shape_for_chirp(const gsdr_chirp_param *cp, long long decim, long long *n_points, long long *group) {
     const char *const me = "gsdr_sweep_shape_for_chirp";
-    if (!cp || !n_points || !group) return sweep_refuse(me, "null pointer");
-    if (decim < 0) return sweep_refuse(me, "decim must be >= 0");
-    if (cp->num_steps < 1 || cp->length < 1 || cp->num_steps > (1ULL << 62) / cp->length) return sweep_refuse(me, "cp: num_steps and length must be >= 1, their product <= 2^62");
+    if (!cp || !n_points || !group) return stage_refuse(me, "null pointer");
+    if (decim < 0) return stage_refuse(me, "decim must be >= 0");
+    if (cp->num_steps < 1 || cp->length < 1 || cp->num_steps > (1ULL << 62) / cp->length) return stage_refuse(me, "cp: num_steps and length must be >= 1, their product <= 2^62");
     long long np = 0, g = 0;
     if (decim == 0) {
-        if (cp->num_steps > (1ULL << 24) || cp->length > (1ULL << 30)) return sweep_refuse(me, "cp: num_steps > 2^24 or length > 2^30 (the limits of gsdr_sweep_create)");
+        if (cp->num_steps > (1ULL << 24) || cp->length > (1ULL << 30)) return stage_refuse(me, "cp: num_steps > 2^24 or length > 2^30 (the limits of gsdr_sweep_create)");
         np = (long long)cp->num_steps, g = (long long)cp->length;
     } else {
         const unsigned long long period = cp->num_steps * cp->length;
-        if ((unsigned long long)decim > period / cp->length) return sweep_refuse(me, "decim: a row of length * decim samples is longer than the period");
+        if ((unsigned long long)decim > period / cp->length) return stage_refuse(me, "decim: a row of length * decim samples is longer than the period");
         const unsigned long long ppt = cp->length * (unsigned long long)decim;
-        if (period % ppt != 0) return sweep_refuse(me, "decim: length * decim does not divide the period num_steps * length, the points do not repeat from sweep to sweep");
-        if (period / ppt > (1ULL << 24)) return sweep_refuse(me, "cp, decim: more than 2^24 points");
+        if (period % ppt != 0) return stage_refuse(me, "decim: length * decim does not divide the period num_steps * length, the points do not repeat from sweep to sweep");
+        if (period / ppt > (1ULL << 24)) return stage_refuse(me, "cp, decim: more than 2^24 points");
         np = (long long)(period / ppt), g = 1;
     }
     *n_points = np, *group = g;
@@ -1192,10 +1158,10 @@ int gsdr_vna_axis(double rate, double freq0, double chirp_f, double swipe_s, lon
 #pragma clang fp contract(off)
 #endif
     const char *const me = "gsdr_vna_axis";
-    if (!f) return sweep_refuse(me, "null buffer: f");
-    if (!(swipe_s >= 2.0)) return sweep_refuse(me, "swipe_s must be >= 2");
-    if (n_points < 1) return sweep_refuse(me, "n_points must be >= 1");
-    if (!(rate > 0.0)) return sweep_refuse(me, "rate must be > 0");
+    if (!f) return stage_refuse(me, "null buffer: f");
+    if (!(swipe_s >= 2.0)) return stage_refuse(me, "swipe_s must be >= 2");
+    if (n_points < 1) return stage_refuse(me, "n_points must be >= 1");
+    if (!(rate > 0.0)) return stage_refuse(me, "rate must be > 0");
     const double two32m1 = 4294967295.0;
     const double df = std::trunc(two32m1 * (chirp_f - freq0) / (swipe_s - 1.0) / rate);
     const double stop = freq0 + df * (swipe_s - 1.0) * rate / two32m1;
@@ -1214,16 +1180,7 @@ int gsdr_vna_axis(double rate, double freq0, double chirp_f, double swipe_s, lon
 // the device"; the per-sample law: gsdr_resmap_sample, resmap_state.h) --------------------------------------------------
 // The twin calls the function resmap_kernel (resmap_kernels.hip) calls, on the same tables: the bits are the same.
 int gsdr_resmap_dev_create_(gsdr_resmap *r) __attribute__((weak));
-void gsdr_resmap_dev_close_(gsdr_resmap *r) __attribute__((weak));
 int gsdr_resmap_dev_set_offsets_(gsdr_resmap *r, void *hip_stream) __attribute__((weak));
-
-namespace {
-int resmap_refuse(const char *entry, const std::string &what) {
-    const std::string msg = std::string(entry) + ": " + what;
-    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
-    return -1;
-}
-}  // namespace
 
 GSDR_NO_CONTRACT
 int gsdr_resmap_constants(double f_tone, double f0, double A, double phi, double D, double Qe_re, double Qe_im, double *constants) {
@@ -1241,7 +1198,7 @@ int gsdr_resmap_constants(double f_tone, double f0, double A, double phi, double
     else if (!std::isfinite(Qe_im)) bad = "Qe_im must be finite";
     else if (Qe_re == 0.0 && Qe_im == 0.0) bad = "Qe_re and Qe_im: Qe must not be 0";
     else if (!constants) bad = "constants must not be NULL";
-    if (bad) return resmap_refuse(me, bad);
+    if (bad) return stage_refuse(me, bad);
     const double f0_hz = f0 * 1e6;
     const double df = f_tone - f0_hz;
     const double slope = 1e-6 * D;
@@ -1267,34 +1224,33 @@ int gsdr_resmap_constants(double f_tone, double f0, double A, double phi, double
 
 gsdr_resmap *gsdr_resmap_create(int n_ch, int max_rows, int n_out, const int *channels, const double *constants, int kind, int device_index) {
     const char *const me = "gsdr_resmap_create";
-    const char *bad = nullptr;
+    std::string bad;
     if (n_ch < 1 || n_ch > (1 << 20)) bad = "n_ch must be in [1, 1048576]";
     else if (max_rows < 1 || max_rows > (1 << 20)) bad = "max_rows must be in [1, 1048576]";
     else if (n_out < 1 || n_out > (1 << 20)) bad = "n_out must be in [1, 1048576]";
     else if (!channels && n_out != n_ch) bad = "channels must not be NULL with n_out != n_ch (NULL is the identity)";
     else if (!constants) bad = "constants must not be NULL";
     else if (kind != GSDR_RESMAP_CAL && kind != GSDR_RESMAP_X_DQR && kind != GSDR_RESMAP_X_QR) bad = "kind must be GSDR_RESMAP_CAL, GSDR_RESMAP_X_DQR or GSDR_RESMAP_X_QR";
-    else if (device_index < GSDR_RESMAP_HOST) bad = "device_index must be >= -1 or GSDR_RESMAP_HOST";
-    else if (device_index != GSDR_RESMAP_HOST && !gsdr_resmap_dev_create_) bad = "device_index: this build has host objects only (GSDR_RESMAP_HOST)";
-    if (!bad && channels)
+    else bad = stage_device_fault(device_index, "GSDR_RESMAP_HOST", gsdr_resmap_dev_create_ != nullptr);
+    if (bad.empty() && channels)
         for (int k = 0; k < n_out; ++k)
             if (channels[k] < 0 || channels[k] >= n_ch) {
                 bad = "channels must all be in [0, n_ch)";
                 break;
             }
-    if (!bad)
+    if (bad.empty())
         for (size_t i = 0; i < (size_t)n_out * GSDR_RESMAP_NCONST; ++i)
             if (!std::isfinite(constants[i])) {
                 bad = "constants must all be finite";
                 break;
             }
-    if (bad) {
-        resmap_refuse(me, bad);
+    if (!bad.empty()) {
+        stage_refuse(me, bad);
         return nullptr;
     }
     gsdr_resmap *r = new (std::nothrow) gsdr_resmap();
     if (!r) {
-        resmap_refuse(me, "out of memory");
+        stage_refuse(me, "out of memory");
         return nullptr;
     }
     r->n_ch = n_ch, r->max_rows = max_rows, r->n_out = n_out, r->kind = kind, r->device = device_index;
@@ -1304,7 +1260,7 @@ gsdr_resmap *gsdr_resmap_create(int n_ch, int max_rows, int n_out, const int *ch
         r->offsets.assign(2 * (size_t)n_out, 0.0);
     } catch (const std::bad_alloc &) {
         delete r;
-        resmap_refuse(me, "n_out: no host memory for the tables (" + std::to_string(((size_t)n_out * 84) >> 20) + " MiB)");
+        stage_refuse(me, "n_out: no host memory for the tables (" + std::to_string(((size_t)n_out * 84) >> 20) + " MiB)");
         return nullptr;
     }
     r->identity = n_out == n_ch;
@@ -1321,22 +1277,18 @@ gsdr_resmap *gsdr_resmap_create(int n_ch, int max_rows, int n_out, const int *ch
     return r;
 }
 
-void gsdr_resmap_close(gsdr_resmap *r) {
-    if (!r) return;
-    if (r->dev && gsdr_resmap_dev_close_) gsdr_resmap_dev_close_(r);
-    delete r;
-}
+void gsdr_resmap_close(gsdr_resmap *r) { stage_close(r); }
 
 int gsdr_resmap_set_offsets(gsdr_resmap *r, const double *xy, void *hip_stream) {
     const char *const me = "gsdr_resmap_set_offsets";
-    if (!r) return resmap_refuse(me, "null object");
+    if (!r) return stage_refuse(me, "null object");
     if (xy)
         for (size_t i = 0; i < 2 * (size_t)r->n_out; ++i)
-            if (!std::isfinite(xy[i])) return resmap_refuse(me, "xy must all be finite");
+            if (!std::isfinite(xy[i])) return stage_refuse(me, "xy must all be finite");
     if (xy) std::copy(xy, xy + 2 * (size_t)r->n_out, r->offsets.begin());
     else std::fill(r->offsets.begin(), r->offsets.end(), 0.0);
     if (!r->dev) return 0;
-    return gsdr_resmap_dev_set_offsets_ ? gsdr_resmap_dev_set_offsets_(r, hip_stream) : resmap_refuse(me, "no device part in this build");
+    return gsdr_resmap_dev_set_offsets_ ? gsdr_resmap_dev_set_offsets_(r, hip_stream) : stage_refuse(me, "no device part in this build");
 }
 
 int gsdr_resmap_n_out(const gsdr_resmap *r) { return r ? r->n_out : 0; }
@@ -1367,17 +1319,17 @@ int gsdr_resmap_get_channels(const gsdr_resmap *r, int *channels, int cap) {
 
 int gsdr_resmap_feed_host(gsdr_resmap *r, const gsdr_c64 *rows, int n_rows, gsdr_c64 *out) {
     const char *const me = "gsdr_resmap_feed_host";
-    if (!r) return resmap_refuse(me, "null object");
-    if (r->device != GSDR_RESMAP_HOST) return resmap_refuse(me, "a device object takes gsdr_resmap_feed or gsdr_resmap_feed_device");
-    if (n_rows < 0 || n_rows > r->max_rows) return resmap_refuse(me, "n_rows must be in [0, max_rows]");
+    if (!r) return stage_refuse(me, "null object");
+    if (r->device != GSDR_RESMAP_HOST) return stage_refuse(me, "a device object takes gsdr_resmap_feed or gsdr_resmap_feed_device");
+    if (n_rows < 0 || n_rows > r->max_rows) return stage_refuse(me, "n_rows must be in [0, max_rows]");
     if (n_rows == 0) return 0;
-    if (!rows) return resmap_refuse(me, "null buffer: rows");
-    if (!out) return resmap_refuse(me, "null buffer: out");
+    if (!rows) return stage_refuse(me, "null buffer: rows");
+    if (!out) return stage_refuse(me, "null buffer: out");
     const size_t n_ch = (size_t)r->n_ch, n_out = (size_t)r->n_out;
     if (!(rows == out && r->identity)) {
         const uintptr_t a = reinterpret_cast<uintptr_t>(rows), b = reinterpret_cast<uintptr_t>(out);
         const uintptr_t na = (uintptr_t)n_rows * n_ch * sizeof(gsdr_c64), nb = (uintptr_t)n_rows * n_out * sizeof(gsdr_c64);
-        if (a < b + nb && b < a + na) return resmap_refuse(me, "out overlaps rows (out == rows is allowed with the identity channel list only)");
+        if (a < b + nb && b < a + na) return stage_refuse(me, "out overlaps rows (out == rows is allowed with the identity channel list only)");
     }
     for (size_t i = 0; i < (size_t)n_rows; ++i) {
         const gsdr_c64 *x = rows + i * n_ch;

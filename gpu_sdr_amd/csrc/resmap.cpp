@@ -1,6 +1,7 @@
 // resmap.cpp -- the device part of a resmap object (the contract: include/gsdr.h, "resonator map on the device"): what
 // it owns on the GPU, the one launch of a feed and the offsets' way to the device.  Creation, the refusals of the
-// arguments, gsdr_resmap_constants and the host twin are in host_logic.cpp, the kernel in resmap_kernels.hip.
+// arguments, gsdr_resmap_constants and the host twin are in host_logic.cpp, the kernel in resmap_kernels.hip, the
+// frame of every stage in stage_dev.h.
 //
 // The object carries no stream state: a feed needs the tables and the caller's two pointers, nothing is read back.
 //
@@ -11,8 +12,8 @@
 #include <cstring>
 #include <string>
 
-#include "host_util.h"
 #include "resmap_kernels.h"
+#include "stage_dev.h"
 
 namespace gsdr {
 
@@ -35,7 +36,7 @@ class PinnedDoubles {
     }
 };
 
-struct ResmapDev {
+struct ResmapDev : StageDev {
     DevBuf<gsdr_resmap_col> cols;            // [n_out]
     DevBuf<double2> offs;                    // [n_out]
     DevBuf<int> channels;                    // [n_out]; empty where the list is the identity
@@ -47,24 +48,15 @@ struct ResmapDev {
 
 }  // namespace gsdr
 
-using gsdr::create_error;
+using gsdr::refuse;
 using gsdr::ResmapDev;
+using gsdr::result;
+using gsdr::set_device;
 
 namespace {
 
-int refuse(const char *entry, const std::string &what) {
-    create_error() = std::string(entry) + ": " + what;
-    return -1;
-}
-
-bool set_device(const gsdr_resmap *r) { return r->device < 0 || hipSetDevice(r->device) == hipSuccess; }
-
 // nullptr or why a device entry cannot take this object
-const char *object_fault(const gsdr_resmap *r) {
-    if (!r) return "null object";
-    if (r->device == GSDR_RESMAP_HOST || !r->dev) return "a host object (GSDR_RESMAP_HOST) takes gsdr_resmap_feed_host";
-    return nullptr;
-}
+const char *object_fault(const gsdr_resmap *r) { return gsdr::object_fault(r, "a host object (GSDR_RESMAP_HOST) takes gsdr_resmap_feed_host"); }
 
 // the launch of one feed on st; n_rows, or -1 with the reason noted.  n_rows >= 1, the arguments checked.
 int enqueue_feed(gsdr_resmap *r, const char *me, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, hipStream_t st) {
@@ -75,8 +67,7 @@ int enqueue_feed(gsdr_resmap *r, const char *me, const gsdr_c64 *rows_dev, int n
     f.cols = v->cols, f.offs = v->offs;
     f.channels = r->identity ? nullptr : static_cast<const int *>(v->channels);
     f.n_rows = n_rows, f.n_ch = r->n_ch, f.n_out = r->n_out, f.kind = r->kind;
-    const hipError_t e = gsdr::launch_resmap_feed(f, st);
-    return e == hipSuccess ? n_rows : refuse(me, hipGetErrorString(e));
+    return result(me, gsdr::launch_resmap_feed(f, st), n_rows);
 }
 
 // nullptr, or what is wrong with the two extents of a feed of n_rows >= 1 rows
@@ -94,29 +85,13 @@ const char *extents_fault(const gsdr_resmap *r, const void *rows, int n_rows, co
 extern "C" {
 
 int gsdr_resmap_dev_create_(gsdr_resmap *r) {
-    const char *const me = "gsdr_resmap_create";
-    if (r->device >= 0 && hipSetDevice(r->device) != hipSuccess) return refuse(me, "device_index: hipSetDevice failed (no such GPU?)");
     const size_t n_out = (size_t)r->n_out;
     const size_t bytes = n_out * (sizeof(gsdr_resmap_col) + sizeof(double2) + (r->identity ? 0 : sizeof(int)));
-    ResmapDev *v = new ResmapDev();
-    r->dev = v;
-    const bool ok = v->cols.upload(r->cols) == hipSuccess && v->offs.alloc_zeroed(n_out) == hipSuccess &&
-                    (r->identity || v->channels.upload(r->channels) == hipSuccess) && v->pinned.alloc(2 * n_out) == hipSuccess &&
-                    hipEventCreateWithFlags(v->copied.out(), hipEventDisableTiming) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete v;
-        r->dev = nullptr;
-        return refuse(me, "device allocation failed (n_out: " + std::to_string(bytes >> 20) + " MiB of tables)");
-    }
-    return 0;
-}
-
-void gsdr_resmap_dev_close_(gsdr_resmap *r) {
-    if (r->device >= 0) (void)hipSetDevice(r->device);
-    (void)hipDeviceSynchronize();                    // the owners order nothing (dev_owner.h)
-    delete static_cast<ResmapDev *>(r->dev);
-    r->dev = nullptr;
+    return gsdr::create_dev<ResmapDev>(r, "gsdr_resmap_create", "(n_out: " + std::to_string(bytes >> 20) + " MiB of tables)", [&](ResmapDev &v) {
+        return v.cols.upload(r->cols) == hipSuccess && v.offs.alloc_zeroed(n_out) == hipSuccess &&
+               (r->identity || v.channels.upload(r->channels) == hipSuccess) && v.pinned.alloc(2 * n_out) == hipSuccess &&
+               hipEventCreateWithFlags(v.copied.out(), hipEventDisableTiming) == hipSuccess;
+    });
 }
 
 int gsdr_resmap_dev_set_offsets_(gsdr_resmap *r, void *hip_stream) {
@@ -132,7 +107,7 @@ int gsdr_resmap_dev_set_offsets_(gsdr_resmap *r, void *hip_stream) {
     }
     if (e == hipSuccess) e = hipEventRecord(v->copied, st);
     if (e == hipSuccess) v->in_flight = true;
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    return result(me, e);
 }
 
 int gsdr_resmap_feed_device(gsdr_resmap *r, const gsdr_c64 *rows_dev, int n_rows, gsdr_c64 *out_dev, void *hip_stream) {
@@ -158,15 +133,11 @@ int gsdr_resmap_feed(gsdr_resmap *r, const gsdr_c64 *rows_dev, int n_rows, gsdr_
     if (!set_device(r)) return refuse(me, "hipSetDevice failed");
     ResmapDev *v = static_cast<ResmapDev *>(r->dev);
     const size_t cells = (size_t)r->max_rows * (size_t)r->n_out;
-    if (!v->stage && v->stage.alloc(cells) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!gsdr::staging_ready(v->stage, cells))
         return refuse(me, "device allocation failed (the staging of a feed to the host, max_rows n_out: " + std::to_string((cells * sizeof(float2)) >> 20) + " MiB)");
-    }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (enqueue_feed(r, me, rows_dev, n_rows, reinterpret_cast<gsdr_c64 *>((float2 *)v->stage), st) < 0) return -1;
-    hipError_t e = hipMemcpyAsync(out_host, v->stage, (size_t)n_rows * (size_t)r->n_out * sizeof(gsdr_c64), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? n_rows : refuse(me, hipGetErrorString(e));
+    return result(me, gsdr::fetch(hipSuccess, st, {{out_host, v->stage, (size_t)n_rows * (size_t)r->n_out * sizeof(gsdr_c64)}}), n_rows);
 }
 
 }  // extern "C"

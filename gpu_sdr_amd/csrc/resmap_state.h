@@ -2,7 +2,7 @@
 // resmap_kernels.hip share it: the object, a column's constants as the tables hold them, and THE PER-SAMPLE LAW, one
 // inline host-and-device function that the kernel and the host twin both include -- there is one text of the
 // arithmetic.  host_logic.cpp owns creation, the refusals, gsdr_resmap_constants and the host twin; resmap.cpp hangs the
-// device part on `dev` through the hooks below.  No HIP here: host_logic.cpp is built alone by a host compiler
+// device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host compiler
 // (tests/test_resmap_sanitizers.py), where the hooks are absent and only host objects exist.
 #ifndef GSDR_RESMAP_STATE_H
 #define GSDR_RESMAP_STATE_H
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/gsdr.h"
+#include "stage_state.h"
 
 #if defined(__HIPCC__)
 #define GSDR_RESMAP_HD __host__ __device__ inline __attribute__((always_inline))
@@ -30,7 +31,7 @@ struct gsdr_resmap {
     std::vector<int> channels;                // [n_out], the identity written out
     std::vector<gsdr_resmap_col> cols;        // [n_out]
     std::vector<double> offsets;              // [n_out][x0, y0]: what set_offsets was given last
-    void *dev = nullptr;                      // gsdr::ResmapDev (resmap.cpp)
+    gsdr::StageDev *dev = nullptr;            // gsdr::ResmapDev (resmap.cpp)
 };
 
 // The law of include/gsdr.h, operation for operation.  No product here feeds a plain addition or subtraction: each is
@@ -75,7 +76,6 @@ extern "C" {
 // message noted; it is called after every bound has been checked.  _set_offsets_: r->offsets to the device, ordered on
 // the stream.
 int gsdr_resmap_dev_create_(gsdr_resmap *r);
-void gsdr_resmap_dev_close_(gsdr_resmap *r);
 int gsdr_resmap_dev_set_offsets_(gsdr_resmap *r, void *hip_stream);
 }
 

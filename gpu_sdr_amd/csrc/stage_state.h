@@ -1,0 +1,54 @@
+// stage_state.h -- what the five objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
+// gsdr_sweep_*, gsdr_resmap_*: the STAGES) share between host_logic.cpp and their device sources: the type of `dev`,
+// the one release hook, the host side's refusal and the device_index check of every create.  The X_state.h of each
+// stage includes it.  No HIP here: host_logic.cpp is built alone by a host compiler (tests/test_*_sanitizers.py), where
+// the hooks are absent and only host objects exist.
+#ifndef GSDR_STAGE_STATE_H
+#define GSDR_STAGE_STATE_H
+
+#include <string>
+
+#include "../../include/gsdr.h"
+
+static_assert(GSDR_TRIGGER_HOST == -2 && GSDR_WELCH_HOST == -2 && GSDR_DECIM_HOST == -2 && GSDR_SWEEP_HOST == -2 && GSDR_RESMAP_HOST == -2,
+              "every stage names its host twin by the same device_index");
+
+namespace gsdr {
+
+constexpr int kStageHost = -2;                // GSDR_X_HOST of every stage
+
+// What a stage owns on the GPU: X.cpp derives its XDev from this and hangs it on `dev` of the object.  The destructor is
+// all that host_logic.cpp and the release hook need of it.
+struct StageDev {
+    virtual ~StageDev() = default;
+};
+
+}  // namespace gsdr
+
+extern "C" {
+// demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (host_logic.cpp alone) has nobody to tell
+void gsdr_note_error_(const char *msg) __attribute__((weak));
+// stage_dev.cpp; weak in host_logic.cpp.  Waits for the device, then releases what `dev` owns.
+void gsdr_stage_dev_close_(int device, gsdr::StageDev *dev);
+}
+
+namespace gsdr {
+
+// The refusal of a host-side entry: notes "entry: what" for gsdr_last_error(NULL), returns -1.
+inline int stage_refuse(const char *entry, const std::string &what) {
+    const std::string msg = std::string(entry) + ": " + what;
+    if (gsdr_note_error_) gsdr_note_error_(msg.c_str());
+    return -1;
+}
+
+// The two device_index checks of every create: "" or the refusal.  host_name is the stage's GSDR_X_HOST as the caller
+// writes it; has_device_part is false in a build without X.cpp.
+inline std::string stage_device_fault(int device_index, const char *host_name, bool has_device_part) {
+    if (device_index < kStageHost) return std::string("device_index must be >= -1 or ") + host_name;
+    if (device_index != kStageHost && !has_device_part) return std::string("device_index: this build has host objects only (") + host_name + ")";
+    return std::string();
+}
+
+}  // namespace gsdr
+
+#endif

@@ -1,17 +1,18 @@
 // sweep.cpp -- the device part of a sweep object (the contract: include/gsdr.h, "VNA sweep accumulator on the device"):
 // what it owns on the GPU, the one launch of a feed, the reads and the slope.  Creation, the refusals of the arguments,
-// the counts and the host twin are in host_logic.cpp, the kernels in sweep_kernels.hip.
+// the counts and the host twin are in host_logic.cpp, the kernels in sweep_kernels.hip, the frame of every stage in
+// stage_dev.h.
 //
 // What the HOST has to know of the stream is only first_row and the number of rows fed: from them follow the points a
 // feed touches and every n[p].  Nothing is read back by a feed.
 #include <string>
 
-#include "host_util.h"
+#include "stage_dev.h"
 #include "sweep_kernels.h"
 
 namespace gsdr {
 
-struct SweepDev {
+struct SweepDev : StageDev {
     DevBuf<double> acc;                      // [n_points][n_ch][4]
     DevBuf<double2> blocks;                  // [slope blocks][n_ch]: scratch of the slope
     DevBuf<double2> d;                       // [n_ch]: the slope
@@ -20,23 +21,16 @@ struct SweepDev {
 
 }  // namespace gsdr
 
-using gsdr::create_error;
+using gsdr::refuse;
+using gsdr::result;
+using gsdr::set_device;
 using gsdr::SweepDev;
 
 namespace {
 
-int refuse(const char *entry, const std::string &what) {
-    create_error() = std::string(entry) + ": " + what;
-    return -1;
-}
-
-bool set_device(const gsdr_sweep *s) { return s->device < 0 || hipSetDevice(s->device) == hipSuccess; }
-
 // nullptr or why a device entry cannot take this object
 const char *object_fault(const gsdr_sweep *s) {
-    if (!s) return "null object";
-    if (s->device == GSDR_SWEEP_HOST || !s->dev) return "a host object (GSDR_SWEEP_HOST) takes gsdr_sweep_feed_host and gsdr_sweep_read_host";
-    return nullptr;
+    return gsdr::object_fault(s, "a host object (GSDR_SWEEP_HOST) takes gsdr_sweep_feed_host and gsdr_sweep_read_host");
 }
 
 gsdr::SweepRead read_of(const gsdr_sweep *s) {
@@ -53,38 +47,18 @@ gsdr::SweepRead read_of(const gsdr_sweep *s) {
 extern "C" {
 
 int gsdr_sweep_dev_create_(gsdr_sweep *s) {
-    const char *const me = "gsdr_sweep_create";
-    if (s->device >= 0 && hipSetDevice(s->device) != hipSuccess) return refuse(me, "device_index: hipSetDevice failed (no such GPU?)");
     const size_t cells = (size_t)s->n_points * (size_t)s->n_ch, nb = (size_t)gsdr_sweep_slope_blocks(s->n_points) * (size_t)s->n_ch;
     const size_t bytes = cells * 4 * sizeof(double) + (nb + (size_t)s->n_ch) * sizeof(double2);
-    SweepDev *v = new SweepDev();
-    s->dev = v;
-    const bool ok = v->acc.alloc_zeroed(cells * 4) == hipSuccess && v->blocks.alloc(nb) == hipSuccess && v->d.alloc((size_t)s->n_ch) == hipSuccess &&
-                    hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete v;
-        s->dev = nullptr;
-        return refuse(me, "device allocation failed (n_ch, n_points: " + std::to_string(bytes >> 20) + " MiB)");
-    }
-    return 0;
-}
-
-void gsdr_sweep_dev_close_(gsdr_sweep *s) {
-    if (s->device >= 0) (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();                    // the owners order nothing (dev_owner.h)
-    delete static_cast<SweepDev *>(s->dev);
-    s->dev = nullptr;
+    return gsdr::create_dev<SweepDev>(s, "gsdr_sweep_create", "(n_ch, n_points: " + std::to_string(bytes >> 20) + " MiB)", [&](SweepDev &v) {
+        return v.acc.alloc_zeroed(cells * 4) == hipSuccess && v.blocks.alloc(nb) == hipSuccess && v.d.alloc((size_t)s->n_ch) == hipSuccess;
+    });
 }
 
 int gsdr_sweep_dev_reset_(gsdr_sweep *s) {
     const char *const me = "gsdr_sweep_reset";
     if (!set_device(s)) return refuse(me, "hipSetDevice failed");
     SweepDev *v = static_cast<SweepDev *>(s->dev);
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemset(v->acc, 0, (size_t)s->n_points * (size_t)s->n_ch * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    return result(me, gsdr::zero_behind_all({{v->acc, (size_t)s->n_points * (size_t)s->n_ch * 4 * sizeof(double)}}));
 }
 
 int gsdr_sweep_dev_slope_(gsdr_sweep *s, double *d_host, void *hip_stream) {
@@ -92,10 +66,8 @@ int gsdr_sweep_dev_slope_(gsdr_sweep *s, double *d_host, void *hip_stream) {
     if (!set_device(s)) return refuse(me, "hipSetDevice failed");
     SweepDev *v = static_cast<SweepDev *>(s->dev);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    hipError_t e = gsdr::launch_sweep_slope(read_of(s), v->blocks, v->d, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_host, v->d, (size_t)s->n_ch * sizeof(double2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    const hipError_t e = gsdr::launch_sweep_slope(read_of(s), v->blocks, v->d, st);
+    return result(me, gsdr::fetch(e, st, {{d_host, v->d, (size_t)s->n_ch * sizeof(double2)}}));
 }
 
 int gsdr_sweep_feed_device(gsdr_sweep *s, const gsdr_c64 *rows_dev, int n_rows, void *hip_stream) {
@@ -112,7 +84,7 @@ int gsdr_sweep_feed_device(gsdr_sweep *s, const gsdr_c64 *rows_dev, int n_rows, 
     f.n = n_rows, f.n_ch = s->n_ch, f.n_points = s->n_points, f.group = s->group;
     f.row0 = s->first_row + s->total;
     const hipError_t e = gsdr::launch_sweep_feed(f, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return refuse(me, hipGetErrorString(e));
+    if (e != hipSuccess) return result(me, e);
     s->total += n_rows;
     return 0;
 }
@@ -124,7 +96,7 @@ int gsdr_sweep_read_device(gsdr_sweep *s, gsdr_c64 *mean_dev, gsdr_c64 *var_dev,
     if (!set_device(s)) return refuse(me, "hipSetDevice failed");
     const hipError_t e = gsdr::launch_sweep_read(read_of(s), reinterpret_cast<float2 *>(mean_dev), reinterpret_cast<float2 *>(var_dev),
                                                  static_cast<hipStream_t>(hip_stream));
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    return result(me, e);
 }
 
 int gsdr_sweep_read(gsdr_sweep *s, gsdr_c64 *mean_host, gsdr_c64 *var_host, void *hip_stream) {
@@ -134,17 +106,12 @@ int gsdr_sweep_read(gsdr_sweep *s, gsdr_c64 *mean_host, gsdr_c64 *var_host, void
     if (!set_device(s)) return refuse(me, "hipSetDevice failed");
     SweepDev *v = static_cast<SweepDev *>(s->dev);
     const size_t cells = (size_t)s->n_points * (size_t)s->n_ch;
-    if (!v->stage && v->stage.alloc(2 * cells) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!gsdr::staging_ready(v->stage, 2 * cells))
         return refuse(me, "device allocation failed (the staging of a read to the host: " + std::to_string((2 * cells * sizeof(float2)) >> 20) + " MiB)");
-    }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     float2 *mean = v->stage, *var = var_host ? mean + cells : nullptr;
-    hipError_t e = gsdr::launch_sweep_read(read_of(s), mean, var, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mean_host, mean, cells * sizeof(float2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && var) e = hipMemcpyAsync(var_host, var, cells * sizeof(float2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    const hipError_t e = gsdr::launch_sweep_read(read_of(s), mean, var, st);
+    return result(me, gsdr::fetch(e, st, {{mean_host, mean, cells * sizeof(float2)}, {var_host, var, cells * sizeof(float2)}}));
 }
 
 }  // extern "C"

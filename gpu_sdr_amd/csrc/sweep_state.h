@@ -1,6 +1,6 @@
 // sweep_state.h -- the VNA sweep accumulator (include/gsdr.h, "VNA sweep accumulator on the device") as host_logic.cpp,
 // sweep.cpp and sweep_kernels.hip share it: the closed forms of the fold.  host_logic.cpp owns creation, the refusals,
-// the counts and the host twin; sweep.cpp hangs the device part on `dev` through the hooks below.  No HIP here:
+// the counts and the host twin; sweep.cpp hangs the device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here:
 // host_logic.cpp is built alone by a host compiler (tests/test_sweep_sanitizers.py), where the hooks are absent and
 // only host objects exist.
 //
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/gsdr.h"
+#include "stage_state.h"
 
 #if defined(__HIPCC__)
 #define GSDR_SWEEP_HD __host__ __device__ inline
@@ -27,7 +28,7 @@ struct gsdr_sweep {
     long long total = 0;                      // rows fed since creation / reset
     int device = GSDR_SWEEP_HOST;
     std::vector<double> acc;                  // host twin: [n_points][n_ch][S.re, S.im, Q.re, Q.im]
-    void *dev = nullptr;                      // gsdr::SweepDev (sweep.cpp)
+    gsdr::StageDev *dev = nullptr;            // gsdr::SweepDev (sweep.cpp)
 };
 
 constexpr long long kSweepSlopeBlock = 256;   // consecutive terms of the phase slope that are summed into one block sum
@@ -91,7 +92,6 @@ extern "C" {
 // after every bound has been checked.  _reset_: waits for the device and zeroes the accumulators.  _slope_: the slope
 // kernels on the stream, waits, copies n_ch complex128.
 int gsdr_sweep_dev_create_(gsdr_sweep *s);
-void gsdr_sweep_dev_close_(gsdr_sweep *s);
 int gsdr_sweep_dev_reset_(gsdr_sweep *s);
 int gsdr_sweep_dev_slope_(gsdr_sweep *s, double *d_host, void *hip_stream);
 }

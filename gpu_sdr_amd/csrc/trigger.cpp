@@ -1,6 +1,6 @@
 // trigger.cpp -- the device part of a trigger object (the contract: include/gsdr.h, "trigger on the device"): what it
 // owns on the GPU and the sequencing of a feed.  Creation, the refusals of the arguments and the host twin are in
-// host_logic.cpp, the kernels in trigger_kernels.hip.
+// host_logic.cpp, the kernels in trigger_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is three launches on the caller's stream and no host synchronisation.  Everything a feed inherits lives in two
 // sets used in turn -- a feed reads set `cur` and writes the other one, as d_avg_acc does for the frame average -- so no
@@ -10,12 +10,12 @@
 #include <algorithm>
 #include <string>
 
-#include "host_util.h"
+#include "stage_dev.h"
 #include "trigger_kernels.h"
 
 namespace gsdr {
 
-struct TriggerDev {
+struct TriggerDev : StageDev {
     DevBuf<float> levels;                    // [n_ch][6]
     DevBuf<gsdr_trigger_rec> rec[2];         // windows: post - 1 + max_rows records
     DevBuf<unsigned char> flag[2];           // ... and as many flag bytes, padded by the 64 the selection reads in one step
@@ -31,22 +31,16 @@ struct TriggerDev {
 
 }  // namespace gsdr
 
-using gsdr::create_error;
+using gsdr::refuse;
+using gsdr::result;
+using gsdr::set_device;
 using gsdr::TriggerDev;
 
 namespace {
 
-int refuse(const char *entry, const std::string &what) {
-    create_error() = std::string(entry) + ": " + what;
-    return -1;
-}
-
-bool set_device(const gsdr_trigger *t) { return t->device < 0 || hipSetDevice(t->device) == hipSuccess; }
-
 // the checks both device feeds share; nullptr or the refusal
 const char *feed_fault(const gsdr_trigger *t, int n_rows) {
-    if (!t) return "null object";
-    if (t->device == GSDR_TRIGGER_HOST || !t->dev) return "a host object (GSDR_TRIGGER_HOST) takes gsdr_trigger_feed_host";
+    if (const char *bad = gsdr::object_fault(t, "a host object (GSDR_TRIGGER_HOST) takes gsdr_trigger_feed_host")) return bad;
     if (n_rows < 0 || n_rows > t->max_rows) return "n_rows must be in [0, max_rows]";
     return nullptr;
 }
@@ -82,32 +76,16 @@ hipError_t enqueue(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsdr_t
 extern "C" {
 
 int gsdr_trigger_dev_create_(gsdr_trigger *t, const gsdr_trigger_level *levels) {
-    const char *const me = "gsdr_trigger_create";
-    if (t->device >= 0 && hipSetDevice(t->device) != hipSuccess) return refuse(me, "device_index: hipSetDevice failed (no such GPU?)");
-    TriggerDev *d = new TriggerDev();
-    t->dev = d;
     const size_t window = (size_t)(t->post - 1) + (size_t)t->max_rows;
     const size_t carry = (size_t)(t->pre + t->post - 1) * (size_t)t->n_ch;
-    bool ok = d->levels.alloc((size_t)t->n_ch * 6) == hipSuccess && d->last_hit.alloc_zeroed(1) == hipSuccess;
-    for (int s = 0; ok && s < 2; ++s)
-        ok = d->rec[s].alloc_zeroed(window) == hipSuccess && d->flag[s].alloc_zeroed(window + 64) == hipSuccess &&
-             d->carry[s].alloc_zeroed(carry) == hipSuccess;
-    ok = ok && hipMemcpy(d->levels, levels, (size_t)t->n_ch * sizeof(gsdr_trigger_level), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete d;
-        t->dev = nullptr;
-        return refuse(me, "device allocation failed (n_ch, max_rows, pre + post: " +
-                              std::to_string((2 * carry * sizeof(float2) + 2 * window * 17) >> 20) + " MiB)");
-    }
-    return 0;
-}
-
-void gsdr_trigger_dev_close_(gsdr_trigger *t) {
-    if (t->device >= 0) (void)hipSetDevice(t->device);
-    (void)hipDeviceSynchronize();                    // the owners order nothing (dev_owner.h)
-    delete static_cast<TriggerDev *>(t->dev);
-    t->dev = nullptr;
+    const std::string asked = "(n_ch, max_rows, pre + post: " + std::to_string((2 * carry * sizeof(float2) + 2 * window * 17) >> 20) + " MiB)";
+    return gsdr::create_dev<TriggerDev>(t, "gsdr_trigger_create", asked, [&](TriggerDev &d) {
+        bool ok = d.levels.alloc((size_t)t->n_ch * 6) == hipSuccess && d.last_hit.alloc_zeroed(1) == hipSuccess;
+        for (int s = 0; ok && s < 2; ++s)
+            ok = d.rec[s].alloc_zeroed(window) == hipSuccess && d.flag[s].alloc_zeroed(window + 64) == hipSuccess &&
+                 d.carry[s].alloc_zeroed(carry) == hipSuccess;
+        return ok && hipMemcpy(d.levels, levels, (size_t)t->n_ch * sizeof(gsdr_trigger_level), hipMemcpyHostToDevice) == hipSuccess;
+    });
 }
 
 int gsdr_trigger_dev_set_levels_(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream) {
@@ -120,7 +98,7 @@ int gsdr_trigger_dev_set_levels_(gsdr_trigger *t, const gsdr_trigger_level *leve
     hipError_t e = hipMemcpyAsync(d->levels, levels, (size_t)t->n_ch * sizeof(gsdr_trigger_level), hipMemcpyHostToDevice,
                                   static_cast<hipStream_t>(hip_stream));
     if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(hip_stream));
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    return result(me, e);
 }
 
 int gsdr_trigger_feed_device(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsdr_trigger_event *events_dev,
@@ -132,7 +110,7 @@ int gsdr_trigger_feed_device(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_ro
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const hipError_t e = n_rows == 0 ? hipMemsetAsync(counts_dev, 0, 2 * sizeof(int), st)
                                      : enqueue(t, rows_dev, n_rows, events_dev, snippets_dev, counts_dev, st);
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
+    return result(me, e);
 }
 
 int gsdr_trigger_feed(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsdr_trigger_event *events_host,
@@ -157,15 +135,14 @@ int gsdr_trigger_feed(gsdr_trigger *t, const gsdr_c64 *rows_dev, int n_rows, gsd
     int counts[2] = {0, 0};
     hipError_t e = enqueue(t, rows_dev, n_rows, d->events, reinterpret_cast<gsdr_c64 *>(static_cast<float2 *>(d->snippets)),
                            d->counts, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d->counts, sizeof(counts), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    e = gsdr::fetch(e, st, {{counts, d->counts, sizeof(counts)}});
     // only what was emitted crosses to the host
     if (e == hipSuccess && counts[0] > 0) {
         e = hipMemcpy(events_host, d->events, (size_t)counts[0] * sizeof(gsdr_trigger_event), hipMemcpyDeviceToHost);
         if (e == hipSuccess)
             e = hipMemcpy(snippets_host, d->snippets, (size_t)counts[0] * snip * sizeof(gsdr_c64), hipMemcpyDeviceToHost);
     }
-    if (e != hipSuccess) return refuse(me, hipGetErrorString(e));
+    if (e != hipSuccess) return result(me, e);
     if (n_dropped) *n_dropped = counts[1];
     return counts[0];
 }

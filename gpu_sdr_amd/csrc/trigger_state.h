@@ -1,13 +1,15 @@
 // trigger_state.h -- the trigger object (include/gsdr.h, "trigger on the device") as host_logic.cpp and trigger.cpp
 // share it.  host_logic.cpp owns creation, the refusals, the host twin and the bookkeeping every object has;
-// trigger.cpp hangs the device part on `dev` through the three hooks below.  No HIP here: host_logic.cpp is built
-// alone by a host compiler (tests/test_trigger_sanitizers.py), where the hooks are absent and only host objects exist.
+// trigger.cpp hangs the device part on `dev` through the two hooks below (its release: stage_state.h).  No HIP here:
+// host_logic.cpp is built alone by a host compiler (tests/test_trigger_sanitizers.py), where the hooks are absent and
+// only host objects exist.
 #ifndef GSDR_TRIGGER_STATE_H
 #define GSDR_TRIGGER_STATE_H
 
 #include <vector>
 
 #include "../../include/gsdr.h"
+#include "stage_state.h"
 
 // what a row leaves behind: the event fields without the row number, n_hit == 0 for a row that does not hit
 struct gsdr_trigger_rec {
@@ -26,7 +28,7 @@ struct gsdr_trigger {
     std::vector<gsdr_trigger_rec> recs;       // records of the last post - 1 rows, right-aligned
     std::vector<unsigned char> trig;          // ... and whether each was a trigger
     long long last_hit = -1;                  // the last hitting row, -1: none yet
-    void *dev = nullptr;                      // gsdr::TriggerDev (trigger.cpp)
+    gsdr::StageDev *dev = nullptr;            // gsdr::TriggerDev (trigger.cpp)
 };
 
 extern "C" {
@@ -34,7 +36,6 @@ extern "C" {
 // after every bound has been checked.
 int gsdr_trigger_dev_create_(gsdr_trigger *t, const gsdr_trigger_level *levels);
 int gsdr_trigger_dev_set_levels_(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream);
-void gsdr_trigger_dev_close_(gsdr_trigger *t);
 }
 
 #endif

@@ -1,6 +1,6 @@
 // welch.cpp -- the device part of a welch object (the contract: include/gsdr.h, "Welch spectra on the device"): what
 // it owns on the GPU and the sequencing of a feed and of a read.  Creation, the refusals of the arguments and the host
-// twin are in host_logic.cpp, the kernels in welch_kernels.hip.
+// twin are in host_logic.cpp, the kernels in welch_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is three launches on the caller's stream (one when it completes no segment) and no host synchronisation.  What
 // the HOST has to know of the stream is only the number of rows fed: from it follow the ring position of the feed, the
@@ -11,12 +11,12 @@
 #include <string>
 #include <vector>
 
-#include "host_util.h"
+#include "stage_dev.h"
 #include "welch_kernels.h"
 
 namespace gsdr {
 
-struct WelchDev {
+struct WelchDev : StageDev {
     DevBuf<float2> hist;                     // [n_ch][H], H = nperseg - 1 + max_rows: the ring
     DevBuf<float> window;                    // nperseg
     DevBuf<float2> tw;                       // w_N^k, k < N, built in double as the PFB's table
@@ -32,25 +32,18 @@ struct WelchDev {
 
 }  // namespace gsdr
 
-using gsdr::create_error;
+using gsdr::refuse;
+using gsdr::result;
+using gsdr::set_device;
 using gsdr::WelchDev;
 
 namespace {
-
-int refuse(const char *entry, const std::string &what) {
-    create_error() = std::string(entry) + ": " + what;
-    return -1;
-}
-
-bool set_device(const gsdr_welch *w) { return w->device < 0 || hipSetDevice(w->device) == hipSuccess; }
 
 int count(long long n_seg) { return n_seg > INT_MAX ? INT_MAX : (int)n_seg; }
 
 // nullptr or why a device entry cannot take this object
 const char *object_fault(const gsdr_welch *w) {
-    if (!w) return "null object";
-    if (w->device == GSDR_WELCH_HOST || !w->dev) return "a host object (GSDR_WELCH_HOST) takes gsdr_welch_feed_host / gsdr_welch_read_host";
-    return nullptr;
+    return gsdr::object_fault(w, "a host object (GSDR_WELCH_HOST) takes gsdr_welch_feed_host / gsdr_welch_read_host");
 }
 
 // psd and / or mean on st; the checks of the arguments are the callers'
@@ -78,33 +71,26 @@ extern "C" {
 
 int gsdr_welch_dev_create_(gsdr_welch *w) {
     const char *const me = "gsdr_welch_create";
-    if (w->device >= 0 && hipSetDevice(w->device) != hipSuccess) return refuse(me, "device_index: hipSetDevice failed (no such GPU?)");
     const size_t N = (size_t)w->nperseg, K1 = N / 2 + 1, n_ch = (size_t)w->n_ch;
     const size_t H = N - 1 + (size_t)w->max_rows;
     const size_t max_segs = (size_t)w->max_rows / (size_t)w->step + 1;
     const size_t bytes = n_ch * H * sizeof(float2) + max_segs * n_ch * (3 * K1 * sizeof(float) + 2 * sizeof(double)) +
                          n_ch * (3 * K1 * sizeof(double) + 2 * sizeof(double) + 2 * K1 * sizeof(float) + 2 * sizeof(float2));
     const std::string asked = "(n_ch, max_rows, nperseg, step: " + std::to_string(bytes >> 20) + " MiB)";
+    // a bound like those of host_logic.cpp (it is here for `asked`): decided before the device is touched
     if (max_segs * n_ch > (size_t)INT_MAX) return refuse(me, "n_ch x (max_rows / step + 1) segments per feed exceed 2^31 - 1 " + asked);
-    WelchDev *d = new WelchDev();
-    w->dev = d;
-    d->H = (unsigned)H, d->max_segs = (long long)max_segs;
     std::vector<float2> tw(N);
     for (size_t k = 0; k < N; ++k) {
         const double a = -2.0 * M_PI * (double)k / (double)N;
         tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    const bool ok = d->hist.alloc(n_ch * H) == hipSuccess && d->window.upload(w->window) == hipSuccess && d->tw.upload(tw) == hipSuccess &&
-                    d->stage.alloc(max_segs * n_ch * 3 * K1) == hipSuccess && d->stage_mean.alloc(max_segs * n_ch * 2) == hipSuccess &&
-                    d->acc.alloc_zeroed(n_ch * 3 * K1) == hipSuccess && d->msum.alloc_zeroed(n_ch * 2) == hipSuccess &&
-                    d->psd.alloc(n_ch * 2 * K1) == hipSuccess && d->mean.alloc(n_ch) == hipSuccess && d->gain.alloc(n_ch) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete d;
-        w->dev = nullptr;
-        return refuse(me, "device allocation failed " + asked);
-    }
-    return 0;
+    return gsdr::create_dev<WelchDev>(w, me, asked, [&](WelchDev &d) {
+        d.H = (unsigned)H, d.max_segs = (long long)max_segs;
+        return d.hist.alloc(n_ch * H) == hipSuccess && d.window.upload(w->window) == hipSuccess && d.tw.upload(tw) == hipSuccess &&
+               d.stage.alloc(max_segs * n_ch * 3 * K1) == hipSuccess && d.stage_mean.alloc(max_segs * n_ch * 2) == hipSuccess &&
+               d.acc.alloc_zeroed(n_ch * 3 * K1) == hipSuccess && d.msum.alloc_zeroed(n_ch * 2) == hipSuccess &&
+               d.psd.alloc(n_ch * 2 * K1) == hipSuccess && d.mean.alloc(n_ch) == hipSuccess && d.gain.alloc(n_ch) == hipSuccess;
+    });
 }
 
 int gsdr_welch_dev_reset_(gsdr_welch *w) {
@@ -113,17 +99,7 @@ int gsdr_welch_dev_reset_(gsdr_welch *w) {
     WelchDev *d = static_cast<WelchDev *>(w->dev);
     const size_t K1 = (size_t)w->nperseg / 2 + 1, n_ch = (size_t)w->n_ch;
     // the ring needs no clearing: a young stream reads only rows it has written
-    hipError_t e = hipMemset(d->acc, 0, n_ch * 3 * K1 * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(d->msum, 0, n_ch * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    return e == hipSuccess ? 0 : refuse(me, hipGetErrorString(e));
-}
-
-void gsdr_welch_dev_close_(gsdr_welch *w) {
-    if (w->device >= 0) (void)hipSetDevice(w->device);
-    (void)hipDeviceSynchronize();                    // the owners order nothing (dev_owner.h)
-    delete static_cast<WelchDev *>(w->dev);
-    w->dev = nullptr;
+    return result(me, gsdr::zero_behind_all({{d->acc, n_ch * 3 * K1 * sizeof(double)}, {d->msum, n_ch * 2 * sizeof(double)}}));
 }
 
 int gsdr_welch_feed_device(gsdr_welch *w, const gsdr_c64 *rows_dev, int n_rows, void *hip_stream) {
@@ -146,7 +122,7 @@ int gsdr_welch_feed_device(gsdr_welch *w, const gsdr_c64 *rows_dev, int n_rows, 
     f.window = d->window, f.tw = d->tw, f.stage = d->stage, f.stage_mean = d->stage_mean, f.acc = d->acc, f.msum = d->msum;
     if ((long long)f.n_segs > d->max_segs) return refuse(me, "internal: more segments than the staging holds");
     const hipError_t e = gsdr::launch_welch_feed(f, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return refuse(me, hipGetErrorString(e));
+    if (e != hipSuccess) return result(me, e);
     w->total += n_rows;
     return 0;
 }
@@ -161,7 +137,7 @@ int gsdr_welch_read_device(gsdr_welch *w, int mode, const gsdr_c64 *gain_dev, do
     if (!set_device(w)) return refuse(me, "hipSetDevice failed");
     const hipError_t e = enqueue_read(w, mode, reinterpret_cast<const float2 *>(gain_dev), fs, psd_dev, nullptr, n_seg,
                                       static_cast<hipStream_t>(hip_stream));
-    return e == hipSuccess ? count(n_seg) : refuse(me, hipGetErrorString(e));
+    return result(me, e, count(n_seg));
 }
 
 int gsdr_welch_mean_device(gsdr_welch *w, gsdr_c64 *mean_dev, void *hip_stream) {
@@ -173,7 +149,7 @@ int gsdr_welch_mean_device(gsdr_welch *w, gsdr_c64 *mean_dev, void *hip_stream) 
     if (!set_device(w)) return refuse(me, "hipSetDevice failed");
     const hipError_t e = enqueue_read(w, GSDR_WELCH_RAW, nullptr, 1.0, nullptr, reinterpret_cast<float2 *>(mean_dev), n_seg,
                                       static_cast<hipStream_t>(hip_stream));
-    return e == hipSuccess ? count(n_seg) : refuse(me, hipGetErrorString(e));
+    return result(me, e, count(n_seg));
 }
 
 int gsdr_welch_read(gsdr_welch *w, int mode, const gsdr_c64 *gain_host, double fs, float *psd_host, gsdr_c64 *mean_host,
@@ -195,10 +171,8 @@ int gsdr_welch_read(gsdr_welch *w, int mode, const gsdr_c64 *gain_host, double f
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e == hipSuccess) e = enqueue_read(w, mode, d->gain, fs, d->psd, d->mean, n_seg, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(psd_host, d->psd, n_ch * 2 * K1 * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mean_host) e = hipMemcpyAsync(mean_host, d->mean, n_ch * sizeof(gsdr_c64), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? count(n_seg) : refuse(me, hipGetErrorString(e));
+    e = gsdr::fetch(e, st, {{psd_host, d->psd, n_ch * 2 * K1 * sizeof(float)}, {mean_host, d->mean, n_ch * sizeof(gsdr_c64)}});
+    return result(me, e, count(n_seg));
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // welch_state.h -- the Welch accumulator (include/gsdr.h, "Welch spectra on the device") as host_logic.cpp and welch.cpp
 // share it.  host_logic.cpp owns creation, the refusals, the host twin and the bookkeeping every object has; welch.cpp
-// hangs the device part on `dev` through the hooks below.  No HIP here: host_logic.cpp is built alone by a host
+// hangs the device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host
 // compiler (tests/test_welch_sanitizers.py), where the hooks are absent and only host objects exist.
 #ifndef GSDR_WELCH_STATE_H
 #define GSDR_WELCH_STATE_H
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gsdr.h"
+#include "stage_state.h"
 
 struct gsdr_welch {
     int n_ch = 0, max_rows = 0, nperseg = 0, step = 0, detrend = 0;
@@ -21,7 +22,7 @@ struct gsdr_welch {
     std::vector<double> acc;                  // [n_ch][3][nperseg / 2 + 1]: |X|^2, |Y|^2, Re X conj Y
     std::vector<double> msum;                 // [n_ch][2]: sum of the rows [0, n_seg * step)
     std::vector<double> tw;                   // (cos, -sin)(2 pi k / nperseg), k < nperseg / 2
-    void *dev = nullptr;                      // gsdr::WelchDev (welch.cpp)
+    gsdr::StageDev *dev = nullptr;            // gsdr::WelchDev (welch.cpp)
 };
 
 // segments complete after `total` rows
@@ -34,7 +35,6 @@ extern "C" {
 // after every bound has been checked.  _reset_: zeroes the device accumulators (waits for the device).
 int gsdr_welch_dev_create_(gsdr_welch *w);
 int gsdr_welch_dev_reset_(gsdr_welch *w);
-void gsdr_welch_dev_close_(gsdr_welch *w);
 }
 
 #endif

@@ -18,9 +18,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .demodulator import GsdrError
-
-DECIM_HOST = -2      # GSDR_DECIM_HOST
+from ._lib import DECIM_HOST
+from ._stage import DeviceStage, Stage
+from .demodulator import GsdrError  # noqa: F401  (raised by Stage; kept importable from here)
 
 
 def fir_taps(q: int) -> np.ndarray:
@@ -32,12 +32,12 @@ def fir_taps(q: int) -> np.ndarray:
     return w
 
 
-class _decimator:
+class _decimator(Stage):
     """What device_decimator and host_decimator share: the object and its bookkeeping."""
 
+    _NAME = "decim"
+
     def __init__(self, n_ch, max_rows, q, taps, offset, device_index):
-        self._L = _lib.lib()
-        self._h = None
         self.n_ch, self.max_rows, self.q = int(n_ch), int(max_rows), int(q)
         t = None
         if taps is not None:
@@ -45,15 +45,8 @@ class _decimator:
         n_taps = 0 if t is None else int(t.shape[0])
         T = n_taps if t is not None else 20 * self.q + 1
         self.offset = (T - 1) // 2 if offset is None else int(offset)
-        h = self._L.gsdr_decim_create(self.n_ch, self.max_rows, self.q, n_taps, t.ctypes.data if t is not None else None,
-                                      self.offset, int(device_index))
-        if not h:
-            raise GsdrError(self._L.gsdr_last_error(None).decode())
-        self._h = h
-        self.n_taps = int(self._L.gsdr_decim_get_taps(h, None, 0))
-
-    def _fail(self):
-        raise GsdrError(self._L.gsdr_last_error(None).decode())
+        self._create(self.n_ch, self.max_rows, self.q, n_taps, t.ctypes.data if t is not None else None, self.offset, int(device_index))
+        self.n_taps = int(self._L.gsdr_decim_get_taps(self._h, None, 0))
 
     @property
     def taps(self) -> np.ndarray:
@@ -86,17 +79,6 @@ class _decimator:
         if self._L.gsdr_decim_reset(self._h) != 0:
             self._fail()
 
-    def close(self):
-        if self._h:
-            self._L.gsdr_decim_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class host_decimator(_decimator):
     """The library's host twin (GSDR_DECIM_HOST): numpy complex64 rows in, complex64 rows out, the device's bits."""
@@ -114,28 +96,13 @@ class host_decimator(_decimator):
         return out[:m]
 
 
-class device_decimator(_decimator):
+class device_decimator(DeviceStage, _decimator):
     """The decimator on the GPU, behind rows that are already in device memory (what gsdr_demod_process_device /
     _submit_device wrote).  ``feed_device`` is asynchronous and leaves its rows on the device; ``feed`` waits for the
     stream and returns a host array."""
 
     def __init__(self, n_ch, max_rows, q, taps=None, offset=None, device_index: int = 0):
-        if int(device_index) < -1:
-            raise ValueError("device_index must be >= -1 (host_decimator is the host-only object)")
-        super().__init__(n_ch, max_rows, q, taps, offset, device_index)
-
-    def _stream(self, stream):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
-
-    def _rows(self, rows):
-        import torch
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.complex64 and rows.is_contiguous()):
-            raise TypeError("rows must be a contiguous CUDA complex64 tensor [n][n_ch]")
-        if rows.numel() % self.n_ch:
-            raise ValueError("rows is not a whole number of rows")
-        return rows.numel() // self.n_ch
+        super().__init__(n_ch, max_rows, q, taps, offset, self._device_index(device_index, "host_decimator"))
 
     def feed_device(self, rows, out, stream=None) -> int:
         """rows: contiguous CUDA complex64 [n][n_ch], n <= max_rows; out: contiguous CUDA complex64 with room for

@@ -16,9 +16,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import RESMAP_HOST
+from ._stage import DeviceStage, Stage
 from .demodulator import GsdrError
 
-RESMAP_HOST = -2     # GSDR_RESMAP_HOST
 KINDS = {"cal": 0, "x_dqr": 1, "x_qr": 2}      # GSDR_RESMAP_CAL, GSDR_RESMAP_X_DQR, GSDR_RESMAP_X_QR
 NCONST = _lib.RESMAP_NCONST
 
@@ -44,12 +45,12 @@ def resmap_constants(fits, tones) -> np.ndarray:
     return out
 
 
-class _resmap:
+class _resmap(Stage):
     """What device_resmap and host_resmap share: the object, its tables and its offsets."""
 
+    _NAME = "resmap"
+
     def __init__(self, n_ch, max_rows, constants, channels, kind, device_index):
-        self._L = _lib.lib()
-        self._h = None
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {sorted(KINDS)}")
         self.n_ch, self.max_rows, self.kind = int(n_ch), int(max_rows), kind
@@ -59,15 +60,9 @@ class _resmap:
         ch = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
         if ch is not None and ch.shape[0] != k.shape[0]:
             raise ValueError(f"{k.shape[0]} columns of constants for {ch.shape[0]} channels")
-        h = self._L.gsdr_resmap_create(self.n_ch, self.max_rows, int(k.shape[0]), ch.ctypes.data if ch is not None else None,
-                                       k.ctypes.data, KINDS[kind], int(device_index))
-        if not h:
-            raise GsdrError(self._L.gsdr_last_error(None).decode())
-        self._h = h
-        self.n_out = int(self._L.gsdr_resmap_n_out(h))
-
-    def _fail(self):
-        raise GsdrError(self._L.gsdr_last_error(None).decode())
+        self._create(self.n_ch, self.max_rows, int(k.shape[0]), ch.ctypes.data if ch is not None else None, k.ctypes.data,
+                     KINDS[kind], int(device_index))
+        self.n_out = int(self._L.gsdr_resmap_n_out(self._h))
 
     @property
     def constants(self) -> np.ndarray:
@@ -97,17 +92,6 @@ class _resmap:
         if self._L.gsdr_resmap_set_offsets(self._h, a.ctypes.data if a is not None else None, stream) != 0:
             self._fail()
 
-    def close(self):
-        if self._h:
-            self._L.gsdr_resmap_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class host_resmap(_resmap):
     """The library's host twin (GSDR_RESMAP_HOST): numpy complex64 rows in, complex64 rows out, the device's bits."""
@@ -130,28 +114,13 @@ class host_resmap(_resmap):
         return out[:m]
 
 
-class device_resmap(_resmap):
+class device_resmap(DeviceStage, _resmap):
     """The map on the GPU, behind rows that are already in device memory (what gsdr_demod_process_device /
     _submit_device wrote).  ``feed_device`` is asynchronous and leaves its rows on the device; ``feed`` waits for the
     stream and returns a host array."""
 
     def __init__(self, n_ch, max_rows, constants, channels=None, kind="x_dqr", device_index: int = 0):
-        if int(device_index) < -1:
-            raise ValueError("device_index must be >= -1 (host_resmap is the host-only object)")
-        super().__init__(n_ch, max_rows, constants, channels, kind, device_index)
-
-    def _stream(self, stream):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
-
-    def _rows(self, rows):
-        import torch
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.complex64 and rows.is_contiguous()):
-            raise TypeError("rows must be a contiguous CUDA complex64 tensor [n][n_ch]")
-        if rows.numel() % self.n_ch:
-            raise ValueError("rows is not a whole number of rows")
-        return rows.numel() // self.n_ch
+        super().__init__(n_ch, max_rows, constants, channels, kind, self._device_index(device_index, "host_resmap"))
 
     def set_offsets(self, xy=None, stream=None):
         """xy: float64 [n_out][2] = (x0, y0) per column, or None for zeros; copied before the call returns.  Ordered on

@@ -10,26 +10,24 @@ in device memory, so that only ``n_ch x 2 x (nperseg/2 + 1)`` floats reach the h
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from .demodulator import GsdrError
+from ._lib import WELCH_HOST
+from ._stage import DeviceStage, Stage
+from .demodulator import GsdrError  # noqa: F401  (raised by Stage; kept importable from here)
 
-WELCH_HOST = -2      # GSDR_WELCH_HOST
 DETREND = {"none": 0, "constant": 1, "linear": 2, None: 0, False: 0}      # GSDR_WELCH_DETREND_*
 MODES = {"raw": 0, "rotate": 1, "dbc": 2, "gain": 3}                      # GSDR_WELCH_*
 
 
-class _welch:
+class _welch(Stage):
     """What device_welch and host_welch share: the object and its bookkeeping."""
 
+    _NAME = "welch"
+
     def __init__(self, n_ch, max_rows, nperseg, step, detrend, window, device_index):
-        self._L = _lib.lib()
         self.n_ch, self.max_rows, self.nperseg = int(n_ch), int(max_rows), int(nperseg)
         self.step = self.nperseg // 2 if step is None else int(step)
-        self._h = None
         if detrend not in DETREND:
             raise ValueError(f"detrend must be one of 'linear', 'constant', 'none' (got {detrend!r})")
         win = None
@@ -37,11 +35,8 @@ class _welch:
             win = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
             if win.shape[0] != self.nperseg:
                 raise ValueError(f"window: {win.shape[0]} taps for nperseg {self.nperseg}")
-        h = self._L.gsdr_welch_create(self.n_ch, self.max_rows, self.nperseg, self.step, DETREND[detrend],
-                                      win.ctypes.data if win is not None else None, int(device_index))
-        if not h:
-            raise GsdrError(self._L.gsdr_last_error(None).decode())
-        self._h = h
+        self._create(self.n_ch, self.max_rows, self.nperseg, self.step, DETREND[detrend],
+                     win.ctypes.data if win is not None else None, int(device_index))
 
     @property
     def bins(self) -> int:
@@ -50,9 +45,6 @@ class _welch:
     def freqs(self, fs: float = 1.0) -> np.ndarray:
         """The bin frequencies, as numpy.fft.rfftfreq(nperseg, 1 / fs)."""
         return np.arange(self.bins, dtype=np.float64) * (float(fs) / self.nperseg)
-
-    def _fail(self):
-        raise GsdrError(self._L.gsdr_last_error(None).decode())
 
     def _mode(self, mode, gain):
         if mode not in MODES:
@@ -73,17 +65,6 @@ class _welch:
         """Zeroes the accumulators and restarts the row numbering.  Order it behind the feeds in flight."""
         if self._L.gsdr_welch_reset(self._h) != 0:
             self._fail()
-
-    def close(self):
-        if self._h:
-            self._L.gsdr_welch_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class host_welch(_welch):
@@ -119,29 +100,17 @@ class host_welch(_welch):
         return self._read("raw", 1.0, None)[1]
 
 
-class device_welch(_welch):
+class device_welch(DeviceStage, _welch):
     """The accumulator on the GPU, behind rows that are already in device memory (what gsdr_demod_process_device /
     _submit_device wrote).  ``feed`` and ``feed_device`` are the same asynchronous call; ``read`` waits for the stream and
     returns host arrays, ``read_device`` leaves the spectra on the device."""
 
     def __init__(self, n_ch, max_rows, nperseg, step=None, detrend="linear", window=None, device_index: int = 0):
-        if int(device_index) < -1:
-            raise ValueError("device_index must be >= -1 (host_welch is the host-only object)")
-        super().__init__(n_ch, max_rows, nperseg, step, detrend, window, device_index)
-
-    def _stream(self, stream):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
+        super().__init__(n_ch, max_rows, nperseg, step, detrend, window, self._device_index(device_index, "host_welch"))
 
     def feed_device(self, rows, stream=None):
         """rows: contiguous CUDA complex64 [n][n_ch], n <= max_rows.  Asynchronous on the stream; nothing is read back."""
-        import torch
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.complex64 and rows.is_contiguous()):
-            raise TypeError("rows must be a contiguous CUDA complex64 tensor [n][n_ch]")
-        if rows.numel() % self.n_ch:
-            raise ValueError("rows is not a whole number of rows")
-        n_rows = rows.numel() // self.n_ch
+        n_rows = self._rows(rows)
         if self._L.gsdr_welch_feed_device(self._h, rows.data_ptr() if n_rows else None, n_rows, self._stream(stream)) != 0:
             self._fail()
 

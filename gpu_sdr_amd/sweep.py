@@ -18,9 +18,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import SWEEP_HOST
+from ._stage import DeviceStage, Stage
 from .demodulator import GsdrError, chirp_derive
-
-SWEEP_HOST = -2      # GSDR_SWEEP_HOST
 
 
 def sweep_shape(rate, freq0, chirp_f, swipe_s, chirp_t, decim):
@@ -47,20 +47,14 @@ def vna_axis(rate, freq0, chirp_f, swipe_s, n_points, rf=0.0) -> np.ndarray:
     return f
 
 
-class _sweep:
+class _sweep(Stage):
     """What device_sweep and host_sweep share: the object and its bookkeeping."""
 
-    def __init__(self, n_ch, n_points, group, first_row, device_index):
-        self._L = _lib.lib()
-        self._h = None
-        self.n_ch, self.n_points, self.group, self.first_row = int(n_ch), int(n_points), int(group), int(first_row)
-        h =self._L.gsdr_sweep_create(self.n_ch, self.n_points, self.group, int(first_row), int(device_index))
-        if not h:
-            raise GsdrError(self._L.gsdr_last_error(None).decode())
-        self._h = h
+    _NAME = "sweep"
 
-    def _fail(self):
-        raise GsdrError(self._L.gsdr_last_error(None).decode())
+    def __init__(self, n_ch, n_points, group, first_row, device_index):
+        self.n_ch, self.n_points, self.group, self.first_row = int(n_ch), int(n_points), int(group), int(first_row)
+        self._create(self.n_ch, self.n_points, self.group, int(first_row), int(device_index))
 
     @property
     def rows_seen(self) -> int:
@@ -104,17 +98,6 @@ class _sweep:
             self._fail()
         self.first_row = int(first_row)
 
-    def close(self):
-        if self._h:
-            self._L.gsdr_sweep_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class host_sweep(_sweep):
     """The library's host twin (GSDR_SWEEP_HOST): numpy complex64 rows in, the device's bits out."""
@@ -138,20 +121,13 @@ class host_sweep(_sweep):
         return (mean, var) if variance else mean
 
 
-class device_sweep(_sweep):
+class device_sweep(DeviceStage, _sweep):
     """The accumulator on the GPU, behind rows that are already in device memory (what gsdr_demod_process_device /
     _submit_device wrote).  ``feed_device`` is one asynchronous launch; ``read_device`` leaves the means on the device;
     ``read``, ``slope`` and ``line_delay`` wait for the stream and return host arrays."""
 
     def __init__(self, n_ch, n_points, group=1, first_row=0, device_index: int = 0):
-        if int(device_index) < -1:
-            raise ValueError("device_index must be >= -1 (host_sweep is the host-only object)")
-        super().__init__(n_ch, n_points, group, first_row, device_index)
-
-    def _stream(self, stream):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
+        super().__init__(n_ch, n_points, group, first_row, self._device_index(device_index, "host_sweep"))
 
     def _out(self, t, name):
         import torch
@@ -163,12 +139,7 @@ class device_sweep(_sweep):
 
     def feed_device(self, rows, stream=None):
         """rows: contiguous CUDA complex64 [n][n_ch].  Asynchronous on the stream; nothing is read back."""
-        import torch
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.complex64 and rows.is_contiguous()):
-            raise TypeError("rows must be a contiguous CUDA complex64 tensor [n][n_ch]")
-        if rows.numel() % self.n_ch:
-            raise ValueError("rows is not a whole number of rows")
-        n_rows = rows.numel() // self.n_ch
+        n_rows = self._rows(rows)
         if self._L.gsdr_sweep_feed_device(self._h, rows.data_ptr() if n_rows else None, n_rows, self._stream(stream)) != 0:
             self._fail()
 

@@ -16,13 +16,13 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from .demodulator import GsdrError
+from ._lib import TRIGGER_HOST
+from ._stage import DeviceStage, Stage
+from .demodulator import GsdrError  # noqa: F401  (raised by Stage; kept importable from here)
 
 #: numpy layouts of struct gsdr_trigger_level and struct gsdr_trigger_event (24 bytes each)
 LEVEL_DTYPE = np.dtype([("bx", "<f4"), ("by", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("lo", "<f4"), ("hi", "<f4")])
 EVENT_DTYPE = np.dtype([("row", "<i8"), ("channel", "<i4"), ("side", "<i4"), ("q", "<f4"), ("n_hit", "<i4")])
-TRIGGER_HOST = -2      # GSDR_TRIGGER_HOST
 
 
 def as_levels(levels, n_ch: int) -> np.ndarray:
@@ -59,30 +59,22 @@ def levels_from_rows(rows, nsigma: float, direction=(1, 0), channels=None) -> np
     return lv
 
 
-class _trigger:
+class _trigger(Stage):
     """What device_trigger and host_trigger share: the object, its bookkeeping and the reference's trigger surface."""
 
+    _NAME = "trigger"
     trigger_control = "AUTO"
 
     def __init__(self, n_ch, max_rows, pre, post, holdoff, max_events, levels, device_index):
-        self._L = _lib.lib()
         self.n_ch, self.max_rows, self.pre, self.post = int(n_ch), int(max_rows), int(pre), int(post)
         self.holdoff, self.max_events = int(holdoff), int(max_events)
-        self._h = None
         lv = as_levels(levels, self.n_ch) if self.n_ch >= 1 else np.zeros(1, dtype=LEVEL_DTYPE)
-        h = self._L.gsdr_trigger_create(self.n_ch, self.max_rows, self.pre, self.post, self.holdoff, self.max_events,
-                                        lv.ctypes.data, int(device_index))
-        if not h:
-            raise GsdrError(self._L.gsdr_last_error(None).decode())
-        self._h = h
+        self._create(self.n_ch, self.max_rows, self.pre, self.post, self.holdoff, self.max_events, lv.ctypes.data, int(device_index))
         self.dropped = 0          # triggers counted but not written since creation, by feed() / trigger()
 
     @property
     def snippet_rows(self) -> int:
         return self.pre + self.post
-
-    def _fail(self):
-        raise GsdrError(self._L.gsdr_last_error(None).decode())
 
     def set_levels(self, levels, stream=None):
         """Levels for the rows of later feeds; rows already fed keep their records."""
@@ -101,17 +93,6 @@ class _trigger:
     @property
     def rows_seen(self) -> int:
         return int(self._L.gsdr_trigger_rows(self._h))
-
-    def close(self):
-        if self._h:
-            self._L.gsdr_trigger_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _out(self):
         ev = np.zeros(self.max_events, dtype=EVENT_DTYPE)
@@ -157,28 +138,13 @@ class host_trigger(_trigger):
         return ev[:n].copy(), sn[:n].copy(), dropped.value
 
 
-class device_trigger(_trigger):
+class device_trigger(DeviceStage, _trigger):
     """The trigger on the GPU, behind rows that are already in device memory (what gsdr_demod_process_device /
     _submit_device wrote).  ``feed`` returns host arrays and copies only the emitted events and snippets;
     ``feed_device`` leaves everything on the device and does not synchronise."""
 
     def __init__(self, n_ch, max_rows, pre, post, holdoff, max_events, levels, device_index: int = 0):
-        if int(device_index) < -1:
-            raise ValueError("device_index must be >= -1 (host_trigger is the host-only object)")
-        super().__init__(n_ch, max_rows, pre, post, holdoff, max_events, levels, device_index)
-
-    def _stream(self, stream):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
-
-    def _rows(self, rows):
-        import torch
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.complex64 and rows.is_contiguous()):
-            raise TypeError("rows must be a contiguous CUDA complex64 tensor [n][n_ch]")
-        if rows.numel() % self.n_ch:
-            raise ValueError("rows is not a whole number of rows")
-        return rows.numel() // self.n_ch
+        super().__init__(n_ch, max_rows, pre, post, holdoff, max_events, levels, self._device_index(device_index, "host_trigger"))
 
     def _packet_rows(self, data):
         import torch

@@ -3,13 +3,7 @@ stand-alone program with its own main, built from host_logic.cpp alone with plai
 only GSDR_TRIGGER_HOST objects exist in such a build).  Every buffer is a heap block of exactly the documented extent,
 so one sample read or written past an end is a report.  Nothing is loaded into Python, nothing is preloaded; in the
 style of tests/test_sc16_tx_sanitizers.py."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _sanitized import build_and_run
 
 DRIVER = r'''
 #include <cstdio>
@@ -101,20 +95,7 @@ int main() {
 
 
 def test_trigger_host_under_asan_and_ubsan(tmp_path):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    (tmp_path / "driver.cpp").write_text(DRIVER)
-    exe = tmp_path / "driver"
-    src = os.path.join(ROOT, "gpu_sdr_amd", "csrc", "host_logic.cpp")
-    build = subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fsanitize=float-cast-overflow",
-                            "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"),
-                            str(tmp_path / "driver.cpp"), src, "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
-        pytest.skip("no sanitizer runtime")
-    assert build.returncode == 0, build.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
+    run = build_and_run(DRIVER, tmp_path)
     assert run.returncode == 0, (run.stdout[-500:], run.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
     assert run.stdout.strip() == "runs 5 bad 0", run.stdout
