@@ -86,6 +86,24 @@ class PfbPlanOutC(C.Structure):
         "len", "n_radices")] + [("radices", C.c_int * 16)]
 
 
+class DdcPlanInC(C.Structure):
+    """struct gsdr_ddc_plan_in"""
+    _fields_ = [(n, C.c_longlong) for n in ("decim", "pf_average", "buffer_len")] + [(n, C.c_int) for n in (
+        "tones", "rate", "rows", "overlapped", "cus",
+        "ddc_mfma", "ddc_few", "ddc_pipe", "ddc_k", "ddc_waves", "ddc_nch",
+        "mfma_asm", "mfma_tt", "mfma_pk", "mfma_w", "mfma_rt", "mfma_w8", "mfma_prec",
+        "mfma_3m", "mfma_3m_rot", "mfma_fold", "mfma_fold_products", "mfma_wave_tones", "mfma_span")]
+
+
+class DdcPlanOutC(C.Structure):
+    """struct gsdr_ddc_plan_out"""
+    _fields_ = [(n, C.c_int) for n in (
+        "engine", "K", "pad", "R", "target_waves", "tails_nch", "chunks", "chunks_want",
+        "complex_mac", "rotation_blocks", "fold", "fold_products", "wave_tones", "span_samples",
+        "images", "preconverted", "row_tiles_per_workgroup", "eight_waves",
+        "complex_mac_min_blocks", "rotation_min_blocks", "fold_min_blocks", "span128_min_blocks")]
+
+
 # every symbol include/gsdr.h declares: (name, restype, argtypes)
 _vp, _ip, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
 SIGNATURES = [
@@ -139,6 +157,7 @@ SIGNATURES = [
     ("gsdr_pfb_plan", C.c_int, [C.POINTER(PfbPlanInC), C.POINTER(PfbPlanOutC)]),
     ("gsdr_pfb_plan_many", C.c_int, [_vp, C.c_int, _vp]),
     ("gsdr_pfb_blue_length", C.c_int, [C.c_int] * 5),
+    ("gsdr_ddc_plan", C.c_int, [C.POINTER(DdcPlanInC), C.POINTER(DdcPlanOutC)]),
     ("gsdr_txgen_tones_create", C.c_void_p, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int]),
     ("gsdr_txgen_tones_fill", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
     ("gsdr_txgen_close", None, [C.c_void_p]),

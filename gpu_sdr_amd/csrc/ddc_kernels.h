@@ -5,7 +5,9 @@
 #include <vector>
 
 #include "chirp_plan.h"
+#include "ddc_plan.h"
 #include "pfb_plan.h"
+#include "switches.h"
 #include "dev_owner.h"
 
 // No packed FP32 (v_pk_*_f32) in a kernel that may share a SIMD with the matrix-core DDC loop of another
@@ -18,61 +20,6 @@
 #endif
 
 namespace gsdr {
-
-// The run-time GSDR_* switches (A/B runs and the tests; INTEGRATION.md, "Run-time knobs"), read from the environment
-// by read_switches() when a handle is created and kept by it: nothing reads the environment after that.  Each field
-// holds what the variable selects, with the default when it is unset or empty; -1 / 0 marked "unset" leave the
-// default to the one place that uses the field.
-struct Switches {
-    bool ddc_mfma = true;       // GSDR_DDC_MFMA, 1: matrix-core DDC where its shape rules hold; 0: ddc_flat_kernel (F <= 4)
-    bool ddc_few = true;        // GSDR_DDC_FEW, 1: ddc_few_kernel for a handful of tones at decim >= 512; 0: never
-    bool ddc_pipe = true;       // GSDR_DDC_PIPE, 1: ddc_flat_kernel where it may run; 0: the generic ddc_kernel
-    int ddc_k = -1;             // GSDR_DDC_K, -1 unset: phasor-table length 16 / the flat kernel's sub-block by shape
-    int ddc_waves = 0;          // GSDR_DDC_WAVES_PER_SIMD, 0 unset: resident waves per SIMD, 6 (flat kernel) or 4; <= 0: 4
-    int ddc_nch = 0;            // GSDR_DDC_NCH, 0: chunks per DDC launch by the grid rule; > 0: that many
-    unsigned ddc_lds = 0;       // GSDR_DDC_LDS, 0: dummy LDS bytes per DDC workgroup (occupancy cap)
-    int ddc_prefetch = 1;       // GSDR_DDC_PREFETCH, 1: ddc_flat_kernel prefetches the IQ stream into L2; 0: not
-    bool ddc_autotune = true;   // GSDR_DDC_AUTOTUNE, 1: ddc_flat_kernel's grid timed at create; 0: ratio 1.3
-    int mfma_asm = 4;           // GSDR_MFMA_ASM, 4: ring16 loop; 5: its 8-wave form; 2: round 1's ring; else the C++ kernel
-    int mfma_tt = 1;            // GSDR_MFMA_TT, 1: C++ kernel tone tiles per wave (1 or 2)
-    int mfma_pk = 32;           // GSDR_MFMA_PK, 32: C++ kernel phasor block (16 or 32)
-    int mfma_w = 4;             // GSDR_MFMA_W, 4: C++ kernel waves per workgroup (2 or 4)
-    int mfma_rt = 0;            // GSDR_MFMA_RT, 0: ring kernel row tiles per workgroup chosen per launch; 1, 2: forced
-    bool mfma_w8 = true;        // GSDR_MFMA_W8, 1: in-order launches that fit run the 8-wave ring16 kernel; 0: never
-    int mfma_prec = -1;         // GSDR_MFMA_PREC, -1: pre-converted operands per launch; 1: always; else never
-    int mfma_3m = -1;           // GSDR_MFMA_3M, -1 unset: three real products per complex multiply on handles with pre-converted
-                                // images and a window of kMac3MinBlocks blocks or more; 1: wherever there are images; else never
-    int mfma_3m_rot = -1;       // GSDR_MFMA_3M_ROT, -1 unset: three-product handles with a window of kRot2MinBlocks blocks or more
-                                // rotate their partial sums once per pair of blocks; 2: every three-product handle; else per block
-    int mfma_fold = -1;         // GSDR_MFMA_FOLD, -1 unset: handles that rotate per pair and have a window of kFoldMinBlocks blocks or
-                                // more fold each 64-sample span about its centre (48 MFMAs per span for 72); 1: every such handle; else never
-    int mfma_fold_products = -1;    // GSDR_MFMA_FOLD_PRODUCTS, -1 unset: a folded handle sums the plain four products straight into Re and Im
-                                // (ddc_mfma_ring16p4f_kernel); 3: Gauss's three (ddc_mfma_ring16p3f_kernel); 4: the four
-    int mfma_wave_tones = -1;   // GSDR_MFMA_WAVE_TONES, -1 unset: a handle that sums the plain four products takes the loop with wave tiles of
-                                // 16 rows x 64 tones (ddc_mfma_ring16p4fw_kernel) when that launches no more waves; 64: every such handle; 32: never
-    int mfma_span = -1;         // GSDR_MFMA_SPAN, -1 unset: a handle that took the wide tile by its own rule (GSDR_MFMA_WAVE_TONES unset) and has a
-                                // window of kSpan128MinBlocks blocks or more rotates once per 128 samples (ddc_mfma_ring16p4fw2_kernel); 128: every
-                                // handle on the wide tile; 64 (or anything else): never
-    int mfma_timing = 0;        // GSDR_MFMA_TIMING, 0: timing-only modes 1 - 3 (builds with -DGSDR_TIMING_BUILD only)
-    bool noise_fft = true;      // GSDR_NOISE_FFT, 1: NOISE through the polyphase filter + FFT; 0: every bin a DDC tone
-    bool tones_fft = true;      // GSDR_TONES_FFT, 1: TONES through filter + FFT + bin selection; 0: every bin a DDC tone
-    bool pfb_lds = true;        // GSDR_PFB_LDS, 1: TONES / NOISE inside the LDS where the frame fits; 0: never
-    int pfb_bluestein = -1;     // GSDR_PFB_BLUESTEIN, -1 unset: Bluestein in the LDS for primes above 127 only; 1: also others; 0: never
-    int pfb_cu = -1;            // GSDR_PFB_CU, -1: pfb_cu_kernel by shape; 0: never; 1: forced (other values: forced, fill rule kept)
-    bool pfb_direct = true;     // GSDR_PFB_DIRECT, 1: pfb_cu_kernel filters straight out of global memory; 0: through the LDS
-    int pfb_col = -1;           // GSDR_PFB_COL, -1: staged filter column-wise by shape; 1: column-wise; 0: point-wise
-    int pfb_cu_nt = 0;          // GSDR_PFB_CU_NT, 0: pfb_cu_kernel workgroup by shape; 512: two per unit; else 1024
-    bool pfb_teams = true;      // GSDR_PFB_TEAMS, 1: the frames of a run go through their stages in teams; 0: in step
-    bool pfb_radix8 = true;     // GSDR_PFB_RADIX8, 1: radix 8 / 6 / 10 stages in the LDS; 0: radix 4 / 2
-    int pfb_fr = 0;             // GSDR_PFB_FR, 0: pfb_lds_kernel frames per workgroup by shape; > 0: that many
-    int pfb_wide = -1;          // GSDR_PFB_WIDE, -1: pfb_lds_kernel 512 threads from 2048 points; 1: always; 0: 256
-    int mix_few = 32;           // GSDR_MIX_FEW, 32: up to how many tones mix_few_kernel runs (decim 0); 0: never
-    bool chirp_split = true;    // GSDR_CHIRP_SPLIT, 1: long lock-in points summed by several waves; 0: a wave per point
-    bool pipe_queues = true;    // GSDR_PIPE_QUEUES, 1: compute streams with a CU mask (a queue each); 0: plain streams
-    bool pipe_overlap = true;   // GSDR_PIPE_OVERLAP, 1: consecutive submitted DIRECT buffers on rotating streams; 0: one
-    int pipe_streams = 3;       // GSDR_PIPE_STREAMS, 3: compute streams the overlap rotates over (1 ... 3, else 3)
-};
-Switches read_switches();
 
 // Shape of one DDC launch; passed to the kernels by value.
 struct DdcShape {
@@ -232,21 +179,12 @@ struct StageLaunch {
     long long tail0;
 };
 hipError_t launch_absmax(const StageLaunch &s, hipStream_t st);
-// AsmRing16 / AsmRing16P / AsmRing16W8: assembly main loops on the 16x16x32 MFMA (production, pre-converted
-// operands, eight-wave workgroups); AsmRing16P3: the pre-converted loop with three real products per complex
-// multiply (chosen per handle, demod.cpp), AsmRing16P3R2: that loop rotating its partial sums once per pair of
-// blocks (tables of mfma_build_tables3 with span 2 in bfrag3 / ptab3), AsmRing16P3F: three products over 64-sample spans
-// folded about their centre (images of ddc_convert3f_kernel, tables of mfma_build_tables3f in bfrag3 / ptab3), AsmRing16P4F: that fold with the plain four products (images of
-// ddc_convert4f_kernel, tables of mfma_build_tables4f), AsmRing16P4FW: that loop, images and tables on wave tiles of 16 rows x 64 tones; AsmRing16P4FW2: the wide-tile loop
-// over spans of 128 samples folded about their centre (images of ddc_convert4f2_kernel, tables of mfma_build_tables4f2); AsmRing:
-// round 1's loop on the 32x32x16 MFMA; Cxx: compiler-scheduled (TT, PK, W apply to it only; the assembly kernels are
-// TT = 1, PK = 32, W = 4).
-enum class MfmaKernel { AsmRing, Cxx, AsmRing16, AsmRing16W8, AsmRing16P, AsmRing16P3, AsmRing16P3R2, AsmRing16P3F, AsmRing16P4F, AsmRing16P4FW, AsmRing16P4FW2 };
+// (the kernels: enum class MfmaKernel, ddc_plan.h)
 hipError_t launch_ddc_mfma(MfmaKernel kind, int TT, int PK, int W, const MfmaLaunch &a, hipStream_t st);
 const char *ddc_mfma_kernel_name(MfmaKernel kind);
 // What the host knows of one loop of the pre-converted family (AsmRing16P ... AsmRing16P4FW, all named
 // ddc_mfma_ring16p_kernel).  The rows stand in ddc_mfma.hip next to launch_ddc_mfma, which keeps each loop's conversion
-// kernel, loop kernel and grid rule beside them; demod.cpp picks a handle's row once (product_loop_chosen) and sizes,
+// kernel, loop kernel and grid rule beside them; demod_ddc.cpp picks a handle's row once (product_loop_chosen, ddc_plan.h) and sizes,
 // fills, launches and describes by it.
 struct ProductLoop {
     MfmaKernel kind;
@@ -296,18 +234,6 @@ hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, cons
                           int nfft, int avg, int frames_n, const int *sel, int n_out, float2 *out,
                           float2 *carry_out, int spare_begin, int spare_n, long long window_len, hipStream_t st,
                           const FftPlan *blue, const Switches &sw, const char **kernel, PfbChoice *used = nullptr);
-// the rule of pfb_plan.h asked with a handle's switches and its Bluestein plan (null: none)
-inline PfbSwitches pfb_switches(const Switches &sw) {
-    PfbSwitches p;
-    p.pfb_cu = sw.pfb_cu; p.pfb_direct = sw.pfb_direct; p.pfb_col = sw.pfb_col; p.pfb_cu_nt = sw.pfb_cu_nt;
-    p.pfb_teams = sw.pfb_teams; p.pfb_radix8 = sw.pfb_radix8; p.pfb_fr = sw.pfb_fr; p.pfb_wide = sw.pfb_wide;
-    return p;
-}
-inline bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw) { return pfb_cu_fits(nfft, avg, len, pfb_switches(sw)); }
-inline PfbChoice pfb_choose(int nfft, int avg, const FftPlan *blue, int frames_n, int n_out, int cus, const Switches &sw) {
-    return pfb_choose(nfft, avg, blue ? blue->m : 0, blue ? blue->n_radices : 0, blue ? blue->radices : nullptr, frames_n, n_out,
-                      cus, pfb_switches(sw));
-}
 
 // ---- chirp ---------------------------------------------------------------
 // (every chirp launcher below leaves the form it launched in *used when that is given: chirp_plan.h)

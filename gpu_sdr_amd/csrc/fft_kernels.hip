@@ -1488,7 +1488,8 @@ hipError_t launch_pfb_lds(const float2 *carry, int new_0, const float2 *in, cons
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         cu_count[dev].store(cus);
     }
-    const PfbChoice c = pfb_choose(nfft, avg, blue, frames_n, n_out, cu_count[dev].load(), sw);
+    const PfbChoice c = pfb_choose(nfft, avg, blue ? blue->m : 0, blue ? blue->n_radices : 0, blue ? blue->radices : nullptr, frames_n,
+                                   n_out, cu_count[dev].load(), sw);
     if (used) *used = c;
     if (c.cu)
         return launch_pfb_cu(c, carry, new_0, in, window, tw, nfft, avg, frames_n, sel, n_out, out, carry_out, spare_begin,

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "chirp_plan.h"
+#include "ddc_plan.h"
 #include "decim_state.h"
 #include "pfb_plan.h"
 #include "resmap_state.h"
@@ -259,7 +260,7 @@ int gsdr_pfb_plan(const gsdr_pfb_plan_in *in, gsdr_pfb_plan_out *out) {
     if (!in || !out) return -1;
     if (in->nfft < 1 || in->nfft > gsdr::kPfbLdsMaxN || in->avg < 1 || in->frames < 0 || in->n_out < 1 || in->cus < 1 || in->blue_m < 0)
         return -1;
-    gsdr::PfbSwitches sw;
+    gsdr::Switches sw;
     sw.pfb_cu = in->pfb_cu; sw.pfb_direct = in->pfb_direct != 0; sw.pfb_col = in->pfb_col; sw.pfb_cu_nt = in->pfb_cu_nt;
     sw.pfb_teams = in->pfb_teams != 0; sw.pfb_radix8 = in->pfb_radix8 != 0; sw.pfb_fr = in->pfb_fr; sw.pfb_wide = in->pfb_wide;
     int r[32], nr;
@@ -293,10 +294,68 @@ int gsdr_pfb_plan_many(const gsdr_pfb_plan_in *in, int count, gsdr_pfb_plan_out 
 
 int gsdr_pfb_blue_length(int nfft, int avg, int pfb_bluestein, int pfb_direct, int pfb_radix8) {
     if (nfft < 1 || avg < 1) return 0;
-    gsdr::PfbSwitches sw;
+    gsdr::Switches sw;
     sw.pfb_direct = pfb_direct != 0;
     sw.pfb_radix8 = pfb_radix8 != 0;
     return gsdr::pfb_blue_length(nfft, avg, pfb_bluestein, sw);
+}
+
+// The engine of a DIRECT handle and the shape of one of its launches (ddc_plan.h: the functions the handle itself asks,
+// in the order setup_direct, setup_mfma and enqueue_mfma ask them).
+int gsdr_ddc_plan(const gsdr_ddc_plan_in *in, gsdr_ddc_plan_out *out) {
+    if (!in || !out) return -1;
+    if (in->rate < 1 || in->tones < 1 || in->buffer_len < 1 || in->cus < 1 || in->rows < 0) return -1;
+    const bool decimated = in->decim > 0;
+    if (decimated && (in->buffer_len % in->decim != 0 || in->pf_average < 1 || in->pf_average > gsdr::kMaxF ||
+                      in->decim > 0x7fffffffLL / in->pf_average))
+        return -1;
+    const long long L = in->buffer_len;
+    const int N = in->tones, M = decimated ? (int)in->decim : 1, F = decimated ? (int)in->pf_average : 1;
+    const long long max_rows = decimated ? L / M : 1;
+    if (max_rows > 0x7fffffffLL || in->rows > max_rows) return -1;
+    const long long rows = in->rows > 0 ? in->rows : max_rows;
+    const bool overlap = in->overlapped != 0;
+    gsdr::Switches sw;
+    sw.ddc_mfma = in->ddc_mfma != 0; sw.ddc_few = in->ddc_few != 0; sw.ddc_pipe = in->ddc_pipe != 0; sw.ddc_k = in->ddc_k;
+    sw.ddc_waves = in->ddc_waves; sw.ddc_nch = in->ddc_nch; sw.mfma_asm = in->mfma_asm; sw.mfma_tt = in->mfma_tt;
+    sw.mfma_pk = in->mfma_pk; sw.mfma_w = in->mfma_w; sw.mfma_rt = in->mfma_rt; sw.mfma_w8 = in->mfma_w8 != 0;
+    sw.mfma_prec = in->mfma_prec; sw.mfma_3m = in->mfma_3m; sw.mfma_3m_rot = in->mfma_3m_rot; sw.mfma_fold = in->mfma_fold;
+    sw.mfma_fold_products = in->mfma_fold_products; sw.mfma_wave_tones = in->mfma_wave_tones; sw.mfma_span = in->mfma_span;
+    *out = gsdr_ddc_plan_out{};
+    out->complex_mac_min_blocks = (int)gsdr::kMac3MinBlocks;
+    out->rotation_min_blocks = (int)gsdr::kRot2MinBlocks;
+    out->fold_min_blocks = (int)gsdr::kFoldMinBlocks;
+    out->span128_min_blocks = (int)gsdr::kSpan128MinBlocks;
+    const int simds = in->cus * 4;
+    const gsdr::DdcEngine engine = gsdr::ddc_direct_engine(in->decim, N, M, F, L, sw);
+    out->engine = (int)engine;
+    if (engine != gsdr::DdcEngine::Mfma) {
+        const bool flat = engine == gsdr::DdcEngine::Flat;
+        const gsdr::DdcBlocking b = gsdr::ddc_blocking(flat, M, sw);
+        const int TW = (N + 63) / 64;
+        out->K = b.K; out->pad = b.pad; out->R = b.R;
+        out->target_waves = gsdr::ddc_target_waves(simds, flat, sw);
+        out->tails_nch = gsdr::ddc_tails_nch(F, (int)max_rows, out->target_waves, TW, sw.ddc_nch);
+        out->chunks_want = (int)((long long)(1.3 * out->target_waves) / TW);
+        out->chunks = gsdr::pick_chunks((int)rows, 1.3, out->target_waves, TW, F, out->tails_nch, sw.ddc_nch);
+        return 0;
+    }
+    const gsdr::MfmaTile tile = gsdr::mfma_tile(sw);
+    const int nk8 = (M * F + 7) / 8, ntg = ((N + 31) / 32 + tile.TT - 1) / tile.TT, ntq = (ntg + tile.W - 1) / tile.W;
+    const long long nhi = (nk8 + 3) / 4, ngt = (rows + 31) / 32;
+    const bool images = tile.kind == gsdr::MfmaKernel::AsmRing16 && gsdr::prec_pays(simds, (max_rows + 31) / 32, ntq, nk8, /*overlap=*/true, sw);
+    const gsdr::ProductRule rule = images ? gsdr::product_rule(nhi, max_rows, ntg, sw) : gsdr::ProductRule{};
+    const bool one_loop = rule.mac3;                     // every loop of the family but AsmRing16P belongs to a handle
+    const gsdr::ProductDescribe d = gsdr::product_describe(rule);
+    out->complex_mac = d.complex_mac; out->rotation_blocks = d.rotation_blocks; out->fold = d.fold;
+    out->fold_products = d.fold_products; out->wave_tones = d.wave_tones; out->span_samples = d.span_samples;
+    out->images = images;
+    out->row_tiles_per_workgroup = gsdr::mfma_row_tiles(one_loop, overlap, nk8, ngt, ntq, sw);
+    const gsdr::MfmaKernel kind = one_loop ? gsdr::product_loop_chosen(rule)
+                                           : gsdr::mfma_launch_kernel(tile.kind, images, out->row_tiles_per_workgroup, simds, ngt, ntq, ntg, nk8, overlap, sw);
+    out->preconverted = one_loop || kind == gsdr::MfmaKernel::AsmRing16P;
+    out->eight_waves = kind == gsdr::MfmaKernel::AsmRing16W8;
+    return 0;
 }
 
 // sc16 input widened on the host: an exact int16 -> float conversion and one IEEE multiply per component, what

@@ -1,4 +1,4 @@
-// host_util.h -- what the host sources of libgsdr.so share: demod.cpp (the RX handle) and txgen.cpp (the synthetic
+// host_util.h -- what the host sources of libgsdr.so share: demod.cpp and its demod_*.cpp (the RX handle) and txgen.cpp (the synthetic
 // sources and the TX generator).  Internal to csrc/; nothing here is part of the C ABI.
 #ifndef GSDR_HOST_UTIL_H
 #define GSDR_HOST_UTIL_H

@@ -1,5 +1,5 @@
 // pfb_plan.h -- which kernel takes a TONES / NOISE call in the LDS and in what shape, decided in one place:
-// launch_pfb_lds (fft_kernels.hip) launches what pfb_choose says, the demodulator (demod.cpp) asks the same functions
+// launch_pfb_lds (fft_kernels.hip) launches what pfb_choose says, the demodulator (demod_pfb.cpp) asks the same functions
 // when a handle is created, gsdr_pfb_plan (host_logic.cpp) shows the choice to a caller without a GPU.  No HIP here:
 // host_logic.cpp is built alone by a host compiler.  A Bluestein plan enters as plain integers (its padded length m
 // and the stages of m), not as an FftPlan, which owns device buffers.
@@ -7,6 +7,8 @@
 #define GSDR_PFB_PLAN_H
 
 #include <cstddef>
+
+#include "switches.h"
 
 namespace gsdr {
 
@@ -20,18 +22,6 @@ constexpr int kPfbLdsMaxBytes = (2 * kPfbLdsMaxN + kPfbLdsMaxPrime + 1) * 8;   /
 constexpr int kPfbCuThreads = 1024;
 constexpr int kPfbCuPts = 6;                     // filter points per thread at most: G * n <= 6 * 1024
 constexpr int kPfbCuMaxBytes = 156 * 1024;       // of the 160 KiB of a compute unit
-
-// the GSDR_PFB_* switches the rule reads (Switches, ddc_kernels.h, holds the same values under the same names)
-struct PfbSwitches {
-    int pfb_cu = -1;            // GSDR_PFB_CU, -1: pfb_cu_kernel by shape; 0: never; 1: forced (other values: forced, fill rule kept)
-    bool pfb_direct = true;     // GSDR_PFB_DIRECT, 1: pfb_cu_kernel filters straight out of global memory; 0: through the LDS
-    int pfb_col = -1;           // GSDR_PFB_COL, -1: staged filter column-wise by shape; 1: column-wise; 0: point-wise
-    int pfb_cu_nt = 0;          // GSDR_PFB_CU_NT, 0: pfb_cu_kernel workgroup by shape; 512: two per unit; else 1024
-    bool pfb_teams = true;      // GSDR_PFB_TEAMS, 1: the frames of a run go through their stages in teams; 0: in step
-    bool pfb_radix8 = true;     // GSDR_PFB_RADIX8, 1: radix 8 / 6 / 10 stages in the LDS; 0: radix 4 / 2
-    int pfb_fr = 0;             // GSDR_PFB_FR, 0: pfb_lds_kernel frames per workgroup by shape; > 0: that many
-    int pfb_wide = -1;          // GSDR_PFB_WIDE, -1: pfb_lds_kernel 512 threads from 2048 points; 1: always; 0: 256
-};
 
 // Which of the two kernels launch_pfb_lds() runs for a call of frames_n frames, and its shape
 struct PfbChoice {
@@ -102,7 +92,7 @@ inline int pfb_lds_plan(int n, int *radices, bool radix8) {    // number of stag
 // same box, per 1 M-sample buffer: 256 points 10.1 against 10.3 us, 512: 10.2 / 10.8, 1024: 10.7 / 12.2, 2048:
 // 10.4 / 11.9; 16 points 9.9 against 9.4 and 64 points equal: short frames stay a frame set per workgroup
 // (profiles/r03_pfb_ab_direct.log).  GSDR_PFB_DIRECT=0 switches the direct filter off, and this rule with it.
-inline bool pfb_cu_direct_pays(int nfft, int avg, const PfbSwitches &sw) {
+inline bool pfb_cu_direct_pays(int nfft, int avg, const Switches &sw) {
     return sw.pfb_direct && avg >= 1 && avg <= 4 && nfft >= 128;
 }
 
@@ -148,7 +138,7 @@ inline double pfb_cu_fill(int nfft, int avg, int len, int frames_n, int cus) {
 }
 
 // does one frame fit the run kernel's LDS layout
-inline bool pfb_cu_fits(int nfft, int avg, int len, const PfbSwitches &sw) {
+inline bool pfb_cu_fits(int nfft, int avg, int len, const Switches &sw) {
     int G, bo, bl, twl;
     size_t bytes;
     if (!(nfft >= 1 && avg >= 1 && len >= nfft && len <= kPfbLdsMaxN)) return false;
@@ -161,7 +151,7 @@ inline bool pfb_cu_fits(int nfft, int avg, int len, const PfbSwitches &sw) {
 // The padded length m = 2^ceil(log2(2 nfft - 1)) a handle transforms its frames at through Bluestein's identity inside
 // the workgroup, 0 when it does not: a prime factor above kPfbLdsMaxPrime (or pfb_bluestein 1, GSDR_PFB_BLUESTEIN=1: any
 // length, for tests; 0: never), when a frame at that length fits the LDS.
-inline int pfb_blue_length(int nfft, int avg, int pfb_bluestein, const PfbSwitches &sw) {
+inline int pfb_blue_length(int nfft, int avg, int pfb_bluestein, const Switches &sw) {
     int r[16];
     const bool direct_ok = pfb_lds_plan(nfft, r, sw.pfb_radix8) >= 0;
     long long m = 1;
@@ -173,7 +163,7 @@ inline int pfb_blue_length(int nfft, int avg, int pfb_bluestein, const PfbSwitch
 // The run kernel's shape for a call of frames_n frames; false when it does not take the call.  radices: the stages
 // of the transform (of length len: nfft, or Bluestein's m when blue).
 inline bool pfb_cu_choose(PfbChoice &c, int nfft, int avg, int len, bool blue, int n_radices, const int *radices,
-                          int frames_n, int n_out, int cus, const PfbSwitches &sw) {
+                          int frames_n, int n_out, int cus, const Switches &sw) {
     // one workgroup per compute unit: G consecutive frames each (frames_n == 0: a launch that only copies the carry)
     const int want = frames_n > 0 ? (frames_n + cus - 1) / cus : 1;
     if (n_out > nfft) return false;                       // the bin table in the LDS is sized for n_out <= nfft
@@ -237,7 +227,7 @@ inline bool pfb_cu_choose(PfbChoice &c, int nfft, int avg, int len, bool blue, i
 
 // blue_m > 0: the frames go through Bluestein's identity at that padded length, whose stages are blue_radices
 inline PfbChoice pfb_choose(int nfft, int avg, int blue_m, int blue_n_radices, const int *blue_radices, int frames_n, int n_out,
-                            int cus, const PfbSwitches &sw) {
+                            int cus, const Switches &sw) {
     PfbChoice c{};
     int r[16];
     const int nr = pfb_lds_plan(nfft, r, sw.pfb_radix8);

@@ -432,6 +432,46 @@ int gsdr_pfb_plan_many(const gsdr_pfb_plan_in *in, int count, gsdr_pfb_plan_out 
  * and pfb_radix8 as above. */
 int gsdr_pfb_blue_length(int nfft, int avg, int pfb_bluestein, int pfb_direct, int pfb_radix8);
 
+/* The engine a DIRECT handle takes and the shape of one of its launches (csrc/ddc_plan.h: the functions the handle
+ * itself asks when it is created and call by call; host only, no GPU needed).  in: the shape (tones, rate, decim,
+ * pf_average, buffer_len) as gsdr_param_c holds it; rows, the output rows of the launch asked about (0: those of a
+ * whole buffer, buffer_len / decim, which is what every DIRECT call launches); overlapped 0 an in-order entry
+ * (gsdr_demod_process*), 1 a pipelined one (gsdr_demod_submit*); the device's compute units; and the switches by value
+ * as read_switches leaves them (unset: ddc_mfma 1, ddc_few 1, ddc_pipe 1, ddc_k -1, ddc_waves 0, ddc_nch 0, mfma_asm 4,
+ * mfma_tt 1, mfma_pk 32, mfma_w 4, mfma_rt 0, mfma_w8 1, and -1 for mfma_prec, mfma_3m, mfma_3m_rot, mfma_fold,
+ * mfma_fold_products, mfma_wave_tones, mfma_span).
+ * out: the engine; for the VALU engines (FLAT, GENERIC, and the table length K of MIX) the sub-block length K with pad
+ * and R, the resident waves the grid is sized for, the chunk slots of the tails buffer, and the chunks of a launch of
+ * `rows` blocks at the grid ratio 1.3 (a handle on the flat kernel times its own ratio at creation) with the count the
+ * balancing started from; for the matrix cores the values gsdr_demod_describe reports -- complex_mac, rotation_blocks,
+ * fold, fold_products, wave_tones, span_samples --, whether the handle holds pre-converted images (apart from the
+ * 8 GiB cap of an image set, which only the handle applies), whether this launch is pre-converted,
+ * row_tiles_per_workgroup and whether it runs the eight-wave kernel; fields of the other engines are 0.  The four
+ * thresholds (windows in 32-sample blocks) are given whatever the engine.
+ * Returns 0, or -1 for what gsdr_demod_create refuses of these fields (rate, tones, buffer_len < 1; with decim > 0:
+ * buffer_len no multiple of decim, pf_average outside [1, 8], decim * pf_average above 2^31 - 1) and for rows outside
+ * [0, buffer_len / decim] or cus < 1. */
+#define GSDR_DDC_ENGINE_MIX 0        /* decim <= 0: mix_kernel / mix_few_kernel */
+#define GSDR_DDC_ENGINE_FEW 1        /* ddc_few_kernel */
+#define GSDR_DDC_ENGINE_FLAT 2       /* ddc_flat_kernel */
+#define GSDR_DDC_ENGINE_GENERIC 3    /* ddc_kernel */
+#define GSDR_DDC_ENGINE_MFMA 4       /* the matrix cores */
+typedef struct gsdr_ddc_plan_in {
+    long long decim, pf_average, buffer_len;
+    int tones, rate, rows, overlapped, cus;
+    int ddc_mfma, ddc_few, ddc_pipe, ddc_k, ddc_waves, ddc_nch;
+    int mfma_asm, mfma_tt, mfma_pk, mfma_w, mfma_rt, mfma_w8, mfma_prec;
+    int mfma_3m, mfma_3m_rot, mfma_fold, mfma_fold_products, mfma_wave_tones, mfma_span;
+} gsdr_ddc_plan_in;
+typedef struct gsdr_ddc_plan_out {
+    int engine;
+    int K, pad, R, target_waves, tails_nch, chunks, chunks_want;
+    int complex_mac, rotation_blocks, fold, fold_products, wave_tones, span_samples;
+    int images, preconverted, row_tiles_per_workgroup, eight_waves;
+    int complex_mac_min_blocks, rotation_min_blocks, fold_min_blocks, span128_min_blocks;
+} gsdr_ddc_plan_out;
+int gsdr_ddc_plan(const gsdr_ddc_plan_in *in, gsdr_ddc_plan_out *out);
+
 /* ---- the pyUSRP command surface (host only) ------------------------------
  * One JSON command per measurement arrives on the async socket, framed by an
  * 8-byte header; results leave on the data socket as 21-byte header + complex64

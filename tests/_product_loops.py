@@ -52,7 +52,7 @@ def is_loop(dem, name):
     return True
 
 
-# DIRECT_CASES the matrix-core engine does not take (setup rules of csrc/demod.cpp: the zero padding
+# DIRECT_CASES the matrix-core engine does not take (setup rules of csrc/ddc_plan.h: the zero padding
 # behind a window must fit the next block, a buffer holds at least F-1 blocks): they run the generic
 # VALU kernel under every GSDR_MFMA_* setting, today's mfma16p engine included
 VALU_CASES = {(1, 1000, 10, 8, 1000, 5), (5, 1000, 50, 4, 100, 7), (4, 1_000_000, 7, 3, 7000, 3)}
@@ -266,9 +266,11 @@ FUZZ_N = (1, 2, 5, 31, 32, 33, 63, 64, 65, 130, 257)
 
 
 def matrix_cores_take(M, F, L):
-    """The setup rule of csrc/demod.cpp (setup_direct): a buffer holds the carry, and the zero padding behind a window
-    fits the next block."""
-    return L // M >= F - 1 and L >= 4 and (M * F + 31) // 32 * 32 - M * F <= M
+    """The setup rule of csrc/ddc_plan.h (ddc_mfma_takes_direct), asked of the library under the switches of COMMON: a
+    buffer holds the carry, and the zero padding behind a window fits the next block."""
+    import _ddc_plan
+    from gpu_sdr_amd import _lib
+    return _ddc_plan.plan(_lib.lib(), 1, M, F, L, env=COMMON)["engine"] == "mfma"
 
 
 def loop_fuzz_shapes():

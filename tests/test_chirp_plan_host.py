@@ -9,7 +9,7 @@ import ctypes as C
 import pytest
 
 PLAIN, SPLIT, GENERIC = 0, 1, 2
-CAP = 16384                     # kChirpPartials of csrc/demod.cpp
+CAP = 16384                     # kChirpPartials of csrc/demod_state.h
 
 
 def plan(lib, steps, length, ppt, index0, valid, chirps, split=1, cap=CAP):

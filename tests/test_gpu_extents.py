@@ -23,6 +23,7 @@ import os
 import numpy as np
 import pytest
 
+import _ddc_plan
 from _extents import PATTERNS, check_input_untouched, check_output, guarded_input, guarded_output
 from _product_loops import LOOPS
 from test_gpu_parity import (CHIRP_CASES, PFB_LDS_KERNELS, PFB_VARIANTS, TOL, crandn, make_chirp, make_direct, make_pfb,
@@ -195,7 +196,7 @@ S_C3 = (7, 200_000_000, 1000, 4, 50_000)        # the C3 block, 50 rows
 S_TWO_ROWS = (5, 1000, 50, 4, 100)              # two rows, the carry (150 samples) longer than a buffer
 DIRECT_SHAPES = [S_LAST_ROW, S_N65, S_ODD, S_C3, S_TWO_ROWS]
 
-# Shapes an engine's chooser refuses (csrc/demod.cpp, gsdr_demod_create) run on the smallest shape it takes that
+# Shapes an engine's chooser refuses (csrc/ddc_plan.h, gsdr_demod_create) run on the smallest shape it takes that
 # keeps what the shape is there for:
 #   matrix cores   the zero padding behind a window must fit one row stride, (M*F + 31)/32*32 - M*F <= M (middle rows
 #                  read the caller's buffer in whole blocks), and a buffer holds the carry, L/M >= F - 1.
@@ -211,8 +212,8 @@ REPLACED = {
 # the library's own choice: the generic kernel where the matrix cores refuse, ddc_few_kernel for <= 32 tones at M >= 512
 DEFAULT_KERNEL = {S_LAST_ROW: "ddc_kernel", S_N65: "ddc_mfma_ring16_kernel", S_ODD: "ddc_mfma_ring16_kernel",
                   S_C3: "ddc_few_kernel", S_TWO_ROWS: "ddc_kernel"}
-MAC3_MIN_BLOCKS = 94        # kMac3MinBlocks = kRot2MinBlocks (csrc/demod.cpp): a pre-converted handle left to itself takes
-#                             three products and the pair rotation from windows of 94 blocks
+# kMac3MinBlocks = kRot2MinBlocks (csrc/ddc_plan.h, read from gsdr_ddc_plan): a pre-converted handle left to itself takes
+# three products and the pair rotation from windows of that many blocks
 
 
 def direct_inputs(shape, oracle_mod):
@@ -242,7 +243,7 @@ def test_direct_extents(cuda_device, gsdr_lib, oracle_mod, monkeypatch, engine, 
     N, rate, M, F, L = shape
     new = ()
     if mac == "by window":
-        mac = (3, 2) if (M * F + 31) // 32 >= MAC3_MIN_BLOCKS else (4, 1)
+        mac = (3, 2) if (M * F + 31) // 32 >= _ddc_plan.plan(gsdr_lib, N, M, F, L, env=env)["complex_mac_min_blocks"] else (4, 1)
         new = ("ddc_mfma_ring16_kernel",) if mac == (4, 1) else ()
     clean_env(monkeypatch, env)
     freq, xs, yrs = direct_inputs(shape, oracle_mod)

@@ -115,7 +115,7 @@ def _fold_of(M):
 
 
 def test_hdr_comb_fold_keeps_the_rule(cuda_device, gsdr_lib, oracle_mod, monkeypatch):
-    """The measurement behind kFoldMinBlocks (csrc/demod.cpp): the 60 dB comb of test_gpu_mfma3.py (64 tones at
+    """The measurement behind kFoldMinBlocks (csrc/ddc_plan.h): the 60 dB comb of test_gpu_mfma3.py (64 tones at
     200 Msps, F = 4, L = 200 * M, pre-converted operands forced), windows of 94, 125, 250 blocks, three buffers.
     Rule, per tone: err <= max(1e-5, 3 x err32), err32 the error of the reference's own fp32 order of operations
     (oracle/recipe_b.py, complex64) against the fp64 oracle on the same buffers.  Asserted for GSDR_MFMA_FOLD unset

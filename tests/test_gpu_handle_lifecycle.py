@@ -33,7 +33,7 @@ def chirp(decim, L=500):
 # id: (environment of the creation, parameters, frame average, what describe() must say)
 PATHS = {
     # decim 10 x pf_average 4: the 24 samples that pad the 40-sample window to whole 32-sample blocks are more than a
-    # block of 10, which fails the padding condition of setup_direct (csrc/demod.cpp): this shape runs the generic
+    # block of 10, which fails the padding condition of ddc_mfma_takes_direct (csrc/ddc_plan.h): this shape runs the generic
     # ddc_kernel; the two shapes below it do run the matrix cores
     "direct": ({}, direct(10, 1000), 1, dict(family="fp32 VALU")),
     "direct_mfma": ({}, direct(32, 3200), 1, dict(family="f16 MFMA, hi/lo split", complex_mac=4)),

@@ -81,7 +81,7 @@ HDR_DECIMS = [256, 375, 500, 750, 1000, 2000]       # windows of 32, 47, 63, 94,
 
 @pytest.mark.parametrize("span_db", [60, 40])
 def test_hdr_comb_sets_threshold(cuda_device, gsdr_lib, oracle_mod, monkeypatch, span_db):
-    """(e) The measurement behind kMac3MinBlocks (csrc/demod.cpp).  64 tones spanning 40 / 60 dB at
+    """(e) The measurement behind kMac3MinBlocks (csrc/ddc_plan.h).  64 tones spanning 40 / 60 dB at
     200 Msps, F = 4, L = 200 * M, windows of 32 ... 250 blocks, pre-converted operands forced.  Rule, per tone:
     err <= max(1e-5, 3 x err32), err32 the error of the reference's own fp32 order of operations
     (oracle/recipe_b.py, complex64) on the same buffers -- the rule of test_direct_high_dynamic_range_comb.

@@ -99,7 +99,7 @@ HDR_R2_DECIMS = [750, 1000, 2000]        # windows of 94, 125, 250 blocks
 
 
 def test_hdr_comb_default_keeps_the_rule(cuda_device, gsdr_lib, oracle_mod, monkeypatch):
-    """The measurement behind kRot2MinBlocks (csrc/demod.cpp): the 60 dB comb of test_gpu_mfma3.py
+    """The measurement behind kRot2MinBlocks (csrc/ddc_plan.h): the 60 dB comb of test_gpu_mfma3.py
     (64 tones at 200 Msps, F = 4, L = 200 * M, pre-converted operands forced), windows of 94, 125, 250 blocks.
     Rule, per tone: err <= max(1e-5, 3 x err32), err32 the error of the reference's own fp32 order of operations
     (oracle/recipe_b.py, complex64) against the fp64 oracle on the same buffers.  Asserted for GSDR_MFMA_3M_ROT unset
