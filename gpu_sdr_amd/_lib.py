@@ -257,6 +257,20 @@ SIGNATURES = [
     ("gsdr_resmap_get_offsets", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int]),
     ("gsdr_resmap_get_channels", C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     ("gsdr_resmap_close", None, [_vp]),
+    ("gsdr_stats_create", _vp, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    ("gsdr_stats_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_stats_feed_host", C.c_int, [_vp, _vp, C.c_int]),
+    ("gsdr_stats_read_device", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_stats_read", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_stats_read_host", C.c_int, [_vp, _vp]),
+    ("gsdr_stats_counts", C.c_int, [_vp, _vp, _vp]),
+    ("gsdr_stats_quantiles", C.c_int, [_vp, C.POINTER(C.c_double), C.c_int, _vp, _vp]),
+    ("gsdr_stats_levels", C.c_int, [_vp, C.c_int, C.c_double, _vp, _vp, _vp]),
+    ("gsdr_stats_reset", C.c_int, [_vp, _vp]),
+    ("gsdr_stats_rows", C.c_longlong, [_vp]),
+    ("gsdr_stats_lanes", C.c_int, [_vp]),
+    ("gsdr_stats_n_bins", C.c_int, [_vp]),
+    ("gsdr_stats_close", None, [_vp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
@@ -268,6 +282,12 @@ SWEEP_HOST = -2             # GSDR_SWEEP_HOST
 SWEEP_MAX_FEED = 1 << 24    # GSDR_SWEEP_MAX_FEED
 RESMAP_HOST = -2            # GSDR_RESMAP_HOST
 RESMAP_NCONST = 7           # GSDR_RESMAP_NCONST
+STATS_HOST = -2             # GSDR_STATS_HOST
+STATS_MAX_BINS = 4096       # GSDR_STATS_MAX_BINS
+STATS_MAX_LANES = 32768     # GSDR_STATS_MAX_LANES
+STATS_MAX_QUANTILES = 16    # GSDR_STATS_MAX_QUANTILES
+STATS_CENTRE_MEAN = 0       # GSDR_STATS_CENTRE_MEAN
+STATS_CENTRE_MEDIAN = 1     # GSDR_STATS_CENTRE_MEDIAN
 
 
 class TriggerLevelC(C.Structure):

@@ -1,5 +1,5 @@
-// stage_state.h -- what the five objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
-// gsdr_sweep_*, gsdr_resmap_*: the STAGES) share between host_logic.cpp and their device sources: the type of `dev`,
+// stage_state.h -- what the six objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
+// gsdr_sweep_*, gsdr_resmap_*, gsdr_stats_*: the STAGES) share between host_logic.cpp and their device sources: the type of `dev`,
 // the one release hook, the host side's refusal and the device_index check of every create.  The X_state.h of each
 // stage includes it.  No HIP here: host_logic.cpp is built alone by a host compiler (tests/test_*_sanitizers.py), where
 // the hooks are absent and only host objects exist.
@@ -10,7 +10,8 @@
 
 #include "../../include/gsdr.h"
 
-static_assert(GSDR_TRIGGER_HOST == -2 && GSDR_WELCH_HOST == -2 && GSDR_DECIM_HOST == -2 && GSDR_SWEEP_HOST == -2 && GSDR_RESMAP_HOST == -2,
+static_assert(GSDR_TRIGGER_HOST == -2 && GSDR_WELCH_HOST == -2 && GSDR_DECIM_HOST == -2 && GSDR_SWEEP_HOST == -2 && GSDR_RESMAP_HOST == -2 &&
+                  GSDR_STATS_HOST == -2,
               "every stage names its host twin by the same device_index");
 
 namespace gsdr {

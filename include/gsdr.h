@@ -994,6 +994,108 @@ int gsdr_resmap_get_offsets(const gsdr_resmap *r, double *xy, int cap);
 int gsdr_resmap_get_channels(const gsdr_resmap *r, int *channels, int cap);
 void gsdr_resmap_close(gsdr_resmap *r);
 
+/* ---- row statistics on the device: per-channel moments, histograms and trigger levels, behind demodulated rows (an
+ * extension: the reference's only trigger in use takes the median and the standard deviation of each packet on the host,
+ * ref: pyUSRP/USRP_triggers.py:165-248, amplitude_trigger) ---------------------------------------------------------------
+ * A stats object sees ONE stream of rows of n_ch complex64 each -- the [row][channel] layout every RX entry and the
+ * resmap object write -- numbered 0, 1, 2, ... from creation (or from gsdr_stats_reset), arriving in FEEDS of
+ * 0 <= n_rows <= max_rows rows.  Per channel it keeps sums in double, the extremes and a histogram of one real quantity
+ * q; a read gives the mean, the variance and the extremes, gsdr_stats_quantiles order statistics to within one bin, and
+ * gsdr_stats_levels a table gsdr_trigger_set_levels takes: rows -> (resmap ->) stats -> levels -> trigger stays on the
+ * card, 24 bytes per channel cross to the host and back.
+ * Axes.  axes[c] is the trigger's own struct.  {bx, by, dx, dy} are the projection; lo < hi, both finite, is the
+ *   HISTOGRAM RANGE of channel c (not a trigger level).  From them the host derives once, in double:
+ *   p = 0.5 ((double)lo + (double)hi), the pivot; inv_w = n_bins / ((double)hi - (double)lo);
+ *   w = ((double)hi - (double)lo) / n_bins, the width of a bin.
+ * Per sample y of channel c, every operation one IEEE operation rounded to nearest, nothing fused:
+ *     t0 = y.x - bx;  t1 = y.y - by;  p0 = t0 * dx;  p1 = t1 * dy;  q = p0 + p1        (float32: exactly the trigger's q)
+ *   A non-finite q (NaN, +-Inf) counts in `bad` and enters nothing else.  Otherwise:
+ *   Chains.  Row r of channel c belongs to chain j = r mod lanes.  With d = (double)q - p the chain does S_j = S_j + d
+ *     and Q_j = Q_j + fl64(d d), and keeps min_j = (q < min_j ? q : min_j) and max_j = (q > max_j ? q : max_j) in
+ *     float32 (an equal value, -0 against +0 included, leaves the earlier one).  A chain starts at S = Q = +0,
+ *     min = +Inf, max = -Inf and takes its rows in stream order.
+ *   Bins.  q < lo: `under`.  Otherwise k = floor(((double)q - (double)lo) inv_w) in double; k >= n_bins: `over` (so
+ *     q == hi is over); else bins[k].  Counters are unsigned 64-bit; counts[c] has n_bins + 3 of them:
+ *     [0] = under, [1 .. n_bins] = the bins, [n_bins + 1] = over, [n_bins + 2] = bad.
+ * Read (does not disturb the accumulation; any number of reads).  n = under + sum of bins + over.  The chains are combined
+ *   by the fixed halving tree: for h = lanes/2, lanes/4, ..., 1: s[j] = s[j] (+) s[j + h] for j < h, where (+) adds S and
+ *   Q in double and takes min and max by the rule above with s[j] the earlier.  mean = p + S / n;
+ *   var = (Q - S (S / n)) / (n - 1), a negative result replaced by +0, a NaN kept: every operation rounded, no fma.
+ *   n == 0: mean and var are NaN, min = +Inf, max = -Inf.  n == 1: var is NaN.  One gsdr_stats_summary of 64 bytes per
+ *   channel.  The variance divides by n - 1.
+ *   What the pivot buys: the sums hold d = q - p, not q, so the variance loses n 2^-52 (1 + ((mean - p) / sigma)^2) at
+ *   the worst -- below 1e-9 relative up to n = 2^17 with the pivot within 10 sigma of the mean.  A range that wide of
+ *   the data is what the two-pass use is for: a coarse range first, gsdr_stats_levels, then gsdr_stats_reset with
+ *   mean -/+ 8 sigma.
+ * Quantile pr in (0, 1].  t = max(1, ceil(pr (double)n)), one double multiply.  n == 0: NaN.  under >= t: -Inf.
+ *   Otherwise the first bin k whose cumulative count under + bins[0] + ... + bins[k] reaches t; with C the count below
+ *   it and h its own: (double)lo + ((double)k + (((double)(t - C) - 0.5) / (double)h)) w, in that order of operations.  A
+ *   rank in `over`: +Inf.  The estimate and the order statistic x_(t) lie in the same bin: the error is below w by
+ *   construction.
+ * Levels.  gsdr_stats_levels writes out_host[n_ch]: bx .. dy copied from the axes, lo = fl32(c - nsigma sigma),
+ *   hi = fl32(c + nsigma sigma) with c the mean (GSDR_STATS_CENTRE_MEAN) or the quantile 0.5
+ *   (GSDR_STATS_CENTRE_MEDIAN), sigma = sqrt(var) and nsigma sigma one double product.  A channel is switched off
+ *   (lo = -Inf, hi = +Inf) when on is not NULL and on[c] == 0, when n < 2, or when c or sigma is not finite.  sigma
+ *   divides by n - 1 where the reference's np.std divides by n: the ratio is sqrt(1 - 1/n).  nsigma must be finite
+ *   and >= 0.
+ * Consequences.  No result depends, bit for bit, on where the stream is cut into feeds.  The host twin returns the
+ *   device's bits.  A non-finite sample changes only its own channel's `bad`.  The sums (not the counts, the extremes
+ *   or the quantiles) depend on `lanes`, reproducibly, and on nothing else about the launch.
+ * gsdr_stats_create: 1 <= n_ch <= 2^20, 1 <= max_rows <= 2^20, 1 <= n_bins <= 4096; lanes 0 (a host rule picks it, a
+ *   pure function of n_ch and max_rows: the smallest power of two with n_ch lanes >= 65536, at most the largest power
+ *   of two <= max_rows and at most 32768) or a power of two in [1, 32768]; axes[n_ch] not NULL with lo < hi finite in
+ *   every entry; device_index >= -1 as in gsdr_param_c or GSDR_STATS_HOST for a host-only object that touches no GPU.
+ *   Anything else is refused before the device is touched: NULL, and gsdr_last_error(NULL) starts with
+ *   "gsdr_stats_create: " and names the argument.  Everything every entry needs is allocated here (24 bytes per chain
+ *   and channel, 8 (n_bins + 3) per channel, the staging of the reads), every byte count in 64 bits; a failed
+ *   allocation is a refusal that states the MiB.
+ * gsdr_stats_feed_device: ONE launch on hip_stream (hipStream_t as void*): no allocation, no synchronisation, no
+ *   read-back; reads exactly rows_dev[0, n_rows n_ch) and writes nothing the caller can see; 0, or -1 with
+ *   gsdr_last_error(NULL).  rows_dev needs 8-byte alignment only and may point anywhere into a larger allocation.
+ *   n_rows == 0 is valid and touches no pointer; n_rows outside [0, max_rows]: -1, state unchanged.
+ * gsdr_stats_read_device: one launch on hip_stream; writes exactly summary_dev[0, n_ch) (8-byte aligned).
+ *   gsdr_stats_read: the same launch into the object's staging, then waits for hip_stream and copies to summary_host.
+ * gsdr_stats_counts (counts_host[n_ch][n_bins + 3]), gsdr_stats_quantiles (1 <= n_p <= GSDR_STATS_MAX_QUANTILES,
+ *   every pr in (0, 1], out_host[n_ch][n_p] doubles) and gsdr_stats_levels take either kind of object: on a device
+ *   object they enqueue on hip_stream, wait for it and copy; on a host object the stream is ignored.
+ * gsdr_stats_feed_host / _read_host: GSDR_STATS_HOST objects only (and the device feed and reads are refused on them): a
+ *   BIT TWIN of the device.
+ * gsdr_stats_reset(s, axes): restarts the row numbering at 0 and empties the chains and the counters; with axes not NULL
+ *   the object takes the new ranges and projections (checked as at creation; a refusal leaves everything as it was).
+ *   On a device object it waits for the device, zeroes, and waits again.
+ * Stream order is the caller's, as for the trigger: the object remembers no stream and waits for none.  Consecutive calls
+ *   on one object must be ordered by the caller (one stream, or events between streams); rows_dev must stay unchanged
+ *   until the feed that reads it has finished.  On a NULL object close is a no-op, the getters return 0, the rest
+ *   return -1 with the reason. */
+#define GSDR_STATS_HOST (-2)
+#define GSDR_STATS_MAX_BINS 4096
+#define GSDR_STATS_MAX_LANES 32768
+#define GSDR_STATS_MAX_QUANTILES 16
+#define GSDR_STATS_CENTRE_MEAN 0
+#define GSDR_STATS_CENTRE_MEDIAN 1
+typedef struct gsdr_stats_summary {
+    unsigned long long n, bad, under, over;
+    double mean, var;
+    float min, max;
+    unsigned char reserved[8]; /* zero */
+} gsdr_stats_summary;
+typedef struct gsdr_stats gsdr_stats;
+gsdr_stats *gsdr_stats_create(int n_ch, int max_rows, int n_bins, int lanes, const gsdr_trigger_level *axes, int device_index);
+int gsdr_stats_feed_device(gsdr_stats *s, const gsdr_c64 *rows_dev, int n_rows, void *hip_stream);
+int gsdr_stats_feed_host(gsdr_stats *s, const gsdr_c64 *rows, int n_rows);
+int gsdr_stats_read_device(gsdr_stats *s, gsdr_stats_summary *summary_dev, void *hip_stream);
+int gsdr_stats_read(gsdr_stats *s, gsdr_stats_summary *summary_host, void *hip_stream);
+int gsdr_stats_read_host(gsdr_stats *s, gsdr_stats_summary *summary);
+int gsdr_stats_counts(gsdr_stats *s, unsigned long long *counts_host /* n_ch x (n_bins + 3) */, void *hip_stream);
+int gsdr_stats_quantiles(gsdr_stats *s, const double *pr, int n_p, double *out_host /* n_ch x n_p */, void *hip_stream);
+int gsdr_stats_levels(gsdr_stats *s, int centre, double nsigma, const unsigned char *on /* n_ch bytes, or NULL */,
+                      gsdr_trigger_level *out_host, void *hip_stream);
+int gsdr_stats_reset(gsdr_stats *s, const gsdr_trigger_level *axes /* n_ch, or NULL */);
+long long gsdr_stats_rows(const gsdr_stats *s);
+int gsdr_stats_lanes(const gsdr_stats *s);
+int gsdr_stats_n_bins(const gsdr_stats *s);
+void gsdr_stats_close(gsdr_stats *s);
+
 #ifdef __cplusplus
 }
 #endif
