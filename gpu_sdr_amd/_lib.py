@@ -270,6 +270,7 @@ SIGNATURES = [
     ("gsdr_stats_rows", C.c_longlong, [_vp]),
     ("gsdr_stats_lanes", C.c_int, [_vp]),
     ("gsdr_stats_n_bins", C.c_int, [_vp]),
+    ("gsdr_stats_plan", C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     ("gsdr_stats_close", None, [_vp]),
 ]
 

@@ -1549,6 +1549,14 @@ int gsdr_stats_lanes(const gsdr_stats *s) { return s ? s->lanes : 0; }
 
 int gsdr_stats_n_bins(const gsdr_stats *s) { return s ? s->n_bins : 0; }
 
+// The launch of a feed (stats_state.h: the function launch_stats_feed itself asks).
+int gsdr_stats_plan(int n_ch, int n_bins, int lanes, int out[4]) {
+    if (!out || !gsdr::stats_shape_ok(n_ch, n_bins, lanes)) return -1;
+    const gsdr::StatsPlan p = gsdr::stats_plan_of(n_ch, n_bins, lanes);
+    out[0] = p.tile, out[1] = p.tiles, out[2] = p.splits, out[3] = (int)p.lds_bytes;
+    return 0;
+}
+
 int gsdr_stats_reset(gsdr_stats *s, const gsdr_trigger_level *axes) {
     const char *const me = "gsdr_stats_reset";
     if (!s) return stage_refuse(me, "null object");

@@ -30,14 +30,8 @@ struct StatsFeed {
     long long row0;
 };
 
-// What a feed's launch looks like: `tile` channels by 256 / tile chains per workgroup, a grid of tiles x splits.
-struct StatsPlan {
-    int tile, tiles, splits;
-    unsigned lds_bytes;                  // tile x (n_bins + 3) counters of 32 bits
-};
-StatsPlan stats_plan_of(int n_ch, int n_bins, int lanes);
-
-// stats_feed_kernel on st
+// stats_feed_kernel on st, in the shape stats_plan_of (stats_state.h) gives: `tile` channels by 256 / tile chains per
+// workgroup, a grid of tiles x splits, lds_bytes of dynamic LDS
 hipError_t launch_stats_feed(const StatsFeed &f, hipStream_t st);
 
 // A read: the summaries and, with n_p > 0, the quantiles quant[n_ch][n_p].  Either output may be null.

@@ -32,8 +32,6 @@ namespace gsdr {
 namespace {
 
 constexpr int kStatsDepth = 8;           // rows a thread of stats_feed_kernel has in flight
-constexpr int kStatsMaxTile = 32;        // channels of a workgroup: 256 bytes of a row per wave-instruction
-constexpr unsigned kStatsMaxLds = 65536; // bytes of the table a workgroup may ask for
 
 struct StatsFeedArgs {
     StatsFeed f;
@@ -206,33 +204,14 @@ __global__ __launch_bounds__(256) GSDR_NO_PK void stats_read_kernel(const StatsR
     }
 }
 
-bool pow2(int v) { return v >= 1 && (v & (v - 1)) == 0; }
-
-bool shape_ok(int n_ch, int n_bins, int lanes) {
-    return n_ch >= 1 && n_ch <= (1 << 20) && n_bins >= 1 && n_bins <= GSDR_STATS_MAX_BINS && pow2(lanes) && lanes <= GSDR_STATS_MAX_LANES;
-}
-
 }  // namespace
 
-StatsPlan stats_plan_of(int n_ch, int n_bins, int lanes) {
-    StatsPlan p{};
-    const unsigned per_channel = (unsigned)(n_bins + 3) * (unsigned)sizeof(unsigned);     // <= 16396
-    p.tile = 1;
-    // as many channels as the table has room for, no more than there are, at most kStatsMaxTile
-    while (2 * p.tile <= kStatsMaxTile && (unsigned)(2 * p.tile) * per_channel <= kStatsMaxLds && p.tile < n_ch) p.tile *= 2;
-    p.tiles = (n_ch + p.tile - 1) / p.tile;
-    const int chains = 256 / p.tile;
-    p.splits = (lanes + chains - 1) / chains;
-    p.lds_bytes = (unsigned)p.tile * per_channel;
-    return p;
-}
-
 hipError_t launch_stats_feed(const StatsFeed &f, hipStream_t st) {
-    if (!shape_ok(f.n_ch, f.n_bins, f.lanes) || f.n_rows < 1 || f.n_rows > (1 << 20) || f.row0 < 0 || !f.rows || !f.axes || !f.counts ||
+    if (!stats_shape_ok(f.n_ch, f.n_bins, f.lanes) || f.n_rows < 1 || f.n_rows > (1 << 20) || f.row0 < 0 || !f.rows || !f.axes || !f.counts ||
         !f.chains.S || !f.chains.Q || !f.chains.mn || !f.chains.mx)
         return hipErrorInvalidValue;
     const StatsPlan p = stats_plan_of(f.n_ch, f.n_bins, f.lanes);
-    if (p.lds_bytes > kStatsMaxLds || p.tiles < 1 || p.splits < 1 || p.splits > 65535) return hipErrorInvalidValue;
+    if (p.lds_bytes > kStatsMaxLds || p.tiles < 1 || p.splits < 1 || p.splits > kStatsMaxSplits) return hipErrorInvalidValue;
     StatsFeedArgs a{};
     a.f = f, a.tile = p.tile;
     while ((1 << a.tile_log2) < p.tile) ++a.tile_log2;
@@ -242,7 +221,7 @@ hipError_t launch_stats_feed(const StatsFeed &f, hipStream_t st) {
 }
 
 hipError_t launch_stats_read(const StatsRead &r, hipStream_t st) {
-    if (!shape_ok(r.n_ch, r.n_bins, r.lanes) || !r.axes || !r.counts || !r.chains.S || !r.chains.Q || !r.chains.mn || !r.chains.mx ||
+    if (!stats_shape_ok(r.n_ch, r.n_bins, r.lanes) || !r.axes || !r.counts || !r.chains.S || !r.chains.Q || !r.chains.mn || !r.chains.mx ||
         (!r.summary && !r.quant) || r.n_p < 0 || r.n_p > GSDR_STATS_MAX_QUANTILES || (r.quant && r.n_p < 1))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(stats_read_kernel, dim3((unsigned)r.n_ch), dim3(256), 0, st, r);

@@ -1,7 +1,8 @@
 // stats_state.h -- the row statistics (include/gsdr.h, "row statistics on the device") as host_logic.cpp, stats.cpp and
 // stats_kernels.hip share them: the object, a channel's axis as the tables hold it, a chain, and THE LAWS -- the
 // per-sample law, the combination of two chains, the summary and the quantile -- as inline host-and-device functions
-// that the kernels and the host twin both include: there is one text of the arithmetic.  host_logic.cpp owns creation,
+// that the kernels and the host twin both include: there is one text of the arithmetic -- and the launch rule of a feed
+// (stats_plan_of), which the launcher and gsdr_stats_plan both ask.  host_logic.cpp owns creation,
 // the refusals, the lanes rule, the levels and the host twin; stats.cpp hangs the device part on `dev` through the hooks
 // below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host compiler
 // (tests/test_stats_sanitizers.py), where the hooks are absent and only host objects exist.
@@ -62,6 +63,42 @@ inline int gsdr_stats_lanes_rule(int n_ch, int max_rows) {
     while (lanes < GSDR_STATS_MAX_LANES && (long long)lanes * n_ch < kStatsChainTarget && 2 * lanes <= max_rows) lanes *= 2;
     return lanes;
 }
+
+// THE LAUNCH RULE of a feed (stats_kernels.hip launches what it says and decides nothing itself; gsdr_stats_plan gives
+// the same answer without a GPU; tests/test_stats_host.py pins it at its edges).  A workgroup of 256 threads owns `tile`
+// channels by 256 / tile chains and counts the bins in an LDS table [tile][n_bins + 3] of 32-bit counters; the grid is
+// tiles x splits.
+namespace gsdr {
+
+constexpr int kStatsMaxTile = 32;        // channels of a workgroup: 256 bytes of a row per wave-instruction
+constexpr unsigned kStatsMaxLds = 65536; // bytes of the table a workgroup may ask for
+constexpr int kStatsMaxSplits = 65535;   // the grid's y
+
+struct StatsPlan {
+    int tile, tiles, splits;
+    unsigned lds_bytes;                  // tile x (n_bins + 3) counters of 32 bits
+};
+
+// what gsdr_stats_create accepts of the three (a lanes of 0 has become the rule's value by then)
+inline bool stats_shape_ok(int n_ch, int n_bins, int lanes) {
+    return n_ch >= 1 && n_ch <= (1 << 20) && n_bins >= 1 && n_bins <= GSDR_STATS_MAX_BINS && lanes >= 1 && lanes <= GSDR_STATS_MAX_LANES &&
+           (lanes & (lanes - 1)) == 0;
+}
+
+inline StatsPlan stats_plan_of(int n_ch, int n_bins, int lanes) {
+    StatsPlan p{};
+    const unsigned per_channel = (unsigned)(n_bins + 3) * (unsigned)sizeof(unsigned);     // <= 16396
+    p.tile = 1;
+    // as many channels as the table has room for, no more than there are, at most kStatsMaxTile
+    while (2 * p.tile <= kStatsMaxTile && (unsigned)(2 * p.tile) * per_channel <= kStatsMaxLds && 2 * p.tile <= n_ch) p.tile *= 2;
+    p.tiles = (n_ch + p.tile - 1) / p.tile;
+    const int chains = 256 / p.tile;
+    p.splits = (lanes + chains - 1) / chains;
+    p.lds_bytes = (unsigned)p.tile * per_channel;
+    return p;
+}
+
+}  // namespace gsdr
 
 GSDR_STATS_HD bool gsdr_stats_finite(float q) { return __builtin_fabsf(q) <= 3.402823466e+38f; }
 

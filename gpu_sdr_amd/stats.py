@@ -16,6 +16,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from ._lib import STATS_CENTRE_MEAN, STATS_CENTRE_MEDIAN, STATS_HOST, STATS_MAX_QUANTILES
 from ._stage import DeviceStage, Stage
 from .trigger import LEVEL_DTYPE, as_levels
@@ -142,6 +143,16 @@ class device_stats(DeviceStage, _stats):
         return out
 
 
+def feed_plan(n_ch, n_bins, lanes) -> dict:
+    """The launch of one feed (gsdr_stats_plan; no GPU needed): ``tile`` channels by 256 / tile chains per workgroup, a
+    grid of ``tiles`` x ``splits``, ``lds_bytes`` = tile (n_bins + 3) 4 of counters.  ``lanes``: what the object reports.
+    No result depends on any of them.  ValueError for what gsdr_stats_create refuses of the three."""
+    out = (C.c_int * 4)()
+    if _lib.lib().gsdr_stats_plan(int(n_ch), int(n_bins), int(lanes), out) != 0:
+        raise ValueError(f"gsdr_stats_plan refuses n_ch {n_ch}, n_bins {n_bins}, lanes {lanes}")
+    return dict(zip(("tile", "tiles", "splits", "lds_bytes"), (int(v) for v in out)))
+
+
 def axes_around(levels) -> np.ndarray:
     """The axes of a second pass from the levels of a first: the same projection, [lo, hi] as the histogram range.
     Channels that are switched off (an infinite level) cannot serve as a range: ValueError."""
@@ -151,4 +162,4 @@ def axes_around(levels) -> np.ndarray:
     return lv
 
 
-__all__ = ["device_stats", "host_stats", "axes_around", "SUMMARY_DTYPE", "STATS_MAX_QUANTILES"]
+__all__ = ["device_stats", "host_stats", "axes_around", "feed_plan", "SUMMARY_DTYPE", "STATS_MAX_QUANTILES"]

@@ -1066,7 +1066,15 @@ void gsdr_resmap_close(gsdr_resmap *r);
  * Stream order is the caller's, as for the trigger: the object remembers no stream and waits for none.  Consecutive calls
  *   on one object must be ordered by the caller (one stream, or events between streams); rows_dev must stay unchanged
  *   until the feed that reads it has finished.  On a NULL object close is a no-op, the getters return 0, the rest
- *   return -1 with the reason. */
+ *   return -1 with the reason.
+ * gsdr_stats_plan: the launch of one feed of an object with n_ch channels, n_bins bins and `lanes` chains per channel
+ *   (what gsdr_stats_lanes reports; csrc/stats_state.h: the function the feed itself asks; host only, no GPU needed,
+ *   like gsdr_pfb_plan and gsdr_ddc_plan).  out[0] tile: the channels of a workgroup, the largest power of two that is
+ *   at most n_ch, at most 32, and whose table tile (n_bins + 3) 4 bytes fits into 65536 bytes of LDS; out[1] tiles:
+ *   ceil(n_ch / tile), the grid's x; out[2] splits: ceil(lanes / (256 / tile)), the grid's y; out[3] lds_bytes: the
+ *   table's bytes.  No result of the object depends on any of them.  Returns 0, or -1 for a NULL out and for what
+ *   gsdr_stats_create refuses of n_ch and n_bins; lanes must be a power of two in [1, 32768] (0, the rule, needs
+ *   max_rows: ask the object). */
 #define GSDR_STATS_HOST (-2)
 #define GSDR_STATS_MAX_BINS 4096
 #define GSDR_STATS_MAX_LANES 32768
@@ -1094,6 +1102,7 @@ int gsdr_stats_reset(gsdr_stats *s, const gsdr_trigger_level *axes /* n_ch, or N
 long long gsdr_stats_rows(const gsdr_stats *s);
 int gsdr_stats_lanes(const gsdr_stats *s);
 int gsdr_stats_n_bins(const gsdr_stats *s);
+int gsdr_stats_plan(int n_ch, int n_bins, int lanes, int out[4] /* tile, tiles, splits, lds_bytes */);
 void gsdr_stats_close(gsdr_stats *s);
 
 #ifdef __cplusplus

@@ -189,6 +189,32 @@ def stream(n, n_ch, seed=1, wide=()):
     return np.ascontiguousarray(rows), axes
 
 
+PIVOT_AXIS = (0, 0, 1, 0, -2.0 ** 23, 2.0 ** 23)       # q = Re x, the pivot is 0
+
+
+def after_a_prefix_of_pivot_rows(T0, tail, axes, n_bins, lanes):
+    """The Model of a stream no model can take: T0 rows whose q EQUALS the pivot (0 + 0j on PIVOT_AXIS), then `tail`.
+
+    Such a row adds exactly +0 to S and Q of its chain, which leaves them +0, makes min = max = +0 and counts in one known
+    bin: the chains after the prefix are those after ANY number >= 1 of such rows.  So the stream is modelled by
+    z = T0 mod lanes pivot rows (z = lanes where that is 0), which put the tail's rows into the chains they have behind T0
+    rows, and the T0 - z rows left out are added to the pivot's counter before anything is derived from the counts.
+    (The extremes of chains that got a pivot row in the real stream only are +-Inf here; the tree joins them with a chain
+    that has one, so min and max of the channel are the same -- as long as z >= 1, and no tail value is a zero of the
+    other sign.)"""
+    tail = np.ascontiguousarray(tail, dtype=np.complex64)
+    n_ch = tail.shape[1]
+    assert T0 >= 1 and np.array_equal(axes, np.array([PIVOT_AXIS] * n_ch, dtype=LEVEL_DTYPE)) and not (project(tail, axes) == 0).any()
+    z = T0 % lanes or lanes
+    assert z <= T0
+    m = Model(np.concatenate([np.zeros((z, n_ch), dtype=np.complex64), tail]), axes, n_bins, lanes)
+    slot = np.argmax(Model(np.zeros((1, n_ch), dtype=np.complex64), axes, n_bins, 1).counts, axis=1)
+    assert (slot >= 1).all() and (slot <= n_bins).all()
+    m.counts[np.arange(n_ch), slot] += np.uint64(T0 - z)
+    m.pivot_slot = slot
+    return m
+
+
 def cuttings(n, max_rows):
     """name -> feed lengths that add up to n, each <= max_rows."""
     def pieces(total, m):

@@ -31,6 +31,7 @@ def case(n, n_ch, seed, wide=()):
 
 
 PR = [0.01, 0.25, 0.5, 0.999, 1.0]
+PR16 = [k / 16 for k in range(1, 17)]
 
 
 def run_twin(stats, rows, axes, n_bins, lanes, cut, max_rows):
@@ -214,6 +215,74 @@ def test_the_lanes_rule(stats):
         h = stats.host_stats(n_ch, max_rows, 1, np.tile(axes, n_ch))
         assert h.lanes == want, (n_ch, max_rows)
         h.close()
+
+
+def test_the_feed_plan_at_its_edges(stats, gsdr_lib):
+    """gsdr_stats_plan (stats_plan_of in csrc/stats_state.h, the function the feed's launcher asks): the tile is the
+    largest power of two that is at most n_ch, at most 32, and whose table tile (n_bins + 3) 4 fits into 65 536 bytes --
+    pinned on both sides of the four n_bins at which the table of a tile is EXACTLY 65 536 bytes, and over every n_bins."""
+    plan = stats.feed_plan
+    for n_bins, tile in ((509, 32), (1021, 16), (2045, 8), (4093, 4)):
+        for n_ch in (tile, tile + 1, 2 * tile - 1, 2 * tile, 100, 1 << 20):
+            a, b = plan(n_ch, n_bins, 8), plan(n_ch, n_bins + 1, 8)
+            assert (a["tile"], a["lds_bytes"]) == (tile, 65536), (n_ch, n_bins)
+            assert (b["tile"], b["lds_bytes"]) == (tile // 2, (tile // 2) * (n_bins + 4) * 4), (n_ch, n_bins)
+            assert plan(tile - 1, n_bins, 8)["tile"] == tile // 2                    # fewer channels than the table has room for
+    channels = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 130, 2048, (1 << 20) - 1, 1 << 20)
+    out = (C.c_int * 4)()
+    for n_bins in range(1, 4097):
+        per = (n_bins + 3) * 4
+        for n_ch in channels:
+            assert gsdr_lib.gsdr_stats_plan(n_ch, n_bins, 64, out) == 0
+            tile, tiles, splits, lds = out
+            assert tile in (1, 2, 4, 8, 16, 32) and tile <= n_ch and lds == tile * per <= 65536, (n_ch, n_bins)
+            assert tile == 32 or 2 * tile > n_ch or 2 * tile * per > 65536, (n_ch, n_bins)      # and no smaller than it has to be
+            assert tiles == -(-n_ch // tile) and splits == -(-64 // (256 // tile)), (n_ch, n_bins)
+    # the grid's y over every lanes creation accepts
+    for n_bins in (1, 256, 509, 510, 1021, 1022, 2045, 2046, 4093, 4094, 4096):
+        for n_ch in channels:
+            for lanes in (1 << e for e in range(16)):
+                p = plan(n_ch, n_bins, lanes)
+                assert p["splits"] == -(-lanes // (256 // p["tile"])) and 1 <= p["splits"] <= 65535, (n_ch, n_bins, lanes)
+    assert plan(1 << 20, 1, 32768) == dict(tile=32, tiles=32768, splits=4096, lds_bytes=512)
+    assert plan(1, 4096, 1) == dict(tile=1, tiles=1, splits=1, lds_bytes=16396)
+    # it refuses what creation refuses (a lanes of 0 is the rule, which needs max_rows: the object reports its lanes)
+    for args in ((0, 8, 1), ((1 << 20) + 1, 8, 1), (2, 0, 1), (2, 4097, 1), (2, 8, 0), (2, 8, -1), (2, 8, 3), (2, 8, 65536)):
+        assert gsdr_lib.gsdr_stats_plan(*args, out) == -1, args
+        with pytest.raises(ValueError):
+            plan(*args)
+    assert gsdr_lib.gsdr_stats_plan(2, 8, 1, None) == -1
+
+
+def test_the_model_behind_a_prefix_of_pivot_rows_is_the_twin(stats):
+    """tests/_stats.py, after_a_prefix_of_pivot_rows -- the expected result of the GPU test that feeds more than 2^32
+    rows -- against the twin at a T0 the twin can take: 41 feeds of 997 rows of 0 + 0j, then 3 001 wide rows in pieces
+    that begin at stream positions which are no multiple of lanes."""
+    from _stats import PIVOT_AXIS, after_a_prefix_of_pivot_rows
+    n_ch, n_bins, lanes, per, K = 2, 256, 64, 997, 41
+    tail, axes = case(3001, n_ch, 17, wide=(0, 1))
+    assert np.array_equal(axes, np.array([PIVOT_AXIS] * n_ch, dtype=LEVEL_DTYPE))
+    T0 = K * per
+    assert T0 % lanes == 45
+    h = stats.host_stats(n_ch, per, n_bins, axes, lanes=lanes)
+    zeros = np.zeros((per, n_ch), dtype=np.complex64)
+    for _ in range(K):
+        h.feed(zeros)
+    feed_cut(h, tail, [7, 401, 997, 997, 599])
+    assert h.rows_seen == T0 + 3001
+    got = h.read(), h.counts(), h.quantiles(PR16), h.levels(5.0, "median"), h.levels(3.0, "mean")
+    h.close()
+    m = after_a_prefix_of_pivot_rows(T0, tail, axes, n_bins, lanes)
+    assert (got[1][np.arange(n_ch), m.pivot_slot] >= T0).all() and np.array_equal(got[1], m.counts)
+    assert same_summary(got[0], m.summary()) == "" and same_doubles(got[2], m.quantiles(PR16))
+    assert got[3].tobytes() == m.levels(5.0, "median").tobytes() and got[4].tobytes() == m.levels(3.0, "mean").tobytes()
+    # What this cannot see, by design: the tree joins chains j and j + h, so moving EVERY row by the same number of chains
+    # gives the same sums (the tail alone, in one piece, has the twin's S and Q).  Only the phase of one feed against
+    # another shows -- hence the pieces above, and a tail piece moved by one chain against the others has other sums.
+    whole = Model(tail, axes, n_bins, lanes)
+    assert np.array_equal(whole.S, m.S) and np.array_equal(whole.Q, m.Q)
+    moved = Model(np.concatenate([np.zeros((T0 % lanes, n_ch), np.complex64), tail[:7], np.zeros((1, n_ch), np.complex64), tail[7:]]), axes, n_bins, lanes)
+    assert not np.array_equal(moved.S, m.S)
 
 
 def test_every_refusal(stats, gsdr_lib):
