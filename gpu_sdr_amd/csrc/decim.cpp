@@ -1,6 +1,6 @@
 // decim.cpp -- the device part of a decim object (the contract: include/gsdr.h, "FIR decimation on the device"): what
 // it owns on the GPU and the sequencing of a feed.  Creation, the refusals of the arguments, the default taps and the
-// host twin are in host_logic.cpp, the kernels in decim_kernels.hip, the frame of every stage in stage_dev.h.
+// host twin are in decim_host.cpp, the kernels in decim_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is two launches on the caller's stream (one when it completes no output row) and no host synchronisation.
 // What the HOST has to know of the stream is only the number of rows fed: from it follow the blocks the feed touches,

@@ -1,6 +1,6 @@
-// decim_state.h -- the FIR decimator (include/gsdr.h, "FIR decimation on the device") as host_logic.cpp and decim.cpp
-// share it.  host_logic.cpp owns creation, the refusals, the default taps, the count law and the host twin; decim.cpp
-// hangs the device part on `dev` through the hook below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host
+// decim_state.h -- the FIR decimator (include/gsdr.h, "FIR decimation on the device") as decim_host.cpp and decim.cpp
+// share it.  decim_host.cpp owns creation, the refusals, the default taps, the count law and the host twin; decim.cpp
+// hangs the device part on `dev` through the hook below (its release: stage_state.h).  No HIP here: decim_host.cpp is built without decim.cpp by a host
 // compiler (tests/test_decim_sanitizers.py), where the hooks are absent and only host objects exist.
 //
 // Blocks.  The contract's block B is the q rows that end on row B q + p.  Both sides count blocks from the one that
@@ -36,7 +36,7 @@ inline long long gsdr_decim_out_of(long long total, long long offset, int q) {
 inline long long gsdr_decim_r0(long long offset, int q) { return offset % q + 1 - q; }
 
 extern "C" {
-// decim.cpp; weak in host_logic.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
+// decim.cpp; weak in decim_host.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
 // after every bound has been checked.
 int gsdr_decim_dev_create_(gsdr_decim *d);
 }

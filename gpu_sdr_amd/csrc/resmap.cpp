@@ -1,6 +1,6 @@
 // resmap.cpp -- the device part of a resmap object (the contract: include/gsdr.h, "resonator map on the device"): what
 // it owns on the GPU, the one launch of a feed and the offsets' way to the device.  Creation, the refusals of the
-// arguments, gsdr_resmap_constants and the host twin are in host_logic.cpp, the kernel in resmap_kernels.hip, the
+// arguments, gsdr_resmap_constants and the host twin are in resmap_host.cpp, the kernel in resmap_kernels.hip, the
 // frame of every stage in stage_dev.h.
 //
 // The object carries no stream state: a feed needs the tables and the caller's two pointers, nothing is read back.

@@ -1,8 +1,8 @@
-// resmap_state.h -- the resonator map (include/gsdr.h, "resonator map on the device") as host_logic.cpp, resmap.cpp and
+// resmap_state.h -- the resonator map (include/gsdr.h, "resonator map on the device") as resmap_host.cpp, resmap.cpp and
 // resmap_kernels.hip share it: the object, a column's constants as the tables hold them, and THE PER-SAMPLE LAW, one
 // inline host-and-device function that the kernel and the host twin both include -- there is one text of the
-// arithmetic.  host_logic.cpp owns creation, the refusals, gsdr_resmap_constants and the host twin; resmap.cpp hangs the
-// device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host compiler
+// arithmetic.  resmap_host.cpp owns creation, the refusals, gsdr_resmap_constants and the host twin; resmap.cpp hangs the
+// device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: resmap_host.cpp is built without resmap.cpp by a host compiler
 // (tests/test_resmap_sanitizers.py), where the hooks are absent and only host objects exist.
 #ifndef GSDR_RESMAP_STATE_H
 #define GSDR_RESMAP_STATE_H
@@ -72,7 +72,7 @@ GSDR_RESMAP_HD void gsdr_resmap_sample(int kind, const gsdr_resmap_col &c, doubl
 }
 
 extern "C" {
-// resmap.cpp; weak in host_logic.cpp.  _create_: allocates and uploads the tables (offsets zero), 0 or -1 with the
+// resmap.cpp; weak in resmap_host.cpp.  _create_: allocates and uploads the tables (offsets zero), 0 or -1 with the
 // message noted; it is called after every bound has been checked.  _set_offsets_: r->offsets to the device, ordered on
 // the stream.
 int gsdr_resmap_dev_create_(gsdr_resmap *r);

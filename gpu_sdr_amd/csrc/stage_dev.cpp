@@ -1,4 +1,4 @@
-// stage_dev.cpp -- the one release hook of the five stages (stage_state.h): what gsdr_X_close of host_logic.cpp calls
+// stage_dev.cpp -- the one release hook of the six stages (stage_state.h): what gsdr_X_close of X_host.cpp calls
 // for an object with a device part, whichever stage it belongs to.
 #include "stage_dev.h"
 

@@ -36,7 +36,7 @@ const char *object_fault(const Stage *s, const char *hint) {
     return nullptr;
 }
 
-// The creation of a stage's device part, behind the bounds host_logic.cpp has checked: chooses the device, hangs a new
+// The creation of a stage's device part, behind the bounds X_host.cpp has checked: chooses the device, hangs a new
 // Dev on s->dev and lets `allocate(Dev &)` make and fill what it owns (true: every step succeeded).  0, or -1 with
 // "device allocation failed " + asked noted, nothing kept and s->dev null again.
 template <class Dev, class Stage, class Allocate>

@@ -1,14 +1,29 @@
 // stage_state.h -- what the six objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
-// gsdr_sweep_*, gsdr_resmap_*, gsdr_stats_*: the STAGES) share between host_logic.cpp and their device sources: the type of `dev`,
-// the one release hook, the host side's refusal and the device_index check of every create.  The X_state.h of each
-// stage includes it.  No HIP here: host_logic.cpp is built alone by a host compiler (tests/test_*_sanitizers.py), where
-// the hooks are absent and only host objects exist.
+// gsdr_sweep_*, gsdr_resmap_*, gsdr_stats_*: the STAGES) share between their host sources (X_host.cpp) and their device
+// sources: the type of `dev`, the one release hook, the host side's refusal, the device_index check of every create and
+// the two macros that keep a host twin's arithmetic uncontracted.  The X_state.h of each stage includes it.  No HIP
+// here: the X_host.cpp are built without the device sources by a host compiler (tests/test_*_sanitizers.py), where the
+// hooks are absent and only host objects exist.
 #ifndef GSDR_STAGE_STATE_H
 #define GSDR_STAGE_STATE_H
 
 #include <string>
 
 #include "../../include/gsdr.h"
+
+// A function whose sums and products must stay the IEEE operations they are written as (the host twins, bit for bit
+// what the kernels give) carries both: GSDR_NO_CONTRACT in front of it, for gcc, and GSDR_NO_CONTRACT_BODY as the first
+// statement of its body, for clang.
+#if defined(__clang__)
+#define GSDR_NO_CONTRACT
+#define GSDR_NO_CONTRACT_BODY _Pragma("clang fp contract(off)")
+#elif defined(__GNUC__)
+#define GSDR_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#define GSDR_NO_CONTRACT_BODY
+#else
+#define GSDR_NO_CONTRACT
+#define GSDR_NO_CONTRACT_BODY
+#endif
 
 static_assert(GSDR_TRIGGER_HOST == -2 && GSDR_WELCH_HOST == -2 && GSDR_DECIM_HOST == -2 && GSDR_SWEEP_HOST == -2 && GSDR_RESMAP_HOST == -2 &&
                   GSDR_STATS_HOST == -2,
@@ -19,7 +34,7 @@ namespace gsdr {
 constexpr int kStageHost = -2;                // GSDR_X_HOST of every stage
 
 // What a stage owns on the GPU: X.cpp derives its XDev from this and hangs it on `dev` of the object.  The destructor is
-// all that host_logic.cpp and the release hook need of it.
+// all that X_host.cpp and the release hook need of it.
 struct StageDev {
     virtual ~StageDev() = default;
 };
@@ -27,9 +42,9 @@ struct StageDev {
 }  // namespace gsdr
 
 extern "C" {
-// demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (host_logic.cpp alone) has nobody to tell
+// demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (no demod.cpp) has nobody to tell
 void gsdr_note_error_(const char *msg) __attribute__((weak));
-// stage_dev.cpp; weak in host_logic.cpp.  Waits for the device, then releases what `dev` owns.
+// stage_dev.cpp; weak in stage_host.h.  Waits for the device, then releases what `dev` owns.
 void gsdr_stage_dev_close_(int device, gsdr::StageDev *dev);
 }
 

@@ -1,6 +1,6 @@
 // stats.cpp -- the device part of a stats object (the contract: include/gsdr.h, "row statistics on the device"): what it
 // owns on the GPU, the one launch of a feed, the reads and the way of the axes to the device.  Creation, the refusals of
-// the arguments, the lanes rule, the levels and the host twin are in host_logic.cpp, the kernels in stats_kernels.hip,
+// the arguments, the lanes rule, the levels and the host twin are in stats_host.cpp, the kernels in stats_kernels.hip,
 // the frame of every stage in stage_dev.h.
 //
 // What the HOST has to know of the stream is only the number of rows fed: from it follows the chain of every row of a

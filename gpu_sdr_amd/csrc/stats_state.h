@@ -1,10 +1,10 @@
-// stats_state.h -- the row statistics (include/gsdr.h, "row statistics on the device") as host_logic.cpp, stats.cpp and
+// stats_state.h -- the row statistics (include/gsdr.h, "row statistics on the device") as stats_host.cpp, stats.cpp and
 // stats_kernels.hip share them: the object, a channel's axis as the tables hold it, a chain, and THE LAWS -- the
 // per-sample law, the combination of two chains, the summary and the quantile -- as inline host-and-device functions
 // that the kernels and the host twin both include: there is one text of the arithmetic -- and the launch rule of a feed
-// (stats_plan_of), which the launcher and gsdr_stats_plan both ask.  host_logic.cpp owns creation,
+// (stats_plan_of), which the launcher and gsdr_stats_plan both ask.  stats_host.cpp owns creation,
 // the refusals, the lanes rule, the levels and the host twin; stats.cpp hangs the device part on `dev` through the hooks
-// below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host compiler
+// below (its release: stage_state.h).  No HIP here: stats_host.cpp is built without stats.cpp by a host compiler
 // (tests/test_stats_sanitizers.py), where the hooks are absent and only host objects exist.
 //
 // No law below has a product that feeds an addition in one expression: every product is stored first, and contraction
@@ -188,7 +188,7 @@ GSDR_STATS_HD double gsdr_stats_in_bin(const gsdr_stats_axis &a, int k, unsigned
 }
 
 extern "C" {
-// stats.cpp; weak in host_logic.cpp.  _create_: allocates, zeroes and uploads s->axes, 0 or -1 with the message noted;
+// stats.cpp; weak in stats_host.cpp.  _create_: allocates, zeroes and uploads s->axes, 0 or -1 with the message noted;
 // called after every bound has been checked.  _reset_: waits for the device, zeroes the chains and the counters,
 // uploads s->axes where `upload` is set, waits.  _fetch_: on the stream a read with the n_p quantiles pr, waits and
 // copies what is asked for (each of the three may be NULL).

@@ -1,6 +1,6 @@
 // sweep.cpp -- the device part of a sweep object (the contract: include/gsdr.h, "VNA sweep accumulator on the device"):
 // what it owns on the GPU, the one launch of a feed, the reads and the slope.  Creation, the refusals of the arguments,
-// the counts and the host twin are in host_logic.cpp, the kernels in sweep_kernels.hip, the frame of every stage in
+// the counts and the host twin are in sweep_host.cpp, the kernels in sweep_kernels.hip, the frame of every stage in
 // stage_dev.h.
 //
 // What the HOST has to know of the stream is only first_row and the number of rows fed: from them follow the points a

@@ -1,7 +1,7 @@
-// sweep_state.h -- the VNA sweep accumulator (include/gsdr.h, "VNA sweep accumulator on the device") as host_logic.cpp,
-// sweep.cpp and sweep_kernels.hip share it: the closed forms of the fold.  host_logic.cpp owns creation, the refusals,
+// sweep_state.h -- the VNA sweep accumulator (include/gsdr.h, "VNA sweep accumulator on the device") as sweep_host.cpp,
+// sweep.cpp and sweep_kernels.hip share it: the closed forms of the fold.  sweep_host.cpp owns creation, the refusals,
 // the counts and the host twin; sweep.cpp hangs the device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here:
-// host_logic.cpp is built alone by a host compiler (tests/test_sweep_sanitizers.py), where the hooks are absent and
+// sweep_host.cpp is built without sweep.cpp by a host compiler (tests/test_sweep_sanitizers.py), where the hooks are absent and
 // only host objects exist.
 //
 // The fold.  Stream row r lies in GROUP r / group, and group G belongs to point G mod n_points.  One PASS is
@@ -88,7 +88,7 @@ inline long long gsdr_sweep_slope_blocks(long long n_points) {
 }
 
 extern "C" {
-// sweep.cpp; weak in host_logic.cpp.  _create_: allocates and zeroes, 0 or -1 with the message noted; it is called
+// sweep.cpp; weak in sweep_host.cpp.  _create_: allocates and zeroes, 0 or -1 with the message noted; it is called
 // after every bound has been checked.  _reset_: waits for the device and zeroes the accumulators.  _slope_: the slope
 // kernels on the stream, waits, copies n_ch complex128.
 int gsdr_sweep_dev_create_(gsdr_sweep *s);

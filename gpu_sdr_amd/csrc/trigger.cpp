@@ -1,6 +1,6 @@
 // trigger.cpp -- the device part of a trigger object (the contract: include/gsdr.h, "trigger on the device"): what it
 // owns on the GPU and the sequencing of a feed.  Creation, the refusals of the arguments and the host twin are in
-// host_logic.cpp, the kernels in trigger_kernels.hip, the frame of every stage in stage_dev.h.
+// trigger_host.cpp, the kernels in trigger_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is three launches on the caller's stream and no host synchronisation.  Everything a feed inherits lives in two
 // sets used in turn -- a feed reads set `cur` and writes the other one, as d_avg_acc does for the frame average -- so no

@@ -1,7 +1,7 @@
-// trigger_state.h -- the trigger object (include/gsdr.h, "trigger on the device") as host_logic.cpp and trigger.cpp
-// share it.  host_logic.cpp owns creation, the refusals, the host twin and the bookkeeping every object has;
+// trigger_state.h -- the trigger object (include/gsdr.h, "trigger on the device") as trigger_host.cpp and trigger.cpp
+// share it.  trigger_host.cpp owns creation, the refusals, the host twin and the bookkeeping every object has;
 // trigger.cpp hangs the device part on `dev` through the two hooks below (its release: stage_state.h).  No HIP here:
-// host_logic.cpp is built alone by a host compiler (tests/test_trigger_sanitizers.py), where the hooks are absent and
+// trigger_host.cpp is built without trigger.cpp by a host compiler (tests/test_trigger_sanitizers.py), where the hooks are absent and
 // only host objects exist.
 #ifndef GSDR_TRIGGER_STATE_H
 #define GSDR_TRIGGER_STATE_H
@@ -32,7 +32,7 @@ struct gsdr_trigger {
 };
 
 extern "C" {
-// trigger.cpp; weak in host_logic.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
+// trigger.cpp; weak in trigger_host.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
 // after every bound has been checked.
 int gsdr_trigger_dev_create_(gsdr_trigger *t, const gsdr_trigger_level *levels);
 int gsdr_trigger_dev_set_levels_(gsdr_trigger *t, const gsdr_trigger_level *levels, void *hip_stream);

@@ -1,6 +1,6 @@
 // welch.cpp -- the device part of a welch object (the contract: include/gsdr.h, "Welch spectra on the device"): what
 // it owns on the GPU and the sequencing of a feed and of a read.  Creation, the refusals of the arguments and the host
-// twin are in host_logic.cpp, the kernels in welch_kernels.hip, the frame of every stage in stage_dev.h.
+// twin are in welch_host.cpp, the kernels in welch_kernels.hip, the frame of every stage in stage_dev.h.
 //
 // A feed is three launches on the caller's stream (one when it completes no segment) and no host synchronisation.  What
 // the HOST has to know of the stream is only the number of rows fed: from it follow the ring position of the feed, the
@@ -77,7 +77,7 @@ int gsdr_welch_dev_create_(gsdr_welch *w) {
     const size_t bytes = n_ch * H * sizeof(float2) + max_segs * n_ch * (3 * K1 * sizeof(float) + 2 * sizeof(double)) +
                          n_ch * (3 * K1 * sizeof(double) + 2 * sizeof(double) + 2 * K1 * sizeof(float) + 2 * sizeof(float2));
     const std::string asked = "(n_ch, max_rows, nperseg, step: " + std::to_string(bytes >> 20) + " MiB)";
-    // a bound like those of host_logic.cpp (it is here for `asked`): decided before the device is touched
+    // a bound like those of welch_host.cpp (it is here for `asked`): decided before the device is touched
     if (max_segs * n_ch > (size_t)INT_MAX) return refuse(me, "n_ch x (max_rows / step + 1) segments per feed exceed 2^31 - 1 " + asked);
     std::vector<float2> tw(N);
     for (size_t k = 0; k < N; ++k) {

@@ -1,6 +1,6 @@
-// welch_state.h -- the Welch accumulator (include/gsdr.h, "Welch spectra on the device") as host_logic.cpp and welch.cpp
-// share it.  host_logic.cpp owns creation, the refusals, the host twin and the bookkeeping every object has; welch.cpp
-// hangs the device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: host_logic.cpp is built alone by a host
+// welch_state.h -- the Welch accumulator (include/gsdr.h, "Welch spectra on the device") as welch_host.cpp and welch.cpp
+// share it.  welch_host.cpp owns creation, the refusals, the host twin and the bookkeeping every object has; welch.cpp
+// hangs the device part on `dev` through the hooks below (its release: stage_state.h).  No HIP here: welch_host.cpp is built without welch.cpp by a host
 // compiler (tests/test_welch_sanitizers.py), where the hooks are absent and only host objects exist.
 #ifndef GSDR_WELCH_STATE_H
 #define GSDR_WELCH_STATE_H
@@ -31,7 +31,7 @@ inline long long gsdr_welch_segments_of(long long total, int nperseg, int step) 
 }
 
 extern "C" {
-// welch.cpp; weak in host_logic.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
+// welch.cpp; weak in welch_host.cpp.  _create_: allocates and uploads, 0 or -1 with the message noted; it is called
 // after every bound has been checked.  _reset_: zeroes the device accumulators (waits for the device).
 int gsdr_welch_dev_create_(gsdr_welch *w);
 int gsdr_welch_dev_reset_(gsdr_welch *w);

@@ -1,5 +1,5 @@
-"""The FIR decimator's host twin (gsdr_decim_* in host_logic.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: a
-stand-alone program with its own main, built from host_logic.cpp alone with plain g++ (no HIP header, no device part:
+"""The FIR decimator's host twin (gsdr_decim_* in decim_host.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: a
+stand-alone program with its own main, built from the host sources alone with plain g++ (no HIP header, no device part:
 only GSDR_DECIM_HOST objects exist in such a build).  Every buffer is a heap block of exactly the documented extent, so
 one sample read or written past an end is a report.  Nothing is loaded into Python, nothing is preloaded; built exactly
 as tests/test_welch_sanitizers.py builds its program."""

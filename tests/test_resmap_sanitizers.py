@@ -1,5 +1,5 @@
-"""The resonator map's host twin and gsdr_resmap_constants (gsdr_resmap_* in host_logic.cpp) under AddressSanitizer +
-UndefinedBehaviorSanitizer: a stand-alone program with its own main, built from host_logic.cpp alone with plain g++ (no
+"""The resonator map's host twin and gsdr_resmap_constants (gsdr_resmap_* in resmap_host.cpp) under AddressSanitizer +
+UndefinedBehaviorSanitizer: a stand-alone program with its own main, built from the host sources alone with plain g++ (no
 HIP header, no device part: only GSDR_RESMAP_HOST objects exist in such a build).  Every buffer is a heap block of
 exactly the documented extent, so one sample, constant, offset or channel read or written past an end is a report.
 Nothing is loaded into Python, nothing is preloaded; built exactly as tests/test_sweep_sanitizers.py builds its

@@ -1,8 +1,9 @@
-"""Every refusal of the five row-stage objects (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*, gsdr_sweep_*, gsdr_resmap_*)
-that returns before the first HIP call: the return value and the exact bytes gsdr_last_error(NULL) gives afterwards, in
+"""Every refusal of five of the six row-stage objects (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*, gsdr_sweep_*,
+gsdr_resmap_*; those of gsdr_stats_*: tests/test_stats_host.py) that returns before the first HIP call: the return value and the exact bytes gsdr_last_error(NULL) gives afterwards, in
 the manner of tests/test_entry_refusals.py.  No GPU call is made: every object below is a host twin, and no call passes
 every check of a device entry.  The one text libgsdr.so cannot give -- "this build has host objects only", the answer
-of a build without a device part -- is pinned by a stand-alone program built from host_logic.cpp alone."""
+of a build without a device part -- is pinned for all six by a stand-alone program built from the host sources alone
+(host_logic.cpp and the X_host.cpp: tests/_sanitized.py)."""
 import ctypes as C
 import os
 import shutil
@@ -10,6 +11,7 @@ import subprocess
 
 import pytest
 
+from _sanitized import HOST_SOURCES
 from gpu_sdr_amd._lib import ChirpParamC, TriggerLevelC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -474,11 +476,12 @@ extern "C" void gsdr_note_error_(const char *msg) { noted = msg ? msg : ""; }
 
 int main() {
     const gsdr_trigger_level levels[2] = {};
+    const gsdr_trigger_level axes[2] = {{0.f, 0.f, 1.f, 0.f, -1.f, 1.f}, {0.f, 0.f, 1.f, 0.f, -1.f, 1.f}};
     const float taps[3] = {0.25f, 0.5f, 0.25f};
     double constants[2 * GSDR_RESMAP_NCONST];
     for (double &c : constants) c = 1.0;
     for (int device_index = -1; device_index <= 0; ++device_index) {
-        void *made[5] = {gsdr_trigger_create(2, 8, 1, 2, 0, 4, levels, device_index), nullptr, nullptr, nullptr, nullptr};
+        void *made[6] = {gsdr_trigger_create(2, 8, 1, 2, 0, 4, levels, device_index), nullptr, nullptr, nullptr, nullptr, nullptr};
         std::printf("%s\n", noted.c_str());
         made[1] = gsdr_welch_create(2, 64, 16, 8, 2, nullptr, device_index);
         std::printf("%s\n", noted.c_str());
@@ -488,6 +491,8 @@ int main() {
         std::printf("%s\n", noted.c_str());
         made[4] = gsdr_resmap_create(2, 8, 2, nullptr, constants, GSDR_RESMAP_X_DQR, device_index);
         std::printf("%s\n", noted.c_str());
+        made[5] = gsdr_stats_create(2, 8, 4, 0, axes, device_index);
+        std::printf("%s\n", noted.c_str());
         for (void *m : made)
             if (m) return 1;
     }
@@ -495,7 +500,7 @@ int main() {
 }
 '''
 HOST_ONLY_LINES = ["gsdr_%s_create: device_index: this build has host objects only (GSDR_%s_HOST)" % (s, s.upper())
-                   for s in ("trigger", "welch", "decim", "sweep", "resmap")] * 2
+                   for s in ("trigger", "welch", "decim", "sweep", "resmap", "stats")] * 2
 
 
 def test_create_refusal_of_a_build_without_a_device_part(tmp_path):
@@ -504,8 +509,7 @@ def test_create_refusal_of_a_build_without_a_device_part(tmp_path):
         pytest.skip("no g++")
     (tmp_path / "driver.cpp").write_text(HOST_ONLY_DRIVER)
     exe = tmp_path / "driver"
-    src = os.path.join(ROOT, "gpu_sdr_amd", "csrc", "host_logic.cpp")
-    build = subprocess.run([gxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(tmp_path / "driver.cpp"), src, "-o", str(exe)],
+    build = subprocess.run([gxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(tmp_path / "driver.cpp"), *HOST_SOURCES, "-o", str(exe)],
                            capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-3000:]
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)

@@ -1,5 +1,5 @@
-"""The row statistics' host twin (gsdr_stats_* in host_logic.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: a
-stand-alone program with its own main, built from host_logic.cpp alone with plain g++ (no HIP header, no device part:
+"""The row statistics' host twin (gsdr_stats_* in stats_host.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: a
+stand-alone program with its own main, built from the host sources alone with plain g++ (no HIP header, no device part:
 only GSDR_STATS_HOST objects exist in such a build).  Every buffer -- the axes, the rows of a feed, the summaries, the
 counters, the quantiles, the levels, the flags -- is a heap block of exactly the documented extent, so one element read
 or written past an end is a report.  Nothing is loaded into Python, nothing is preloaded; built exactly as

@@ -1,4 +1,4 @@
-"""The sweep accumulator's host twin (gsdr_sweep_* with GSDR_SWEEP_HOST, host_logic.cpp) against the model of
+"""The sweep accumulator's host twin (gsdr_sweep_* with GSDR_SWEEP_HOST, sweep_host.cpp) against the model of
 tests/_sweep.py, bit for bit: means, variances and the phase slope for every shape under every cutting and first_row;
 partial sweeps; the counts against enumeration; poison; every refusal; sweep_shape against gsdr_chirp_derive; vna_axis
 against numpy.linspace; the line delay of a noiseless cable and the variance against numpy.var.  No GPU."""

@@ -1,4 +1,4 @@
-"""The trigger's host twin (gsdr_trigger_* over GSDR_TRIGGER_HOST, host_logic.cpp) against the literal model of
+"""The trigger's host twin (gsdr_trigger_* over GSDR_TRIGGER_HOST, trigger_host.cpp) against the literal model of
 tests/_trigger.py, bit for bit; the refusals, the struct layouts and the Python mirror.  The vectorised model is pinned to
 the literal one on every small case, and the host twin to the vectorised one on the long feeds and past row 2^31.  No GPU."""
 import ctypes as C
