@@ -272,6 +272,18 @@ SIGNATURES = [
     ("gsdr_stats_n_bins", C.c_int, [_vp]),
     ("gsdr_stats_plan", C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     ("gsdr_stats_close", None, [_vp]),
+    ("gsdr_cov_create", _vp, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    ("gsdr_cov_feed_device", C.c_int, [_vp, _vp, C.c_int, _vp]),
+    ("gsdr_cov_feed_host", C.c_int, [_vp, _vp, C.c_int]),
+    ("gsdr_cov_read_device", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("gsdr_cov_read", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("gsdr_cov_read_host", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("gsdr_cov_reset", C.c_int, [_vp, _vp]),
+    ("gsdr_cov_rows", C.c_longlong, [_vp]),
+    ("gsdr_cov_lanes", C.c_int, [_vp]),
+    ("gsdr_cov_n_var", C.c_int, [_vp]),
+    ("gsdr_cov_plan", C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
+    ("gsdr_cov_close", None, [_vp]),
 ]
 
 CREATE_MULTI_CHIRP = 1      # GSDR_CREATE_MULTI_CHIRP
@@ -289,6 +301,10 @@ STATS_MAX_LANES = 32768     # GSDR_STATS_MAX_LANES
 STATS_MAX_QUANTILES = 16    # GSDR_STATS_MAX_QUANTILES
 STATS_CENTRE_MEAN = 0       # GSDR_STATS_CENTRE_MEAN
 STATS_CENTRE_MEDIAN = 1     # GSDR_STATS_CENTRE_MEDIAN
+COV_HOST = -2               # GSDR_COV_HOST
+COV_MAX_VARS = 4096         # GSDR_COV_MAX_VARS
+COV_MAX_LANES = 4096        # GSDR_COV_MAX_LANES
+COV_SUMS, COV_COV, COV_CORR = 0, 1, 2       # GSDR_COV_SUMS, GSDR_COV_COV, GSDR_COV_CORR
 
 
 class TriggerLevelC(C.Structure):

@@ -1,5 +1,5 @@
-"""What the Python faces of the six objects behind demodulated rows share (trigger.py, spectrum.py, decimate.py,
-sweep.py, resmap.py, stats.py): the handle with its creation-or-raise and its release, and, for the device classes, the stream,
+"""What the Python faces of the seven objects behind demodulated rows share (trigger.py, spectrum.py, decimate.py,
+sweep.py, resmap.py, stats.py, covariance.py): the handle with its creation-or-raise and its release, and, for the device classes, the stream,
 the check of the rows and the check of device_index."""
 from __future__ import annotations
 
@@ -10,7 +10,7 @@ from .demodulator import GsdrError
 
 
 class Stage:
-    """Base of _trigger, _welch, _decimator, _sweep, _resmap and _stats: the library ``_L`` and the object ``_h`` of
+    """Base of _trigger, _welch, _decimator, _sweep, _resmap, _stats and _cov: the library ``_L`` and the object ``_h`` of
     gsdr_<_NAME>_create, released by gsdr_<_NAME>_close."""
 
     _NAME = ""

@@ -1,5 +1,5 @@
-// stage_dev.h -- what the device sources of the six stages (trigger.cpp, welch.cpp, decim.cpp, sweep.cpp, resmap.cpp,
-// stats.cpp; stage_state.h) share: the refusal, the choice of the device, the object check of a device entry, the creation of the
+// stage_dev.h -- what the device sources of the seven stages (trigger.cpp, welch.cpp, decim.cpp, sweep.cpp, resmap.cpp,
+// stats.cpp, cov.cpp; stage_state.h) share: the refusal, the choice of the device, the object check of a device entry, the creation of the
 // device part, the zeroing of a reset and the way of staged results to the host.  What differs from stage to stage --
 // the buffers, the launches, the checks of the arguments -- stays in X.cpp.  Internal to csrc/.
 #ifndef GSDR_STAGE_DEV_H

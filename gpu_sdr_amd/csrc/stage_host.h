@@ -1,5 +1,5 @@
-// stage_host.h -- what the host sources of the six stages (trigger_host.cpp, welch_host.cpp, decim_host.cpp,
-// sweep_host.cpp, resmap_host.cpp, stats_host.cpp; stage_state.h) share: the frame of every create, the object check of
+// stage_host.h -- what the host sources of the seven stages (trigger_host.cpp, welch_host.cpp, decim_host.cpp,
+// sweep_host.cpp, resmap_host.cpp, stats_host.cpp, cov_host.cpp; stage_state.h) share: the frame of every create, the object check of
 // a host entry and the close.  The counterpart of stage_dev.h; only the X_host.cpp include it, because it declares the
 // release hook weak: in a build without stage_dev.cpp the hook is absent and only host objects exist.  No HIP here.
 #ifndef GSDR_STAGE_HOST_H

@@ -1,7 +1,8 @@
-// stage_state.h -- what the six objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
-// gsdr_sweep_*, gsdr_resmap_*, gsdr_stats_*: the STAGES) share between their host sources (X_host.cpp) and their device
-// sources: the type of `dev`, the one release hook, the host side's refusal, the device_index check of every create and
-// the two macros that keep a host twin's arithmetic uncontracted.  The X_state.h of each stage includes it.  No HIP
+// stage_state.h -- what the seven objects behind demodulated rows (gsdr_trigger_*, gsdr_welch_*, gsdr_decim_*,
+// gsdr_sweep_*, gsdr_resmap_*, gsdr_stats_*, gsdr_cov_*: the STAGES) share between their host sources (X_host.cpp) and
+// their device sources: the type of `dev`, the one release hook, the host side's refusal, the device_index check of every
+// create, the two macros that keep a host twin's arithmetic uncontracted and the real projection of a sample that the
+// stats and the cov object share.  The X_state.h of each stage includes it.  No HIP
 // here: the X_host.cpp are built without the device sources by a host compiler (tests/test_*_sanitizers.py), where the
 // hooks are absent and only host objects exist.
 #ifndef GSDR_STAGE_STATE_H
@@ -25,8 +26,18 @@
 #define GSDR_NO_CONTRACT_BODY
 #endif
 
+// An inline function of a law that a kernel and a host twin both compile, with contraction off on either side (the
+// pragma inside the body for clang and hipcc, the attribute for gcc).
+#if defined(__HIPCC__)
+#define GSDR_STAGE_HD __host__ __device__ inline __attribute__((always_inline))
+#elif defined(__GNUC__) && !defined(__clang__)
+#define GSDR_STAGE_HD inline __attribute__((optimize("fp-contract=off")))
+#else
+#define GSDR_STAGE_HD inline
+#endif
+
 static_assert(GSDR_TRIGGER_HOST == -2 && GSDR_WELCH_HOST == -2 && GSDR_DECIM_HOST == -2 && GSDR_SWEEP_HOST == -2 && GSDR_RESMAP_HOST == -2 &&
-                  GSDR_STATS_HOST == -2,
+                  GSDR_STATS_HOST == -2 && GSDR_COV_HOST == -2,
               "every stage names its host twin by the same device_index");
 
 namespace gsdr {
@@ -40,6 +51,19 @@ struct StageDev {
 };
 
 }  // namespace gsdr
+
+// The real projection of one sample x + iy, the trigger's q: five float32 operations, each rounded, nothing fused.  The
+// stats object (gsdr_stats_sample) and the cov object (gsdr_cov_sample) both call this text.
+GSDR_STAGE_HD float gsdr_stage_project(float bx, float by, float dx, float dy, float x, float y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float t0 = x - bx;
+    const float t1 = y - by;
+    const float p0 = t0 * dx;
+    const float p1 = t1 * dy;
+    return p0 + p1;
+}
 
 extern "C" {
 // demod.cpp keeps the text for gsdr_last_error(NULL); a host-only build (no demod.cpp) has nobody to tell

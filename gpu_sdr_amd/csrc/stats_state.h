@@ -17,13 +17,7 @@
 #include "../../include/gsdr.h"
 #include "stage_state.h"
 
-#if defined(__HIPCC__)
-#define GSDR_STATS_HD __host__ __device__ inline __attribute__((always_inline))
-#elif defined(__GNUC__) && !defined(__clang__)
-#define GSDR_STATS_HD inline __attribute__((optimize("fp-contract=off")))
-#else
-#define GSDR_STATS_HD inline
-#endif
+#define GSDR_STATS_HD GSDR_STAGE_HD
 
 // one channel's axis, 48 bytes: what the device table and the twin hold
 struct gsdr_stats_axis {
@@ -107,11 +101,7 @@ GSDR_STATS_HD int gsdr_stats_sample(const gsdr_stats_axis &a, int n_bins, float 
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const float t0 = x - a.bx;
-    const float t1 = y - a.by;
-    const float p0 = t0 * a.dx;
-    const float p1 = t1 * a.dy;
-    q = p0 + p1;
+    q = gsdr_stage_project(a.bx, a.by, a.dx, a.dy, x, y);
     if (!gsdr_stats_finite(q)) return n_bins + 2;
     if (q < a.lo) return 0;
     const double off = (double)q - (double)a.lo;

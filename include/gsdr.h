@@ -1105,6 +1105,98 @@ int gsdr_stats_n_bins(const gsdr_stats *s);
 int gsdr_stats_plan(int n_ch, int n_bins, int lanes, int out[4] /* tile, tiles, splits, lds_bytes */);
 void gsdr_stats_close(gsdr_stats *s);
 
+/* ---- channel covariance on the device: sums of products across channels, covariance and correlation matrices, behind
+ * demodulated rows (an extension: the reference's users take numpy.cov of timestreams that have crossed PCIe and TCP) -----
+ * A cov object sees ONE stream of rows of n_ch complex64 each -- the [row][channel] layout every RX entry and the resmap
+ * object write -- numbered 0, 1, 2, ... from creation (or from gsdr_cov_reset), arriving in FEEDS of 0 <= n_rows <=
+ * max_rows rows.  It keeps, in double, the sums and the sums of products of n_var real VARIABLES; only n_var^2 doubles
+ * leave the card, and only when read.
+ * Variables.  Variable i is a real projection of ONE channel: axes[i] = {channel, bx, by, dx, dy, reserved = 0, pivot},
+ *   32 bytes, 0 <= channel < n_ch.  A channel may appear in any order, more than once, or not at all: two axes on one
+ *   channel ({dx, dy} = {1, 0} and {0, 1}) give both quadratures, so the full real covariance of complex data is
+ *   expressible.
+ * Per sample y of the channel of variable i, every operation one IEEE operation rounded to nearest, nothing fused:
+ *     t0 = y.x - bx;  t1 = y.y - by;  p0 = t0 * dx;  p1 = t1 * dy;  v = p0 + p1      (float32: exactly the trigger's and the
+ *   stats object's q);  d_i = (double)v - pivot, one double subtraction.
+ * Accumulation.  Row r belongs to chain r mod lanes.  Per chain, in stream order, a row does S[i] = S[i] + d_i for every
+ *   i and G[i][j] = fma(d_i, d_j, G[i][j]) for every j <= i: ONE fused multiply-add per row and cell (the cell (i, j) with
+ *   j > i IS the cell (j, i)).  A chain starts at +0 everywhere.
+ * Read (does not disturb the accumulation; any number of reads).  The chains are joined by the fixed halving tree of the
+ *   stats object, per cell of S and G: for h = lanes/2, lanes/4, ..., 1: X[k] = X[k] + X[k + h] for k < h.  With n the
+ *   rows fed (the host knows it: nothing is read back) a read writes out[n_var][n_var] doubles, the cell j <= i mirrored
+ *   into (j, i), and, where asked for, mean[n_var]:
+ *   GSDR_COV_SUMS  out = the joined G, mean = the joined S.
+ *   GSDR_COV_COV   m_j = S_j / n;  C_ij = fma(-S_i, m_j, G_ij) / (n - 1) for j <= i; a diagonal cell below 0 becomes +0, a
+ *                  NaN stays;  mean_i = pivot_i + S_i / n.  n < 2: every cell is NaN; n == 0: the mean is NaN too.
+ *   GSDR_COV_CORR  s_i = sqrt(C_ii) (of the diagonal as GSDR_COV_COV gives it); rho_ij = C_ij / p with p = s_i s_j one
+ *                  double product stored first; the diagonal is exactly 1.0 where C_ii is finite and > 0 and NaN otherwise;
+ *                  mean as for GSDR_COV_COV.
+ *   What the pivot buys: the sums hold d = v - pivot, so C loses about n 2^-53 |mean - pivot|^2 / sigma^2 relative: with
+ *   the pivots at the carriers 1e-12 sqrt(C_ii C_jj) holds with three decades to spare; with pivots of 0 on carriers
+ *   1 000 sigma away the distance to numpy.cov is 2e-10 - 3e-9 (profiles/cov_margins.json): 9 digits, and the bar is missed.
+ * Consequences.  No result depends, bit for bit, on where the stream is cut into feeds, or on anything about the launch
+ *   except `lanes`.  The host twin returns the device's bits.  A non-finite sample of variable i takes what IEEE gives:
+ *   it reaches S[i] and row and column i of G, and every other cell is bitwise that of the clean stream.  There is NO
+ *   per-pair exclusion of non-finite samples (and no count of them: the stats object has one).
+ *   The arithmetic is plain double FMAs in a fixed order per cell; the matrix-core FP64 instructions are not used,
+ *   because the order in which they add their k terms is not documented.
+ * gsdr_cov_create: 1 <= n_ch <= 2^20, 1 <= n_var <= GSDR_COV_MAX_VARS, 1 <= max_rows <= 2^20; lanes 0 (a host rule picks
+ *   it, a pure function of n_var and max_rows: the smallest power of two with pairs x lanes >= 512 x 128 / tile workgroups
+ *   -- pairs and tile as gsdr_cov_plan reports them -- at most the largest power of two <= max_rows, at most
+ *   GSDR_COV_MAX_LANES, and within the bound on the cells) or a power of two in [1, GSDR_COV_MAX_LANES]; lanes x n_var (n_var + 1) / 2 <= 2^28
+ *   cells (2 GiB of doubles); axes[n_var] not NULL, every field finite, reserved 0, channel in [0, n_ch);
+ *   device_index >= -1 as in gsdr_param_c, or GSDR_COV_HOST for a host-only object that touches no GPU.  Anything else
+ *   is refused before the device is touched: NULL, and gsdr_last_error(NULL) starts with "gsdr_cov_create: " and names
+ *   the argument.  Everything every entry needs is allocated here (the chains, max_rows x n_var doubles of projected
+ *   rows, the staging of gsdr_cov_read), every byte count in 64 bits; a failed allocation is a refusal that states the MiB.
+ * gsdr_cov_feed_device: at most TWO launches on hip_stream (hipStream_t as void*): no allocation, no synchronisation, no
+ *   read-back; reads exactly rows_dev[0, n_rows n_ch) (8-byte aligned, anywhere in a larger allocation) and writes
+ *   nothing the caller can see; 0, or -1 with gsdr_last_error(NULL).  n_rows == 0 is valid and touches no pointer;
+ *   n_rows outside [0, max_rows]: -1, state unchanged.
+ * gsdr_cov_read_device: one launch on hip_stream; writes exactly out_dev[0, n_var^2) and, where mean_dev is not NULL,
+ *   mean_dev[0, n_var) (both 8-byte aligned).  gsdr_cov_read: the same launch into the object's staging, then waits for
+ *   hip_stream and copies to out_host and, where not NULL, mean_host.  kind is one of the three GSDR_COV_* kinds.
+ * gsdr_cov_feed_host / _read_host: GSDR_COV_HOST objects only (and the device entries are refused on them): a BIT TWIN
+ *   of the device.
+ * gsdr_cov_reset(c, axes): restarts the row numbering at 0 and zeroes the chains; with axes not NULL the object takes new
+ *   variables (n_var of them, checked as at creation; a refusal leaves everything as it was).  On a device object it
+ *   waits for the device, zeroes, and waits again.
+ * Stream order is the caller's, as for the stats object: the object remembers no stream and waits for none; rows_dev must
+ *   stay unchanged until the feed that reads it has finished.  On a NULL object close is a no-op, the getters return 0,
+ *   the rest return -1 with the reason.
+ * gsdr_cov_plan: the launches of one feed (csrc/cov_state.h: the function the feed itself asks; host only).  out[0]
+ *   tile T: 16, 32 or 64 -- the smallest that holds n_var -- or 128 beyond; out[1] tiles = ceil(n_var / T); out[2] pairs
+ *   = tiles (tiles + 1) / 2, the accumulate grid's x; out[3] the accumulate grid's y = lanes; out[4] the bytes of LDS of
+ *   an accumulate workgroup, 256 T; out[5] the variables a workgroup of the project pass spans (by 256 / out[5] rows): the
+ *   smallest power of two that holds n_var, at most 256.  No result depends on any of them.  Returns 0, or -1 for a NULL out and for what gsdr_cov_create
+ *   refuses of n_ch, n_var and lanes (lanes must be a power of two here: 0, the rule, needs max_rows: ask the object). */
+#define GSDR_COV_HOST (-2)
+#define GSDR_COV_MAX_VARS 4096
+#define GSDR_COV_MAX_LANES 4096
+#define GSDR_COV_SUMS 0
+#define GSDR_COV_COV 1
+#define GSDR_COV_CORR 2
+typedef struct gsdr_cov_axis {
+    int channel;
+    float bx, by, dx, dy;
+    int reserved; /* zero */
+    double pivot;
+} gsdr_cov_axis;
+typedef struct gsdr_cov gsdr_cov;
+gsdr_cov *gsdr_cov_create(int n_ch, int n_var, int max_rows, int lanes, const gsdr_cov_axis *axes, int device_index);
+int gsdr_cov_feed_device(gsdr_cov *c, const gsdr_c64 *rows_dev, int n_rows, void *hip_stream);
+int gsdr_cov_feed_host(gsdr_cov *c, const gsdr_c64 *rows, int n_rows);
+int gsdr_cov_read_device(gsdr_cov *c, int kind, double *out_dev /* n_var x n_var */, double *mean_dev /* n_var, or NULL */,
+                         void *hip_stream);
+int gsdr_cov_read(gsdr_cov *c, int kind, double *out_host, double *mean_host /* or NULL */, void *hip_stream);
+int gsdr_cov_read_host(gsdr_cov *c, int kind, double *out, double *mean /* or NULL */);
+int gsdr_cov_reset(gsdr_cov *c, const gsdr_cov_axis *axes /* n_var, or NULL */);
+long long gsdr_cov_rows(const gsdr_cov *c);
+int gsdr_cov_lanes(const gsdr_cov *c);
+int gsdr_cov_n_var(const gsdr_cov *c);
+int gsdr_cov_plan(int n_ch, int n_var, int lanes, int out[6] /* tile, tiles, pairs, lanes, lds_bytes, project_x */);
+void gsdr_cov_close(gsdr_cov *c);
+
 #ifdef __cplusplus
 }
 #endif
